@@ -2,6 +2,7 @@
 """Benchmark of the hot path (BASELINE.json) on N MI355X GPUs of one node.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   (+ roofline, cpu_baseline and every extra)
     python bench.py --gpus N --steps K --warmup W          (spawns its own N ranks, one per GPU; or, equivalently:)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -16,7 +17,10 @@ masked MSE + backward + RCCL all-reduce of the flat gradient over xGMI + clip + 
 (no collective) goes to `extra`.
 
 Synthetic data (x_t, t, length, xf_proj, xf_out ~ seed 0; zero-init parameters overwritten with N(0, 0.02) so no
-work is skipped).  Rank 0 prints ONE JSON line.  Beside the headline: `roofline` for the dominant kernel class
+work is skipped).  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps of the headline and
+prints the line (`ms_per_step` = milliseconds of one timed step); `--dump-outputs DIR` also writes what the last timed
+step computed (N = 1: the forward's output; N > 1: rank 0's loss and a seeded sample of the updated parameters) as
+DIR/<name>.npy.  Everything else below runs only with `--full`.  Beside the headline: `roofline` for the dominant kernel class
 (the fp32 FFN GEMM), `cpu_baseline` = the oracle (CPU restatement of the reference, pinned by tests/golden) timed
 on the host cores, and in `extra` the train step, the REAL 1000-step hipGraph DDPM sampling loop (fp32 products and
 bf16 storage), the bf16-storage forwards, the HBM-bound kernels, the two-person model, text head and evaluator.
@@ -453,6 +457,35 @@ def spawn_ranks(n):
     sys.exit(0)
 
 
+SHAPE_TXT = ("B=%d/GPU T=196 F=150 d=512 L=8 H=8 ff=1024 N=77 Lt=256, linear attention, text embeddings "
+             "supplied (CLIP stubbed)")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def common_fields(a, world):
+    return {"n_gpus": world, "steps": a.steps, "warmup": a.warmup, "higher_is_better": True,
+            "scaling": "strong" if a.strong else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic"}
+
+
+def headline_config(B):
+    return {"workload": "MotionTransformer forward incl. the per-call cross-attention text side, BASELINE "
+                        "config 2: " + SHAPE_TXT % B, "parallelism": "dp1"}
+
+
+def dump_outputs(outdir, arrays):
+    """`--dump-outputs DIR`: each tensor as DIR/<name>.npy in float32 (float64 tensors stay float64), so that two builds
+    run with the same arguments -- same seeded inputs and parameters -- can be compared output for output."""
+    import numpy as np
+    host = {k: v.detach().cpu() for k, v in arrays.items()}
+    host = {k: (v if v.dtype == torch.float64 else v.float()).numpy() for k, v in host.items()}
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(outdir, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -463,7 +496,14 @@ def main():
     ap.add_argument("--ddpm-steps", type=int, default=1000, help="diffusion steps of the sampling loop (the real loop: 1000)")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling (SURVEY 8d config 4): global batch 512 split over the ranks instead of 64 per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run everything else this file measures: roofline, CPU baseline, extras "
+                         "(other precisions, shapes, models), and at N > 1 the forward and the single-GPU reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -500,10 +540,28 @@ def main():
     # One forward = everything the reference computes per call, including the cross-attention text side
     # (transformer.py:144-150): the text-context cache (a product feature for the sampling loop) is OFF here.
     model.cache_text_context = False
-    el = timed(fwd, a.steps, a.warmup, world)
     gflop = flops_per_frame_fwd(c) * B * T / 1e9          # executed == algorithmic: nothing is hoisted
-    fwd_res = {"frames_per_s": round(B * T * a.steps * world / el, 1), "ms_per_step": round(el / a.steps * 1e3, 4),
-               "fwd_tflops": round(gflop * a.steps * world / el / 1e3, 2)}
+    fwd_res = None
+    if world == 1 or a.full:                  # (N > 1 headlines the training step: the forward is an extra there)
+        last = {}
+
+        def fwd_step():
+            last["out"] = fwd()
+
+        el = timed(fwd_step, a.steps, a.warmup, world)
+        fwd_res = {"frames_per_s": round(B * T * a.steps * world / el, 1), "ms_per_step": round(el / a.steps * 1e3, 4),
+                   "fwd_tflops": round(gflop * a.steps * world / el / 1e3, 2)}
+        if world == 1 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"denoiser_out": last["out"]})
+        del last
+    if world == 1 and not a.full:
+        # a plain run: the headline and nothing else
+        res = dict({"metric": "denoiser-fwd frames/s @ B=64·T=196", "value": fwd_res["frames_per_s"],
+                    "unit": "frames/s", "ms_per_step": fwd_res["ms_per_step"]}, **common_fields(a, world))
+        res["config"] = headline_config(B)
+        res["fwd_tflops"] = fwd_res["fwd_tflops"]
+        print(json.dumps(res))
+        return
 
     # ---- training step: q_sample + fwd + masked MSE + bwd (+ RCCL all-reduce) + clip + Adam ----
     import types
@@ -571,17 +629,20 @@ def main():
                      "step_form": step_form}
         if form_probe:
             train_res["step_form_probe"] = form_probe
+        if world > 1 and rank == 0 and a.dump_outputs:
+            # what the caller of the timed step holds after it: the loss and the updated parameters (a seeded sample)
+            flat = model.flat_params()
+            idx = torch.randperm(flat.core_numel, generator=torch.Generator().manual_seed(0))[:1 << 20].to(device)
+            dump_outputs(a.dump_outputs, {"train_loss": trainer.fused_state()["loss"],
+                                          "params_sample": flat.flat[:flat.core_numel][idx]})
     model.eval()
 
-    common = {"n_gpus": world, "steps": a.steps, "warmup": a.warmup, "higher_is_better": True,
-              "scaling": "strong" if a.strong else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic"}
-    shape_txt = ("B=%d/GPU T=196 F=150 d=512 L=8 H=8 ff=1024 N=77 Lt=256, linear attention, text embeddings "
-                 "supplied (CLIP stubbed)" % B)
+    common = common_fields(a, world)
+    shape_txt = SHAPE_TXT % B
     if world == 1:
         res = dict({"metric": "denoiser-fwd frames/s @ B=64·T=196", "value": fwd_res["frames_per_s"],
                     "unit": "frames/s", "ms_per_step": fwd_res["ms_per_step"]}, **common)
-        res["config"] = {"workload": "MotionTransformer forward incl. the per-call cross-attention text side, BASELINE "
-                                     "config 2: " + shape_txt, "parallelism": "dp1"}
+        res["config"] = headline_config(B)
         res["fwd_tflops"] = fwd_res["fwd_tflops"]
     else:
         # BASELINE config 4: data-parallel training, weak scaling (B=64 per GPU; --strong: global 512 split)
@@ -595,6 +656,8 @@ def main():
                                         (world, model.flat_params().core_numel * 4 / 1e6)}
         res["train_tflops"] = round(3 * gflop * train_res["steps"] * world /
                                     (train_res["ms_per_step"] * train_res["steps"] * 1e-3) / 1e3, 2)
+
+    if world > 1 and a.full:
         # scaling reference measured in the SAME job: the identical step with the gradient exchange switched off, i.e.
         # what one GPU does alone (the N = 1 run of this script headlines the forward, not the training step)
         fst = trainer.fused_state()
@@ -611,9 +674,9 @@ def main():
                     "is the weak-scaling efficiency of the data-parallel step"}
 
     extra = {}
-    if world > 1:
+    if world > 1 and a.full:
         extra["fwd_f32"] = dict(fwd_res, what="denoiser forward incl. text side, no collective (independent batches)")
-    if not a.no_extra:
+    if a.full and not a.no_extra:
         extra["train_step_f32"] = train_res
         # ---- the forward as the sampling loop runs it: step-invariant text context hoisted (cached) ----
         model.cache_text_context = True
@@ -1012,7 +1075,8 @@ def main():
             extra["hbm_bound_kernels"]["counter_based"] = ("FETCH_SIZE / WRITE_SIZE passes of the same kernels: %s (not collected "
                                                            "in this run)" % (os.path.relpath(pm[-1], ROOT) if pm else "none committed"))
             extra["roofline_bf16_ffn_gemm"] = ffn_gemm_bf16_roofline(c, device)
-        res["roofline"] = ffn_gemm_roofline(c, device)
+        if a.full:
+            res["roofline"] = ffn_gemm_roofline(c, device)
         if not a.no_cpu_baseline and world == 1:
             gpu_out = fwd()
             cb, rel = cpu_baseline(c, model, inp, gpu_out)

@@ -72,7 +72,8 @@ def pytest_collection_finish(session):
         env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
         out, log = open(os.path.join(outdir, "stdout.txt"), "wb"), open(os.path.join(outdir, "rank0.log"), "wb")
         _DP["benchspawn"] = {"outdir": outdir, "n": 1, "procs": [subprocess.Popen(
-            [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline"],
+            [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-extra",
+             "--no-cpu-baseline"],
             env=env, stdout=out, stderr=log)]}
 
 

@@ -46,27 +46,44 @@ def test_g2_denoiser_forward(gold, case, no_eff):
             assert rel(inter[k], g[tag + "." + k]) < tol, k
 
 
+def _g3_backward(case, dtype):
+    c = fill.CASES[case]
+    p = {k: v.to(dtype).requires_grad_(True) for k, v in
+         fill.core_params(c["F"], c["d"], c["ff"], c["L"], c["Lt"], c["num_frames"]).items()}
+    inp = fill.inputs(c["B"], c["T"], c["F"], c["d"], c["N"], c["Lt"], c["lengths"], c["t"])
+    x, xp, xo = (inp[k].to(dtype).clone().requires_grad_(True) for k in ("x", "xf_proj", "xf_out"))
+    out = R.denoiser_forward(p, x, inp["t"], inp["length"], xp, xo, c["H"], c["L"])
+    r = fill.tensor_for("loss.r." + case, out.shape).to(dtype) * 10.0
+    (out * r).sum().backward()
+    return p, x, xp, xo
+
+
 @pytest.mark.parametrize("case", ["tiny", "config1"])
 def test_g3_denoiser_backward(gold, case):
     g = gold("g3_denoiser_bwd.npz")
-    c = fill.CASES[case]
     tag = case + ".lin"
-    p = {k: v.requires_grad_(True) for k, v in
-         fill.core_params(c["F"], c["d"], c["ff"], c["L"], c["Lt"], c["num_frames"]).items()}
-    inp = fill.inputs(c["B"], c["T"], c["F"], c["d"], c["N"], c["Lt"], c["lengths"], c["t"])
-    x, xp, xo = (inp[k].clone().requires_grad_(True) for k in ("x", "xf_proj", "xf_out"))
-    out = R.denoiser_forward(p, x, inp["t"], inp["length"], xp, xo, c["H"], c["L"])
-    r = fill.tensor_for("loss.r." + case, out.shape) * 10.0
-    (out * r).sum().backward()
+    p, x, xp, xo = _g3_backward(case, torch.float32)
     assert rel(x.grad, g[tag + ".dx"]) < 1e-5
     assert rel(xp.grad, g[tag + ".dxf_proj"]) < 1e-5
     assert rel(xo.grad, g[tag + ".dxf_out"]) < 1e-5
+    tot = torch.sqrt(sum((v.grad.double() ** 2).sum() for v in p.values())).item()
+    # key.bias grads are mathematically 0 (column softmax is shift invariant).  In fp32 both the golden value and ours are
+    # rounding noise of a cancelling sum, of the size of the abs floor below, whose realisation depends on the host's
+    # reduction order (thread count, vector width).  So the fp32 pass must only show them to be zero at fp32 resolution,
+    # and the SAME oracle in float64 (where they come out ~1e-14 on any host) is held to the golden with the usual gate.
+    p64 = None
     for k in g.files:
         if k.startswith(tag + ".g."):
-            # key.bias grads are mathematically 0 (column softmax is shift invariant): abs floor
-            a, b = p[k[len(tag) + 3:]].grad.double(), torch.as_tensor(g[k]).double()
+            name = k[len(tag) + 3:]
+            b = torch.as_tensor(g[k]).double()
+            if name.endswith(".key.bias"):
+                assert p[name].grad.double().norm() <= torch.finfo(torch.float32).eps * tot, k
+                if p64 is None:
+                    p64 = _g3_backward(case, torch.float64)[0]
+                a = p64[name].grad
+            else:
+                a = p[name].grad.double()
             assert (a - b).norm() <= 1e-5 * b.norm() + 1e-6 * b.numel() ** 0.5, k
-    tot = torch.sqrt(sum((v.grad.double() ** 2).sum() for v in p.values())).item()
     assert abs(tot - float(g[tag + ".gnorm_core"])) / float(g[tag + ".gnorm_core"]) < 1e-5
 
 

@@ -46,7 +46,7 @@ for pattern, name in (("ws16_stamps.txt", "_ws16_stamps.txt"), ("apply16_stamps.
     if f:
         shutil.copy(f, os.path.join(dst, tag + name))
 lines = ["# %s: rocprofv3 summaries (MI355X, one GPU)" % tag, "",
-         "Command profiled: `python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra`", "",
+         "Command profiled: `python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra`", "",
          "## Kernel time (rocprofv3 --kernel-trace --stats), top 12", "",
          "| kernel | calls | total ms | avg us | % |", "|---|---|---|---|---|"]
 for r in list(csv.DictReader(open(ks)))[:12]:
