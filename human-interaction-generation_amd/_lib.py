@@ -11,8 +11,22 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhig.so")
 
-NGLOBAL = 15
-NLAYER = 36
+# table slots of include/hig.h (HIG_ prefix dropped; checked against the header by the CPU test-suite)
+(P_SEQ_EMB, P_JOINT_W, P_JOINT_B, P_TE0_W, P_TE0_B, P_TE2_W, P_TE2_B, P_STY_EMB_W, P_STY_EMB_B, P_OUT_W, P_OUT_B,
+ P_JOINT2_W, P_JOINT2_B, P_OUT2_W, P_OUT2_B, NGLOBAL) = range(16)
+(L_SA_NORM_W, L_SA_NORM_B, L_SA_QKV_W, L_SA_QKV_B, L_SA_STY_NORM_W, L_SA_STY_NORM_B, L_SA_STY_OUT_W, L_SA_STY_OUT_B,
+ L_CA_NORM_W, L_CA_NORM_B, L_CA_TNORM_W, L_CA_TNORM_B, L_CA_Q_W, L_CA_Q_B, L_CA_KV_W, L_CA_KV_B,
+ L_CA_STY_NORM_W, L_CA_STY_NORM_B, L_CA_STY_OUT_W, L_CA_STY_OUT_B,
+ L_FFN_W1, L_FFN_B1, L_FFN_W2, L_FFN_B2, L_FFN_STY_NORM_W, L_FFN_STY_NORM_B, L_FFN_STY_OUT_W, L_FFN_STY_OUT_B,
+ L_INT_NORM_W, L_INT_NORM_B, L_INT_QKV_W, L_INT_QKV_B, L_INT_STY_NORM_W, L_INT_STY_NORM_B, L_INT_STY_OUT_W, L_INT_STY_OUT_B,
+ NLAYER) = range(37)
+# derived-operand tables: per-layer slots, then the globals at [*_NLAYER * L + g]
+(D32_SA_QKV_W, D32_SA_QKV_COLSUM, D32_SA_QKV_B, D32_CA_Q_W, D32_CA_Q_COLSUM, D32_CA_Q_B, D32_NLAYER) = range(7)
+D32_TEXT_KV_W, D32_TEXT_KV_B, D32_TEXT_ONES, D32_TEXT_ZEROS, D32_NGLOBAL = range(5)
+(D16_SA_QKV_W, D16_SA_QKV_COLSUM, D16_SA_QKV_B, D16_CA_Q_W, D16_CA_Q_COLSUM, D16_CA_Q_B,
+ D16_INT_QKV_W, D16_INT_QKV_COLSUM, D16_INT_QKV_B,
+ D16_SA_STY_OUT_FRAG, D16_CA_STY_OUT_FRAG, D16_INT_STY_OUT_FRAG, D16_FFN_STY_OUT_FRAG, D16_NLAYER) = range(14)
+D16_JOINT_W, D16_TEXT_KV_W, D16_TEXT_KV_B, D16_TEXT_ONES, D16_TEXT_ZEROS, D16_NGLOBAL = range(6)
 ATTN_LINEAR, ATTN_FULL = 0, 1
 PREC_F32, PREC_BF16X3, PREC_BF16 = 0, 1, 2
 XF_NONE, XF_LN, XF_LN_MOD_SILU, XF_SILU = 0, 1, 2, 3

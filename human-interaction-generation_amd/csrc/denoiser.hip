@@ -285,6 +285,32 @@ inline float* GL(void* const* t, int l, int idx) {
   return static_cast<float*>(t[HIG_NGLOBAL + l * HIG_NLAYER + idx]);
 }
 
+// A caller-derived operand table (include/hig.h: HIG_D32_* / HIG_D16_*): `nlayer` slots per layer for L layers, then the
+// globals.  An absent table reads as all NULL.
+struct Derived {
+  const void* const* t;
+  int nlayer, L;
+  template <class T = void> const T* layer(int l, int slot) const {
+    return t ? static_cast<const T*>(t[nlayer * l + slot]) : nullptr;
+  }
+  template <class T = void> const T* global(int slot) const {
+    return t ? static_cast<const T*>(t[nlayer * L + slot]) : nullptr;
+  }
+};
+inline Derived derived32_table(const Dims& D, const void* const* t) { return {t, HIG_D32_NLAYER, D.L}; }
+inline Derived derived16_table(const Dims& D, const void* const* t) { return {t, HIG_D16_NLAYER, D.L}; }
+// the fold triples are walked as `*_SA_QKV_W + 3 k`, the stylization-out fragments by their slot of the modulation table
+static_assert(HIG_D32_SA_QKV_COLSUM == HIG_D32_SA_QKV_W + 1 && HIG_D32_SA_QKV_B == HIG_D32_SA_QKV_W + 2 &&
+              HIG_D32_CA_Q_W == HIG_D32_SA_QKV_W + 3 && HIG_D32_CA_Q_COLSUM == HIG_D32_SA_QKV_W + 4 &&
+              HIG_D32_CA_Q_B == HIG_D32_SA_QKV_W + 5, "fp32 fold triples: W, COLSUM, B of k = 0, 1 contiguous");
+static_assert(HIG_D16_SA_QKV_COLSUM == HIG_D16_SA_QKV_W + 1 && HIG_D16_SA_QKV_B == HIG_D16_SA_QKV_W + 2 &&
+              HIG_D16_CA_Q_W == HIG_D16_SA_QKV_W + 3 && HIG_D16_CA_Q_COLSUM == HIG_D16_SA_QKV_W + 4 &&
+              HIG_D16_CA_Q_B == HIG_D16_SA_QKV_W + 5 && HIG_D16_INT_QKV_W == HIG_D16_SA_QKV_W + 6 &&
+              HIG_D16_INT_QKV_COLSUM == HIG_D16_SA_QKV_W + 7 && HIG_D16_INT_QKV_B == HIG_D16_SA_QKV_W + 8,
+              "bf16 fold triples: W, COLSUM, B of k = 0, 1, 2 contiguous");
+static_assert(HIG_D16_CA_STY_OUT_FRAG == HIG_D16_SA_STY_OUT_FRAG + 1 && HIG_D16_INT_STY_OUT_FRAG == HIG_D16_SA_STY_OUT_FRAG + 2 &&
+              HIG_D16_FFN_STY_OUT_FRAG == HIG_D16_SA_STY_OUT_FRAG + 3, "fragments in stylization order sa, ca, int_ca, ffn");
+
 }  // namespace
 
 namespace {
@@ -338,13 +364,14 @@ namespace {
 // layer_done (nullable): event l is recorded on `st` behind layer l's launches (hig_denoiser_fwd_text waits for it in front of
 // layer l's cross-attention)
 // Does the text side run in its batched form (one key/value GEMM + one context build for all layers)?  Inference, linear
-// attention, fp32 storage, and the caller's derived-operand table carries the stacked folded weights (entries 6 L .. 6 L + 3).
+// attention, fp32 storage, and the caller's derived-operand table carries the stacked folded weights (HIG_D32_TEXT_*).
 bool text_batched(const Dims& D, const void* const* derived32, int training) {
   static const int batch_env = getenv("HIG_TEXT_BATCH") ? atoi(getenv("HIG_TEXT_BATCH")) : 1;   // tuning knob
-  return batch_env && derived32 && !training && !D.full && !D.bf16 && derived32[6 * D.L] && derived32[6 * D.L + 1] &&
-         derived32[6 * D.L + 2] && derived32[6 * D.L + 3];
+  const Derived d32 = derived32_table(D, derived32);
+  return batch_env && !training && !D.full && !D.bf16 && d32.global(HIG_D32_TEXT_KV_W) && d32.global(HIG_D32_TEXT_KV_B) &&
+         d32.global(HIG_D32_TEXT_ONES) && d32.global(HIG_D32_TEXT_ZEROS);
 }
-// derived32 (nullable): the caller's derived-operand table (hig_denoiser_fwd_x); entries [6 L .. 6 L + 3] select the BATCHED form
+// derived32 (nullable): the caller's derived-operand table (hig_denoiser_fwd_x); its HIG_D32_TEXT_* globals select the BATCHED form
 int text_context_impl(const Dims& D, const void* const* params, const void* const* derived32, const float* xf_out, void* textctx,
                       int training, hipStream_t st, hipEvent_t* layer_done) {
   hig_stream_t stream = reinterpret_cast<hig_stream_t>(st);
@@ -360,10 +387,11 @@ int text_context_impl(const Dims& D, const void* const* params, const void* cons
     float* xhat = base + tl.xhat;
     float* kvall = base + tl.kvall;
     const int64_t ldkv = (int64_t)D.L * 2 * D.d;
-    HIG_TRY(hig_layernorm(xf_out, D.Lt, D.Mt, D.Lt, static_cast<const float*>(derived32[6 * D.L + 2]),
-                          static_cast<const float*>(derived32[6 * D.L + 3]), xhat, D.Lt, stt, stream));
-    HIG_TRY(hig_gemm_launch(G(xhat, D.Lt, 0, static_cast<const float*>(derived32[6 * D.L]), D.Lt, 0, kvall, ldkv, D.Mt, ldkv, D.Lt)
-                                .epi(HIG_EPI_BIAS, static_cast<const float*>(derived32[6 * D.L + 1])).prec(D.prec).g, 1, nullptr, st));
+    const Derived d32 = derived32_table(D, derived32);
+    HIG_TRY(hig_layernorm(xf_out, D.Lt, D.Mt, D.Lt, d32.global<float>(HIG_D32_TEXT_ONES), d32.global<float>(HIG_D32_TEXT_ZEROS),
+                          xhat, D.Lt, stt, stream));
+    HIG_TRY(hig_gemm_launch(G(xhat, D.Lt, 0, d32.global<float>(HIG_D32_TEXT_KV_W), D.Lt, 0, kvall, ldkv, D.Mt, ldkv, D.Lt)
+                                .epi(HIG_EPI_BIAS, d32.global<float>(HIG_D32_TEXT_KV_B)).prec(D.prec).g, 1, nullptr, st));
     // the stacked weights put all keys in front of all values ([K_0 .. K_{L-1} | V_0 .. V_{L-1}]): head l H + h of "L H heads"
     // is layer l's head h, and ONE context-build launch serves every layer (4096 workgroups instead of 8 x 512)
     const float* Kall = kvall;
@@ -593,6 +621,7 @@ static int denoiser_fwd_impl(const hig_dims* dims, const void* const* params, co
   // LayerNorm fold (fp32 storage): inference only, d a multiple of 128, operands derived by the caller per parameter version
   static const int fold_env = getenv("HIG_LNFOLD32") ? atoi(getenv("HIG_LNFOLD32")) : 1;   // tuning knob
   const bool fold32 = fold_env && derived32 && !training && d % 128 == 0 && d <= 1024;
+  const Derived d32 = derived32_table(D, derived32);
   int layer_rc = HIG_OK;   // the code of the launch that failed inside `layer` (it returns NULL then)
   auto layer = [&](int l, const float* hin_full, int b0, int nb, hipStream_t s, float* cscr) -> const float* {
     hig_stream_t hs = reinterpret_cast<hig_stream_t>(s);
@@ -614,14 +643,14 @@ static int denoiser_fwd_impl(const hig_dims* dims, const void* const* params, co
     // (layer 0's first projection has no producer: plain LayerNorm)
     const int np = d >> 6;
     float* lnst = ws + w.lnstats + r0 * np * 2;
-    auto folded = [&](int k) { return fold32 && derived32[6 * l + 3 * k] != nullptr; };
+    auto folded = [&](int k) { return fold32 && d32.layer(l, HIG_D32_SA_QKV_W + 3 * k) != nullptr; };
     auto ln_proj = [&](int k, bool have_stats, const float* hrows, int norm_w, int norm_b, int lin_w, int lin_b, float* xn, float* st,
                        float* outp, int ncols) -> int {
       if (have_stats && folded(k)) {
-        G gf(hrows, d, 0, static_cast<const float*>(derived32[6 * l + 3 * k]), d, 0, outp, ncols, Mh, ncols, d);
-        gf.epi(HIG_EPI_BIAS, static_cast<const float*>(derived32[6 * l + 3 * k + 2])).prec(D.prec);
+        G gf(hrows, d, 0, d32.layer<float>(l, HIG_D32_SA_QKV_W + 3 * k), d, 0, outp, ncols, Mh, ncols, d);
+        gf.epi(HIG_EPI_BIAS, d32.layer<float>(l, HIG_D32_SA_QKV_B + 3 * k)).prec(D.prec);
         gf.g.row_stats_in = lnst;
-        gf.g.ln_colsum = static_cast<const float*>(derived32[6 * l + 3 * k + 1]);
+        gf.g.ln_colsum = d32.layer<float>(l, HIG_D32_SA_QKV_COLSUM + 3 * k);
         return hig_gemm_launch(gf.g, 1, nullptr, s);
       }
       HIG_TRY(hig_layernorm(hrows, d, Mh, d, PL(params, l, norm_w), PL(params, l, norm_b), xn, d, st, hs));
@@ -709,7 +738,7 @@ static int denoiser_fwd_impl(const hig_dims* dims, const void* const* params, co
     {
       G gs(R(w.a3, d), d, 0, PL(params, l, HIG_L_FFN_STY_OUT_W), d, 0, R(w.h3, d), d, Mh, d, d);
       gs.epi(HIG_EPI_BIAS_RES, PL(params, l, HIG_L_FFN_STY_OUT_B)).res(hffn, d).prec(D.prec);
-      if (fold32 && l + 1 < D.L && derived32[6 * (l + 1)] != nullptr) gs.g.row_stats_out = lnst;   // h3's statistics for the next layer's q/k/v
+      if (fold32 && l + 1 < D.L && d32.layer(l + 1, HIG_D32_SA_QKV_W) != nullptr) gs.g.row_stats_out = lnst;   // h3's statistics for the next layer's q/k/v
       HIG_L(hig_gemm_launch(gs.g, 1, nullptr, s));
     }
 #undef HIG_L
@@ -936,12 +965,14 @@ extern "C" int hig_text_context_bf16(const hig_dims* dims, const void* const* pa
   HIG_REQUIRE(params && params16 && xf_out && textctx, "hig_text_context_bf16: null argument");
   return text_context16_impl(D, params, params16, nullptr, xf_out, textctx, hig_stream(stream), nullptr);
 }
-// derived (nullable): the caller's derived-operand table of hig_denoiser_fwd_bf16_x; entries [13 L + 1 .. 13 L + 4] select the
+// derived (nullable): the caller's derived-operand table of hig_denoiser_fwd_bf16_x; its HIG_D16_TEXT_* globals select the
 // BATCHED form (text_context_impl above: one key/value GEMM over the stacked text_norm-folded bf16 weights of all layers, one
 // context build over L H heads)
 static bool text16_batched(const Dims& D, const void* const* derived) {
   static const int batch_env = getenv("HIG_TEXT_BATCH") ? atoi(getenv("HIG_TEXT_BATCH")) : 1;   // tuning knob
-  return batch_env && derived && !D.full && derived[13 * D.L + 1] && derived[13 * D.L + 2] && derived[13 * D.L + 3] && derived[13 * D.L + 4];
+  const Derived d16 = derived16_table(D, derived);
+  return batch_env && !D.full && d16.global(HIG_D16_TEXT_KV_W) && d16.global(HIG_D16_TEXT_KV_B) && d16.global(HIG_D16_TEXT_ONES) &&
+         d16.global(HIG_D16_TEXT_ZEROS);
 }
 static int text_context16_impl(const Dims& D, const void* const* params, const void* const* params16, const void* const* derived,
                                const float* xf_out, void* textctx, hipStream_t st, hipEvent_t* layer_done) {
@@ -952,10 +983,11 @@ static int text_context16_impl(const Dims& D, const void* const* params, const v
   if (text16_batched(D, derived) && tl.kvall >= 0) {
     char* kvall = base + tl.kvall;
     const int64_t ldkv = (int64_t)D.L * 2 * D.d;
-    HIG_TRY(hig_ln_bf16(xf_out, 1, D.Lt, D.Mt, D.Lt, static_cast<const float*>(derived[13 * D.L + 3]),
-                        static_cast<const float*>(derived[13 * D.L + 4]), nullptr, 0, 0, 0, xfn, D.Lt, stream));
-    HIG_TRY(hig_gemm16_launch(G16(xfn, D.Lt, derived[13 * D.L + 1], D.Lt, kvall, ldkv, D.Mt, ldkv, D.Lt)
-                                  .epi(HIG_EPI_BIAS, static_cast<const float*>(derived[13 * D.L + 2])).g, st));
+    const Derived d16 = derived16_table(D, derived);
+    HIG_TRY(hig_ln_bf16(xf_out, 1, D.Lt, D.Mt, D.Lt, d16.global<float>(HIG_D16_TEXT_ONES), d16.global<float>(HIG_D16_TEXT_ZEROS),
+                        nullptr, 0, 0, 0, xfn, D.Lt, stream));
+    HIG_TRY(hig_gemm16_launch(G16(xfn, D.Lt, d16.global(HIG_D16_TEXT_KV_W), D.Lt, kvall, ldkv, D.Mt, ldkv, D.Lt)
+                                  .epi(HIG_EPI_BIAS, d16.global<float>(HIG_D16_TEXT_KV_B)).g, st));
     const char* Kall = kvall;
     const char* Vall = kvall + (int64_t)D.L * D.d * 2;
     int rc = hig_linattn_ctx16_groups(Kall, Vall, ldkv, D.B, D.N, D.H, D.L, D.hd,
@@ -991,24 +1023,24 @@ static int text_context16_impl(const Dims& D, const void* const* params, const v
   return HIG_OK;
 }
 
-static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, const void* const* params16, const void* const* lnfold,
+static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, const void* const* params16, const void* const* derived,
                                const float* x, const int64_t* t, const int64_t* length, const float* xf_proj, const float* xf_out_for_text,
                                const void* textctx, float* out, void* workspace, hig_stream_t stream);
 extern "C" int hig_denoiser_fwd_bf16(const hig_dims* dims, const void* const* params, const void* const* params16,
-                                     const void* const* lnfold, const float* x, const int64_t* t, const int64_t* length,
+                                     const void* const* derived, const float* x, const int64_t* t, const int64_t* length,
                                      const float* xf_proj,
                                      const void* textctx, float* out, void* workspace, hig_stream_t stream) {
-  return denoiser_fwd16_impl(dims, params, params16, lnfold, x, t, length, xf_proj, nullptr, textctx, out, workspace, stream);
+  return denoiser_fwd16_impl(dims, params, params16, derived, x, t, length, xf_proj, nullptr, textctx, out, workspace, stream);
 }
 // The general form (include/hig.h): xf_out (nullable) = compute the text side here, on a library-owned stream next to the
 // first layers.
 extern "C" int hig_denoiser_fwd_bf16_x(const hig_dims* dims, const void* const* params, const void* const* params16,
-                                       const void* const* lnfold, const float* x, const int64_t* t, const int64_t* length,
+                                       const void* const* derived, const float* x, const int64_t* t, const int64_t* length,
                                        const float* xf_proj, const float* xf_out, void* textctx, float* out, void* workspace,
                                        hig_stream_t stream) {
-  return denoiser_fwd16_impl(dims, params, params16, lnfold, x, t, length, xf_proj, xf_out, textctx, out, workspace, stream);
+  return denoiser_fwd16_impl(dims, params, params16, derived, x, t, length, xf_proj, xf_out, textctx, out, workspace, stream);
 }
-static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, const void* const* params16, const void* const* lnfold,
+static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, const void* const* params16, const void* const* derived,
                                const float* x, const int64_t* t, const int64_t* length, const float* xf_proj, const float* xf_out_for_text,
                                const void* textctx, float* out, void* workspace, hig_stream_t stream) {
   Dims D;
@@ -1037,7 +1069,8 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
   static const int fork_knob = getenv("HIG_FWD16_FORK") ? atoi(getenv("HIG_FWD16_FORK")) : -1;   // tuning knob: bit 0 embedding chain, bit 1 text side
   // (round 6: the BATCHED text side -- three launches, two of them chip-wide -- is faster in front of the frame-row launches than
   // next to them: B = 64 1.488 against 1.540 ms, per-layer form 1.539 forked / 1.603 in front; not forked by default)
-  const bool batched_text = xf_out_for_text && text16_batched(D, lnfold);
+  const bool batched_text = xf_out_for_text && text16_batched(D, derived);
+  const Derived d16 = derived16_table(D, derived);
   const int fork_env = fork_knob >= 0 ? fork_knob : ((batched_text ? 0 : 2) | (((int64_t)E * ss_ld * 2 >= (256ll << 20)) ? 1 : 0));
   SideStream* fs = (fork_env && D.L < kMaxTextLayers) ? side_stream_for_current_device(st) : nullptr;
   if (fs) {
@@ -1073,7 +1106,7 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
   if (fork_emb && hipEventRecord(emb_ev, se) != hipSuccess) return join_side(hig_set_error(HIG_EHIP, "hipEventRecord failed"));
   hipEvent_t* text_ev = nullptr;
   if (xf_out_for_text) {
-    HIG_TRY_SIDE(text_context16_impl(D, params, params16, lnfold, xf_out_for_text, const_cast<void*>(textctx), fork_text ? fs->s3 : st,
+    HIG_TRY_SIDE(text_context16_impl(D, params, params16, derived, xf_out_for_text, const_cast<void*>(textctx), fork_text ? fs->s3 : st,
                                      fork_text ? fs->text_done : nullptr));
     if (fork_text) text_ev = fs->text_done;
   }
@@ -1089,8 +1122,8 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
   static const int joint16 = getenv("HIG_JOINT16") ? atoi(getenv("HIG_JOINT16")) : 1;   // tuning knob
   if (joint16 && d % 128 == 0 && D.F <= 512) {
     // own kernel pair (weight padded / rounded to bf16, x rounded in LDS, bf16 MFMA): 31 -> ~8 us at B = 32
-    if (lnfold && lnfold[13 * D.L])   // (weight padded / rounded once, next to the caller's bf16 shadow)
-      HIG_TRY(hig_joint_embed_bf16_w(x, M, D.F, lnfold[13 * D.L], P(params, HIG_P_JOINT_B), P(params, HIG_P_SEQ_EMB), d, D.T,
+    if (d16.global(HIG_D16_JOINT_W))   // (weight padded / rounded once, next to the caller's bf16 shadow)
+      HIG_TRY(hig_joint_embed_bf16_w(x, M, D.F, d16.global(HIG_D16_JOINT_W), P(params, HIG_P_JOINT_B), P(params, HIG_P_SEQ_EMB), d, D.T,
                                      D.two ? 1 : 0, ws + w.h, d, d, stream));
     else
       HIG_TRY(hig_joint_embed_bf16(x, M, D.F, P(params, HIG_P_JOINT_W), P(params, HIG_P_JOINT_B), P(params, HIG_P_SEQ_EMB), d,
@@ -1132,7 +1165,7 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
   // one stylization block: h += Lin_out( silu( LN(y) (1 + scale) + shift ) )      (transformer.py:81-85)
   // LayerNorm fold (see include/hig.h): when the NEXT consumer of the residual stream is a LayerNorm + Linear pair, the
   // stylization-out GEMM also writes the row statistics of the new h (`want_stats` set by the layer loop below)
-  const bool fold = lnfold && lnfold[0] && hig_gemm_ws16_lnfold_ok(M, d);
+  const bool fold = d16.layer(0, HIG_D16_SA_QKV_W) && hig_gemm_ws16_lnfold_ok(M, d);
   float* stats = reinterpret_cast<float*>(ws + w.stats);
   bool want_stats = false, have_stats = false;
   auto sty_out = [&](int l, int out_w, int out_b) -> int {
@@ -1145,11 +1178,11 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
   // xn-free projection of LN(h): out = LN(h) W^T + b through the folded operands (k = 0: q/k/v, k = 1: cross-attention query,
   // k = 2: q/k/v of the person <-> person attention)
   auto ln_proj = [&](int l, int k, int norm_w, int norm_b, int lin_w, int lin_b, void* outp, int64_t ncols) -> int {
-    if (have_stats && lnfold[13 * l + 3 * k]) {
-      G16 g(h, d, lnfold[13 * l + 3 * k], d, outp, ncols, M, ncols, d);
-      g.epi(HIG_EPI_BIAS, static_cast<const float*>(lnfold[13 * l + 3 * k + 2]));
+    if (have_stats && d16.layer(l, HIG_D16_SA_QKV_W + 3 * k)) {
+      G16 g(h, d, d16.layer(l, HIG_D16_SA_QKV_W + 3 * k), d, outp, ncols, M, ncols, d);
+      g.epi(HIG_EPI_BIAS, d16.layer<float>(l, HIG_D16_SA_QKV_B + 3 * k));
       g.g.row_stats_in = stats;
-      g.g.ln_colsum = static_cast<const float*>(lnfold[13 * l + 3 * k + 1]);
+      g.g.ln_colsum = d16.layer<float>(l, HIG_D16_SA_QKV_COLSUM + 3 * k);
       return hig_gemm16_launch(g.g, st);
     }
     HIG_TRY(hig_ln_bf16(h, 0, d, M, d, PL(params, l, norm_w), PL(params, l, norm_b), nullptr, 0, 0, 0, xn, d, stream));
@@ -1183,7 +1216,7 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
     HIG_TRY(need_emb());
     if (fuse_apply) {
       const float* ssl = ss + (int64_t)(D.nsty * l + slot) * 2 * d;
-      const void* wfrag = (fuse_out && slot < 3 && lnfold) ? lnfold[13 * l + 9 + slot] : nullptr;
+      const void* wfrag = (fuse_out && slot < 3) ? d16.layer(l, HIG_D16_SA_STY_OUT_FRAG + slot) : nullptr;
       if (wfrag) {   // apply + stylization front + output projection + residual update as ONE launch
         const bool st_out = fold && want_stats;
         HIG_TRY(hig_attn_out16(q, ldq, ctx_t16, PL(params, l, norm_w), PL(params, l, norm_b), ssl, ss_ld, d, wfrag, PL(params, l, out_b),
@@ -1234,15 +1267,16 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
       HIG_TRY(ctx16(D, qkv + (int64_t)d * 2, qkv + (int64_t)2 * d * 2, 3 * d, D.B, D.T, len_partner, A1, kst1, cscr,
                     fuse_mm16 ? ws + w.At1 : nullptr, stream));
       const int64_t halfA = (int64_t)Bp * D.H * D.hd * D.hd, halfM = (int64_t)Bp * D.T;
-      if (fuse_out && lnfold && lnfold[13 * l + 11]) {
+      const void* wfrag = fuse_out ? d16.layer(l, HIG_D16_INT_STY_OUT_FRAG) : nullptr;
+      if (wfrag) {
         // each half of the batch against the OTHER half's context matrices; apply + stylization block + residual update fused
         const float* ssl = ss + (int64_t)(D.nsty * l + 2) * 2 * d;
         const char* At = ws + w.At1;
         char* hb = static_cast<char*>(h);
         HIG_TRY(hig_attn_out16(qkv, 3 * d, At + halfA * 2, PL(params, l, HIG_L_INT_STY_NORM_W), PL(params, l, HIG_L_INT_STY_NORM_B), ssl,
-                               ss_ld, d, lnfold[13 * l + 11], PL(params, l, HIG_L_INT_STY_OUT_B), hb, d, nullptr, Bp, D.T, D.H, D.hd, stream));
+                               ss_ld, d, wfrag, PL(params, l, HIG_L_INT_STY_OUT_B), hb, d, nullptr, Bp, D.T, D.H, D.hd, stream));
         HIG_TRY(hig_attn_out16(qkv + halfM * 3 * d * 2, 3 * d, At, PL(params, l, HIG_L_INT_STY_NORM_W), PL(params, l, HIG_L_INT_STY_NORM_B),
-                               ssl + (int64_t)Bp * ss_ld, ss_ld, d, lnfold[13 * l + 11], PL(params, l, HIG_L_INT_STY_OUT_B),
+                               ssl + (int64_t)Bp * ss_ld, ss_ld, d, wfrag, PL(params, l, HIG_L_INT_STY_OUT_B),
                                hb + halfM * d * 2, d, nullptr, Bp, D.T, D.H, D.hd, stream));
         have_stats = false;
       } else if (fuse_mm16) {
@@ -1268,10 +1302,11 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
     HIG_TRY(hig_gemm16_launch(G16(f1, D.ff, PL16(params16, l, HIG_L_FFN_W2), D.ff, y, d, M, d, D.ff)
                                   .epi(HIG_EPI_BIAS, PL(params, l, HIG_L_FFN_B2)).g, st));
     want_stats = l + 1 < D.L;                    // the FFN stylization block feeds the next layer's self-attention LayerNorm
-    if (fuse_out && lnfold && lnfold[13 * l + 12]) {   // stylization front + output projection + residual update as ONE launch
+    const void* wfrag = fuse_out ? d16.layer(l, HIG_D16_FFN_STY_OUT_FRAG) : nullptr;
+    if (wfrag) {   // stylization front + output projection + residual update as ONE launch
       const bool st_out = fold && want_stats;
       HIG_TRY(hig_rows_out16(y, d, PL(params, l, HIG_L_FFN_STY_NORM_W), PL(params, l, HIG_L_FFN_STY_NORM_B),
-                             ss + (int64_t)(D.nsty * l + D.nsty - 1) * 2 * d, ss_ld, d, lnfold[13 * l + 12], PL(params, l, HIG_L_FFN_STY_OUT_B),
+                             ss + (int64_t)(D.nsty * l + D.nsty - 1) * 2 * d, ss_ld, d, wfrag, PL(params, l, HIG_L_FFN_STY_OUT_B),
                              h, d, st_out ? stats : nullptr, D.B, D.T, d, stream));
       have_stats = st_out;
     } else {

@@ -247,6 +247,11 @@ class _FlatParams:
             arr[i] = self.grad.data_ptr() + 4 * next(it) if present else None
         return arr
 
+    def layer_param(self, l, slot, n):
+        """The first n floats of group `slot` (_lib.L_*) of decoder layer l in the flat buffer; None for an empty group."""
+        o = self.group_offsets[_lib.NGLOBAL + l * _lib.NLAYER + slot]
+        return None if o is None else self.flat[o:o + n]
+
     def layer_buckets(self, num_layers, nsty, d, E):
         """Element ranges [(start, stop), ...] of the flat gradient that are FINAL when decoder layer l's backward is
         done (`per_layer[l]`: the layer's own parameters + its rows of the stacked stylization emb_layers.1.weight), and
@@ -258,7 +263,7 @@ class _FlatParams:
             return next(o for o in offs[ng + l * nl: ng + (l + 1) * nl] if o is not None)
 
         starts = [first_of_layer(l) for l in range(num_layers)] + [self.core_numel]
-        o_w = offs[7]                                    # HIG_P_STY_EMB_W
+        o_w = offs[_lib.P_STY_EMB_W]
         rows = nsty * 2 * d * E
         per_layer = [[(starts[l], starts[l + 1]), (o_w + l * rows, o_w + (l + 1) * rows)] for l in range(num_layers)]
         tail = [(0, o_w), (o_w + num_layers * rows, starts[0])]
@@ -296,6 +301,26 @@ class _FlatParams:
         return all(p.is_cuda and base <= p.data_ptr() < end for p in self.params[:3] + self.params[-3:]) \
             and all(p.data_ptr() == base + 4 * o for p, o in zip(self.params[:8], self.offsets[:8])) \
             and all(p.data_ptr() == base + 4 * o for p, o in zip(self.text_params, self.text_offsets))
+
+
+class _DerivedTable:
+    """A derived-operand table of include/hig.h (_lib.D32_* / _lib.D16_*): `nlayer` slots per layer for L layers, then the
+    globals; NULL where nothing is set.  Keeps the tensors it points to alive."""
+
+    def __init__(self, nlayer, nglobal, L):
+        self.nlayer, self.L = nlayer, L
+        self.ptrs = (C.c_void_p * (nlayer * L + nglobal))()
+        self.bufs = []
+
+    def set_layer(self, l, slot, t):
+        self._set(self.nlayer * l + slot, t)
+
+    def set_global(self, slot, t):
+        self._set(self.nlayer * self.L + slot, t)
+
+    def _set(self, i, t):
+        self.bufs.append(t)
+        self.ptrs[i] = t.data_ptr()
 
 
 _POISON = __import__("os").environ.get("HIG_POISON", "0") == "1"
@@ -627,121 +652,103 @@ class MotionTransformer(nn.Module):
         J, R = W16.shape
         return W16.view(J // 32, 32, R // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
 
+    def _text_kv_fold(self, fp):
+        """The batched text side's operands (include/hig.h, the TEXT_* derived globals): [key; value](LN_text(xf)) =
+        xhat (gamma (.) W)^T + (W beta + b) with xhat = (xf - mean) rstd the same in every layer (transformer.py:146,150), so
+        the folded weights of ALL layers stacked make ONE GEMM.  Returns the stacked fp32 weights (L 2d, Lt), all keys in front
+        of all values ([K_0 .. K_{L-1} | V_0 .. V_{L-1}]: one context-build launch for all layers), the bias' in the same
+        order, and Lt ones / Lt zeros (the affine-free LayerNorm of the text rows).  fp64 arithmetic, fp32 results."""
+        d, Lt = self.latent_dim, self.text_latent_dim
+        wt, bt = [], []
+        for l in range(self.num_layers):
+            g_t, b_t = fp.layer_param(l, _lib.L_CA_TNORM_W, Lt).double(), fp.layer_param(l, _lib.L_CA_TNORM_B, Lt).double()
+            Wkv = fp.layer_param(l, _lib.L_CA_KV_W, 2 * d * Lt).view(2 * d, Lt).double()
+            bkv = fp.layer_param(l, _lib.L_CA_KV_B, 2 * d).double()
+            wt.append((Wkv * g_t[None, :]).float())         # rows [0, d): key, [d, 2 d): value
+            bt.append((bkv + Wkv @ b_t).float())
+        Wt = torch.cat([w[:d] for w in wt] + [w[d:] for w in wt], 0).contiguous()
+        Bt = torch.cat([b[:d] for b in bt] + [b[d:] for b in bt], 0).contiguous()
+        return Wt, Bt, torch.ones(Lt, device=Wt.device), torch.zeros(Lt, device=Wt.device)
+
     def _derived16(self, fp):
         """Operands of the bf16-storage forward derived from the parameters, kept next to the bf16 shadow and rebuilt
-        when the parameters change (`derived` of hig_denoiser_fwd_bf16): 13 L + 5 device pointers, NULL where a piece does
-        not apply (the library then runs its LayerNorm kernel / pads per call).
-        [13 l + 3 k + 0 .. 2] (d = 512 or 1024): the LayerNorm-folded projection k of layer l -- k = 0 self-attention q/k/v, 1
-        cross-attention query, 2 q/k/v of the person <-> person attention (two-person model) -- as [W' (bf16), colsum, bias']
-        with W' = gamma (.) W, colsum[j] = sum_r float(W'[j][r]), bias' = b + W beta: LayerNorm(x) W^T + b == rstd (x W'^T) -
-        rstd mean colsum + bias' (transformer.py:108-110,144; interaction_transformer.py:181-190); applied wherever the
-        producer of x wrote its row statistics.
-        [13 l + 9 + s] (d = 512): the stylization-out weight of the self- (s = 0) / cross- (1) / person <-> person (2) attention /
-        FFN (3) block in matrix-core operand order (_frag16) for the fused kernels hig_attn_out16 / hig_rows_out16.
-        [13 L]: joint_embed weight (transformer.py:418) rounded to bf16 and padded to a multiple of 32 columns.
-        [13 L + 1 .. 13 L + 4] (linear attention): the text side's key/value weights of ALL layers with their text_norm folded
-        in (gamma (.) W, every layer's key rows then every layer's value rows, bf16), the bias' b + W beta in the same order
-        (fp32), Lt ones, Lt zeros -- the per-call text side then runs ONE GEMM and ONE context build (transformer.py:146-152)."""
+        when the parameters change (`derived` of hig_denoiser_fwd_bf16, slots _lib.D16_*), NULL where a piece does not apply
+        (the library then runs its LayerNorm kernel / pads per call):
+        the LayerNorm-folded projections (d = 512 or 1024) -- self-attention q/k/v, cross-attention query, q/k/v of the
+        person <-> person attention (two-person model; interaction_transformer.py:181-190) -- as W' (bf16), colsum, bias',
+        computed in fp32; the stylization-out weights (d = 512) in matrix-core operand order (_frag16) for the fused kernels
+        hig_attn_out16 / hig_rows_out16; the joint_embed weight (transformer.py:418) rounded to bf16 and padded to a multiple
+        of 32 columns; and (linear attention) the batched text side of _text_kv_fold with its weights rounded to bf16."""
         ver = (self._param_version(), fp.flat.data_ptr())
         if getattr(self, "_derived", None) is None or self._derived[0] != ver:
-            d, nl, ng, offs, L = self.latent_dim, _lib.NLAYER, _lib.NGLOBAL, fp.group_offsets, self.num_layers
-            arr, bufs = (C.c_void_p * (13 * L + 5))(), []
-            Lt = self.text_latent_dim
-            wt, bt = [], []
+            d, L, Lt = self.latent_dim, self.num_layers, self.text_latent_dim
+            tab = _DerivedTable(_lib.D16_NLAYER, _lib.D16_NGLOBAL, L)
             with torch.no_grad():
-                for l in range(0 if self.no_eff else L):
-                    def tgrp(idx, n):
-                        o = offs[ng + l * nl + idx]
-                        return fp.flat[o:o + n]
-                    # text side, batched (see _derived32): gamma (.) [Wk; Wv] rounded to bf16, bias' = b + W beta in fp32
-                    g_t, b_t = tgrp(10, Lt).double(), tgrp(11, Lt).double()
-                    Wkv, bkv = tgrp(14, 2 * d * Lt).view(2 * d, Lt).double(), tgrp(15, 2 * d).double()
-                    wt.append((Wkv * g_t[None, :]).float())
-                    bt.append((bkv + Wkv @ b_t).float())
-                if wt and Lt % 8 == 0:
-                    Wt = torch.cat([w[:d] for w in wt] + [w[d:] for w in wt], 0).to(torch.bfloat16).contiguous()
-                    Bt = torch.cat([b[:d] for b in bt] + [b[d:] for b in bt], 0).contiguous()
-                    ones, zeros = torch.ones(Lt, device=Wt.device), torch.zeros(Lt, device=Wt.device)
-                    bufs += [Wt, Bt, ones, zeros]
-                    arr[13 * L + 1], arr[13 * L + 2], arr[13 * L + 3], arr[13 * L + 4] = Wt.data_ptr(), Bt.data_ptr(), ones.data_ptr(), zeros.data_ptr()
+                if not self.no_eff and Lt % 8 == 0:
+                    Wt, Bt, ones, zeros = self._text_kv_fold(fp)
+                    tab.set_global(_lib.D16_TEXT_KV_W, Wt.to(torch.bfloat16).contiguous())
+                    tab.set_global(_lib.D16_TEXT_KV_B, Bt)
+                    tab.set_global(_lib.D16_TEXT_ONES, ones)
+                    tab.set_global(_lib.D16_TEXT_ZEROS, zeros)
+                # (W' slot; LayerNorm weight, bias; Linear weight, bias; output rows): W', colsum, bias' at slot, slot + 1, + 2
+                folds = ((_lib.D16_SA_QKV_W, _lib.L_SA_NORM_W, _lib.L_SA_NORM_B, _lib.L_SA_QKV_W, _lib.L_SA_QKV_B, 3 * d),
+                         (_lib.D16_CA_Q_W, _lib.L_CA_NORM_W, _lib.L_CA_NORM_B, _lib.L_CA_Q_W, _lib.L_CA_Q_B, d),
+                         (_lib.D16_INT_QKV_W, _lib.L_INT_NORM_W, _lib.L_INT_NORM_B, _lib.L_INT_QKV_W, _lib.L_INT_QKV_B, 3 * d))
+                frags = ((_lib.D16_SA_STY_OUT_FRAG, _lib.L_SA_STY_OUT_W), (_lib.D16_CA_STY_OUT_FRAG, _lib.L_CA_STY_OUT_W),
+                         (_lib.D16_INT_STY_OUT_FRAG, _lib.L_INT_STY_OUT_W), (_lib.D16_FFN_STY_OUT_FRAG, _lib.L_FFN_STY_OUT_W))
                 for l in range(L if d in (512, 1024) else 0):
-                    def grp(idx, n):
-                        o = offs[ng + l * nl + idx]
-                        return None if o is None else fp.flat[o:o + n]
-                    # (norm weight, norm bias, Linear weight, Linear bias, output rows) by index in the layer table (hig.h)
-                    for k, (nw, nb, wi, bi, rows) in enumerate(((0, 1, 2, 3, 3 * d), (8, 9, 12, 13, d), (28, 29, 30, 31, 3 * d))):
-                        gamma = grp(nw, d)
+                    for slot, nw, nb, wi, bi, rows in folds:
+                        gamma = fp.layer_param(l, nw, d)
                         if gamma is None:           # (the interaction block exists in the two-person model only)
                             continue
-                        beta, W, b = grp(nb, d), grp(wi, rows * d).view(rows, d), grp(bi, rows)
+                        beta, b = fp.layer_param(l, nb, d), fp.layer_param(l, bi, rows)
+                        W = fp.layer_param(l, wi, rows * d).view(rows, d)
                         Wp = (W * gamma[None, :]).to(torch.bfloat16).contiguous()
-                        cs = Wp.float().sum(dim=1).contiguous()
-                        bp = (b + W @ beta).contiguous()
-                        bufs += [Wp, cs, bp]
-                        arr[13 * l + 3 * k], arr[13 * l + 3 * k + 1], arr[13 * l + 3 * k + 2] = Wp.data_ptr(), cs.data_ptr(), bp.data_ptr()
-                    # stylization-out weights of the attention blocks in matrix-core operand order (hig_attn_out16: d = 512)
-                    for s, wi in enumerate((6, 18, 34, 26)):
-                        w = grp(wi, d * d) if d == 512 else None
+                        tab.set_layer(l, slot, Wp)
+                        tab.set_layer(l, slot + 1, Wp.float().sum(dim=1).contiguous())
+                        tab.set_layer(l, slot + 2, (b + W @ beta).contiguous())
+                    for slot, wi in frags:
+                        w = fp.layer_param(l, wi, d * d) if d == 512 else None
                         if w is not None:
-                            wf = self._frag16(w.view(d, d).to(torch.bfloat16))
-                            bufs.append(wf)
-                            arr[13 * l + 9 + s] = wf.data_ptr()
+                            tab.set_layer(l, slot, self._frag16(w.view(d, d).to(torch.bfloat16)))
                 F = self.input_feats
                 Fp = (F + 31) // 32 * 32
                 wj = torch.zeros(d, Fp, device=fp.flat.device, dtype=torch.bfloat16)
                 wj[:, :F] = self.joint_embed.weight.detach().to(torch.bfloat16)
-                bufs.append(wj)
-                arr[13 * L] = wj.data_ptr()
-            self._derived = (ver, arr, bufs)
-        return self._derived[1]
+                tab.set_global(_lib.D16_JOINT_W, wj)
+            self._derived = (ver, tab)
+        return self._derived[1].ptrs
 
     def _derived32(self, fp):
         """Operands of the fp32 inference forward derived from the parameters, rebuilt when they change (`derived32` of
-        hig_denoiser_fwd_x): per layer the LayerNorm-folded projections k = 0 (self-attention q/k/v) and k = 1 (cross-attention
-        query) as [W' = gamma (.) W, colsum = row sums of W', bias' = b + W beta] -- LayerNorm(x) W^T + b == rstd (x W'^T) - rstd
-        mean colsum + bias' (transformer.py:108-110,144), applied where the producer of x wrote its row statistics; and
-        [6 L .. 6 L + 3] the text side's key/value weights of ALL layers with their text_norm folded in, stacked (L 2d, Lt: every
-        layer's key rows, then every layer's value rows), the
-        stacked bias', and a ones / zeros vector (the affine-free LayerNorm of the text rows) -- the per-call text side then runs
-        one GEMM instead of L (transformer.py:146,150).  fp64 arithmetic for the derived vectors, fp32 storage; latent_dim % 128
-        == 0 only (NULL table otherwise)."""
+        hig_denoiser_fwd_x, slots _lib.D32_*): per layer the LayerNorm-folded self-attention q/k/v and cross-attention query
+        projections as W', colsum, bias', and (linear attention) the batched text side of _text_kv_fold.  fp64 arithmetic for
+        the derived vectors, fp32 storage; latent_dim % 128 == 0 only (NULL table otherwise)."""
         d = self.latent_dim
         if d % 128 != 0 or d > 1024:
             return None
         ver = (self._param_version(), fp.flat.data_ptr())
         if getattr(self, "_derived_f32", None) is None or self._derived_f32[0] != ver:
-            nl, ng, offs, L = _lib.NLAYER, _lib.NGLOBAL, fp.group_offsets, self.num_layers
-            arr, bufs = (C.c_void_p * (6 * L + 4))(), []
-            Lt = self.text_latent_dim
-            wt, bt = [], []
+            L = self.num_layers
+            tab = _DerivedTable(_lib.D32_NLAYER, _lib.D32_NGLOBAL, L)
+            # (W' slot; LayerNorm weight, bias; Linear weight, bias; output rows): W', colsum, bias' at slot, slot + 1, + 2
+            folds = ((_lib.D32_SA_QKV_W, _lib.L_SA_NORM_W, _lib.L_SA_NORM_B, _lib.L_SA_QKV_W, _lib.L_SA_QKV_B, 3 * d),
+                     (_lib.D32_CA_Q_W, _lib.L_CA_NORM_W, _lib.L_CA_NORM_B, _lib.L_CA_Q_W, _lib.L_CA_Q_B, d))
             with torch.no_grad():
                 for l in range(L):
-                    def grp(idx, n):
-                        o = offs[ng + l * nl + idx]
-                        return fp.flat[o:o + n]
-                    # text side (transformer.py:146,150): [key; value](LN_text(xf)) = xhat (gamma (.) W)^T + (W beta + b) with
-                    # xhat = (xf - mean) rstd the same in every layer -- the folded weights of ALL layers stacked, one GEMM
-                    g_t, b_t = grp(10, Lt).double(), grp(11, Lt).double()
-                    Wkv, bkv = grp(14, 2 * d * Lt).view(2 * d, Lt).double(), grp(15, 2 * d).double()
-                    wt.append((Wkv * g_t[None, :]).float())         # rows [0, d): key, [d, 2 d): value
-                    bt.append((bkv + Wkv @ b_t).float())
-                    for k, (nw, nb, wi, bi, rows) in enumerate(((0, 1, 2, 3, 3 * d), (8, 9, 12, 13, d))):
-                        gamma, beta = grp(nw, d).double(), grp(nb, d).double()
-                        W, b = grp(wi, rows * d).view(rows, d).double(), grp(bi, rows).double()
+                    for slot, nw, nb, wi, bi, rows in folds:
+                        gamma, beta = fp.layer_param(l, nw, d).double(), fp.layer_param(l, nb, d).double()
+                        W, b = fp.layer_param(l, wi, rows * d).view(rows, d).double(), fp.layer_param(l, bi, rows).double()
                         Wp = (W * gamma[None, :]).float().contiguous()
-                        cs = Wp.double().sum(dim=1).float().contiguous()
-                        bp = (b + W @ beta).float().contiguous()
-                        bufs += [Wp, cs, bp]
-                        arr[6 * l + 3 * k], arr[6 * l + 3 * k + 1], arr[6 * l + 3 * k + 2] = Wp.data_ptr(), cs.data_ptr(), bp.data_ptr()
+                        tab.set_layer(l, slot, Wp)
+                        tab.set_layer(l, slot + 1, Wp.double().sum(dim=1).float().contiguous())
+                        tab.set_layer(l, slot + 2, (b + W @ beta).float().contiguous())
                 if not self.no_eff:
-                    # all keys in front of all values: [K_0 .. K_{L-1} | V_0 .. V_{L-1}] (one context-build launch for all layers)
-                    Wt = torch.cat([w[:d] for w in wt] + [w[d:] for w in wt], 0).contiguous()
-                    Bt = torch.cat([b[:d] for b in bt] + [b[d:] for b in bt], 0).contiguous()
-                    ones, zeros = torch.ones(Lt, device=Wt.device), torch.zeros(Lt, device=Wt.device)
-                    bufs += [Wt, Bt, ones, zeros]
-                    arr[6 * L], arr[6 * L + 1], arr[6 * L + 2], arr[6 * L + 3] = Wt.data_ptr(), Bt.data_ptr(), ones.data_ptr(), zeros.data_ptr()
-            self._derived_f32 = (ver, arr, bufs)
-        return self._derived_f32[1]
+                    for slot, t in zip((_lib.D32_TEXT_KV_W, _lib.D32_TEXT_KV_B, _lib.D32_TEXT_ONES, _lib.D32_TEXT_ZEROS),
+                                       self._text_kv_fold(fp)):
+                        tab.set_global(slot, t)
+            self._derived_f32 = (ver, tab)
+        return self._derived_f32[1].ptrs
 
     def _launch_forward(self, x, t, length, xf_proj, xf_out, training):
         B, T, N = x.shape[0], x.shape[1], xf_out.shape[1]

@@ -152,6 +152,72 @@ enum {
   HIG_NLAYER
 };
 
+/* Derived-operand tables of the inference forwards: device pointers the caller derives from the parameters and rebuilds
+ * when they change.  Like the parameter table they have a per-layer block and globals, but here the L per-layer blocks
+ * come FIRST: entry (layer l, slot s) is at [NLAYER l + s], global g at [NLAYER L + g].  Any entry may be NULL (the
+ * library then runs that piece per call / unfused); the table itself may be NULL.
+ *
+ * LayerNorm fold (the *_W, *_COLSUM, *_B triples): for a LayerNorm (gamma, beta) in front of a Linear (W, b),
+ *   W' = gamma (.) W, colsum[j] = sum_r W'[j][r] (the bf16 table: sum_r float(W'[j][r])), bias' = b + W beta,
+ * so LayerNorm(x) W^T + b == rstd (x W'^T) - rstd mean colsum + bias' (transformer.py:108-110,144).  Where the producer of
+ * x wrote its row statistics (row_stats_out of hig_gemm_desc / hig_gemm16_desc), the LayerNorm launch in front of that
+ * projection disappears.
+ *
+ * Batched text side (the TEXT_* globals; all four or none; linear attention; read when the forward computes the text side):
+ * the key/value weights of ALL layers with their text_norm folded in, stacked as one (L 2d, Lt) matrix -- every layer's key
+ * rows gamma_l (.) Wk_l, then every layer's value rows gamma_l (.) Wv_l -- the bias' b_l + W_l beta_l (fp32, L 2d) in the
+ * same order, and Lt ones / Lt zeros (fp32: the affine-free LayerNorm of the text rows).  The per-call text side then runs
+ * ONE key/value GEMM and ONE context build instead of L of each (`textctx`: hig_textctx_bytes(dims, 0) covers that form's
+ * staging).  HIG_TEXT_BATCH=0 keeps the per-layer form. */
+
+/* `derived32` of hig_denoiser_fwd_x (fp32 storage; fold needs d % 128 == 0).  Every entry fp32. */
+enum {
+  HIG_D32_SA_QKV_W = 0, /* self-attention q/k/v: W' (3d, d) */
+  HIG_D32_SA_QKV_COLSUM,
+  HIG_D32_SA_QKV_B,
+  HIG_D32_CA_Q_W,       /* cross-attention query: W' (d, d) */
+  HIG_D32_CA_Q_COLSUM,
+  HIG_D32_CA_Q_B,
+  HIG_D32_NLAYER
+};
+enum {
+  HIG_D32_TEXT_KV_W = 0, /* (L 2d, Lt) */
+  HIG_D32_TEXT_KV_B,
+  HIG_D32_TEXT_ONES,
+  HIG_D32_TEXT_ZEROS,
+  HIG_D32_NGLOBAL
+};
+#define HIG_D32_COUNT(L) (HIG_D32_NLAYER * (L) + HIG_D32_NGLOBAL)
+
+/* `derived` of hig_denoiser_fwd_bf16 / _bf16_x (bf16 storage).  W' and the stacked text weights bf16, the rest fp32. */
+enum {
+  HIG_D16_SA_QKV_W = 0,  /* fold (d == 512 or 1024, >= 2048 rows: hig_gemm16_desc): self-attention q/k/v, W' (3d, d) */
+  HIG_D16_SA_QKV_COLSUM,
+  HIG_D16_SA_QKV_B,
+  HIG_D16_CA_Q_W,        /* cross-attention query, W' (d, d) */
+  HIG_D16_CA_Q_COLSUM,
+  HIG_D16_CA_Q_B,
+  HIG_D16_INT_QKV_W,     /* person <-> person attention q/k/v (two-person model), W' (3d, d) */
+  HIG_D16_INT_QKV_COLSUM,
+  HIG_D16_INT_QKV_B,
+  /* the stylization-out weight (d, d) of each block in matrix-core operand order (hig_weight_frag16) for hig_attn_out16 /
+   * hig_rows_out16, in the order of the modulation table `ss` (two-person model): */
+  HIG_D16_SA_STY_OUT_FRAG,
+  HIG_D16_CA_STY_OUT_FRAG,
+  HIG_D16_INT_STY_OUT_FRAG,
+  HIG_D16_FFN_STY_OUT_FRAG,
+  HIG_D16_NLAYER
+};
+enum {
+  HIG_D16_JOINT_W = 0, /* joint_embed weight padded and rounded for hig_joint_embed_bf16_w ((d, Fp) bf16, Fp = F rounded up to 32) */
+  HIG_D16_TEXT_KV_W,   /* (L 2d, Lt) bf16 */
+  HIG_D16_TEXT_KV_B,
+  HIG_D16_TEXT_ONES,
+  HIG_D16_TEXT_ZEROS,
+  HIG_D16_NGLOBAL
+};
+#define HIG_D16_COUNT(L) (HIG_D16_NLAYER * (L) + HIG_D16_NGLOBAL)
+
 /* Bytes of scratch the forward needs.  training != 0 keeps every layer's activations for
  * hig_denoiser_bwd; training == 0 reuses one layer's buffers for all layers. */
 int64_t hig_workspace_bytes(const hig_dims* dims, int training);
@@ -181,18 +247,7 @@ int hig_denoiser_fwd_text(const hig_dims* dims, const void* const* params, const
                           void* workspace, int training, hig_stream_t stream);
 
 /* The general fp32-storage forward.  xf_out (nullable): compute the text side in this call (hig_denoiser_fwd_text), else
- * `textctx` is an input.  derived32 (nullable; inference only): 6 L + 4 device pointers the caller derives from the parameters and
- * rebuilds when they change -- [6 l + 3 k + 0 .. 2], k = 0 self-attention q/k/v (3d rows), k = 1 cross-attention query (d rows):
- * W' (fp32, rows x d) = gamma (.) W of the LayerNorm in front of the projection, colsum (rows) = row sums of W', bias' (rows) =
- * b + W beta.  With them the LayerNorm launches in front of those projections disappear (d % 128 == 0): the stylization-out
- * GEMM that produces the residual stream writes its row statistics (hig_gemm_desc.row_stats_out), the projection applies them
- * in its epilogue (row_stats_in).  Any entry may be NULL (that projection then keeps its LayerNorm kernel).
- * The table has 6 L + 4 entries: [6 L + 0 .. 3] (all four or none; linear attention only) = the text side's key/value weights of
- * ALL layers with their text_norm folded in, stacked as one (L 2d, Lt) fp32 matrix [gamma_l (.) Wk_l, l = 0 .. L-1; gamma_l (.) Wv_l,
- * l = 0 .. L-1] (every layer's key rows, then every layer's value rows), the bias' in the same order
- * b_l + W_l beta_l (L 2d), a vector of Lt ones and one of Lt zeros: with xf_out given, the L key/value GEMMs of the per-call
- * text side run as ONE product over the affine-free LayerNorm of the text rows (`textctx` must then have hig_textctx_bytes(dims,
- * 0) bytes, which includes that form's staging).  HIG_TEXT_BATCH=0 keeps the per-layer form. */
+ * `textctx` is an input.  derived32 (nullable; inference only): the HIG_D32_COUNT(L) derived operands (HIG_D32_*). */
 int hig_denoiser_fwd_x(const hig_dims* dims, const void* const* params, const void* const* derived32, const float* x,
                        const int64_t* t, const int64_t* length, const float* xf_proj, const float* xf_out, void* textctx,
                        float* out, void* workspace, int training, hig_stream_t stream);
@@ -204,22 +259,7 @@ int hig_denoiser_fwd_x(const hig_dims* dims, const void* const* params, const vo
  * Workspace / text-context sizes: hig_workspace_bytes / hig_textctx_bytes with the same dims (training = 0). */
 int hig_text_context_bf16(const hig_dims* dims, const void* const* params, const void* const* params16,
                           const float* xf_out, void* textctx, hig_stream_t stream);
-/* derived (nullable): 13 L + 5 device pointers the caller derives from the parameters and keeps next to the bf16 shadow
- * (rebuilt when the parameters change); any entry may be NULL (the library then does that piece per call / unfused).
- * [13 l + 3 k + 0 .. 2], k = 0, 1, 2, d == 512 or 1024: W' (bf16, rows x d), colsum (fp32, rows), bias' (fp32, rows) of the LayerNorm +
- * Linear pair k of layer l -- k = 0 self-attention q/k/v (3d rows), k = 1 cross-attention query (d rows), k = 2 q/k/v of the
- * person <-> person attention (two-person model, 3d rows) -- with W' = gamma (.) W of the LayerNorm in front of the Linear,
- * colsum[j] = sum_r float(W'[j][r]), bias' = b + W beta.  With them (and >= 2048 rows) the LayerNorm kernels in front of
- * those projections disappear: the GEMM that produces the residual stream also writes its row statistics, and the
- * projection applies them in its epilogue (hig_gemm16_desc).
- * [13 l + 9 + s], s = 0, 1, 2, 3: the stylization-out weight of the self- / cross- / person <-> person attention / FFN block
- * in matrix-core operand order (hig_weight_frag16) for hig_attn_out16 / hig_rows_out16.
- * [13 L]: joint_embed weight padded and rounded for hig_joint_embed_bf16_w ((d, Fp) bf16, Fp = F rounded up to 32).
- * [13 L + 1 .. 13 L + 4] (all four or none; linear attention; read by hig_denoiser_fwd_bf16_x when it computes the text side):
- * the key/value weights of ALL layers with their text_norm folded in, stacked as one (L 2d, Lt) bf16 matrix (every layer's key
- * rows gamma_l (.) Wk_l, then every layer's value rows), bias' = b_l + W_l beta_l in the same order (fp32, L 2d), Lt ones and
- * Lt zeros (fp32): the text side then runs ONE key/value GEMM over the affine-free LayerNorm of the text rows and ONE context
- * build instead of L of each (`textctx`: hig_textctx_bytes covers that form's staging).  HIG_TEXT_BATCH=0: per-layer form. */
+/* derived (nullable): the HIG_D16_COUNT(L) derived operands (HIG_D16_*), kept by the caller next to the bf16 shadow. */
 int hig_denoiser_fwd_bf16(const hig_dims* dims, const void* const* params, const void* const* params16,
                           const void* const* derived, const float* x,
                           const int64_t* t, const int64_t* length, const float* xf_proj, const void* textctx,

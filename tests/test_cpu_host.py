@@ -34,6 +34,35 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert lib.hig_version() >= 100
 
 
+def _header_constants():
+    """Every integer constant of include/hig.h: `#define HIG_* <int>` and the members of every `enum { ... }` (implicit values
+    counted on from the previous member)."""
+    text = open(os.path.join(ROOT, "include", "hig.h")).read()
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {name: int(v) for name, v in re.findall(r"^#define\s+(HIG_\w+)\s+\(?(-?\d+)\)?\s*$", text, flags=re.M)}
+    for body in re.findall(r"\benum\s*\{(.*?)\}", text, flags=re.S):
+        value = 0
+        for member in filter(None, (m.strip() for m in body.split(","))):
+            name, _, init = (s.strip() for s in member.partition("="))
+            value = int(init) if init else value
+            consts[name] = value
+            value += 1
+    return consts
+
+
+def test_lib_constants_mirror_the_header():
+    """_lib's table slots and codes (header names without `HIG_`) hold the header's values, and every slot of the
+    parameter table and of the derived-operand tables is mirrored."""
+    consts = _header_constants()
+    assert consts["HIG_EINVAL"] == -1 and consts["HIG_NLAYER"] > consts["HIG_L_INT_STY_OUT_B"] > 0, "header not parsed"
+    mirrored = {n: v for n, v in vars(_lib).items() if type(v) is int and "HIG_" + n in consts}
+    wrong = {n: (v, consts["HIG_" + n]) for n, v in mirrored.items() if v != consts["HIG_" + n]}
+    assert not wrong, "_lib value != hig.h value: %s" % wrong
+    tables = [n for n in consts if n.startswith(("HIG_P_", "HIG_L_", "HIG_D32_", "HIG_D16_"))] + ["HIG_NGLOBAL", "HIG_NLAYER"]
+    missing = [n for n in tables if n[len("HIG_"):] not in mirrored]
+    assert not missing, "hig.h table slots without a _lib mirror: %s" % missing
+
+
 def test_abi_struct_sizes_and_dim_validation():
     lib = _lib.lib()
     d = _lib.Dims(B=2, T=16, F=12, d=64, H=8, ff=128, L=2, N=77, Lt=32, num_frames=20, attn_kind=0, prec=0)

@@ -11,6 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import hig_amd  # noqa: E402
+from hig_amd import _lib  # noqa: E402
 from hig_amd.models import gaussian_diffusion as gdm  # noqa: E402
 from oracle import denoiser_ref as R  # noqa: E402
 from oracle import diffusion_ref as D  # noqa: E402
@@ -642,7 +643,7 @@ def test_per_call_forward_with_the_batched_text_side_against_the_oracle_and_the_
     m.cache_text_context = False
     per_call = fwd()
     torch.cuda.synchronize()
-    assert m._derived32(m.flat_params())[6 * c["L"]] is not None          # the stacked text weights exist: the batched form ran
+    assert m._derived32(m.flat_params())[_lib.D32_NLAYER * c["L"] + _lib.D32_TEXT_KV_W] is not None   # stacked text weights: batched form
     assert torch.isfinite(per_call).all()
     assert rel(per_call, cached) < 2e-6
     for _ in range(3):
