@@ -1007,6 +1007,7 @@ int launch(const hig_gemm_desc& g, int splits, float* slabs, int64_t slab, hipSt
     }
   }
   if (!served && a.ntiles > 0 && g.R >= 0) {
+    hig_gemm_path_count(a.tail_s > 1 ? HIG_GEMM_PATH_TAIL32 : splits > 1 ? HIG_GEMM_PATH_SPLIT32 : HIG_GEMM_PATH_TILED32);
     // the bf16 product modes exist for aligned reduce-contiguous operands; anything else
     // (F = 150 projections, reduce-slow dgrad / wgrad layouts) runs the exact fp32 kernel
     bool launched = false;
@@ -1277,6 +1278,16 @@ extern "C" int hig_gemm_debug_stamps(void* buf) {
 }
 
 extern "C" int64_t hig_gemm_tail_ws_bytes(void) { return HIG_GEMM_TAIL_BYTES; }
+
+// Launch counts per GEMM kernel (hig_gemm_path_launches): host side, incremented at each launch site.
+static long long g_path_launches[HIG_GEMM_NPATHS];
+void hig_gemm_path_count(int path) {
+  if (path >= 0 && path < HIG_GEMM_NPATHS) __atomic_fetch_add(&g_path_launches[path], 1, __ATOMIC_RELAXED);
+}
+extern "C" int64_t hig_gemm_path_launches(int32_t path) {
+  if (path < 0 || path >= HIG_GEMM_NPATHS) return -1;
+  return __atomic_load_n(&g_path_launches[path], __ATOMIC_RELAXED);
+}
 
 extern "C" int hig_gemm_ws(const hig_gemm_desc* g, void* ws, int64_t ws_bytes, hig_stream_t stream) {
   HIG_REQUIRE(g, "hig_gemm_ws: null descriptor");

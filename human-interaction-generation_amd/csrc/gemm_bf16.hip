@@ -338,7 +338,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_bf16_kernel(const K16Arg
 }
 
 template <int WM, int WN, int TI, int TJ, int BK, int NS, int EPI>
-int launch16(const hig_gemm16_desc& g, hipStream_t st, int splits = 1, int64_t slab = 0) {
+int launch16(const hig_gemm16_desc& g, hipStream_t st, int splits = 1, int64_t slab = 0, int path = HIG_GEMM_PATH_TILED16) {
   constexpr int use_srd = 1;   // (a former tuning knob, fixed at the value that won its A/B): 0 = global_load_lds
   constexpr int NT = 64 * WM * WN, BM = 32 * TI * WM, BN = 32 * TJ * WN;
   K16Args a;
@@ -364,6 +364,7 @@ int launch16(const hig_gemm16_desc& g, hipStream_t st, int splits = 1, int64_t s
   if (grid > a.ntiles) grid = a.ntiles;
   // (operands beyond 2 GiB would overflow the 32-bit byte offsets of the descriptor form)
   const bool srd_ok = ((int64_t)g.I * g.ldx < (1ll << 30)) && ((int64_t)g.J * g.ldy < (1ll << 30));
+  hig_gemm_path_count(path);
   if (use_srd && srd_ok)
     hipLaunchKernelGGL((gemm_bf16_kernel<WM, WN, TI, TJ, BK, NS, EPI, true>), dim3(grid), dim3(NT), 0, st, a);
   else
@@ -586,6 +587,7 @@ __global__ __launch_bounds__(256) void gemm_fewrow16_lds_kernel(const hig_gemm16
 template <int EPI>
 int launch_fewrow16(const hig_gemm16_desc& g, hipStream_t st) {
   constexpr int lds_on = 1;   // (a former tuning knob, fixed at the value that won its A/B)
+  hig_gemm_path_count(HIG_GEMM_PATH_FEWROW16);
   if (lds_on && g.R % 256 == 0) {               // operands through wave-private LDS rings
     if (g.I <= 32) hipLaunchKernelGGL((gemm_fewrow16_lds_kernel<1, EPI>), dim3(g.J / 32), dim3(256), 0, st, g);
     else hipLaunchKernelGGL((gemm_fewrow16_lds_kernel<2, EPI>), dim3(g.J / 32), dim3(256), 0, st, g);
@@ -859,7 +861,7 @@ int hig_gemm16_split_launch(const hig_gemm16_desc& g0, int splits, float* slabs,
   hig_gemm16_desc g = g0;
   if (splits > 1) g.C = slabs;
   // 128 x 128 tiles, two k-tiles of 64 in flight (long reduce range: the ring covers the DMA latency)
-  HIG_TRY((launch16<2, 2, 2, 2, 64, 2, HIG_EPI_NONE>(g, st, splits, slab)));
+  HIG_TRY((launch16<2, 2, 2, 2, 64, 2, HIG_EPI_NONE>(g, st, splits, slab, HIG_GEMM_PATH_SPLIT16)));
   if (splits > 1) return hig_reduce_slabs(slabs, splits, slab, g0.I * (int64_t)g0.J, static_cast<float*>(g0.C), st);
   return HIG_OK;
 }

@@ -584,6 +584,7 @@ int launch_ws(const hig_gemm16_desc& g, int slots_per_xcd, hipStream_t st) {
   a.store_policy = (g.res && g.res == g.C) ? 0 : store_policy;
   constexpr int store_slack = 0;   // (a former tuning knob, fixed at the value that won its A/B)
   a.store_slack = store_slack;
+  hig_gemm_path_count(HIG_GEMM_PATH_WS16);
   hipLaunchKernelGGL((gemm_ws16_kernel<KW, KSPLIT, NWJ, NCB, EPI, 0, OCC, XT>), dim3(8 * slots_per_xcd), dim3(64 * NWJ * KSPLIT), 0, st, a);
   HIG_CHECK_LAUNCH();
   return HIG_OK;

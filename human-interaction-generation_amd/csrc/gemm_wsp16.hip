@@ -478,6 +478,7 @@ int launch_wsp(const hig_gemm16_desc& g, hipStream_t st) {
   constexpr int store_policy = 1;   // (a former tuning knob, fixed at the value that won its A/B) (gemm_ws16.hip): 0 plain, else sc1
   const bool plain = (g.res && g.res == g.C) || store_policy == 0;
   const dim3 gr(256), bl(512);
+  hig_gemm_path_count(HIG_GEMM_PATH_WSP16);
   if constexpr (!AUX && XT == 0 && (EPI == HIG_EPI_BIAS || EPI == HIG_EPI_BIAS_GELU || EPI == HIG_EPI_BIAS_RES)) {
     if (a.stamps || dbg) {                       // diagnostic instances (tools/gemm_wsp16_stamps.py)
       // (the no-MFMA / no-fragment-read ablations of profiles/r05_notes.md section 2 were separate instances, DIAG = 3 / 5; they

@@ -439,6 +439,7 @@ int hig_wgrad16_launch_group(const hig_wg_problem* probs, int n, float* slabs, i
   g.unit0[n] = u0;
   g.units = u0;
   if (used_floats) *used_floats = off;
+  hig_gemm_path_count(HIG_GEMM_PATH_WGRAD16);
   hipLaunchKernelGGL(wgrad16x_kernel, dim3((g.units + 7) / 8 * 8), dim3(768), 0, st, g);
   HIG_CHECK_LAUNCH();
   if (!deferred) {

@@ -253,6 +253,7 @@ int hig_wgrad_wsp32_try(const hig_gemm_desc& g, int splits, float* slabs, int64_
   a.splits = splits;
   a.nstage = (g.R + WG_BM - 1) / WG_BM;
   if (a.nstage < splits) return 1;
+  hig_gemm_path_count(HIG_GEMM_PATH_WGRAD_WSP32);
   hipLaunchKernelGGL(wgrad_wsp32_kernel, dim3(256), dim3(512), 0, st, a);
   HIG_CHECK_LAUNCH();
   return HIG_OK;

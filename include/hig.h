@@ -503,6 +503,15 @@ int hig_recover_joints(const float* motion, const float* stats, int32_t rows, in
 #define HIG_XF_SILU 3
 #define HIG_EPI_NONE 0
 #define HIG_EPI_BIAS 1
+/* Element-wise error of the activation epilogues at a pre-activation z, against gelu / gelu' / silu evaluated exactly (derived
+ * from the formulas in fp32 with a margin for the hardware exp2 / rcp; tests/test_gpu_gemm_contract.py asserts these numbers
+ * over every normal bf16 input with |z| <= 64 and a dense grid of fp32 inputs, 1e-6 <= |z| <= 1e3).  ulp: one bf16 ulp of
+ * the exact result, 2^(e - 7) for a result in [2^e, 2^(e + 1)).
+ *   GELU, fp32 out:  <= 4e-7 |z| + 2^-23 |gelu(z)|   (Abramowitz-Stegun erf, 1.5e-7 absolute, evaluated in fp32: 1 - p exp(-z^2/2)
+ *                    loses a few ulps of 1 near |z| ~ 0.1 .. 0.4; the tiled kernel's libm erf stays within the same bound)
+ *   GELU, bf16 out:  <= 1 ulp + 2^-126, + 4.1e-11 |z| for |z| > 6.5 (the log2 Q fit is clamped there; Q(6.5) = 4.016e-11)
+ *   DGELU:           gelu'(z) within 4e-7 + 2^-23 |gelu'(z)| (the same erf), times acc; bf16 out: + 1 ulp
+ *   SiLU, bf16 out:  <= 1 ulp + 2^-126 (hardware exp2 / rcp; results below the smallest normal may be flushed) */
 #define HIG_EPI_BIAS_GELU 2 /* out = gelu(acc+bias); aux (if set) receives acc+bias */
 #define HIG_EPI_BIAS_RES 3  /* out = res + acc + bias */
 #define HIG_EPI_BIAS_POS 4  /* out = acc + bias + pos[i % T] (joint_embed + sequence_embedding) */
@@ -603,6 +612,22 @@ int hig_gemm_wsp32_debug_stamps(void* buf);   /* gemm_wsp32.hip: buf[block * 16 
 /* Launches served by the exact-fp32 weight-stationary kernel (gemm_wsp32.hip) since the library was loaded: hig_gemm routes
  * K = 512 / 1024 products with >= 2048 rows there (HIG_F32_WSP=0 switches it off); a test reads the difference around a call. */
 int64_t hig_gemm_wsp32_launches(void);
+/* GEMM paths: one per kernel the GEMM entry points can launch.  hig_gemm_path_launches(path) counts the launches of that
+ * kernel since the library was loaded (monotonic, host side, one path per launch; the slab reductions behind a split launch
+ * are not counted); -1 for an unknown path.  Tests read the difference around a call to prove which kernel served it. */
+#define HIG_GEMM_PATH_TILED32 0       /* hig_gemm / hig_gemm_ws: the tiled exact-fp32 kernel (gemm.hip) */
+#define HIG_GEMM_PATH_WSP32 1         /* hig_gemm / hig_gemm_ws: gemm_wsp32.hip (twice for the two-pass K = 1536 / 2048 form) */
+#define HIG_GEMM_PATH_TAIL32 2        /* hig_gemm_ws: the tiled kernel with its last round split along the reduce range */
+#define HIG_GEMM_PATH_WGRAD_WSP32 3   /* hig_gemm_split: wgrad_wsp32.hip */
+#define HIG_GEMM_PATH_SPLIT32 4       /* hig_gemm_split: the tiled kernel writing split-R slabs (what wgrad_wsp32 declines) */
+#define HIG_GEMM_PATH_WSP16 5         /* hig_gemm_bf16: gemm_wsp16.hip */
+#define HIG_GEMM_PATH_WS16 6          /* hig_gemm_bf16: gemm_ws16.hip */
+#define HIG_GEMM_PATH_FEWROW16 7      /* hig_gemm_bf16: the few-row kernel (gemm_bf16.hip, <= 64 rows) */
+#define HIG_GEMM_PATH_TILED16 8       /* hig_gemm_bf16: the tiled bf16 kernel (gemm_bf16.hip) */
+#define HIG_GEMM_PATH_SPLIT16 9       /* hig_gemm_bf16_split: the tiled bf16 kernel over split-R slabs */
+#define HIG_GEMM_PATH_WGRAD16 10      /* hig_wgrad_bf16: wgrad16.hip */
+#define HIG_GEMM_NPATHS 11
+int64_t hig_gemm_path_launches(int32_t path);
 int hig_wgrad16_debug_stamps(void* buf);      /* wgrad16.hip (see there): 8192 x 8 bytes */
 /* the same for hig_linattn_apply_sty_mm16: 8 stamps per workgroup (see linattn16.hip) */
 int hig_linattn16_debug_stamps(void* buf);

@@ -52,15 +52,27 @@ def _header_constants():
 
 def test_lib_constants_mirror_the_header():
     """_lib's table slots and codes (header names without `HIG_`) hold the header's values, and every slot of the
-    parameter table and of the derived-operand tables is mirrored."""
+    parameter table, of the derived-operand tables and every GEMM path is mirrored."""
     consts = _header_constants()
     assert consts["HIG_EINVAL"] == -1 and consts["HIG_NLAYER"] > consts["HIG_L_INT_STY_OUT_B"] > 0, "header not parsed"
     mirrored = {n: v for n, v in vars(_lib).items() if type(v) is int and "HIG_" + n in consts}
     wrong = {n: (v, consts["HIG_" + n]) for n, v in mirrored.items() if v != consts["HIG_" + n]}
     assert not wrong, "_lib value != hig.h value: %s" % wrong
-    tables = [n for n in consts if n.startswith(("HIG_P_", "HIG_L_", "HIG_D32_", "HIG_D16_"))] + ["HIG_NGLOBAL", "HIG_NLAYER"]
+    tables = [n for n in consts if n.startswith(("HIG_P_", "HIG_L_", "HIG_D32_", "HIG_D16_", "HIG_GEMM_PATH_"))] + ["HIG_NGLOBAL", "HIG_NLAYER"]
     missing = [n for n in tables if n[len("HIG_"):] not in mirrored]
     assert not missing, "hig.h table slots without a _lib mirror: %s" % missing
+
+
+def test_header_states_the_activation_bounds_the_gemm_contract_asserts():
+    """include/hig.h writes the element-wise bounds of the GELU / DGELU / SiLU epilogues next to the HIG_EPI_* defines;
+    tests/test_gpu_gemm_contract.py asserts the same numbers."""
+    header = open(os.path.join(ROOT, "include", "hig.h")).read()
+    contract = open(os.path.join(ROOT, "tests", "test_gpu_gemm_contract.py")).read()
+    for stated, asserted in (("<= 4e-7 |z| + 2^-23 |gelu(z)|", "GELU32_PER_Z = 4e-7"),
+                             ("+ 4.1e-11 |z| for |z| > 6.5", "GELU16_TAIL = 4.1e-11"),
+                             ("gelu'(z) within 4e-7 + 2^-23 |gelu'(z)|", "DGELU_ABS = 4e-7"),
+                             ("<= 1 ulp + 2^-126", "FLOOR16 = 2.0 ** -126")):
+        assert stated in header and asserted in contract, (stated, asserted)
 
 
 def test_abi_struct_sizes_and_dim_validation():

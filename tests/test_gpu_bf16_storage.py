@@ -45,27 +45,34 @@ EPIS = {"none": _lib.EPI_NONE, "bias": _lib.EPI_BIAS, "gelu": _lib.EPI_BIAS_GELU
         "silu": _lib.EPI_BIAS_SILU, "res_silu": _lib.EPI_BIAS_RES_SILU}
 
 
-@pytest.mark.parametrize("I,J,R,epi,c_f32,res_f32", [
-    (300, 200, 64, "bias", 0, 0), (128, 128, 512, "none", 0, 0), (1000, 1024, 512, "gelu", 0, 0),
-    (777, 512, 1024, "res", 0, 0), (64, 2048, 2048, "res_silu", 0, 1), (32, 2048, 512, "silu", 0, 0),
-    (500, 150, 512, "bias", 1, 0), (6272, 1536, 512, "bias", 0, 0), (45, 96, 96, "res", 1, 1),
-    (2464, 1024, 256, "bias", 0, 0), (70, 264, 32, "gelu", 0, 0), (12544, 512, 512, "res", 0, 0),
-    # large enough for the 256 x 256 tiles (8 waves, one workgroup per CU), incl. ragged edges in both directions
-    (12544, 1024, 512, "gelu", 0, 0), (12544, 1536, 512, "bias", 0, 0), (12500, 1000, 512, "res", 0, 0),
-    (9600, 1024, 1024, "res_silu", 1, 1),
+# (I, J, R, epi, c_f32, res_f32, the GEMM path that must serve the case)
+GEMM16_CASES = [
+    (300, 200, 64, "bias", 0, 0, "TILED16"), (128, 128, 512, "none", 0, 0, "TILED16"), (1000, 1024, 512, "gelu", 0, 0, "TILED16"),
+    (777, 512, 1024, "res", 0, 0, "TILED16"), (64, 2048, 2048, "res_silu", 0, 1, "FEWROW16"), (32, 2048, 512, "silu", 0, 0, "FEWROW16"),
+    (500, 150, 512, "bias", 1, 0, "TILED16"), (6272, 1536, 512, "bias", 0, 0, "WSP16"), (45, 96, 96, "res", 1, 1, "TILED16"),
+    (2464, 1024, 256, "bias", 0, 0, "WS16"), (70, 264, 32, "gelu", 0, 0, "TILED16"), (12544, 512, 512, "res", 0, 0, "WSP16"),
+    # many rows at K = 512 (the weight-stationary kernel with specialised waves, gemm_wsp16.hip), incl. ragged edges in both
+    # directions: N % 128 != 0 and an fp32 output leave it to the tiled kernel
+    (12544, 1024, 512, "gelu", 0, 0, "WSP16"), (12544, 1536, 512, "bias", 0, 0, "WSP16"), (12500, 1000, 512, "res", 0, 0, "TILED16"),
+    (9600, 1024, 1024, "res_silu", 1, 1, "TILED16"),
     # a handful of rows (gemm_fewrow16_kernel: <= 64 rows, N % 32 == 0, K % 64 == 0, K >= 256): one and two row blocks,
     # every epilogue, bf16 / fp32 outputs and residuals, the in-place residual
-    (1, 512, 256, "bias", 0, 0), (33, 96, 320, "res", 0, 0), (40, 2048, 2048, "none", 1, 0), (7, 64, 2048, "gelu", 0, 0),
-    (64, 1024, 512, "res", 1, 0), (32, 2048, 2048, "res_silu", 0, 1), (17, 160, 1024, "silu", 1, 0),
-    # the weight-stationary kernel (gemm_ws16.hip: >= 2048 rows, K in {256, 512, 1024}, N % 128 == 0, bf16 out): every
-    # epilogue, both panel widths (N % 256 != 0 forces 128-column panels), the K-split variant, ragged row counts, row
-    # counts that leave some workgroups of an XCD without a tile
-    (6272, 512, 1024, "bias", 0, 0), (9600, 1024, 1024, "res", 0, 0), (4000, 3072, 1024, "gelu", 0, 0),
-    (6250, 512, 512, "res", 0, 0), (2049, 256, 256, "gelu", 0, 0), (3001, 384, 512, "res_silu", 0, 0),
-    (2100, 1536, 512, "silu", 0, 0), (12544, 512, 512, "none", 0, 0), (2464, 1024, 256, "res", 0, 0),
-    (6272, 1024, 512, "gelu", 0, 0), (2177, 640, 1024, "res", 0, 0),
+    (1, 512, 256, "bias", 0, 0, "FEWROW16"), (33, 96, 320, "res", 0, 0, "FEWROW16"), (40, 2048, 2048, "none", 1, 0, "FEWROW16"),
+    (7, 64, 2048, "gelu", 0, 0, "FEWROW16"), (64, 1024, 512, "res", 1, 0, "FEWROW16"), (32, 2048, 2048, "res_silu", 0, 1, "FEWROW16"),
+    (17, 160, 1024, "silu", 1, 0, "FEWROW16"),
+    # the weight-stationary kernels (>= 2048 rows, N % 128 == 0, bf16 out): gemm_ws16.hip at K = 256 / 1024 (every epilogue,
+    # both panel widths, the K-split variant), gemm_wsp16.hip at K = 512; ragged row counts, row counts that leave some
+    # workgroups of an XCD without a tile
+    (6272, 512, 1024, "bias", 0, 0, "WS16"), (9600, 1024, 1024, "res", 0, 0, "WS16"), (4000, 3072, 1024, "gelu", 0, 0, "WS16"),
+    (6250, 512, 512, "res", 0, 0, "WSP16"), (2049, 256, 256, "gelu", 0, 0, "WS16"), (3001, 384, 512, "res_silu", 0, 0, "WSP16"),
+    (2100, 1536, 512, "silu", 0, 0, "WSP16"), (12544, 512, 512, "none", 0, 0, "WSP16"), (2464, 1024, 256, "res", 0, 0, "WS16"),
+    (6272, 1024, 512, "gelu", 0, 0, "WSP16"), (2177, 640, 1024, "res", 0, 0, "WS16"),
     # K = 1024 with a residual: the residual tile lands in the staging buffer itself (no LDS left for its own)
-    (6250, 512, 1024, "res_silu", 0, 0), (2050, 128, 1024, "res", 0, 0), (12544, 1024, 1024, "res", 0, 0)])
+    (6250, 512, 1024, "res_silu", 0, 0, "WS16"), (2050, 128, 1024, "res", 0, 0, "WS16"), (12544, 1024, 1024, "res", 0, 0, "WS16")]
+GEMM16_PATH = {case[:6]: case[6] for case in GEMM16_CASES}
+
+
+@pytest.mark.parametrize("I,J,R,epi,c_f32,res_f32", [case[:6] for case in GEMM16_CASES])
 def test_gemm_bf16_all_epilogues_and_ragged_shapes(I, J, R, epi, c_f32, res_f32):
     g = torch.Generator().manual_seed(I * 7 + J * 3 + R)
     X, Y = bf(torch.randn(I, R, generator=g)), bf(torch.randn(J, R, generator=g) / R ** 0.5)
@@ -80,12 +87,19 @@ def test_gemm_bf16_all_epilogues_and_ragged_shapes(I, J, R, epi, c_f32, res_f32)
     d.bias = bd.data_ptr() if epi != "none" else None
     if "res" in epi:
         d.res, d.ldr, d.res_f32 = rd.data_ptr(), J, res_f32
-    _lib.check(_lib.lib().hig_gemm_bf16(C.byref(d), _lib.stream_ptr()))
+    path = GEMM16_PATH[(I, J, R, epi, c_f32, res_f32)]
+    served = getattr(_lib, "GEMM_PATH_" + path)
+
+    def launch():   # ... on the kernel this case is for (hig_gemm_path_launches)
+        before = _lib.lib().hig_gemm_path_launches(served)
+        _lib.check(_lib.lib().hig_gemm_bf16(C.byref(d), _lib.stream_ptr()))
+        assert _lib.lib().hig_gemm_path_launches(served) - before == 1, "not served by the %s path" % path
+    launch()
     if "res" in epi and not c_f32 and not res_f32:
         # the residual stream is updated IN PLACE by the stylization-out GEMMs (C aliases res)
         inplace = rd.clone()
         d.C, d.res = inplace.data_ptr(), inplace.data_ptr()
-        _lib.check(_lib.lib().hig_gemm_bf16(C.byref(d), _lib.stream_ptr()))
+        launch()
         assert torch.equal(inplace, out)
         d.C, d.res = out.data_ptr(), rd.data_ptr()
     ref = X.double() @ Y.double().t()
@@ -127,7 +141,9 @@ def test_gemm_ws16_every_variant(I, J, R, epi, nwj, monkeypatch):
         "d.epi = {'none': _lib.EPI_NONE, 'bias': _lib.EPI_BIAS, 'gelu': _lib.EPI_BIAS_GELU, 'res': _lib.EPI_BIAS_RES, 'silu': _lib.EPI_BIAS_SILU}[epi]\n"
         "d.bias = bd.data_ptr() if epi != 'none' else None\n"
         "if epi == 'res': d.res, d.ldr, d.res_f32 = rd.data_ptr(), J, 0\n"
+        "n0 = _lib.lib().hig_gemm_path_launches(_lib.GEMM_PATH_WS16)\n"
         "for _ in range(3): _lib.check(_lib.lib().hig_gemm_bf16(C.byref(d), _lib.stream_ptr()))\n"
+        "assert _lib.lib().hig_gemm_path_launches(_lib.GEMM_PATH_WS16) - n0 == 3, 'not served by gemm_ws16'\n"
         "ref = X.double() @ Y.double().t()\n"
         "if epi != 'none': ref = ref + b.double()\n"
         "if epi == 'res': ref = ref + r.double()\n"
