@@ -608,14 +608,18 @@ static int denoiser_fwd_impl(const hig_dims* dims, const void* const* params, co
     HIG_CHECK_LAUNCH();
     len_partner = lp;
   }
-  // inference + linear attention: `apply` and the stylization front that follows it can run as ONE kernel (the (M, d)
-  // attention output never reaches HBM); training keeps the pair -- the backward reads y and the LayerNorm statistics.
-  // Not used (a switch until round 5): measured 34.0 against 36.0 us per attention at B = 64 (head dim 64), equal at B = 32,
-  // 83.8 against 71.1 us at head dim 128, forward 6.24 against 6.26 ms -- the fused kernel's fp32 MFMAs and its
-  // LayerNorm / SiLU arithmetic share the SIMD lanes and a workgroup's chain (load, 2 heads, statistics, epilogue,
-  // store) is 26K cycles long with two workgroups per CU to hide it (profiles/r02_notes.md section 9)
-  constexpr int fuse_env = 0;   // (a former tuning knob, fixed at the value that won its A/B)
-  const bool fuse_apply = fuse_env && !training && !D.full && (D.H == 4 || D.H == 8) && (D.hd == 64 || D.hd == 128);
+  // inference + linear attention, head dim 64 with 4 or 8 heads: `apply` and the stylization front that follows it run as ONE
+  // kernel (hig_linattn_apply_sty -> apply_sty_wave64_kernel, linattn.hip): the (M, d) attention output y never reaches HBM, its
+  // workspace slots (y1, y2) and the statistics slots (st2, st4) are not written.  Self and cross attention of every layer.
+  // Everything else keeps the pair apply + ln_mod_silu: training (the backward reads y and the LayerNorm statistics), full
+  // attention, and head dim 128 (only the older fused kernel exists there, and it lost: 83.8 against 71.1 us per attention).
+  // The entry wants 16-byte aligned rows and parameter vectors: d and the row stride of the scale / shift table are multiples
+  // of 4 floats here (d = 64 H); the workspace slots and the parameter blocks sit at 16-byte aligned offsets (the entry checks
+  // and fails loudly, it never falls back).
+  // Measured per attention, fused against the pair (profiles/r07_notes.md): 28.2-28.7 against 31.2-31.5 us at B = 64, T = 196,
+  // 15.8-16.0 against 20.6-21.4 at B = 32 (the sampling loop), 17.0-17.8 against 21.8-22.8 at T = 91 (the two-person shape; 9.9-10.6
+  // against 12.8-13.2 at B = 32): no row threshold, unlike hig_linattn_apply's.
+  const bool fuse_apply = !training && !D.full && D.hd == 64 && (D.H == 4 || D.H == 8) && ss_ld % 4 == 0;
   // One decoder layer for the samples [b0, b0 + nb) on stream `s` (every kernel of a layer is row- or sample-local, so a
   // batch range is a pointer offset).  `hin` / the returned pointer are the FULL-batch residual stream of the layer.
   // LayerNorm fold (fp32 storage): inference only, d a multiple of 128, operands derived by the caller per parameter version

@@ -1897,21 +1897,226 @@ int launch_apply_sty(const TQ* q, int64_t ldq, const float* A, const float* gamm
   const size_t lds_main = 4 * wbuf * sizeof(float);
   const size_t lds_out = (size_t)32 * (d + 16 / sizeof(TO)) * sizeof(TO);
   const size_t lds = lds_main > lds_out ? lds_main : lds_out;
+  // (fp32 storage at head dim 64 is apply_sty_wave64_kernel's, below: this template is not instantiated for it)
+  constexpr bool HAS64 = !std::is_same<TQ, float>::value;
   static const int big_lds_rc = [] {   // more than the default dynamic-LDS cap
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&apply_sty_kernel<64, TQ, TO>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    hipError_t e1 = hipSuccess;
+    if constexpr (HAS64)
+      e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&apply_sty_kernel<64, TQ, TO>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
     hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&apply_sty_kernel<128, TQ, TO>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
     return (e1 == hipSuccess && e2 == hipSuccess) ? 0 : 1;
   }();
   if (big_lds_rc != 0 || lds > 156 * 1024)
     return hig_set_error(HIG_EHIP, "hig_linattn_apply_sty: cannot reserve %zu bytes of LDS", lds);
-  if (hd == 64)
-    hipLaunchKernelGGL((apply_sty_kernel<64, TQ, TO>), dim3(B * nblk), dim3(256), lds, st, q, ldq, A, gamma, beta, ss, ss_ld,
-                       shift_off, o, ldo, rows, H, nblk);
-  else
+  if (hd == 64) {
+    if constexpr (HAS64)
+      hipLaunchKernelGGL((apply_sty_kernel<64, TQ, TO>), dim3(B * nblk), dim3(256), lds, st, q, ldq, A, gamma, beta, ss, ss_ld,
+                         shift_off, o, ldo, rows, H, nblk);
+    else
+      return hig_set_error(HIG_EUNSUPPORTED, "hig_linattn_apply_sty: head dim 64 has its own fp32 kernel");
+  } else
     hipLaunchKernelGGL((apply_sty_kernel<128, TQ, TO>), dim3(B * nblk), dim3(256), lds, st, q, ldq, A, gamma, beta, ss, ss_ld,
                        shift_off, o, ldo, rows, H, nblk);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// apply + stylization front, exact fp32, head dim 64, H = 4 or 8, on apply_wave64_kernel's per-wave structure (round 7).
+// A workgroup of H waves owns ONE sample and a strip of 16-row tiles (tile = blockIdx.y, + gridDim.y, ...); wave h keeps A[b,h] in
+// its 64 operand registers for the workgroup's life and produces the 16 x 64 block of head h exactly as
+// apply_wave64_kernel::tile_out does (same loads, same softmax, same MFMA operand order: y is bit-identical to the unfused
+// kernel's).  y never leaves the CU:
+//   * LayerNorm statistics in ONE exchange per tile: every wave reduces its block to (sum, sum of squares about the block's own
+//     mean) per row, lane group 0 writes the pair to LDS, one barrier, and every wave merges the H pairs of its rows in the same
+//     fixed order (the merge of gemm_wsp32.hip's panel statistics: M2 = sum_h M2_h + 64 sum_h (mean_h - mean)^2).  The slots
+//     alternate with the tile's parity, so the barrier of tile t + 1 is what separates the reads of tile t from the writes of
+//     tile t + 2.  The barrier waits for LDS only (lds_barrier): the stores of the tile before stay in flight across it.
+//   * gamma, beta, 1 + scale[b] and shift[b] are staged once per workgroup in LDS (8 KB at d = 512) and read per tile as
+//     broadcast float4 (a lane's 16 columns: 16 reads) -- not 64 live registers.  They are NOT recombined: given the row's mean and
+//     rstd the arithmetic per element is ln_mod_silu_kernel's, operation by operation (exact division in the SiLU).
+//   * A[b,h] goes from global memory straight into the operand registers: with output column l = 4 i + blk on operand row i of
+//     column block blk a lane's operands of a k-step are ONE float4 of a row of A (see below) -- no LDS staging, no transpose, and
+//     the launch's start-up is one round of 16 loads per lane.  A wave's 4 KB of LDS hold its 16 x 64 block (y while the statistics
+//     are exchanged, then the output rows): a workgroup of 8 waves holds 42 KB and two of them share a CU (16 waves, 4 per SIMD:
+//     one wave's MFMAs run beside the others' loads, exponentials and divisions).
+// Rows past the end of the sample are clamped on load (a copy of the last row: finite statistics) and dropped on store by the
+// buffer descriptor's range check.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int H>
+__global__ __launch_bounds__(64 * H, 4) void apply_sty_wave64_kernel(const float* __restrict__ Q, int64_t ldq, const float* __restrict__ A,
+                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                    const float* __restrict__ ss, int64_t ss_ld, int shift_off,
+                                                                    float* __restrict__ Out, int64_t ldo, int rows) {
+  constexpr int HD = 64, D = H * HD;
+  __shared__ __attribute__((aligned(16))) float sW[H * 16 * HD];   // per wave 4 KB: its 16 x 64 block -- y during the exchange, then the output rows
+  __shared__ __attribute__((aligned(16))) float sP[4 * D];         // gamma | beta | 1 + scale[b] | shift[b]
+  __shared__ float2 sR[2][H][16];                                  // [tile parity][head][row]: (sum, centred sum of squares) of the head's 64 columns
+  const int tid = threadIdx.x, lane = tid & 63, h = tid >> 6;
+  const int b = blockIdx.x;
+  const int r = lane & 15, kq = lane >> 4;
+  const int ntile = (rows + 15) >> 4, step = gridDim.y;
+  const float* qb = Q + (int64_t)b * rows * ldq + h * HD + 16 * kq;
+  // ONE set of query registers (apply_wave64_kernel holds two: with aop, the exponentials and the accumulators that is more than
+  // the 128 registers of four waves per SIMD)
+  la_f32x4 qt[4];
+  auto fetch = [&](int tile, la_f32x4 (&v)[4]) {                 // (opaque loads and counted waits: see apply_wave64_kernel)
+    const int row = min(min(tile, ntile - 1) * 16 + r, rows - 1);
+    const float* p = qb + (int64_t)row * ldq;
+    asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:16\n\t"
+                 "global_load_dwordx4 %2, %4, off offset:32\n\tglobal_load_dwordx4 %3, %4, off offset:48"
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]) : "v"(p) : "memory");
+  };
+  int tile = blockIdx.y;                                         // (< ntile: the grid has at most ntile strips)
+  fetch(tile, qt);
+  // A[b,h] straight from global memory into operand order, no transpose and no LDS: the MFMA's A-operand row i of column block
+  // blk stands for output column l = 4 i + blk, so lane (r, kq) needs A[16 kq + s][4 r .. 4 r + 3] for k-step s -- ONE float4, the
+  // 16 lanes of a group reading a whole 256-byte row of A -- and ends up (accumulator row 4 q + e of block blk) with the 16
+  // consecutive columns 16 q + 4 e + blk of its tile row.  Which operand row carries a column does not change how the matrix pipe
+  // sums that column: y is still bit-identical to apply_wave64_kernel's (which stages A through LDS for another assignment).
+  float aop[16][4];                                              // [k-step s][blk]: A[16 kq + s][4 r + blk]
+  {
+    const float4* Ab = reinterpret_cast<const float4*>(A + (((int64_t)b * H + h) * HD + 16 * kq) * HD) + r;
+#pragma unroll
+    for (int s2 = 0; s2 < 16; ++s2) {
+      const float4 a4 = Ab[s2 * (HD / 4)];
+      aop[s2][0] = a4.x; aop[s2][1] = a4.y; aop[s2][2] = a4.z; aop[s2][3] = a4.w;
+    }
+    // one float4 per thread: the four parameter vectors of the d columns
+    const int arr = tid / (D / 4), idx = tid % (D / 4);          // (D / 4 = 16 H is a multiple of 64: `arr` is the same for a whole wave)
+    const float* ssrow = ss + (int64_t)b * ss_ld;
+    const float* src = arr == 0 ? gamma : arr == 1 ? beta : arr == 2 ? ssrow : ssrow + shift_off;
+    float4 pv = *reinterpret_cast<const float4*>(src + 4 * idx);
+    if (arr == 2) pv = make_float4(1.0f + pv.x, 1.0f + pv.y, 1.0f + pv.z, 1.0f + pv.w);
+    *reinterpret_cast<float4*>(sP + arr * D + 4 * idx) = pv;
+  }
+  float* const so = sW + h * (16 * HD);
+  __syncthreads();                                               // sP is complete (the loads above have landed, and the first tile's rows in front of them)
+  [[maybe_unused]] __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(Out + (int64_t)b * rows * ldo, 0, (int)(((int64_t)(rows - 1) * ldo + D) * 4), 0x00020000);
+  int par = 0;
+  auto tile_out = [&](int tile, auto younger) {
+    la_f32x4 (&cur)[4] = qt;
+    constexpr int YOUNGER = decltype(younger)::value;            // vector-memory operations issued behind this tile's loads
+    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]) : "n"(YOUNGER) : "memory");
+    // ---- y block = softmax_c(q) . A[b,h]: apply_wave64_kernel::tile_out, operation by operation ----
+    float m = fmaxf(fmaxf(fmaxf(cur[0].x, cur[0].y), fmaxf(cur[0].z, cur[0].w)), fmaxf(fmaxf(cur[1].x, cur[1].y), fmaxf(cur[1].z, cur[1].w)));
+    m = fmaxf(m, fmaxf(fmaxf(fmaxf(cur[2].x, cur[2].y), fmaxf(cur[2].z, cur[2].w)), fmaxf(fmaxf(cur[3].x, cur[3].y), fmaxf(cur[3].z, cur[3].w))));
+    m = fmaxf(m, __shfl_xor(m, 16, 64));
+    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    float p[16];
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      p[4 * i] = __expf(cur[i].x - m); p[4 * i + 1] = __expf(cur[i].y - m); p[4 * i + 2] = __expf(cur[i].z - m); p[4 * i + 3] = __expf(cur[i].w - m);
+      sum += (p[4 * i] + p[4 * i + 1]) + (p[4 * i + 2] + p[4 * i + 3]);
+    }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    const float inv = 1.0f / sum;
+    la_f32x4 acc[4];
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk) acc[blk] = la_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s2 = 0; s2 < 16; ++s2) {
+      const float ps = p[s2] * inv;
+#pragma unroll
+      for (int blk = 0; blk < 4; ++blk) acc[blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(aop[s2][blk], ps, acc[blk], 0, 0, 0);
+    }
+    // ---- row statistics: lane (r, kq) holds columns 16 kq + 4 e + blk of row r; block sum, then squares about the block's mean ----
+    float bs = 0.f;
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk) bs += (acc[blk][0] + acc[blk][1]) + (acc[blk][2] + acc[blk][3]);
+    bs += __shfl_xor(bs, 16, 64);
+    bs += __shfl_xor(bs, 32, 64);
+    const float bm = bs * (1.0f / HD);
+    float bq = 0.f;
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk) {
+      const float d0 = acc[blk][0] - bm, d1 = acc[blk][1] - bm, d2 = acc[blk][2] - bm, d3 = acc[blk][3] - bm;
+      bq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+    bq += __shfl_xor(bq, 16, 64);
+    bq += __shfl_xor(bq, 32, 64);
+    // the block waits in the wave's 4 KB of LDS, not in 16 registers, while the statistics are exchanged (with the operands, the
+    // parameters and the temporaries of the divisions the registers of four waves per SIMD do not reach)
+#pragma unroll
+    for (int e = 0; e < 4; ++e)                                  // (16-byte chunk q of row r at q ^ r: conflict-free both ways)
+      *reinterpret_cast<la_f32x4*>(so + r * HD + ((16 * kq + 4 * e) ^ (4 * r))) = la_f32x4{acc[0][e], acc[1][e], acc[2][e], acc[3][e]};
+    if (kq == 0) sR[par][h][r] = make_float2(bs, bq);
+    lds_barrier();
+    // (two passes over the H pairs, re-read from LDS: all H of them in registers at once are 16 more live values)
+    float tot = 0.f, within = 0.f;
+#pragma unroll
+    for (int hh = 0; hh < H; ++hh) {
+      const float2 ps = sR[par][hh][r];
+      tot += ps.x; within += ps.y;
+    }
+    const float mean = tot * (1.0f / D);
+    asm volatile("" ::: "memory");
+    float between = 0.f;
+#pragma unroll
+    for (int hh = 0; hh < H; ++hh) {
+      const float dm = fmaf(sR[par][hh][r].x, 1.0f / HD, -mean);
+      between = fmaf(dm, dm, between);
+    }
+    par ^= 1;
+    const float rstd = rsqrtf(fmaf((float)HD, between, within) * (1.0f / D) + 1e-5f);
+    // ---- modulate + SiLU (ln_mod_silu_kernel's expression), out through this wave's 4 KB of LDS as whole 256-byte row segments ----
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {                                // four columns at a time: four independent chains of exp and division
+      const int col = h * HD + 16 * kq + 4 * e;
+      const float4 g4 = *reinterpret_cast<const float4*>(sP + col), b4 = *reinterpret_cast<const float4*>(sP + D + col);
+      const float4 sc = *reinterpret_cast<const float4*>(sP + 2 * D + col), sh = *reinterpret_cast<const float4*>(sP + 3 * D + col);
+      float* const yp = so + r * HD + ((16 * kq + 4 * e) ^ (4 * r));
+      const float4 y4 = *reinterpret_cast<const float4*>(yp);
+      float4 o;
+      o.x = hig_silu(((y4.x - mean) * rstd * g4.x + b4.x) * sc.x + sh.x);
+      o.y = hig_silu(((y4.y - mean) * rstd * g4.y + b4.y) * sc.y + sh.y);
+      o.z = hig_silu(((y4.z - mean) * rstd * g4.z + b4.z) * sc.z + sh.z);
+      o.w = hig_silu(((y4.w - mean) * rstd * g4.w + b4.w) * sc.w + sh.w);
+      *reinterpret_cast<float4*>(yp) = o;
+      asm volatile("" ::: "memory");                             // (one group's 16 parameters at a time: hoisted together they are 64 registers)
+    }
+    // the next tile's rows are requested only HERE, behind the arithmetic: 16 registers in flight during the statistics or the SiLU
+    // are more than four waves per SIMD leave (spills), and a strip is one to four tiles long -- what covers the latency is the
+    // stores below and the three other waves of the SIMD
+    fetch(tile + step < ntile ? tile + step : tile, qt);         // (past the strip's end: this tile again -- unconditional, never used,
+                                                                 //  and a hit in the cache where the sample's last tile was 4 KB of HBM per wave)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (a wave reads back only what it wrote itself)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int rr = 4 * i + kq, cc = 4 * r;                     // lane (r, kq): row 4 i + kq of the tile, columns 4 r .. 4 r + 3 of the head
+      [[maybe_unused]] const float4 v = *reinterpret_cast<const float4*>(so + rr * HD + (cc ^ (4 * rr)));
+      [[maybe_unused]] const int row = tile * 16 + rr;           // (unconditional: rows past the end fail the descriptor's range check)
+#if defined(__HIP_DEVICE_COMPILE__)
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(la_i32x4, v), rsO, (row * (int)ldo + h * HD + cc) * 4, 0, 0);
+#endif
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
+  // every wave of the workgroup walks the same tiles (the barrier); behind a tile's loads only the four stores of the tile before
+  tile_out(tile, std::integral_constant<int, 0>{});
+  for (tile += step; tile < ntile; tile += step) tile_out(tile, std::integral_constant<int, 4>{});
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // (a clamped, unused prefetch may still be in flight)
+}
+
+// strips per sample: enough workgroups for the 16 wave slots of each of the 256 CUs (two 8-wave or four 4-wave workgroups), then
+// the fewest strips with that many tiles each (a strip's start-up -- 16 KB of A per wave from L2 -- is paid once per workgroup).
+// B = 64, T = 196, H = 8: 7 strips of 2 tiles; B = 32: 13 strips of one.  Measured against half and twice the slots
+// (profiles/r07_notes.md): within 0.5 us at B = 32, 1 - 2 us slower at B = 64 with twice.
+constexpr int APPLY_STY_WAVE_SLOTS = 256 * 16;
+template <int H>
+int launch_apply_sty_wave64(const float* q, int64_t ldq, const float* A, const float* gamma, const float* beta, const float* ss,
+                            int64_t ss_ld, int32_t shift_off, float* o, int64_t ldo, int32_t B, int32_t rows, hipStream_t st) {
+  const int ntile = (rows + 15) / 16;
+  int nstrip = APPLY_STY_WAVE_SLOTS / H / B;
+  nstrip = nstrip < 1 ? 1 : nstrip > ntile ? ntile : nstrip;
+  const int per = (ntile + nstrip - 1) / nstrip;
+  nstrip = (ntile + per - 1) / per;
+  hipLaunchKernelGGL((apply_sty_wave64_kernel<H>), dim3(B, nstrip), dim3(64 * H), 0, st, q, ldq, A, gamma, beta, ss, ss_ld, shift_off, o,
+                     ldo, rows);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -2106,7 +2311,8 @@ extern "C" int hig_linattn_apply_sty_bf16(const void* Q, int64_t ldq, const floa
                                           static_cast<__bf16*>(Out), ldo, B, rows, H, hd, hig_stream(stream));
 }
 
-// fp32 storage form of the same kernel (inference forward of hig_denoiser_fwd): Q and Out fp32.
+// fp32 storage (the inference forward of hig_denoiser_fwd): Q and Out fp32.  Head dim 64 runs apply_sty_wave64_kernel, head dim
+// 128 the apply_sty_kernel template above.
 extern "C" int hig_linattn_apply_sty(const float* Q, int64_t ldq, const float* A, const float* gamma, const float* beta,
                                      const float* ss, int64_t ss_ld, int32_t ss_shift_off, float* Out, int64_t ldo,
                                      int32_t B, int32_t rows, int32_t H, int32_t hd, hig_stream_t stream) {
@@ -2118,6 +2324,11 @@ extern "C" int hig_linattn_apply_sty(const float* Q, int64_t ldq, const float* A
                    (reinterpret_cast<uintptr_t>(gamma) & 15) | (reinterpret_cast<uintptr_t>(beta) & 15) |
                    (reinterpret_cast<uintptr_t>(ss) & 15)) == 0,
               "hig_linattn_apply_sty: alignment");
+  if (hd == 64) {   // the wave-autonomous kernel (32-bit byte offsets into a sample's rows of Out)
+    HIG_REQUIRE(((int64_t)rows + 16) * ldo * 4 < INT32_MAX, "hig_linattn_apply_sty: a sample's output rows exceed 2 GiB");
+    return H == 8 ? launch_apply_sty_wave64<8>(Q, ldq, A, gamma, beta, ss, ss_ld, ss_shift_off, Out, ldo, B, rows, hig_stream(stream))
+                  : launch_apply_sty_wave64<4>(Q, ldq, A, gamma, beta, ss, ss_ld, ss_shift_off, Out, ldo, B, rows, hig_stream(stream));
+  }
   return launch_apply_sty<float, float>(Q, ldq, A, gamma, beta, ss, ss_ld, ss_shift_off, Out, ldo, B, rows, H, hd,
                                         hig_stream(stream));
 }
