@@ -35,6 +35,11 @@ STORE_F32, STORE_BF16 = 0, 1
 # GEMM paths of hig_gemm_path_launches (one per kernel the GEMM entry points launch)
 (GEMM_PATH_TILED32, GEMM_PATH_WSP32, GEMM_PATH_TAIL32, GEMM_PATH_WGRAD_WSP32, GEMM_PATH_SPLIT32, GEMM_PATH_WSP16,
  GEMM_PATH_WS16, GEMM_PATH_FEWROW16, GEMM_PATH_TILED16, GEMM_PATH_SPLIT16, GEMM_PATH_WGRAD16, GEMM_NPATHS) = range(12)
+# attention paths of hig_attn_path_launches (one per kernel the linear- / full-attention entry points launch)
+(ATTN_PATH_CTX, ATTN_PATH_CTX_MFMA, ATTN_PATH_CTX_PART, ATTN_PATH_APPLY, ATTN_PATH_APPLY_MFMA, ATTN_PATH_APPLY_WAVE64,
+ ATTN_PATH_APPLY_STY, ATTN_PATH_APPLY_STY_WAVE64, ATTN_PATH_APPLY_BWD, ATTN_PATH_APPLY_BWD_MFMA, ATTN_PATH_CTX_BWD,
+ ATTN_PATH_CTX_BWD_MFMA, ATTN_PATH_FULL_FWD, ATTN_PATH_FULL_FWD_MFMA, ATTN_PATH_FULL_BWD, ATTN_PATH_FULL_BWD_MFMA,
+ ATTN_NPATHS) = range(17)
 TAB_ROWS = 7
 NORM_BLOCKS = 1024
 COLSUM_CHUNKS = 512
@@ -51,7 +56,7 @@ SYMBOLS = (
     "hig_layernorm", "hig_gather_rows", "hig_scatter_add_rows", "hig_gather_frames", "hig_recover_joints", "hig_transpose_batch", "hig_linattn_ctx_scratch_floats", "hig_pair_mse",
     "hig_fullattn_fwd_kpad", "hig_eval_encoder_workspace_bytes", "hig_eval_encoder_fwd",
     "hig_clip_adam_lrdev", "hig_shutdown", "hig_gemm_split", "hig_gemm_split_scratch_floats",
-    "hig_gemm_bf16", "hig_gemm_bf16_debug_stamps", "hig_gemm_ws16_debug_stamps", "hig_gemm_wsp16_debug_stamps", "hig_gemm_wsp32_debug_stamps", "hig_gemm_wsp32_launches", "hig_gemm_path_launches", "hig_wgrad16_debug_stamps", "hig_linattn16_debug_stamps", "hig_cast_bf16", "hig_ln_bf16", "hig_linattn_ctx_bf16", "hig_linattn_apply_bf16",
+    "hig_gemm_bf16", "hig_gemm_bf16_debug_stamps", "hig_gemm_ws16_debug_stamps", "hig_gemm_wsp16_debug_stamps", "hig_gemm_wsp32_debug_stamps", "hig_gemm_wsp32_launches", "hig_gemm_path_launches", "hig_attn_path_launches", "hig_attn_last_split", "hig_wgrad16_debug_stamps", "hig_linattn16_debug_stamps", "hig_cast_bf16", "hig_ln_bf16", "hig_linattn_ctx_bf16", "hig_linattn_apply_bf16",
     "hig_text_context_bf16", "hig_denoiser_fwd_bf16", "hig_linattn_apply_sty_bf16", "hig_linattn_apply_sty_mm16", "hig_linattn_apply_sty_mm16_y", "hig_linattn_ctx_mm16", "hig_linattn_apply_sty", "hig_joint_embed_bf16", "hig_joint_embed_bf16_w", "hig_attn_out16", "hig_rows_out16", "hig_weight_frag16", "hig_joint_embed_bf16_scratch_bytes", "hig_fullattn_fwd_bf16", "hig_denoiser_bwd_hooked", "hig_denoiser_bwd_bf16_hooked",
     # round 4: bf16-storage training step
     "hig_text_context_bf16_train", "hig_denoiser_fwd_bf16_train", "hig_denoiser_bwd_bf16", "hig_ln_bwd_bf16",
@@ -187,6 +192,10 @@ def lib():
         L.hig_gemm_wsp32_launches.restype = i64
         L.hig_gemm_path_launches.argtypes = [i32]
         L.hig_gemm_path_launches.restype = i64
+        L.hig_attn_path_launches.argtypes = [i32]
+        L.hig_attn_path_launches.restype = i64
+        L.hig_attn_last_split.argtypes = []
+        L.hig_attn_last_split.restype = i32
         L.hig_wgrad16_debug_stamps.argtypes = [vp]
         L.hig_linattn16_debug_stamps.argtypes = [vp]
         L.hig_cast_bf16.argtypes = [vp, vp, i64, vp]

@@ -18,6 +18,8 @@
 //    chunk, the 4 lanes of a row combine by shuffles, probabilities cross lanes through a 64x64 LDS tile.
 #include "hig_common.h"
 
+void hig_attn_path_count(int path, int split);   // linattn.hip: one launch of the kernel of HIG_ATTN_PATH_* `path`
+
 namespace {
 
 constexpr int CH = 64;
@@ -686,12 +688,14 @@ extern "C" int hig_fullattn_fwd_kpad(const float* Q, int64_t ldq, const float* K
       else
         hipLaunchKernelGGL((full_fwd_mfma_kernel<64, NWV, float>), grid, dim3(64 * NWV), 0, hig_stream(stream), Q, ldq, K, V, ldk, Tq,
                            Tk, H, qlen, kpad, Y, ldy, lse);
+      hig_attn_path_count(HIG_ATTN_PATH_FULL_FWD_MFMA, (int)grid.y);
     });
     HIG_CHECK_LAUNCH();
     return HIG_OK;
   }
   FHD_SWITCH(hd, hipLaunchKernelGGL((full_fwd_kernel<HDV>), dim3(B * H, (Tq + CH - 1) / CH), dim3(256), 0,
                                     hig_stream(stream), Q, ldq, K, V, ldk, Tq, Tk, H, qlen, kpad, Y, ldy, lse));
+  hig_attn_path_count(HIG_ATTN_PATH_FULL_FWD, (Tq + CH - 1) / CH);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -716,6 +720,7 @@ extern "C" int hig_fullattn_fwd_bf16(const void* Q, int64_t ldq, const void* K, 
     else
       hipLaunchKernelGGL((full_fwd_mfma_kernel<64, NWV, __bf16>), grid, dim3(64 * NWV), 0, hig_stream(stream), q, ldq, k, v, ldk,
                          Tq, Tk, H, qlen, (const uint8_t*)nullptr, y, ldy, (float*)nullptr);
+    hig_attn_path_count(HIG_ATTN_PATH_FULL_FWD_MFMA, (int)grid.y);
   });
   HIG_CHECK_LAUNCH();
   return HIG_OK;
@@ -744,6 +749,7 @@ extern "C" int hig_fullattn_bwd(const float* dY, int64_t lddy, const float* Y, i
                          Tk, H, qlen, lse, delta, dQ, lddq);
       hipLaunchKernelGGL((full_bwd_kv_mfma_kernel<128, NWV>), gk, dim3(64 * NWV), 0, st, dY, lddy, Q, ldq, K, V, ldk, Tq, Tk, H,
                          qlen, lse, delta, dK, dV, lddk);
+      hig_attn_path_count(HIG_ATTN_PATH_FULL_BWD_MFMA, (int)gq.y);
     } else {
       FNW_SWITCH(true, hd, {
         const dim3 gq(B * H, (Tq + 32 * NWV - 1) / (32 * NWV)), gk(B * H, (Tk + 32 * NWV - 1) / (32 * NWV));
@@ -751,6 +757,7 @@ extern "C" int hig_fullattn_bwd(const float* dY, int64_t lddy, const float* Y, i
                            Tk, H, qlen, lse, delta, dQ, lddq);
         hipLaunchKernelGGL((full_bwd_kv_mfma_kernel<64, NWV>), gk, dim3(64 * NWV), 0, st, dY, lddy, Q, ldq, K, V, ldk, Tq, Tk, H,
                            qlen, lse, delta, dK, dV, lddk);
+        hig_attn_path_count(HIG_ATTN_PATH_FULL_BWD_MFMA, (int)gq.y);
       });
     }
     HIG_CHECK_LAUNCH();
@@ -763,6 +770,7 @@ extern "C" int hig_fullattn_bwd(const float* dY, int64_t lddy, const float* Y, i
   FHD_SWITCH(hd, hipLaunchKernelGGL((full_bwd_kv_kernel<HDV>), dim3(B * H, (Tk + CH - 1) / CH), dim3(256), 0,
                                     hig_stream(stream), dY, lddy, Q, ldq, K, V, ldk, Tq, Tk, H, qlen, lse, delta,
                                     dK, dV, lddk));
+  hig_attn_path_count(HIG_ATTN_PATH_FULL_BWD, (Tq + CH - 1) / CH);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

@@ -8,6 +8,8 @@
 int hig_gemm_launch(const hig_gemm_desc& g, int splits, float* slabs, hipStream_t st);
 // one launch of the GEMM kernel of `path` (HIG_GEMM_PATH_*): called at the launch site (gemm.hip, hig_gemm_path_launches)
 void hig_gemm_path_count(int path);
+// one launch of the attention kernel of `path` (HIG_ATTN_PATH_*) with gridDim.y = split (linattn.hip, hig_attn_path_launches)
+void hig_attn_path_count(int path, int split);
 // I <= 64 rows with EPI_BIAS / EPI_BIAS_RES: split-R over `scratch` so the weight streams through ~1024 workgroups
 int hig_gemm_few_rows(const hig_gemm_desc& g, float* scratch, int64_t scratch_floats, hipStream_t st);
 

@@ -15,6 +15,9 @@
 #include "hig_common.h"
 
 int hig_chip_cus();   // hig_host.h: compute units of the current device
+// one launch of the attention kernel of `path` (HIG_ATTN_PATH_*) with gridDim.y = split: called at the launch site (below,
+// hig_attn_path_launches / hig_attn_last_split)
+void hig_attn_path_count(int path, int split);
 
 namespace {
 
@@ -1608,6 +1611,7 @@ int linattn_ctx_t(const TIO* K, const TIO* V, int64_t ld, int32_t B, int32_t row
                          scratch);
       hipLaunchKernelGGL(ctx_combine_kernel<128>, dim3(B * H), dim3(256), 0, st, scratch, nchunk, A, kstat, At16);
     }
+    hig_attn_path_count(HIG_ATTN_PATH_CTX_PART, nchunk);
     HIG_CHECK_LAUNCH();
     return HIG_OK;
   }
@@ -1615,6 +1619,7 @@ int linattn_ctx_t(const TIO* K, const TIO* V, int64_t ld, int32_t B, int32_t row
     hipLaunchKernelGGL((ctx_mfma_kernel<64, TIO>), dim3(B * H), dim3(256), 0, st, K, V, ld, rows, H, length, A, kstat, At16, CtxGroups{H, 0, 0});
   else
     hipLaunchKernelGGL((ctx_mfma_kernel<128, TIO>), dim3(B * H), dim3(256), 0, st, K, V, ld, rows, H, length, A, kstat, At16, CtxGroups{H, 0, 0});
+  hig_attn_path_count(HIG_ATTN_PATH_CTX_MFMA, 1);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -1634,6 +1639,7 @@ int linattn_apply_t(const TIO* Q, int64_t ldq, const float* A, TIO* Y, int64_t l
         (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
       hipLaunchKernelGGL(apply_wave64_kernel, dim3(B * H), dim3(256), 0, st, reinterpret_cast<const float*>(Q), ldq, A,
                          reinterpret_cast<float*>(Y), ldy, rows, H);
+      hig_attn_path_count(HIG_ATTN_PATH_APPLY_WAVE64, 1);
       HIG_CHECK_LAUNCH();
       return HIG_OK;
     }
@@ -1647,6 +1653,7 @@ int linattn_apply_t(const TIO* Q, int64_t ldq, const float* A, TIO* Y, int64_t l
     hipLaunchKernelGGL((apply_mfma_kernel<64, TIO>), dim3(B * H, gy), dim3(256), 0, st, Q, ldq, A, Y, ldy, rows, H);
   else
     hipLaunchKernelGGL((apply_mfma_kernel<128, TIO>), dim3(B * H, gy), dim3(256), 0, st, Q, ldq, A, Y, ldy, rows, H);
+  hig_attn_path_count(HIG_ATTN_PATH_APPLY_MFMA, gy);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -1660,6 +1667,7 @@ extern "C" int hig_linattn_ctx(const float* K, const float* V, int64_t ld, int32
   if (hd == 64 || hd == 128) return linattn_ctx_t<float>(K, V, ld, B, rows, H, hd, length, A, kstat, scratch, hig_stream(stream));
   HD_SWITCH(hd, hipLaunchKernelGGL((ctx_kernel<HDV>), dim3(B * H), dim3(256), 0, hig_stream(stream), K, V,
                                    ld, rows, H, length, A, kstat));
+  hig_attn_path_count(HIG_ATTN_PATH_CTX, 1);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -1677,6 +1685,7 @@ int hig_linattn_ctx_groups(const float* K, const float* V, int64_t ld, int32_t B
   else
     hipLaunchKernelGGL((ctx_mfma_kernel<128, float>), dim3(B * H * G), dim3(256), 0, st, K, V, ld, rows, H * G, nullptr, A, kstat,
                        nullptr, CtxGroups{H, a_gs, k_gs});
+  hig_attn_path_count(HIG_ATTN_PATH_CTX_MFMA, 1);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -1691,6 +1700,7 @@ extern "C" int hig_linattn_apply(const float* Q, int64_t ldq, const float* A, fl
   if (hd == 64 || hd == 128) return linattn_apply_t<float>(Q, ldq, A, Y, ldy, B, rows, H, hd, hig_stream(stream));
   HD_SWITCH(hd, hipLaunchKernelGGL((apply_kernel<HDV>), dim3(B * H, (rows + CH - 1) / CH), dim3(256), 0,
                                    hig_stream(stream), Q, ldq, A, Y, ldy, rows, H));
+  hig_attn_path_count(HIG_ATTN_PATH_APPLY, (rows + CH - 1) / CH);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -1919,6 +1929,7 @@ int launch_apply_sty(const TQ* q, int64_t ldq, const float* A, const float* gamm
   } else
     hipLaunchKernelGGL((apply_sty_kernel<128, TQ, TO>), dim3(B * nblk), dim3(256), lds, st, q, ldq, A, gamma, beta, ss, ss_ld,
                        shift_off, o, ldo, rows, H, nblk);
+  hig_attn_path_count(HIG_ATTN_PATH_APPLY_STY, 1);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -2117,6 +2128,7 @@ int launch_apply_sty_wave64(const float* q, int64_t ldq, const float* A, const f
   nstrip = (ntile + per - 1) / per;
   hipLaunchKernelGGL((apply_sty_wave64_kernel<H>), dim3(B, nstrip), dim3(64 * H), 0, st, q, ldq, A, gamma, beta, ss, ss_ld, shift_off, o,
                      ldo, rows);
+  hig_attn_path_count(HIG_ATTN_PATH_APPLY_STY_WAVE64, nstrip);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -2180,6 +2192,7 @@ extern "C" int hig_linattn_apply_bwd(const float* dY, int64_t lddy, const float*
     else
       hipLaunchKernelGGL(apply_bwd_mfma_kernel<128>, dim3(B * H, nparts), dim3(256), attn_bwd_lds_bytes<128>(),
                          hig_stream(stream), dY, lddy, Q, ldq, A, dQ, lddq, part, rows, H);
+    hig_attn_path_count(HIG_ATTN_PATH_APPLY_BWD_MFMA, nparts);
     if (nparts == 1) {
       HIG_CHECK_LAUNCH();
       return HIG_OK;
@@ -2187,6 +2200,7 @@ extern "C" int hig_linattn_apply_bwd(const float* dY, int64_t lddy, const float*
   } else {
     HD_SWITCH(hd, hipLaunchKernelGGL((apply_bwd_kernel<HDV>), dim3(B * H, nchunk), dim3(256), 0, hig_stream(stream),
                                      dY, lddy, Q, ldq, A, dQ, lddq, scratch, rows, H));
+    hig_attn_path_count(HIG_ATTN_PATH_APPLY_BWD, nchunk);
   }
   HIG_CHECK_LAUNCH();
   const int64_t n = (int64_t)hd * hd, groups = (int64_t)B * H;
@@ -2218,6 +2232,7 @@ extern "C" int hig_linattn_ctx_bwd(const float* dA, const float* A, const float*
     else
       hipLaunchKernelGGL(ctx_bwd_mfma_kernel<128>, dim3(B * H, gy), dim3(256), attn_bwd_lds_bytes<128>(),
                          hig_stream(stream), dA, A, K, V, ld, kstat, length, dK, dV, ldd, rows, H);
+    hig_attn_path_count(HIG_ATTN_PATH_CTX_BWD_MFMA, gy);
     HIG_CHECK_LAUNCH();
     return HIG_OK;
   }
@@ -2226,6 +2241,7 @@ extern "C" int hig_linattn_ctx_bwd(const float* dA, const float* A, const float*
   HIG_CHECK_LAUNCH();
   HD_SWITCH(hd, hipLaunchKernelGGL((ctx_bwd_finish_kernel<HDV>), dim3(B * H, nchunk), dim3(256), 0,
                                    hig_stream(stream), K, ld, kstat, length, dK, ldd, rows, H, scratch));
+  hig_attn_path_count(HIG_ATTN_PATH_CTX_BWD, nchunk);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -2258,6 +2274,7 @@ extern "C" int hig_linattn_apply_bwd_bf16(const void* dY, int64_t lddy, const vo
   else
     hipLaunchKernelGGL((apply_bwd_mfma_kernel<128, __bf16>), dim3(B * H, nparts), dim3(256), attn_bwd_lds_bytes<128>(), hig_stream(stream),
                        dy, lddy, q, ldq, A, dq, lddq, part, rows, H);
+  hig_attn_path_count(HIG_ATTN_PATH_APPLY_BWD_MFMA, nparts);
   HIG_CHECK_LAUNCH();
   if (nparts == 1) return HIG_OK;
   const int64_t n = (int64_t)hd * hd, groups = (int64_t)B * H;
@@ -2289,6 +2306,7 @@ extern "C" int hig_linattn_ctx_bwd_bf16(const float* dA, const float* A, const v
   else
     hipLaunchKernelGGL((ctx_bwd_mfma_kernel<128, __bf16>), dim3(B * H, gy), dim3(256), attn_bwd_lds_bytes<128>(), hig_stream(stream), dA, A, k,
                        v, ld, kstat, length, static_cast<__bf16*>(dK), static_cast<__bf16*>(dV), ldd, rows, H);
+  hig_attn_path_count(HIG_ATTN_PATH_CTX_BWD_MFMA, gy);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -2332,3 +2350,18 @@ extern "C" int hig_linattn_apply_sty(const float* Q, int64_t ldq, const float* A
   return launch_apply_sty<float, float>(Q, ldq, A, gamma, beta, ss, ss_ld, ss_shift_off, Out, ldo, B, rows, H, hd,
                                         hig_stream(stream));
 }
+
+// Launch counts per attention kernel (hig_attn_path_launches) and the gridDim.y of the latest counted launch
+// (hig_attn_last_split): host side, written at each launch site here and in fullattn.hip.
+static long long g_attn_launches[HIG_ATTN_NPATHS];
+static int g_attn_last_split = 1;
+void hig_attn_path_count(int path, int split) {
+  if (path < 0 || path >= HIG_ATTN_NPATHS) return;
+  __atomic_fetch_add(&g_attn_launches[path], 1, __ATOMIC_RELAXED);
+  __atomic_store_n(&g_attn_last_split, split, __ATOMIC_RELAXED);
+}
+extern "C" int64_t hig_attn_path_launches(int32_t path) {
+  if (path < 0 || path >= HIG_ATTN_NPATHS) return -1;
+  return __atomic_load_n(&g_attn_launches[path], __ATOMIC_RELAXED);
+}
+extern "C" int32_t hig_attn_last_split(void) { return __atomic_load_n(&g_attn_last_split, __ATOMIC_RELAXED); }

@@ -628,6 +628,32 @@ int64_t hig_gemm_wsp32_launches(void);
 #define HIG_GEMM_PATH_WGRAD16 10      /* hig_wgrad_bf16: wgrad16.hip */
 #define HIG_GEMM_NPATHS 11
 int64_t hig_gemm_path_launches(int32_t path);
+/* Attention paths: one per kernel the linear- and full-attention entry points below (csrc/linattn.hip, csrc/fullattn.hip) can
+ * launch; the fp32 and bf16-I/O instances of one kernel share a path.  hig_attn_path_launches(path) counts the launches of that
+ * kernel since the library was loaded (monotonic, host side, one relaxed atomic add at the launch site; the chunk_sum_kernel
+ * behind a split hig_linattn_apply_bwd is not counted); -1 for an unknown path.  hig_attn_last_split() is the gridDim.y of the
+ * most recent counted launch (1 where the grid has no second dimension): how many workgroups shared one (sample, head).  Both
+ * are test hooks: a test reads them around a call to prove which kernel served it and in which split regime.  The launches
+ * inside hig_denoiser_*, hig_text_* and hig_eval_encoder_fwd go through the same launch sites and are counted too. */
+#define HIG_ATTN_PATH_CTX 0               /* hig_linattn_ctx: ctx_kernel (head dim 8 / 16 / 32, VALU) */
+#define HIG_ATTN_PATH_CTX_MFMA 1          /* hig_linattn_ctx[_bf16]: ctx_mfma_kernel, one workgroup walks all chunks of a (sample, head) */
+#define HIG_ATTN_PATH_CTX_PART 2          /* hig_linattn_ctx[_bf16] with scratch: ctx_part_mfma_kernel + ctx_combine_kernel, counted once */
+#define HIG_ATTN_PATH_APPLY 3             /* hig_linattn_apply: apply_kernel (head dim 8 / 16 / 32, VALU) */
+#define HIG_ATTN_PATH_APPLY_MFMA 4        /* hig_linattn_apply[_bf16]: apply_mfma_kernel (split = workgroups walking one (sample, head)) */
+#define HIG_ATTN_PATH_APPLY_WAVE64 5      /* hig_linattn_apply: apply_wave64_kernel (fp32, head dim 64, >= 128 rows) */
+#define HIG_ATTN_PATH_APPLY_STY 6         /* hig_linattn_apply_sty[_bf16]: apply_sty_kernel */
+#define HIG_ATTN_PATH_APPLY_STY_WAVE64 7  /* hig_linattn_apply_sty: apply_sty_wave64_kernel (fp32, head dim 64; split = strips per sample) */
+#define HIG_ATTN_PATH_APPLY_BWD 8         /* hig_linattn_apply_bwd: apply_bwd_kernel (head dim 8 / 16 / 32), one workgroup per chunk */
+#define HIG_ATTN_PATH_APPLY_BWD_MFMA 9    /* hig_linattn_apply_bwd[_bf16]: apply_bwd_mfma_kernel (split = dA partials per (sample, head)) */
+#define HIG_ATTN_PATH_CTX_BWD 10          /* hig_linattn_ctx_bwd: ctx_bwd_kernel + ctx_bwd_finish_kernel, counted once */
+#define HIG_ATTN_PATH_CTX_BWD_MFMA 11     /* hig_linattn_ctx_bwd[_bf16]: ctx_bwd_mfma_kernel (split = workgroups walking one (sample, head)) */
+#define HIG_ATTN_PATH_FULL_FWD 12         /* hig_fullattn_fwd[_kpad]: full_fwd_kernel (head dim 8 / 16 / 32, VALU) */
+#define HIG_ATTN_PATH_FULL_FWD_MFMA 13    /* hig_fullattn_fwd[_kpad / _bf16]: full_fwd_mfma_kernel (split = query blocks) */
+#define HIG_ATTN_PATH_FULL_BWD 14         /* hig_fullattn_bwd: full_bwd_q_kernel + full_bwd_kv_kernel, counted once (split: the query side's) */
+#define HIG_ATTN_PATH_FULL_BWD_MFMA 15    /* hig_fullattn_bwd: full_bwd_q_mfma_kernel + full_bwd_kv_mfma_kernel, counted once (split: the query side's) */
+#define HIG_ATTN_NPATHS 16
+int64_t hig_attn_path_launches(int32_t path);
+int32_t hig_attn_last_split(void);
 int hig_wgrad16_debug_stamps(void* buf);      /* wgrad16.hip (see there): 8192 x 8 bytes */
 /* the same for hig_linattn_apply_sty_mm16: 8 stamps per workgroup (see linattn16.hip) */
 int hig_linattn16_debug_stamps(void* buf);
@@ -704,8 +730,9 @@ int hig_linattn_apply_sty_mm16(const void* Q, int64_t ldq, const void* At16, con
 int hig_linattn_apply_sty_mm16_y(const void* Q, int64_t ldq, const void* At16, const float* gamma, const float* beta,
                                  const float* ss, int64_t ss_ld, int32_t ss_shift_off, void* Out, int64_t ldo, void* Yout, int64_t ldy,
                                  int32_t B, int32_t rows, int32_t H, int32_t hd, hig_stream_t stream);
-/* The same fused kernel with fp32 storage (a standalone entry point: hig_denoiser_fwd runs hig_linattn_apply +
- * hig_ln_mod_silu, which measured equal).  Q, Out fp32, 16-byte aligned. */
+/* The same fused operator with fp32 storage: head dim 64 runs apply_sty_wave64_kernel -- what the inference forward of
+ * hig_denoiser_fwd launches for the self and cross attention of every layer (training, no_eff and head dim 128 keep
+ * hig_linattn_apply + hig_ln_mod_silu) -- head dim 128 the apply_sty_kernel template.  Q, Out fp32, 16-byte aligned. */
 int hig_linattn_apply_sty(const float* Q, int64_t ldq, const float* A, const float* gamma, const float* beta,
                           const float* ss, int64_t ss_ld, int32_t ss_shift_off, float* Out, int64_t ldo,
                           int32_t B, int32_t rows, int32_t H, int32_t hd, hig_stream_t stream);
@@ -734,7 +761,10 @@ int hig_scatter_add_rows(const float* src, int64_t ld, int32_t B, int32_t rows_p
  * head h lives at column h*hd + c.
  * ctx: k = softmax over the `len[b]` leading rows of each sample (masked rows contribute 0),
  *      A[b,h] = k^T v; kstat[b][col] = (column max, column sum of exp).
- * apply: y = softmax_hd(Q) . A[b,h]. */
+ * apply: y = softmax_hd(Q) . A[b,h].
+ * A sample with len[b] == 0 gets A = 0 and kstat = (0, 1) on every column, and dK = dV = 0 on every row from
+ * hig_linattn_ctx_bwd; rows at or beyond len[b] of any sample get dK = dV = 0 exactly, and whatever finite values K and V hold
+ * there never reach A, kstat or a gradient. */
 int hig_linattn_ctx(const float* K, const float* V, int64_t ld, int32_t B, int32_t rows,
                     int32_t H, int32_t hd, const int64_t* length, float* A, float* kstat,
                     float* scratch, hig_stream_t stream);
@@ -766,7 +796,7 @@ int hig_fullattn_fwd(const float* Q, int64_t ldq, const float* K, const float* V
                      float* Y, int64_t ldy, float* lse, hig_stream_t stream);
 /* Same forward with torch's `src_key_padding_mask` (nn.MultiheadAttention): kpad (B, Tk) bytes,
  * non-zero = that key takes no part in the softmax (NULL = none).  Used by the evaluator encoders
- * (interaction_transformer.py:733,827). */
+ * (interaction_transformer.py:733,827).  A sample whose keys are ALL padded is outside the contract (torch returns NaN there). */
 int hig_fullattn_fwd_kpad(const float* Q, int64_t ldq, const float* K, const float* V, int64_t ldk,
                           int32_t B, int32_t Tq, int32_t Tk, int32_t H, int32_t hd, const int64_t* qlen,
                           const uint8_t* kpad, float* Y, int64_t ldy, float* lse, hig_stream_t stream);
