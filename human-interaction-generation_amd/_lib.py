@@ -63,6 +63,7 @@ SYMBOLS = (
     "hig_linattn_apply_bwd_bf16", "hig_linattn_ctx_bwd_bf16", "hig_colsum_bf16", "hig_transpose_bf16_batch", "hig_transpose_bf16",
     "hig_gelu_bf16", "hig_cast_f32", "hig_cast_pad_bf16", "hig_gemm_bf16_split", "hig_gemm_bf16_split_scratch_floats", "hig_clip_adam_shadow",
     "hig_debug_marker", "hig_denoiser_fwd_text", "hig_wgrad_bf16", "hig_wgrad_bf16_scratch_floats", "hig_denoiser_fwd_x", "hig_denoiser_fwd_bf16_x",
+    "hig_gemm_bf16_plan", "hig_gemm_plan", "hig_gemm_bf16_lnfold_plan",
 )
 
 
@@ -192,6 +193,10 @@ def lib():
         L.hig_gemm_wsp32_launches.restype = i64
         L.hig_gemm_path_launches.argtypes = [i32]
         L.hig_gemm_path_launches.restype = i64
+        pi32 = C.POINTER(i32)
+        L.hig_gemm_bf16_plan.argtypes = [C.POINTER(Gemm16Desc), i32, pi32, pi32, pi32]
+        L.hig_gemm_plan.argtypes = [C.POINTER(GemmDesc), i32, i32, pi32, pi32, pi32]
+        L.hig_gemm_bf16_lnfold_plan.argtypes = [i64, i32, i32]
         L.hig_attn_path_launches.argtypes = [i32]
         L.hig_attn_path_launches.restype = i64
         L.hig_attn_last_split.argtypes = []

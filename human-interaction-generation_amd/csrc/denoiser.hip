@@ -2043,9 +2043,9 @@ extern "C" int hig_denoiser_fwd_bf16_train(const hig_dims* dims, const void* con
       G16 g1(hffn, d, PL16(params16, l, HIG_L_FFN_W1), d, lb + w.f1, D.ff, M, D.ff, d);
       g1.epi(HIG_EPI_BIAS_GELU, PL(params, l, HIG_L_FFN_B1));
       g1.g.aux = lb + w.z1; g1.g.ldaux = D.ff;
-      const int rc = hig_gemm_wsp16_try(g1.g, st);
-      if (rc < 0) return rc;
-      if (rc == 1) {
+      if (hig_gemm16_plan(g1.g, hig_gemm_switch_values(), hig_chip_cus()).path == HIG_GEMM_PATH_WSP16) {
+        HIG_TRY(hig_gemm16_launch(g1.g, st));
+      } else {
         HIG_TRY(hig_gemm16_launch(G16(hffn, d, PL16(params16, l, HIG_L_FFN_W1), d, lb + w.z1, D.ff, M, D.ff, d)
                                       .epi(HIG_EPI_BIAS, PL(params, l, HIG_L_FFN_B1)).g, st));
         HIG_TRY(hig_gelu_bf16(lb + w.z1, lb + w.f1, M * D.ff, stream));

@@ -915,17 +915,15 @@ struct TailScratch { unsigned* cnt; float* ws; int64_t ws_bytes; };
 thread_local TailScratch g_tail = {nullptr, nullptr, 0};
 
 template <int BI, int BJ, bool X_RS, bool Y_RS, int XF, bool XF_ON_Y, int EPI>
-int launch(const hig_gemm_desc& g, int splits, float* slabs, int64_t slab, hipStream_t st, const SplitEpilogue& se) {
+int launch(const hig_gemm_desc& g, int splits, float* slabs, int64_t slab, hipStream_t st, const SplitEpilogue& se, int tail_s) {
   KArgs a;
   a.g = g;
   a.tail_s = 1; a.nmain = 0; a.tail_rem = 0; a.tail_chunk = 0; a.tail_ws = nullptr; a.tail_cnt = nullptr;
   a.stamps = g_gemm_stamps;
   a.xsum = nullptr;
   a.xsum_stride = 0;
-  constexpr int epi_flags = 0;   // (a former tuning knob, fixed at the value that won its A/B)
-  a.epi_flags = epi_flags;
-  constexpr int store_policy = 0;   // (a former tuning knob, fixed at the value that won its A/B)
-  a.store_policy = (store_policy && splits == 1 && (((int64_t)g.I - 1) * g.ldc + g.J) * 4 < (1ll << 31) && g.res != g.C) ? store_policy : 0;
+  a.epi_flags = 0;
+  a.store_policy = 0;   // (plain output stores: write-through ones won no A/B here)
   const int nbi = (g.I + BI - 1) / BI;
   a.nbj = (g.J + BJ - 1) / BJ;
   a.ntiles = nbi * a.nbj;
@@ -967,35 +965,20 @@ int launch(const hig_gemm_desc& g, int splits, float* slabs, int64_t slab, hipSt
   per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
   const int max_vgpr_blocks = (BI * BJ >= 128 * 128) ? 2 : 4;   // 128x128: <=256 VGPRs -> 2 waves/SIMD
   if (per_cu > max_vgpr_blocks) per_cu = max_vgpr_blocks;
-  constexpr int forced_per_cu = -1;  // (a former tuning knob, fixed at the value that won its A/B)
-  if (forced_per_cu > 0) per_cu = forced_per_cu;
-  const bool fast = a.vecx && a.vecy && (g.R % BK == 0) && g.R > 0 &&
-                    (!X_RS || (g.I % 4 == 0 && g.I >= 4)) && (!Y_RS || (g.J % 4 == 0 && g.J >= 4));
-  // Split tail.  M = 12 544 leaves every GEMM of the model a last round that fills 12-37 % of the chip (N = 512:
-  // 1568 64x64 tiles = 6 x 256 + 32): cut those remainder tiles along the reduce range so that the last round costs
-  // 1/s of a tile (see KArgs).  Exact-fp32 products, whole rounds in front, reduce slices of >= 2 k-tiles.
-  static const int tail_on = getenv("HIG_GEMM_TAIL") ? atoi(getenv("HIG_GEMM_TAIL")) : 1;   // tuning knob
-  if constexpr (!X_RS) {
-    const int ncu = hig_chip_cus();
-    if (tail_on && BI == 64 && BJ == 64 && splits == 1 && fast && g.prec == HIG_PREC_F32 && g_tail.ws && a.ntiles > ncu &&
-        a.ntiles % ncu != 0) {
-      const int rem = a.ntiles % ncu, nkt = g.R / BK;
-      int s = 1;
-      while (2 * s * rem <= ncu && nkt % (2 * s) == 0 && nkt / (2 * s) >= 2) s *= 2;
-      constexpr int64_t unit_bytes = (int64_t)NTHREADS * (BI / 64) * (BJ / 64) * 16 * 4;
-      if (s > 1 && rem <= HIG_GEMM_TAIL_CNT_BYTES / 4 && rem * s * unit_bytes <= g_tail.ws_bytes) {
-        a.tail_s = s;
-        a.tail_rem = rem;
-        a.nmain = a.ntiles - rem;
-        a.tail_chunk = g.R / s;
-        a.tail_ws = g_tail.ws;
-        a.tail_cnt = g_tail.cnt;
-        a.ntiles = a.nmain + rem * s;
-      }
-    }
+  const bool fast = hig_gemm32_fast(g);
+  // Split tail (the rule: tiled32_tail, gemm_plan.hip): the remainder tiles of the last round are cut into tail_s reduce slices
+  if (tail_s > 1) {
+    const int rem = a.ntiles % hig_chip_cus();
+    a.tail_s = tail_s;
+    a.tail_rem = rem;
+    a.nmain = a.ntiles - rem;
+    a.tail_chunk = g.R / tail_s;
+    a.tail_ws = g_tail.ws;
+    a.tail_cnt = g_tail.cnt;
+    a.ntiles = a.nmain + rem * tail_s;
   }
   int gridx = hig_chip_cus() * per_cu;
-  if (gridx > a.ntiles || forced_per_cu == 0) gridx = a.ntiles;   // 0: one workgroup per tile
+  if (gridx > a.ntiles) gridx = a.ntiles;
   bool served = false;
   if constexpr (X_RS && Y_RS && XF == HIG_XF_NONE && EPI == HIG_EPI_NONE) {
     // weight gradients of the exact-fp32 step: the output-stationary kernel with specialised waves (wgrad_wsp32.hip) writes the
@@ -1043,57 +1026,21 @@ int launch(const hig_gemm_desc& g, int splits, float* slabs, int64_t slab, hipSt
   return HIG_OK;
 }
 
-// Tile choice.  fp32 MFMA is slow enough (64 cycles per 32x32x2) that every tile shape is
-// MFMA-bound, so what matters is how evenly ceil(I/BI)*ceil(J/BJ) tiles spread over 256 CUs:
-// M = 12544 = 2^8 * 49 gives 3.06 128x128 tiles per CU for N = 1024 (4 rounds, 77 % balance)
-// but 12.25 64x64 tiles (13 rounds, 94 %).  Pick the shape with the smallest
-// rounds x tile-area x overhead; smaller tiles pay a little more prologue/epilogue/LDS traffic.
+// The tile a launch runs with: split-R launches (weight gradients: split-R already supplies the parallelism) by the rule of
+// hig_host.h, unsplit ones by the plan (tiled32_tile / tiled32_tail, gemm_plan.hip).  Measured (tools/gemm_bench.py,
+// tools/fwd_time.py with HIG_GEMM_TILE forced): exact-fp32 products never did better than with 64x64 tiles (four co-resident
+// workgroups per CU) on the model's shapes -- B = 32 / 64 forwards 4.07 / 6.90 ms against 4.19-4.67 / 7.5-7.6 ms -- so the
+// round-counting model only breaks ties for shapes with at most one tile per CU; with the 16x faster bf16 MFMAs per-tile
+// latency and the number of workgroups in flight decide: mixed 64x128 / 128x64 tiles are the worst choice, 128x128 wins once
+// it yields enough tiles (300) to occupy the chip, 64x64 below that.
 template <bool X_RS, bool Y_RS, int XF, bool XF_ON_Y, int EPI>
-int launch_sized(const hig_gemm_desc& g, int splits, float* slabs, int64_t slab, hipStream_t st, const SplitEpilogue& se) {
-  if (splits > 1 || X_RS) {  // weight gradients: split-R already supplies the parallelism; tile rule in hig_host.h
-    if (wgrad_tile(g.I, g.J, g.prec) == 128) return launch<128, 128, X_RS, Y_RS, XF, XF_ON_Y, EPI>(g, splits, slabs, slab, st, se);
-    return launch<64, 64, X_RS, Y_RS, XF, XF_ON_Y, EPI>(g, splits, slabs, slab, st, se);
-  }
-  struct Cand { int bi, bj; double ovh; };
-  // measured (tools/gemm_bench.py): with 64-cycle fp32 MFMAs small tiles cost almost nothing;
-  // with the 16x faster bf16 MFMAs the extra LDS/L2 traffic of small tiles shows (x1.1-1.2)
-  const bool bf = g.prec != HIG_PREC_F32;
-  const Cand cands[4] = {{128, 128, 1.00}, {64, 128, bf ? 1.10 : 1.02}, {128, 64, bf ? 1.12 : 1.03},
-                         {64, 64, bf ? 1.20 : 1.04}};
-  int best = 0;
-  double best_cost = 1e300;
-  const int ncu = hig_chip_cus();
-  static const int forced = getenv("HIG_GEMM_TILE") ? atoi(getenv("HIG_GEMM_TILE")) : -1;  // tuning knob
-  for (int c = 0; c < 4 && forced < 0; ++c) {
-    const int64_t tiles = (int64_t)((g.I + cands[c].bi - 1) / cands[c].bi) * ((g.J + cands[c].bj - 1) / cands[c].bj);
-    const int64_t rounds = (tiles + ncu - 1) / ncu;
-    const double cost = (double)rounds * cands[c].bi * cands[c].bj * cands[c].ovh;
-    if (cost < best_cost) { best_cost = cost; best = c; }
-  }
-  // exact-fp32 products: 64x64 tiles (four co-resident workgroups per CU) were never beaten by a larger tile on the
-  // model's shapes -- B = 32 / 64 forwards, tools/fwd_time.py with HIG_GEMM_TILE forced: 4.07 / 6.90 ms against
-  // 4.19-4.67 / 7.5-7.6 ms -- the round-counting model above mis-ranks them by a few per cent, so it only
-  // breaks ties for shapes with at most one tile per CU
-  constexpr int f32_rule = 1;   // (a former tuning knob, fixed at the value that won its A/B)
-  if (!bf && forced < 0 && f32_rule) {
-    const int64_t t64 = (int64_t)((g.I + 63) / 64) * ((g.J + 63) / 64);
-    if (t64 > ncu) best = 3;
-  }
-  if (bf && forced < 0) {
-    // bf16 products: the MFMA part is short, so per-tile latency and the number of workgroups in flight decide.
-    // Measured (tools/fwd_time.py, B = 32 / 64): mixed 64x128 / 128x64 tiles are the worst choice, 128x128 wins
-    // once it yields enough tiles to occupy the chip, 64x64 below that.
-    constexpr int thr = 300;   // (a former tuning knob, fixed at the value that won its A/B)
-    const int64_t t128 = (int64_t)((g.I + 127) / 128) * ((g.J + 127) / 128);
-    best = t128 >= thr ? 0 : 3;
-  }
-  if (forced >= 0) best = forced;
-  if (g.row_stats_out || g.row_stats_in) best = 3;   // the LayerNorm fold lives in the 64 x 64 tile's staged epilogue
-  switch (best) {
-    case 0: return launch<128, 128, X_RS, Y_RS, XF, XF_ON_Y, EPI>(g, splits, slabs, slab, st, se);
-    case 1: return launch<64, 128, X_RS, Y_RS, XF, XF_ON_Y, EPI>(g, splits, slabs, slab, st, se);
-    case 2: return launch<128, 64, X_RS, Y_RS, XF, XF_ON_Y, EPI>(g, splits, slabs, slab, st, se);
-    default: return launch<64, 64, X_RS, Y_RS, XF, XF_ON_Y, EPI>(g, splits, slabs, slab, st, se);
+int launch_sized(const hig_gemm_desc& g, int splits, float* slabs, int64_t slab, hipStream_t st, const SplitEpilogue& se, int variant) {
+  const int tile = splits > 1 ? (wgrad_tile(g.I, g.J, g.prec) == 128 ? 0 : 3) : variant % 16, tail_s = splits > 1 ? 1 : variant / 16;
+  switch (tile) {
+    case 0: return launch<128, 128, X_RS, Y_RS, XF, XF_ON_Y, EPI>(g, splits, slabs, slab, st, se, tail_s);
+    case 1: return launch<64, 128, X_RS, Y_RS, XF, XF_ON_Y, EPI>(g, splits, slabs, slab, st, se, tail_s);
+    case 2: return launch<128, 64, X_RS, Y_RS, XF, XF_ON_Y, EPI>(g, splits, slabs, slab, st, se, tail_s);
+    default: return launch<64, 64, X_RS, Y_RS, XF, XF_ON_Y, EPI>(g, splits, slabs, slab, st, se, tail_s);
   }
 }
 
@@ -1143,86 +1090,25 @@ void hig_gemm_set_tail_scratch(void* ws, int64_t bytes) {
 }
 namespace {
 int gemm_dispatch(const hig_gemm_desc& g, int splits, float* slabs, hipStream_t st, const SplitEpilogue& se) {
-  HIG_REQUIRE(g.X && g.Y && g.C, "hig_gemm: null operand");
-  HIG_REQUIRE(g.I >= 0 && g.J >= 0 && g.R >= 0, "hig_gemm: negative extent");
-  if (g.I == 0 || g.J == 0) return HIG_OK;
-  if (g.xf != HIG_XF_NONE) {
-    // transformed operand: features must come in whole float4 quads
-    const int nfeat = g.xf_on_y ? g.J : g.R;
-    HIG_REQUIRE(nfeat % 4 == 0, "hig_gemm: fused transform needs feature count %% 4 == 0 (got %d)", nfeat);
-    if (g.xf != HIG_XF_SILU) HIG_REQUIRE(g.stats && g.gamma && g.beta, "hig_gemm: LN transform needs stats/gamma/beta");
-    if (g.xf == HIG_XF_LN_MOD_SILU) HIG_REQUIRE(g.ss && g.rows_per_sample > 0, "hig_gemm: modulation needs ss");
-  }
+  // (a split launch is planned as the unsplit one: the same validation, then always the tiled kernel over slabs)
+  const hig_plan p = hig_gemm32_plan(g, g_tail.ws ? g_tail.ws_bytes : 0, hig_gemm_switch_values(), hig_chip_cus());
+  if (p.rc != HIG_OK) return hig_set_error(p.rc, "%s", p.msg);
+  if (p.launches == 0) return HIG_OK;
   const int64_t slab = (int64_t)g.I * g.J;
-  if (g.xcolsum)
-    HIG_REQUIRE(g.x_rs == 1 && g.prec == HIG_PREC_F32 && g.I % 4 == 0 && (g.xf == HIG_XF_NONE || g.xf_on_y),
-                "hig_gemm: xcolsum needs a reduce-slow X operand, fp32 products, I %% 4 == 0");
   if (splits > 1) HIG_REQUIRE(slabs && g.epi == HIG_EPI_NONE && slab % 4 == 0 && g.ldc == g.J,
                               "hig_gemm: split-R needs slabs, EPI_NONE, dense C");
-  if (g.row_stats_out || g.row_stats_in) {   // LayerNorm fold: only the LDS-staged epilogue of the 64-column tiles implements it
-    auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool ok = splits <= 1 && g.x_rs == 0 && g.y_rs == 0 && g.xf == HIG_XF_NONE && g.J % 64 == 0 && g.R % 32 == 0 && g.ldc % 4 == 0 &&
-                    g.ldx % 4 == 0 && g.ldy % 4 == 0 && a16(g.X) && a16(g.Y) && a16(g.C) && a16(g.bias) &&
-                    (g.row_stats_out ? (g.epi == HIG_EPI_BIAS_RES && !g.row_stats_in && g.res && g.ldr % 4 == 0 && a16(g.res) && (reinterpret_cast<uintptr_t>(g.row_stats_out) & 7) == 0)
-                                     : (g.epi == HIG_EPI_BIAS && g.ln_colsum && g.R % 128 == 0 && a16(g.row_stats_in) && a16(g.ln_colsum)));
-    if (!ok) return hig_set_error(HIG_EUNSUPPORTED, "hig_gemm: LayerNorm-fold operands on a launch that cannot apply them "
-                                                    "(needs reduce-contiguous aligned operands, J %% 64 == 0, EPI_BIAS_RES producer / EPI_BIAS consumer with R %% 128 == 0)");
-  }
-  // exact-fp32 products, K = 512 / 1024, many rows: the weight-stationary kernel with specialised waves (gemm_wsp32.hip)
-  if (splits <= 1 && !se.bias) {
-    const int rc = hig_gemm_wsp32_try(g, st);
-    if (rc != 1) return rc;
-    // K = 1536 / 2048 (the data gradient of the stacked q/k/v projection: dqkv (M, 3d) . Wqkv): that kernel's weight panel holds
-    // at most K = 1024, so the reduce range goes through it in passes -- C = X[:, :1024] W[:, :1024]^T (+ bias / res), then
-    // C += X[:, 1024:] W[:, 1024:]^T with C as its own residual (a lane re-reads exactly the element it stores two tiles later).
-    // 153 us for the two passes at M = 12 544 against 197 us on the tiled kernel.
-    if (hig_gemm_wsp32_active() && g.prec == HIG_PREC_F32 && !g.x_rs && !g.y_rs && g.xf == HIG_XF_NONE && !g.xcolsum && !g.row_stats_in &&
-        !g.row_stats_out && g.R > 1024 && g.R <= 2048 && g.R % 512 == 0 && g.I >= 2048 && g.J % 64 == 0 &&
-        (g.epi == HIG_EPI_NONE || g.epi == HIG_EPI_RES || g.epi == HIG_EPI_BIAS || g.epi == HIG_EPI_BIAS_RES)) {
-      hig_gemm_desc p1 = g;
-      p1.R = 1024;
-      const int rc1 = hig_gemm_wsp32_try(p1, st);
-      if (rc1 < 0) return rc1;
-      if (rc1 == HIG_OK) {
-        hig_gemm_desc p2 = g;
-        p2.X = g.X + 1024; p2.Y = g.Y + 1024; p2.R = g.R - 1024;
-        p2.epi = HIG_EPI_RES; p2.bias = nullptr; p2.res = g.C; p2.ldr = g.ldc;
-        const int rc2 = hig_gemm_wsp32_try(p2, st);
-        if (rc2 != 1) return rc2;
-        return hig_set_error(HIG_EHIP, "hig_gemm: second reduce pass declined after the first was launched");
-      }
-    }
+  if (splits <= 1 && p.path == HIG_GEMM_PATH_WSP32) {
+    if (p.launches == 1) return hig_gemm_wsp32_launch(g, p.variant, st);
+    hig_gemm_desc p1, p2;   // K = 1536 / 2048: two passes over the reduce range
+    hig_gemm32_two_pass(g, &p1, &p2);
+    HIG_TRY(hig_gemm_wsp32_launch(p1, p.variant, st));
+    return hig_gemm_wsp32_launch(p2, HIG_WSP_VARIANT(0, 0), st);
   }
 #define CASE(xrs, yrs, xfv, ony, epiv)                                                   \
   if (g.x_rs == xrs && g.y_rs == yrs && g.xf == xfv && (g.xf == HIG_XF_NONE || g.xf_on_y == ony) && \
       g.epi == epiv)                                                                     \
-    return launch_sized<xrs, yrs, xfv, ony, epiv>(g, splits, slabs, slab, st, se);
-#ifdef HIG_GEMM_PROBE  // compile-time aid: build a single combination
-  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_BIAS_GELU)
-  return HIG_EUNSUPPORTED;
-#endif
-  // forward (activations x weight^T)
-  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_NONE)
-  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_BIAS)
-  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_BIAS_GELU)
-  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_BIAS_POS)
-  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_BIAS_RES)
-  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_RES)    // dgrad through a transposed weight copy
-  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_DGELU)
-  CASE(0, 0, HIG_XF_LN, 0, HIG_EPI_BIAS)
-  CASE(0, 0, HIG_XF_LN_MOD_SILU, 0, HIG_EPI_BIAS_RES)
-  CASE(0, 0, HIG_XF_SILU, 0, HIG_EPI_BIAS)
-  CASE(0, 0, HIG_XF_SILU, 0, HIG_EPI_BIAS_RES)
-  CASE(0, 0, HIG_XF_SILU, 0, HIG_EPI_NONE)   // split-R partials of the few-row GEMMs
-  // dgrad (dC x weight)
-  CASE(0, 1, HIG_XF_NONE, 0, HIG_EPI_NONE)
-  CASE(0, 1, HIG_XF_NONE, 0, HIG_EPI_RES)
-  CASE(0, 1, HIG_XF_NONE, 0, HIG_EPI_DGELU)
-  // wgrad (dC^T x activations)
-  CASE(1, 1, HIG_XF_NONE, 0, HIG_EPI_NONE)
-  CASE(1, 1, HIG_XF_LN, 1, HIG_EPI_NONE)
-  CASE(1, 1, HIG_XF_LN_MOD_SILU, 1, HIG_EPI_NONE)
-  CASE(1, 1, HIG_XF_SILU, 1, HIG_EPI_NONE)
+    return launch_sized<xrs, yrs, xfv, ony, epiv>(g, splits, slabs, slab, st, se, p.variant);
+  HIG_GEMM32_COMBOS(CASE)
 #undef CASE
   return hig_set_error(HIG_EUNSUPPORTED, "hig_gemm: combination x_rs=%d y_rs=%d xf=%d on_y=%d epi=%d not built",
                        g.x_rs, g.y_rs, g.xf, g.xf_on_y, g.epi);

@@ -339,7 +339,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_bf16_kernel(const K16Arg
 
 template <int WM, int WN, int TI, int TJ, int BK, int NS, int EPI>
 int launch16(const hig_gemm16_desc& g, hipStream_t st, int splits = 1, int64_t slab = 0, int path = HIG_GEMM_PATH_TILED16) {
-  constexpr int use_srd = 1;   // (a former tuning knob, fixed at the value that won its A/B): 0 = global_load_lds
   constexpr int NT = 64 * WM * WN, BM = 32 * TI * WM, BN = 32 * TJ * WN;
   K16Args a;
   a.g = g;
@@ -355,8 +354,6 @@ int launch16(const hig_gemm16_desc& g, hipStream_t st, int splits = 1, int64_t s
   constexpr int lds = NS * (BM + BN) * BK * 2;
   int per_cu = 160 * 1024 / (lds > 64 * (BN + 4) * 4 ? lds : 64 * (BN + 4) * 4);
   if (per_cu > 4) per_cu = 4;
-  constexpr int forced_per_cu = 0;   // (a former tuning knob, fixed at the value that won its A/B)
-  if (forced_per_cu > 0) per_cu = forced_per_cu;
   static const int dbg = getenv("HIG_BF16_DBG") ? atoi(getenv("HIG_BF16_DBG")) : 0;
   a.dbg = g_stamps ? dbg : (dbg & ~16);
   a.stamps = g_stamps;
@@ -365,7 +362,7 @@ int launch16(const hig_gemm16_desc& g, hipStream_t st, int splits = 1, int64_t s
   // (operands beyond 2 GiB would overflow the 32-bit byte offsets of the descriptor form)
   const bool srd_ok = ((int64_t)g.I * g.ldx < (1ll << 30)) && ((int64_t)g.J * g.ldy < (1ll << 30));
   hig_gemm_path_count(path);
-  if (use_srd && srd_ok)
+  if (srd_ok)   // (else global_load_lds)
     hipLaunchKernelGGL((gemm_bf16_kernel<WM, WN, TI, TJ, BK, NS, EPI, true>), dim3(grid), dim3(NT), 0, st, a);
   else
     hipLaunchKernelGGL((gemm_bf16_kernel<WM, WN, TI, TJ, BK, NS, EPI, false>), dim3(grid), dim3(NT), 0, st, a);
@@ -373,57 +370,34 @@ int launch16(const hig_gemm16_desc& g, hipStream_t st, int splits = 1, int64_t s
   return HIG_OK;
 }
 
-// Tile choice.  Every launch of this model is a short-K problem (K = 256 ... 2048): per-tile fixed costs (first DMA,
-// epilogue) and the number of ROUNDS the tiles take on the chip decide, not the MFMA rate.  Candidates: 128 x 128 and
-// 128 x 192 (2 resident workgroups per CU = 512 slots), 64 x 128 (3 per CU = 768 slots).  Rule: fewest rounds; among
-// equals the larger tile when it still gives every CU a workgroup, else the smaller one (more CUs busy).
+// The instance of a tile / ring variant (HIG_TILE16_VARIANT; the rule that picks it: tiled16_variant, gemm_plan.hip).
 template <int EPI>
-int launch16_sized(const hig_gemm16_desc& g, hipStream_t st) {
-  static const int forced_env = getenv("HIG_BF16_TILE") ? atoi(getenv("HIG_BF16_TILE")) : 0;   // tuning knob: 64 / 128
-  const int forced = (forced_env == 64 || forced_env == 128) ? forced_env : 0;
-  auto tiles = [&](int bm, int bn) { return (int64_t)((g.I + bm - 1) / bm) * ((g.J + bn - 1) / bn); };
-  auto rounds = [](int64_t t, int slots) { return (t + slots - 1) / slots; };
-  const int64_t t128 = tiles(128, 128), t64 = tiles(64, 128);
-  int pick = 64;
-  if (forced) {
-    pick = forced;
-  } else {
-    // estimated time = rounds x relative cost of one tile (fitted to tools/gemm16_bench.py at M = 6272 and 12544,
-    // profiles/r02_notes.md: a 64 x 128 tile costs 0.75 of a 128 x 128 one, not the 0.5 of its area -- it re-reads the
-    // same weight panel for half the rows)
-    const int ncu = hig_chip_cus();   // 2 resident 128-row workgroups per CU, 3 of the 64-row ones
-    const double c128 = (double)rounds(t128, 2 * ncu) * 1.0, c64 = (double)rounds(t64, 3 * ncu) * 0.75;
-    pick = 128;
-    double best = c128;
-    if (t128 < ncu && c64 <= best * 1.25) { pick = 64; best = c64; }        // too few big tiles to occupy the chip
-    else if (c64 < best) { pick = 64; best = c64; }
-    // (a 256 x 256 tile -- 8 waves, one workgroup per CU -- won the wide K = 1024 launches of the d = 1024 model alone, 77 against 89 us,
-    // and lost inside the forward, 4.61-4.64 against 4.57 ms: not built any more)
-  }
+int launch16_tile(const hig_gemm16_desc& g, int variant, hipStream_t st) {
+  // (a 256 x 256 tile -- 8 waves, one workgroup per CU -- won the wide K = 1024 launches of the d = 1024 model alone, 77 against 89 us,
+  // and lost inside the forward, 4.61-4.64 against 4.57 ms: not built any more)
   // (ring shape, re-measured with per-phase stamps at the FFN linear1 shape, profiles/r02_notes.md section 7: the main
   // loops of two co-resident workgroups move 2 x 256 KB in ~19.3K cycles = 27 B/clk per CU, which IS the CU's L2 -> LDS
   // rate (guide: 66-73 GB/s per CU for L2-resident rows, DMA and register staging alike).  4 x BK 32 stages: 18.5K;
   // 3 x BK 64 stages (one workgroup per CU): 10.9K for its single tile but no second workgroup to cover the epilogue,
   // 44.9 against 36.5 us; start-time offsets between the co-resident workgroups: no effect.)
-  // 64-row tiles are what the small-M launches get (M = 6272: one partly filled round of 2-3 workgroups per CU): there a
-  // k-tile is bound by the LATENCY of its DMA, not by the CU's fetch rate, and a third ring stage (72 KB of LDS, still
-  // two workgroups per CU) hides it: stylization-out 14.9 -> 12.8 us, FFN linear2 21.4 -> 18.2 us, config-3 forward
-  // 1.515 -> 1.409 ms (B = 64: 2.30 -> 2.28 ms).  Not for K = 256 (4 k-tiles: 8.8 -> 15.4 us) and not for the 128-row
-  // tile (96 KB = one workgroup per CU: FFN linear1 20.6 -> 24.2 us).  HIG_BF16_RING3=0 switches it off.
-  constexpr int ring3 = 1;   // (a former tuning knob, fixed at the value that won its A/B)
-  if (ring3 && pick == 64 && g.R % 64 == 0 && g.R >= 512) return launch16<1, 4, 2, 1, 64, 3, EPI>(g, st);
-  // 128 x 128 tiles over several rounds (M >= 8192: every launch of the B = 64 forward): four stages of BK = 32 (the
-  // same 64 KB) keep one more k-tile in flight than two of BK = 64: B = 64 forward 2.308 -> 2.261 ms (q/k/v 44.2 ->
-  // 41.8 us); at M = 6272, where these launches are single partly filled rounds, it is neutral to slightly slower
-  // (1.425 -> 1.435 ms), so the rule is on the row count.  HIG_BF16_RING4_ROWS moves the threshold (0 = never).
-  constexpr int ring4_rows = 8192;   // (a former tuning knob, fixed at the value that won its A/B)
-  if (ring4_rows > 0 && pick == 128 && g.I >= ring4_rows && g.R >= 512) return launch16<2, 2, 2, 2, 32, 4, EPI>(g, st);
-  if (g.R % 64 == 0) {
-    if (pick == 128) return launch16<2, 2, 2, 2, 64, 2, EPI>(g, st);
-    return launch16<1, 4, 2, 1, 64, 2, EPI>(g, st);
+  switch (variant) {
+    // 64-row tiles are what the small-M launches get (M = 6272: one partly filled round of 2-3 workgroups per CU): there a
+    // k-tile is bound by the LATENCY of its DMA, not by the CU's fetch rate, and a third ring stage (72 KB of LDS, still
+    // two workgroups per CU) hides it: stylization-out 14.9 -> 12.8 us, FFN linear2 21.4 -> 18.2 us, config-3 forward
+    // 1.515 -> 1.409 ms (B = 64: 2.30 -> 2.28 ms).  Not for K = 256 (4 k-tiles: 8.8 -> 15.4 us) and not for the 128-row
+    // tile (96 KB = one workgroup per CU: FFN linear1 20.6 -> 24.2 us).
+    case HIG_TILE16_VARIANT(64, 64, 3): return launch16<1, 4, 2, 1, 64, 3, EPI>(g, st);
+    // 128 x 128 tiles over several rounds (M >= 8192: every launch of the B = 64 forward): four stages of BK = 32 (the
+    // same 64 KB) keep one more k-tile in flight than two of BK = 64: B = 64 forward 2.308 -> 2.261 ms (q/k/v 44.2 ->
+    // 41.8 us); at M = 6272, where these launches are single partly filled rounds, it is neutral to slightly slower
+    // (1.425 -> 1.435 ms), so the rule is on the row count.
+    case HIG_TILE16_VARIANT(128, 32, 4): return launch16<2, 2, 2, 2, 32, 4, EPI>(g, st);
+    case HIG_TILE16_VARIANT(128, 64, 2): return launch16<2, 2, 2, 2, 64, 2, EPI>(g, st);
+    case HIG_TILE16_VARIANT(64, 64, 2): return launch16<1, 4, 2, 1, 64, 2, EPI>(g, st);
+    case HIG_TILE16_VARIANT(128, 32, 3): return launch16<2, 2, 2, 2, 32, 3, EPI>(g, st);
+    case HIG_TILE16_VARIANT(64, 32, 3): return launch16<1, 4, 2, 1, 32, 3, EPI>(g, st);
+    default: return hig_set_error(HIG_EINVAL, "hig_gemm_bf16: no tiled instance for variant %d", variant);
   }
-  if (pick != 64) return launch16<2, 2, 2, 2, 32, 3, EPI>(g, st);
-  return launch16<1, 4, 2, 1, 32, 3, EPI>(g, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -586,9 +560,8 @@ __global__ __launch_bounds__(256) void gemm_fewrow16_lds_kernel(const hig_gemm16
 
 template <int EPI>
 int launch_fewrow16(const hig_gemm16_desc& g, hipStream_t st) {
-  constexpr int lds_on = 1;   // (a former tuning knob, fixed at the value that won its A/B)
   hig_gemm_path_count(HIG_GEMM_PATH_FEWROW16);
-  if (lds_on && g.R % 256 == 0) {               // operands through wave-private LDS rings
+  if (g.R % 256 == 0) {               // operands through wave-private LDS rings
     if (g.I <= 32) hipLaunchKernelGGL((gemm_fewrow16_lds_kernel<1, EPI>), dim3(g.J / 32), dim3(256), 0, st, g);
     else hipLaunchKernelGGL((gemm_fewrow16_lds_kernel<2, EPI>), dim3(g.J / 32), dim3(256), 0, st, g);
   } else if (g.I <= 32) hipLaunchKernelGGL((gemm_fewrow16_kernel<1, EPI>), dim3(g.J / 32), dim3(256), 0, st, g);
@@ -596,23 +569,6 @@ int launch_fewrow16(const hig_gemm16_desc& g, hipStream_t st) {
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
-
-// Serves: I <= 64, J a multiple of 32 with at most 512 column blocks (beyond that the tiled kernel already has every CU
-// busy), reduce range a multiple of 64 of at least 256.  Returns 1 when the shape is not served.  HIG_BF16_FEWROW=0: off.
-int fewrow16_try(const hig_gemm16_desc& g, hipStream_t st) {
-  static const int on = getenv("HIG_BF16_FEWROW") ? atoi(getenv("HIG_BF16_FEWROW")) : 1;   // tuning knob
-  if (!on || g.I > 64 || g.J % 32 != 0 || g.J / 32 > 512 || g.R % 64 != 0 || g.R < 256) return 1;
-  switch (g.epi) {
-    case HIG_EPI_NONE: return launch_fewrow16<HIG_EPI_NONE>(g, st);
-    case HIG_EPI_BIAS: return launch_fewrow16<HIG_EPI_BIAS>(g, st);
-    case HIG_EPI_BIAS_GELU: return launch_fewrow16<HIG_EPI_BIAS_GELU>(g, st);
-    case HIG_EPI_BIAS_RES: return launch_fewrow16<HIG_EPI_BIAS_RES>(g, st);
-    case HIG_EPI_BIAS_SILU: return launch_fewrow16<HIG_EPI_BIAS_SILU>(g, st);
-    case HIG_EPI_BIAS_RES_SILU: return launch_fewrow16<HIG_EPI_BIAS_RES_SILU>(g, st);
-    default: return 1;
-  }
-}
-
 
 __global__ void cast_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, int64_t n) {
   const int64_t n8 = n / 8;
@@ -792,39 +748,17 @@ __global__ __launch_bounds__(256) void joint_embed16_kernel(const float* __restr
 }  // namespace
 
 int hig_gemm16_launch(const hig_gemm16_desc& g, hipStream_t st) {
-  HIG_REQUIRE(g.X && g.Y && g.C, "hig_gemm_bf16: null operand");
-  HIG_REQUIRE(g.I >= 0 && g.J >= 0 && g.R > 0, "hig_gemm_bf16: bad extent");
-  if (g.I == 0 || g.J == 0) return HIG_OK;
-  if (g.R % 32 != 0)
-    return hig_set_error(HIG_EUNSUPPORTED, "hig_gemm_bf16: the reduce extent must be a multiple of 32 (got %d)", g.R);
-  HIG_REQUIRE(g.ldx % 8 == 0 && g.ldy % 8 == 0 && (reinterpret_cast<uintptr_t>(g.X) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(g.Y) & 15) == 0,
-              "hig_gemm_bf16: operands must be 16-byte aligned with leading dimensions that are multiples of 8");
-  if (epi_has_bias(g.epi)) HIG_REQUIRE(g.bias, "hig_gemm_bf16: epilogue %d needs a bias", g.epi);
-  if (epi_has_res(g.epi)) HIG_REQUIRE(g.res, "hig_gemm_bf16: epilogue %d needs `res`", g.epi);
-  {   // many rows, K = 512: the weight-stationary kernel with specialised waves (gemm_wsp16.hip)
-    const int rc = hig_gemm_wsp16_try(g, st);
-    if (rc <= 0) return rc;
-    if (g.aux) return hig_set_error(HIG_EUNSUPPORTED, "hig_gemm_bf16: `aux` (pre-activation output) on a shape gemm_wsp16 does not serve");
-  }
-  {   // many rows, short reduce range: the weight-stationary kernel (gemm_ws16.hip) when it serves the shape
-    const int rc = hig_gemm_ws16_try(g, st);
-    if (rc <= 0) return rc;
-  }
-  {   // a handful of rows: one workgroup per 32 output columns (gemm_fewrow16_kernel)
-    const int rc = fewrow16_try(g, st);
-    if (rc <= 0) return rc;
-  }
-  switch (g.epi) {
-    case HIG_EPI_NONE: return launch16_sized<HIG_EPI_NONE>(g, st);
-    case HIG_EPI_BIAS: return launch16_sized<HIG_EPI_BIAS>(g, st);
-    case HIG_EPI_BIAS_GELU: return launch16_sized<HIG_EPI_BIAS_GELU>(g, st);
-    case HIG_EPI_BIAS_RES: return launch16_sized<HIG_EPI_BIAS_RES>(g, st);
-    case HIG_EPI_BIAS_SILU: return launch16_sized<HIG_EPI_BIAS_SILU>(g, st);
-    case HIG_EPI_BIAS_RES_SILU: return launch16_sized<HIG_EPI_BIAS_RES_SILU>(g, st);
-    case HIG_EPI_RES: return launch16_sized<HIG_EPI_RES>(g, st);
-    case HIG_EPI_DGELU: return launch16_sized<HIG_EPI_DGELU>(g, st);
-    default: return hig_set_error(HIG_EUNSUPPORTED, "hig_gemm_bf16: epilogue %d not built", g.epi);
+  const hig_plan p = hig_gemm16_plan(g, hig_gemm_switch_values(), hig_chip_cus());
+  if (p.rc != HIG_OK) return hig_set_error(p.rc, "%s", p.msg);
+  const int unbuilt = HIG_EUNSUPPORTED;   // (the plan names only epilogues of the lists below)
+  switch (p.path) {
+    case HIG_GEMM_PATH_WSP16: return hig_gemm_wsp16_launch(g, p.variant, st);   // many rows, K = 512: specialised waves (gemm_wsp16.hip)
+    case HIG_GEMM_PATH_WS16: return hig_gemm_ws16_launch(g, p.variant, st);     // many rows, short reduce range (gemm_ws16.hip)
+    case HIG_GEMM_PATH_FEWROW16:                                                // a handful of rows: one workgroup per 32 output columns
+      return hig_with_epi(hig_epi16_fewrow{}, g.epi, unbuilt, [&](auto e) { return launch_fewrow16<decltype(e)::value>(g, st); });
+    case HIG_GEMM_PATH_TILED16:
+      return hig_with_epi(hig_epi16_all{}, g.epi, unbuilt, [&](auto e) { return launch16_tile<decltype(e)::value>(g, p.variant, st); });
+    default: return HIG_OK;   // an empty problem
   }
 }
 

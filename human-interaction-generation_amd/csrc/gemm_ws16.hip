@@ -578,10 +578,9 @@ int launch_ws(const hig_gemm16_desc& g, int slots_per_xcd, hipStream_t st) {
   // output stores write through (`sc1`): a launch's 13-39 MB of output otherwise sit dirty in the XCDs' L2s until the
   // end-of-kernel write-back, during which nothing runs (same-call A/B at M = 12 544: FFN linear1 25.9 -> 23.4 us, q/k/v 28.5
   // -> 26.4, stylization-out 16.2 -> 15.0; forward B = 64 1.570 -> 1.537 ms; `nt` = 2 is mixed: ca-q 12.6 but FFN linear1 26.9)
-  constexpr int store_policy = 1;   // (a former tuning knob, fixed at the value that won its A/B)
   // in-place residual updates (C aliases res: the inference forward's residual stream) keep plain stores: a later tile's
   // residual DMA must see this kernel's own earlier stores in the same L2
-  a.store_policy = (g.res && g.res == g.C) ? 0 : store_policy;
+  a.store_policy = (g.res && g.res == g.C) ? 0 : 1;
   constexpr int store_slack = 0;   // (a former tuning knob, fixed at the value that won its A/B)
   a.store_slack = store_slack;
   hig_gemm_path_count(HIG_GEMM_PATH_WS16);
@@ -629,79 +628,10 @@ int launch_ws_sized(const hig_gemm16_desc& g, int nwj, hipStream_t st) {
 
 }  // namespace
 
-static inline bool has_res_epi(int epi) { return epi_has_res(epi); }
-
-// Returns HIG_OK when the launch was made, 1 when this kernel does not serve the shape (the caller falls back to the
-// tiled kernel), a negative HIG_E* code on error.
-int hig_gemm_ws16_try(const hig_gemm16_desc& g, hipStream_t st) {
-  static const int ws_on = getenv("HIG_BF16_WS") ? atoi(getenv("HIG_BF16_WS")) : 1;          // tuning knob: 0 = tiled kernel only
-  static const int forced_nwj = getenv("HIG_BF16_WS_NWJ") ? atoi(getenv("HIG_BF16_WS_NWJ")) : 0;   // 4 / 8
-  static const int min_rows = getenv("HIG_BF16_WS_ROWS") ? atoi(getenv("HIG_BF16_WS_ROWS")) : 2048;
-  const bool fold = g.row_stats_out || g.row_stats_in;
-  if (fold) {   // only this kernel implements the LayerNorm fold: the caller checks hig_gemm_ws16_lnfold_ok() first
-    // (a producer's rows are the consumer's X rows: J of the one = K of the other, 512 or 1024)
-    const bool ok = ws_on && !g.c_f32 && !(g.res && g.res_f32) && (g.R == 512 || g.R == 1024) && g.I >= min_rows &&
-                    (g.row_stats_out ? (g.epi == HIG_EPI_BIAS_RES && g.J == g.R && !g.row_stats_in)
-                                     : (g.epi == HIG_EPI_BIAS && g.ln_colsum && g.J % 128 == 0));
-    if (!ok) return hig_set_error(HIG_EUNSUPPORTED, "hig_gemm_bf16: LayerNorm-fold operands on a shape the weight-stationary kernel does not serve");
-  }
-  // `decline`: this kernel does not serve the call.  Without fold operands the caller falls back to the tiled / few-row
-  // kernels; WITH them it must not (those kernels know nothing of row_stats_* / ln_colsum: a producer would silently skip
-  // the statistics, a consumer would multiply un-normalised rows by W'), so every exit below is an error then.
-  auto decline = [&](const char* why) -> int {
-    return fold ? hig_set_error(HIG_EUNSUPPORTED, "hig_gemm_bf16: LayerNorm-fold operands, but %s", why) : 1;
-  };
-  if (!ws_on) return decline("the weight-stationary kernel is switched off (HIG_BF16_WS=0)");
-  // the kernel's work split is compiled for 8 XCDs x 32 CUs (block b -> XCD b & 7, 32 or 64 slots per XCD): another
-  // partitioning of the chip gets the tiled kernel, whose grid follows hig_chip_cus()
-  if (hig_chip_cus() != 256) return decline("the device does not report 256 compute units (8 XCDs x 32)");
-  if (g.c_f32 || (g.res && g.res_f32)) return decline("fp32 output / residual");
-  if (!(g.R == 256 || g.R == 512 || g.R == 1024)) return decline("reduce extent not in {256, 512, 1024}");
-  if (g.I < min_rows) return decline("too few rows");
-  auto al = [](const void* p, int n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; };
-  if (!(g.ldc % 8 == 0 && al(g.C, 16))) return decline("C not 16-byte aligned / ldc not a multiple of 8");
-  if ((int64_t)g.I * g.ldx >= (1ll << 30) || (int64_t)g.J * g.ldy >= (1ll << 30) || (g.res && (int64_t)g.I * g.ldr >= (1ll << 30)) ||
-      (int64_t)g.I * g.ldc >= (1ll << 30))
-    return decline("operand beyond the 32-bit byte offsets of the DMA descriptors");
-  const bool has_res = has_res_epi(g.epi);
-  if (has_res && !(g.ldr % 4 == 0 && al(g.res, 8))) return decline("residual not 8-byte aligned / ldr not a multiple of 4");
-  // columns per CU: the weight panel is fetched once per workgroup (cols x K x 2 bytes at the CU's ~30 B/clk), the X
-  // rows once per panel -- the sum is smallest near cols = sqrt(M N / 256)
-  // (measured, tools/gemm16_bench.py: the 8-wave variant wins for the wide bias-only launches -- q/k/v at M = 12 544: 28 us
-  // against 38 -- ; with a GELU or residual epilogue it spills registers at 256 per wave and the 4-wave variant wins)
-  int nwj = 8;
-  if (g.R == 1024) nwj = 4;
-  else if ((int64_t)g.I * g.J < (int64_t)256 * 192 * 192) nwj = 4;
-  else if (!(g.epi == HIG_EPI_NONE || g.epi == HIG_EPI_BIAS)) nwj = 4;
-  // GELU: every wave is bound by instruction issue (the erf arithmetic alone is 13 instructions per output, ~4 cycles
-  // each from one wave); two 4-wave workgroups per CU put a second, independent wave on every SIMD: FFN linear1 at
-  // M = 12 544 28.5 -> 25.2 us, at M = 6 272 17.2 -> 15.1 us
-  if (g.epi == HIG_EPI_BIAS_GELU && g.R != 1024) nwj = 44;
-  // residual epilogues at K = 512: two workgroups per CU from 8 192 rows up (same-call A/B, forward: B = 64 1.630 -> 1.613 ms,
-  // B = 512 8.72 -> 8.55 ms; B = 32 1.056 -> 1.066: the 3-4 tiles of a workgroup there are too few to share a CU)
-  constexpr int res44 = 8192;   // (a former tuning knob, fixed at the value that won its A/B): rows from which ... (0 = never)
-  if (has_res_epi(g.epi) && g.R == 512 && res44 > 0 && g.I >= res44) nwj = 44;
-  else if (g.row_stats_out) nwj = 4;            // (the statistics are per 128-column panel)
-  if (g.row_stats_out) { if (forced_nwj == 44) nwj = 44; }
-  else if (forced_nwj == 4 || (forced_nwj == 8 && g.R != 1024) || (forced_nwj == 2 && g.R == 512) || (forced_nwj == 44 && g.R != 1024)) nwj = forced_nwj;
-  if (nwj == 8 && !(g.epi == HIG_EPI_NONE || g.epi == HIG_EPI_BIAS)) nwj = 4;   // (a forced 8-wave variant: bias-only epilogues only)
-  if (nwj == 8 && g.row_stats_in) nwj = 4;
-  const int bn = (nwj == 4 || nwj == 44) ? 128 : 256;
-  if (g.J % bn != 0) {
-    if (g.J % 128 == 0) nwj = 4; else return decline("J not a multiple of 128");
-  }
-  if (g.J / ((nwj == 4 || nwj == 44) ? 128 : 256) > 32) return decline("more than 32 column panels");
-  switch (g.epi) {
-    case HIG_EPI_NONE: return launch_ws_sized<HIG_EPI_NONE>(g, nwj, st);
-    case HIG_EPI_BIAS: return launch_ws_sized<HIG_EPI_BIAS>(g, nwj, st);
-    case HIG_EPI_BIAS_GELU: return launch_ws_sized<HIG_EPI_BIAS_GELU>(g, nwj, st);
-    case HIG_EPI_BIAS_RES: return launch_ws_sized<HIG_EPI_BIAS_RES>(g, nwj, st);
-    case HIG_EPI_BIAS_SILU: return launch_ws_sized<HIG_EPI_BIAS_SILU>(g, nwj, st);
-    case HIG_EPI_BIAS_RES_SILU: return launch_ws_sized<HIG_EPI_BIAS_RES_SILU>(g, nwj, st);
-    case HIG_EPI_RES: return launch_ws_sized<HIG_EPI_RES>(g, nwj, st);
-    case HIG_EPI_DGELU: return launch_ws_sized<HIG_EPI_DGELU>(g, nwj, st);
-    default: return decline("epilogue not built for this kernel");
-  }
+// The instance a plan names (HIG_WS16_VARIANT: the nwj code; the fold role is read off the descriptor; eligibility and the
+// measurements behind the nwj rule: ws16_variant, gemm_plan.hip).
+int hig_gemm_ws16_launch(const hig_gemm16_desc& g, int variant, hipStream_t st) {
+  return hig_with_epi(hig_epi16_all{}, g.epi, HIG_EUNSUPPORTED, [&](auto e) { return launch_ws_sized<decltype(e)::value>(g, variant % 256, st); });
 }
 
 // Diagnostic: thread 0 of every workgroup of the weight-stationary kernel writes s_memtime stamps to buf[block * 16 + k]
@@ -710,19 +640,4 @@ int hig_gemm_ws16_try(const hig_gemm16_desc& g, hipStream_t st) {
 extern "C" int hig_gemm_ws16_debug_stamps(void* buf) {
   g_ws_stamps = static_cast<unsigned long long*>(buf);
   return HIG_OK;
-}
-
-// Can a d-wide LayerNorm in front of a GEMM over `rows` rows be folded into the weight-stationary kernels (the producer of
-// the rows writes their statistics, the consumer applies them)?  HIG_LNFOLD=0 switches it off.
-bool hig_gemm_ws16_lnfold_ok(int64_t rows, int d) {
-  static const int on = getenv("HIG_LNFOLD") ? atoi(getenv("HIG_LNFOLD")) : 1;            // tuning knob
-  static const int ws_on = getenv("HIG_BF16_WS") ? atoi(getenv("HIG_BF16_WS")) : 1;
-  static const int min_rows = getenv("HIG_BF16_WS_ROWS") ? atoi(getenv("HIG_BF16_WS_ROWS")) : 2048;
-  static const int forced_nwj = getenv("HIG_BF16_WS_NWJ") ? atoi(getenv("HIG_BF16_WS_NWJ")) : 0;
-  static const int on1024 = getenv("HIG_LNFOLD1024") ? atoi(getenv("HIG_LNFOLD1024")) : 1;   // tuning knob
-  // the same predicates as hig_gemm_ws16_try / hig_gemm_wsp16_try, so that a fold is only chosen where one of those kernels will
-  // accept it (they turn a decline into an error once fold operands are present): the 8 x 32 chip geometry their work split
-  // is compiled for, and the 32-bit byte offsets of their DMA descriptors for the widest consumer (q/k/v: 3 d columns)
-  return on && ws_on && !forced_nwj && (d == 512 || (d == 1024 && on1024)) && rows >= min_rows && hig_chip_cus() == 256 &&
-         rows * (int64_t)3 * d < (1ll << 30);
 }

@@ -475,8 +475,7 @@ int launch_wsp(const hig_gemm16_desc& g, hipStream_t st) {
   // output stores write through (`sc1`, as gemm_ws16.hip: the launch's output otherwise sits dirty in the XCDs' L2s until the
   // end-of-kernel write-back); in-place residual updates (C aliases res: the inference forward's residual stream) keep
   // plain stores
-  constexpr int store_policy = 1;   // (a former tuning knob, fixed at the value that won its A/B) (gemm_ws16.hip): 0 plain, else sc1
-  const bool plain = (g.res && g.res == g.C) || store_policy == 0;
+  const bool plain = g.res && g.res == g.C;
   const dim3 gr(256), bl(512);
   hig_gemm_path_count(HIG_GEMM_PATH_WSP16);
   if constexpr (!AUX && XT == 0 && (EPI == HIG_EPI_BIAS || EPI == HIG_EPI_BIAS_GELU || EPI == HIG_EPI_BIAS_RES)) {
@@ -496,36 +495,15 @@ int launch_wsp(const hig_gemm16_desc& g, hipStream_t st) {
 
 }  // namespace
 
-// Returns HIG_OK when the launch was made, 1 when this kernel does not serve the shape (the caller goes on to
-// gemm_ws16.hip / the tiled kernel), a negative HIG_E* code on error.
-int hig_gemm_wsp16_try(const hig_gemm16_desc& g, hipStream_t st) {
-  static const int on = getenv("HIG_BF16_WSP") ? atoi(getenv("HIG_BF16_WSP")) : 1;   // tuning knob: 0 = this kernel off
-  static const int min_rows = getenv("HIG_BF16_WS_ROWS") ? atoi(getenv("HIG_BF16_WS_ROWS")) : 2048;
-  static const int forced_nwj = getenv("HIG_BF16_WS_NWJ") ? atoi(getenv("HIG_BF16_WS_NWJ")) : 0;   // a gemm_ws16 variant is forced
-  if (!on || forced_nwj || hig_chip_cus() != 256) return 1;
-  if (g.R != KW || g.J % BN != 0 || g.J / BN > 256 || g.I < min_rows) return 1;
-  if (g.c_f32 || (g.res && g.res_f32)) return 1;
-  auto al = [](const void* p, int n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; };
-  if (!(g.ldc % 8 == 0 && al(g.C, 16))) return 1;
-  if ((int64_t)g.I * g.ldx >= (1ll << 30) || (int64_t)g.J * g.ldy >= (1ll << 30) || (g.res && (int64_t)g.I * g.ldr >= (1ll << 30)) ||
-      (int64_t)g.I * g.ldc >= (1ll << 30) || (g.aux && (int64_t)g.I * g.ldaux >= (1ll << 30)))
-    return 1;
-  const bool has_res = epi_has_res(g.epi);
-  if (has_res && !(g.ldr % 8 == 0 && al(g.res, 16))) return 1;
-  if (g.aux && !(g.epi == HIG_EPI_BIAS_GELU && g.ldaux % 8 == 0 && al(g.aux, 16))) return 1;
-  if (g.row_stats_out && !(g.epi == HIG_EPI_BIAS_RES && g.J == g.R && !g.row_stats_in)) return 1;
-  if (g.row_stats_in && !(g.epi == HIG_EPI_BIAS && g.ln_colsum)) return 1;
-  switch (g.epi) {
-    case HIG_EPI_NONE: return launch_wsp<HIG_EPI_NONE, 0, false>(g, st);
-    case HIG_EPI_BIAS: return g.row_stats_in ? launch_wsp<HIG_EPI_BIAS, 2, false>(g, st) : launch_wsp<HIG_EPI_BIAS, 0, false>(g, st);
-    case HIG_EPI_BIAS_GELU: return g.aux ? launch_wsp<HIG_EPI_BIAS_GELU, 0, true>(g, st) : launch_wsp<HIG_EPI_BIAS_GELU, 0, false>(g, st);
-    case HIG_EPI_BIAS_RES: return g.row_stats_out ? launch_wsp<HIG_EPI_BIAS_RES, 1, false>(g, st) : launch_wsp<HIG_EPI_BIAS_RES, 0, false>(g, st);
-    case HIG_EPI_BIAS_SILU: return launch_wsp<HIG_EPI_BIAS_SILU, 0, false>(g, st);
-    case HIG_EPI_BIAS_RES_SILU: return launch_wsp<HIG_EPI_BIAS_RES_SILU, 0, false>(g, st);
-    case HIG_EPI_RES: return launch_wsp<HIG_EPI_RES, 0, false>(g, st);
-    case HIG_EPI_DGELU: return launch_wsp<HIG_EPI_DGELU, 0, false>(g, st);
-    default: return 1;
-  }
+// The instance a plan names (HIG_WSP_VARIANT: XT 1 = LayerNorm-fold producer, 2 = consumer; AUX; eligibility: wsp16_variant, gemm_plan.hip).
+int hig_gemm_wsp16_launch(const hig_gemm16_desc& g, int variant, hipStream_t st) {
+  return hig_with_epi(hig_epi16_all{}, g.epi, HIG_EUNSUPPORTED, [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    if constexpr (EPI == HIG_EPI_BIAS) { if (variant == HIG_WSP_VARIANT(2, 0)) return launch_wsp<EPI, 2, false>(g, st); }
+    if constexpr (EPI == HIG_EPI_BIAS_GELU) { if (variant == HIG_WSP_VARIANT(0, 1)) return launch_wsp<EPI, 0, true>(g, st); }
+    if constexpr (EPI == HIG_EPI_BIAS_RES) { if (variant == HIG_WSP_VARIANT(1, 0)) return launch_wsp<EPI, 1, false>(g, st); }
+    return launch_wsp<EPI, 0, false>(g, st);
+  });
 }
 
 // Diagnostic: thread 0 of every workgroup writes s_memtime stamps to buf[block * 16 + k] (k: 0 start, 1 weights in registers,

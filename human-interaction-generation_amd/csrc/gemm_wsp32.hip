@@ -43,7 +43,7 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int p32_i32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int P32_MAXSEG = 3;
+constexpr int P32_MAXSEG = HIG_P32_MAXSEG;
 struct Wsp32Args {
   const float* X; int64_t ldx;
   const float* W; int64_t ldy;
@@ -527,16 +527,8 @@ int launch_p32(const hig_gemm_desc& g, hipStream_t st) {
   a.bias = g.bias;
   a.I = g.I; a.J = g.J;
   a.ntiles = (g.I + 15) / 16;
-  int np = g.J / BN, p0 = 0;
-  a.nseg = 0;
-  for (int s = 0; s < P32_MAXSEG; ++s) { a.seg_p0[s] = 0; a.seg_np[s] = 1; }
-  while (np > 0) {
-    int n = 256;
-    while (n > np) n >>= 1;
-    if (a.nseg == P32_MAXSEG) return 1;
-    a.seg_p0[a.nseg] = p0; a.seg_np[a.nseg] = n; ++a.nseg;
-    p0 += n; np -= n;
-  }
+  a.nseg = hig_wsp32_segments(g.J / BN, a.seg_p0, a.seg_np);
+  if (a.nseg < 0) return hig_set_error(HIG_EINVAL, "gemm_wsp32: %d column panels do not fit %d segments", g.J / BN, P32_MAXSEG);
   a.stats_out = g.row_stats_out;
   a.stats_in = g.row_stats_in;
   a.colsum = g.ln_colsum;
@@ -562,56 +554,34 @@ int launch_p32(const hig_gemm_desc& g, hipStream_t st) {
   return HIG_OK;
 }
 
+// The instance a plan names (HIG_WSP_VARIANT; K = 256, the text side's key/value projection (transformer.py:146,150), has the
+// plain / bias epilogues only, the fold instances exist at K = 512; eligibility: wsp32_variant, gemm_plan.hip).
 template <int KW>
-int dispatch_p32(const hig_gemm_desc& g, hipStream_t st) {
-  if constexpr (KW == 256) {   // the text side's key/value projection (transformer.py:146,150): plain / bias epilogue only
-    if (g.epi == HIG_EPI_NONE) return launch_p32<KW, HIG_EPI_NONE, 0, false>(g, st);
-    if (g.epi == HIG_EPI_BIAS && !g.row_stats_in) return launch_p32<KW, HIG_EPI_BIAS, 0, false>(g, st);
-    return 1;
-  } else {
+int dispatch_p32(const hig_gemm_desc& g, int variant, hipStream_t st) {
+  const bool aux = variant == HIG_WSP_VARIANT(0, 1);
   switch (g.epi) {
     case HIG_EPI_NONE: return launch_p32<KW, HIG_EPI_NONE, 0, false>(g, st);
     case HIG_EPI_BIAS:
-      if constexpr (KW == 512) { if (g.row_stats_in) return launch_p32<KW, HIG_EPI_BIAS, 2, false>(g, st); }
+      if constexpr (KW == 512) { if (variant == HIG_WSP_VARIANT(2, 0)) return launch_p32<KW, HIG_EPI_BIAS, 2, false>(g, st); }
       return launch_p32<KW, HIG_EPI_BIAS, 0, false>(g, st);
-    case HIG_EPI_BIAS_GELU: return g.aux ? launch_p32<KW, HIG_EPI_BIAS_GELU, 0, true>(g, st) : launch_p32<KW, HIG_EPI_BIAS_GELU, 0, false>(g, st);
-    case HIG_EPI_BIAS_RES:
-      if constexpr (KW == 512) { if (g.row_stats_out) return launch_p32<KW, HIG_EPI_BIAS_RES, 1, false>(g, st); }
-      return launch_p32<KW, HIG_EPI_BIAS_RES, 0, false>(g, st);
-    case HIG_EPI_RES: return launch_p32<KW, HIG_EPI_RES, 0, false>(g, st);
-    case HIG_EPI_DGELU: return launch_p32<KW, HIG_EPI_DGELU, 0, false>(g, st);
-    default: return 1;
   }
+  if constexpr (KW != 256) {
+    switch (g.epi) {
+      case HIG_EPI_BIAS_GELU: return aux ? launch_p32<KW, HIG_EPI_BIAS_GELU, 0, true>(g, st) : launch_p32<KW, HIG_EPI_BIAS_GELU, 0, false>(g, st);
+      case HIG_EPI_BIAS_RES:
+        if constexpr (KW == 512) { if (variant == HIG_WSP_VARIANT(1, 0)) return launch_p32<KW, HIG_EPI_BIAS_RES, 1, false>(g, st); }
+        return launch_p32<KW, HIG_EPI_BIAS_RES, 0, false>(g, st);
+      case HIG_EPI_RES: return launch_p32<KW, HIG_EPI_RES, 0, false>(g, st);
+      case HIG_EPI_DGELU: return launch_p32<KW, HIG_EPI_DGELU, 0, false>(g, st);
+    }
   }
+  return hig_set_error(HIG_EUNSUPPORTED, "gemm_wsp32: epilogue %d not built for K = %d", g.epi, KW);
 }
 
 }  // namespace
 
-// Returns HIG_OK when the launch was made, 1 when this kernel does not serve the call (the caller goes on to the tiled kernel
-// of gemm.hip), a negative HIG_E* code on error.
-bool hig_gemm_wsp32_active() {
-  static const int on = getenv("HIG_F32_WSP") ? atoi(getenv("HIG_F32_WSP")) : 1;                 // tuning knob: 0 = this kernel off
-  return on && hig_chip_cus() == 256;
-}
-int hig_gemm_wsp32_try(const hig_gemm_desc& g, hipStream_t st) {
-  constexpr int min_rows = 2048;   // below that a workgroup has < 4 tiles per segment to pay its weight phase with
-  if (!hig_gemm_wsp32_active()) return 1;
-  if (g.prec != HIG_PREC_F32 || g.x_rs || g.y_rs || g.xf != HIG_XF_NONE || g.xcolsum) return 1;
-  if (!(g.R == 256 || g.R == 512 || g.R == 1024) || g.I < min_rows) return 1;
-  const int bn = 32 * (4 / (g.R / 256));
-  if (g.J % bn != 0 || g.J / bn > 256) return 1;
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (!(g.ldx % 4 == 0 && g.ldy % 4 == 0 && g.ldc % 4 == 0 && al(g.X) && al(g.Y) && al(g.C))) return 1;
-  const int64_t lim = 1ll << 29;               // byte offsets are 32-bit
-  if ((int64_t)g.I * g.ldx >= lim || (int64_t)g.J * g.ldy >= lim || (int64_t)g.I * g.ldc >= lim) return 1;
-  const bool has_bias = p32_has_bias(g.epi), has_res = g.epi == HIG_EPI_BIAS_RES || g.epi == HIG_EPI_RES;
-  if (has_bias && !(g.bias && al(g.bias))) return 1;
-  if (has_res && !(g.res && g.ldr % 4 == 0 && al(g.res) && (int64_t)g.I * g.ldr < lim)) return 1;
-  if ((g.epi == HIG_EPI_DGELU || (g.epi == HIG_EPI_BIAS_GELU && g.aux)) && !(g.aux && g.ldaux % 4 == 0 && al(g.aux) && (int64_t)g.I * g.ldaux < lim)) return 1;
-  if (g.row_stats_out && !(g.R == 512 && g.epi == HIG_EPI_BIAS_RES && !g.row_stats_in && (reinterpret_cast<uintptr_t>(g.row_stats_out) & 7) == 0)) return 1;
-  if (g.row_stats_in && !(g.R == 512 && g.epi == HIG_EPI_BIAS && g.ln_colsum && al(g.row_stats_in) && al(g.ln_colsum))) return 1;
-  if (g.R == 256) return (g.row_stats_out || g.row_stats_in || g.aux) ? 1 : dispatch_p32<256>(g, st);
-  return g.R == 512 ? dispatch_p32<512>(g, st) : dispatch_p32<1024>(g, st);
+int hig_gemm_wsp32_launch(const hig_gemm_desc& g, int variant, hipStream_t st) {
+  return g.R == 256 ? dispatch_p32<256>(g, variant, st) : g.R == 512 ? dispatch_p32<512>(g, variant, st) : dispatch_p32<1024>(g, variant, st);
 }
 
 // Diagnostic: thread 0 (matrix wave 0) of every workgroup writes s_memtime stamps to buf[block * 16 + k] (k: 0 start, 1 weights

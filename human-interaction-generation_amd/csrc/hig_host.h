@@ -3,6 +3,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "hig_common.h"
 
 int hig_gemm_launch(const hig_gemm_desc& g, int splits, float* slabs, hipStream_t st);
@@ -52,21 +54,91 @@ int hig_wgrad16_launch_group(const hig_wg_problem* probs, int n, float* slabs, i
 int64_t hig_wgrad16_rule_floats(int64_t rows, int J, int K, int64_t room);   // slab floats the split rule takes, given `room`
 // out[e] = sum_s slabs[s * slab + e], e < n (n % 4 == 0, 16-byte aligned), in split order (gemm.hip)
 int hig_reduce_slabs(const float* slabs, int splits, int64_t slab, int64_t n, float* out, hipStream_t st);
-// weight-stationary variant (gemm_ws16.hip): HIG_OK = launched, 1 = shape not served (use the tiled kernel), < 0 = error
-int hig_gemm_ws16_try(const hig_gemm16_desc& g, hipStream_t st);
-// weight-stationary kernel with specialised matrix / service waves (gemm_wsp16.hip: K = 512, J % 128 == 0, >= 2048 rows); same codes
-int hig_gemm_wsp16_try(const hig_gemm16_desc& g, hipStream_t st);
+// ---- which kernel serves a GEMM call (gemm_plan.hip): decided apart from the launch ----
+// The GEMM switches ("Switches"), each read once per process by hig_gemm_switch_values().
+struct hig_gemm_switches {
+  int wsp16, ws16, ws_rows, ws_nwj, lnfold, lnfold1024, fewrow16, tile16;   // HIG_BF16_WSP, _WS, _WS_ROWS, _WS_NWJ, HIG_LNFOLD, HIG_LNFOLD1024, HIG_BF16_FEWROW, _TILE
+  int wsp32, tile32, tail32;                                                // HIG_F32_WSP, HIG_GEMM_TILE, HIG_GEMM_TAIL
+};
+const hig_gemm_switches& hig_gemm_switch_values();
+// rc == HIG_OK: `launches` launches of the kernel of `path` (HIG_GEMM_PATH_*; -1 and 0 launches: an empty problem) in the
+// instance `variant` names; else the error the entry point returns, with its message.
+struct hig_plan { int rc, path, launches, variant; char msg[256]; };
+#define HIG_WSP_VARIANT(xt, aux) ((xt) + 4 * ((aux) ? 1 : 0))           /* gemm_wsp16 / gemm_wsp32: the XT / AUX instance (XT 1: fold producer, 2: consumer) */
+#define HIG_WS16_VARIANT(nwj, role) ((nwj) + 256 * (role))              /* gemm_ws16: nwj code 8 / 4 / 2 / 44, fold role as XT */
+#define HIG_TILE16_VARIANT(rows, bk, ns) ((rows) * 1000 + (bk) * 10 + (ns))   /* tiled bf16 kernel: tile rows, k-tile, ring stages */
+#define HIG_TILE32_VARIANT(tile, tail) ((tile) + 16 * (tail))           /* tiled fp32 kernel: tile 0 .. 3 = 128x128, 64x128, 128x64, 64x64; tail slices (1: none) */
+hig_plan hig_gemm16_plan(const hig_gemm16_desc& g, const hig_gemm_switches& sw, int cus);
+// unsplit launches of hig_gemm_launch; tail_ws_bytes: room behind the tickets of the split-tail scratch (0: none set)
+hig_plan hig_gemm32_plan(const hig_gemm_desc& g, int64_t tail_ws_bytes, const hig_gemm_switches& sw, int cus);
 bool hig_gemm_ws16_lnfold_ok(int64_t rows, int d);
+// the launchers of the kernels a plan names (each in its kernel's file; called from hig_gemm16_launch / hig_gemm_launch only)
+int hig_gemm_wsp16_launch(const hig_gemm16_desc& g, int variant, hipStream_t st);
+int hig_gemm_ws16_launch(const hig_gemm16_desc& g, int variant, hipStream_t st);
+int hig_gemm_wsp32_launch(const hig_gemm_desc& g, int variant, hipStream_t st);
+constexpr int64_t HIG_GEMM_TAIL_UNIT_BYTES = 256 * 16 * 4;   // one workgroup's parked partial sums of a 64x64 tile
+// gemm_wsp32's column panels as at most HIG_P32_MAXSEG segments of a power-of-two panel count (<= 256 each); -1: more
+constexpr int HIG_P32_MAXSEG = 3;
+inline int hig_wsp32_segments(int np, int* seg_p0, int* seg_np) {
+  int nseg = 0, p0 = 0;
+  for (int s = 0; s < HIG_P32_MAXSEG; ++s) { seg_p0[s] = 0; seg_np[s] = 1; }
+  while (np > 0) {
+    int n = 256;
+    while (n > np) n >>= 1;
+    if (nseg == HIG_P32_MAXSEG) return -1;
+    seg_p0[nseg] = p0; seg_np[nseg] = n; ++nseg;
+    p0 += n; np -= n;
+  }
+  return nseg;
+}
+// K = 1536 / 2048 through gemm_wsp32 in two passes: C = X[:, :1024] W[:, :1024]^T (+ bias / res), then C += X[:, 1024:] W[:, 1024:]^T
+// with C as its own residual (a lane re-reads exactly the element it stores two tiles later)
+inline void hig_gemm32_two_pass(const hig_gemm_desc& g, hig_gemm_desc* p1, hig_gemm_desc* p2) {
+  *p1 = g; p1->R = 1024;
+  *p2 = g; p2->X = g.X + 1024; p2->Y = g.Y + 1024; p2->R = g.R - 1024;
+  p2->epi = HIG_EPI_RES; p2->bias = nullptr; p2->res = g.C; p2->ldr = g.ldc;
+}
+// the vector-load form of the tiled fp32 kernel: aligned operands, whole k-tiles, whole float4 quads of a reduce-slow operand
+inline bool hig_gemm32_fast(const hig_gemm_desc& g) {
+  auto vec = [](const void* p, int64_t ld) { return ld % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  return vec(g.X, g.ldx) && vec(g.Y, g.ldy) && g.R % 32 == 0 && g.R > 0 && (!g.x_rs || (g.I % 4 == 0 && g.I >= 4)) && (!g.y_rs || (g.J % 4 == 0 && g.J >= 4));
+}
+// the (x_rs, y_rs, xf, xf_on_y, epi) combinations the tiled fp32 kernel is built for
+#ifdef HIG_GEMM_PROBE  // compile-time aid: build a single combination
+#define HIG_GEMM32_COMBOS(CASE) CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_BIAS_GELU)
+#else
+#define HIG_GEMM32_COMBOS(CASE)                                                                                       \
+  /* forward (activations x weight^T) */                                                                              \
+  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_NONE) CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_BIAS) CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_BIAS_GELU) \
+  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_BIAS_POS) CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_BIAS_RES)                           \
+  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_RES) /* dgrad through a transposed weight copy */                                \
+  CASE(0, 0, HIG_XF_NONE, 0, HIG_EPI_DGELU) CASE(0, 0, HIG_XF_LN, 0, HIG_EPI_BIAS) CASE(0, 0, HIG_XF_LN_MOD_SILU, 0, HIG_EPI_BIAS_RES) \
+  CASE(0, 0, HIG_XF_SILU, 0, HIG_EPI_BIAS) CASE(0, 0, HIG_XF_SILU, 0, HIG_EPI_BIAS_RES)                               \
+  CASE(0, 0, HIG_XF_SILU, 0, HIG_EPI_NONE) /* split-R partials of the few-row GEMMs */                                \
+  /* dgrad (dC x weight) */                                                                                           \
+  CASE(0, 1, HIG_XF_NONE, 0, HIG_EPI_NONE) CASE(0, 1, HIG_XF_NONE, 0, HIG_EPI_RES) CASE(0, 1, HIG_XF_NONE, 0, HIG_EPI_DGELU) \
+  /* wgrad (dC^T x activations) */                                                                                    \
+  CASE(1, 1, HIG_XF_NONE, 0, HIG_EPI_NONE) CASE(1, 1, HIG_XF_LN, 1, HIG_EPI_NONE) CASE(1, 1, HIG_XF_LN_MOD_SILU, 1, HIG_EPI_NONE) \
+  CASE(1, 1, HIG_XF_SILU, 1, HIG_EPI_NONE)
+#endif
+// "instantiate this launcher for the runtime epilogue": f(std::integral_constant<int, E>) for the E of the list that equals
+// `epi`; `none` when the list does not hold it
+template <int... E> struct hig_epi_list {};
+using hig_epi16_fewrow = hig_epi_list<HIG_EPI_NONE, HIG_EPI_BIAS, HIG_EPI_BIAS_GELU, HIG_EPI_BIAS_RES, HIG_EPI_BIAS_SILU, HIG_EPI_BIAS_RES_SILU>;
+using hig_epi16_all = hig_epi_list<HIG_EPI_NONE, HIG_EPI_BIAS, HIG_EPI_BIAS_GELU, HIG_EPI_BIAS_RES, HIG_EPI_BIAS_SILU, HIG_EPI_BIAS_RES_SILU, HIG_EPI_RES, HIG_EPI_DGELU>;
+template <int... E, class F>
+int hig_with_epi(hig_epi_list<E...>, int epi, int none, F&& f) {
+  int rc = none;
+  (void)(((epi == E) && ((rc = f(std::integral_constant<int, E>{})), true)) || ...);
+  return rc;
+}
 // linattn.hip: context build of G groups of H heads in one launch (the batched text side); 1 = shape not served
 int hig_linattn_ctx_groups(const float* K, const float* V, int64_t ld, int32_t B, int32_t rows, int32_t H, int32_t G, int32_t hd,
                            float* A, int64_t a_gs, float* kstat, int64_t k_gs, hipStream_t st);
 int hig_linattn_ctx16_groups(const void* K, const void* V, int64_t ld, int32_t B, int32_t rows, int32_t H, int32_t G, int32_t hd,
                              float* A, int64_t a_gs, float* kstat, int64_t k_gs, void* At16, int64_t at_gs, hipStream_t st);   // (linattn16.hip, bf16 rows)
-// exact-fp32 weight-stationary kernel with specialised waves (gemm_wsp32.hip: K = 256 / 512 / 1024, reduce-contiguous aligned
-// operands, >= 2048 rows); same return codes
-int hig_gemm_wsp32_try(const hig_gemm_desc& g, hipStream_t st);
 // weight gradients dW = dC^T . act over >= 2048 rows, I and J multiples of 128, tiles x splits <= 256 (wgrad_wsp32.hip): writes
-// the split-R slabs (+ per-split column sums of dC) of hig_gemm_launch(splits > 1); same return codes
+// the split-R slabs (+ per-split column sums of dC) of hig_gemm_launch(splits > 1); HIG_OK = launched, 1 = shape not served, < 0 = error
 int hig_wgrad_wsp32_try(const hig_gemm_desc& g, int splits, float* slabs, int64_t slab, float* xsum, int64_t xsum_stride, hipStream_t st);
 bool hig_gemm_wsp32_active();   // that kernel is switched on and the chip has the 256 CUs its work split is written for
 
@@ -102,11 +174,9 @@ struct G {  // small builder for gemm descriptors
 // Weight-gradient GEMMs (dW = dC^T . act over the M rows).  Tile: exact-fp32 products run 64x64 tiles (four resident
 // workgroups per CU, 4x fewer split-R slabs to write and sum than with 128x128: forward+backward 20.6 -> 20.2 ms),
 // the bf16 product modes 128x128 (14.9 vs 15.2 ms bf16x3, 12.9 vs 13.5 ms bf16) -- same-box sweeps in
-// profiles/r01_notes.md.  HIG_WGRAD_TILE = 64 / 128 forces one.
+// profiles/r01_notes.md.
 inline int wgrad_tile(int64_t I, int64_t J, int prec) {
-  constexpr int forced = 0;   // (a former tuning knob, fixed at the value that won its A/B)
   if (!(I > 64 && J > 64)) return 64;
-  if (forced == 64 || forced == 128) return forced;
   return prec == HIG_PREC_F32 ? 64 : 128;
 }
 
@@ -116,8 +186,7 @@ inline int wgrad_tile(int64_t I, int64_t J, int prec) {
 inline int wgrad_splits(int64_t I, int64_t J, int64_t R, int64_t slab_floats, int prec) {
   const int bi = wgrad_tile(I, J, prec);
   const int64_t tiles = ((I + bi - 1) / bi) * ((J + bi - 1) / bi);
-  constexpr int forced_target = 0;  // (a former tuning knob, fixed at the value that won its A/B)
-  const int target = forced_target > 0 ? forced_target : (bi == 128 ? 2 : 4) * hig_chip_cus();
+  const int target = (bi == 128 ? 2 : 4) * hig_chip_cus();
   int64_t s = target / tiles;
   const int64_t maxs = R / 256 > 1 ? R / 256 : 1;
   if (s > maxs) s = maxs;

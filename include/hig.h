@@ -628,6 +628,22 @@ int64_t hig_gemm_wsp32_launches(void);
 #define HIG_GEMM_PATH_WGRAD16 10      /* hig_wgrad_bf16: wgrad16.hip */
 #define HIG_GEMM_NPATHS 11
 int64_t hig_gemm_path_launches(int32_t path);
+/* What a GEMM call would do, without doing it (csrc/gemm_plan.hip: the entry points plan, then launch what the plan names):
+ * the return value is the code the call would return (a refusal: *path = -1, *launches = 0); *path the HIG_GEMM_PATH_* whose
+ * counter would move (-1 for an empty problem), *launches by how much (2: the two-pass form of gemm_wsp32), *variant the
+ * instance of that kernel:
+ *   WSP16 / WSP32      XT + 4 AUX   (XT 1: LayerNorm-fold producer, 2: consumer; AUX: the pre-activation output)
+ *   WS16               nwj + 256 XT (nwj 8 / 4 / 2 / 44: waves x column slices of a workgroup, 44 = two 4-wave workgroups per CU)
+ *   TILED16            1000 tile rows + 10 k-tile + ring stages (e.g. 64643)
+ *   TILED32 / TAIL32   tile + 16 tail slices (tile 0 .. 3 = 128x128, 64x128, 128x64, 64x64; 1 slice: no split tail)
+ * Pure functions of the descriptor, the environment switches and the CU count: no launch, no error message, and operand
+ * pointers are read for null-ness and alignment only, never dereferenced (the out pointers may be NULL).  chip_cus <= 0: the
+ * current device's.  has_tail_scratch: plan as hig_gemm_ws with its scratch does, else as hig_gemm.
+ * hig_gemm_bf16_lnfold_plan: 1 when the bf16 forward folds its d-wide LayerNorms into the GEMMs over `rows` rows, i.e. when
+ * every launch of the fold plans onto WSP16 / WS16 (HIG_LNFOLD, HIG_LNFOLD1024), else 0. */
+int hig_gemm_bf16_plan(const hig_gemm16_desc* g, int32_t chip_cus, int32_t* path, int32_t* launches, int32_t* variant);
+int hig_gemm_plan(const hig_gemm_desc* g, int32_t has_tail_scratch, int32_t chip_cus, int32_t* path, int32_t* launches, int32_t* variant);
+int hig_gemm_bf16_lnfold_plan(int64_t rows, int32_t d, int32_t chip_cus);
 /* Attention paths: one per kernel the linear- and full-attention entry points below (csrc/linattn.hip, csrc/fullattn.hip) can
  * launch; the fp32 and bf16-I/O instances of one kernel share a path.  hig_attn_path_launches(path) counts the launches of that
  * kernel since the library was loaded (monotonic, host side, one relaxed atomic add at the launch site; the chunk_sum_kernel

@@ -5,6 +5,7 @@
 // (csrc/Makefile: every .hip compiled --cuda-host-only with -fsanitize=address,undefined) and run by
 // tests/test_cpu_host.py::test_host_entry_points_under_asan_ubsan.
 #include <initializer_list>
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -151,6 +152,50 @@ int main() {
     EXPECT(hig_cast_bf16(nullptr, nullptr, 8, nullptr) != HIG_OK);
     EXPECT(hig_cast_bf16(dummy, b16, 0, nullptr) == HIG_OK);
     EXPECT(hig_joint_embed_bf16(nullptr, 4, 150, nullptr, nullptr, nullptr, 512, 196, 0, nullptr, 512, 512, nullptr, nullptr) != HIG_OK);
+  }
+  // ---- GEMM plan entries: pure host functions; null, misaligned, zero, negative and huge arguments, never a dereference ----
+  {
+    int32_t path = 0, launches = 0, variant = 0;
+    EXPECT(hig_gemm_bf16_plan(nullptr, 256, &path, &launches, &variant) == HIG_EINVAL);
+    EXPECT(hig_gemm_plan(nullptr, 1, 256, &path, &launches, &variant) == HIG_EINVAL);
+    const uintptr_t base = (uintptr_t)1 << 32;                       // made-up addresses: nothing may read through them
+    const int extents[] = {-5, 0, 1, 64, 65, 200, 512, 2047, 2048, 12544, INT32_MAX};
+    const int64_t lds[] = {-8, 0, 8, 512, 516, 520, (int64_t)1 << 20, (int64_t)1 << 40, INT64_MAX};
+    int served = 0, refused = 0;
+    for (int I : extents) for (int J : extents) for (int R : {-32, 0, 32, 192, 256, 512, 1024, 1536, 2048, INT32_MAX}) for (int64_t ld : lds)
+      for (int epi = -1; epi <= 9; ++epi) for (int mis : {0, 2, 8}) for (int cus : {128, 256}) {
+        hig_gemm16_desc h;
+        memset(&h, 0, sizeof(h));
+        h.X = reinterpret_cast<const void*>(base); h.Y = reinterpret_cast<const void*>(2 * base); h.C = reinterpret_cast<void*>(3 * base + mis);
+        h.ldx = ld; h.ldy = ld; h.ldc = ld; h.ldr = ld; h.ldaux = ld; h.I = I; h.J = J; h.R = R; h.epi = epi;
+        h.c_f32 = mis == 2; h.res_f32 = mis == 8;
+        if (epi & 1) h.bias = reinterpret_cast<const float*>(4 * base);
+        if (epi & 2) h.res = reinterpret_cast<const void*>(5 * base + mis);
+        if (epi == 2 && mis) h.aux = reinterpret_cast<void*>(6 * base);
+        if (epi == 3 && mis == 2) h.row_stats_out = reinterpret_cast<float*>(7 * base);
+        if (epi == 1 && mis == 2) { h.row_stats_in = reinterpret_cast<const float*>(7 * base); h.ln_colsum = mis ? reinterpret_cast<const float*>(8 * base) : nullptr; }
+        int rc = hig_gemm_bf16_plan(&h, cus, &path, &launches, &variant);
+        EXPECT((rc == HIG_OK && launches >= 0 && launches <= 1 && (launches == 0) == (path == -1)) || (rc < 0 && launches == 0 && path == -1));
+        rc == HIG_OK ? ++served : ++refused;
+        hig_gemm_desc g;
+        memset(&g, 0, sizeof(g));
+        g.X = reinterpret_cast<const float*>(base); g.Y = reinterpret_cast<const float*>(2 * base); g.C = reinterpret_cast<float*>(3 * base + mis);
+        g.ldx = ld; g.ldy = ld; g.ldc = ld; g.ldr = ld; g.ldaux = ld; g.I = I; g.J = J; g.R = R; g.epi = epi;
+        g.x_rs = mis == 8 && (epi & 1); g.y_rs = mis == 8;
+        if (epi & 1) g.bias = reinterpret_cast<const float*>(4 * base);
+        if (epi & 2) g.res = reinterpret_cast<const float*>(5 * base + mis);
+        if (epi == 2 || epi == 6) g.aux = reinterpret_cast<float*>(6 * base);
+        if (epi == 3 && mis == 2) g.row_stats_out = reinterpret_cast<float*>(7 * base);
+        if (epi == 1 && mis == 2) { g.row_stats_in = reinterpret_cast<const float*>(7 * base); g.ln_colsum = reinterpret_cast<const float*>(8 * base); }
+        rc = hig_gemm_plan(&g, mis == 0, cus, &path, &launches, nullptr);
+        EXPECT((rc == HIG_OK && launches >= 0 && launches <= 2 && (launches == 0) == (path == -1)) || (rc < 0 && launches == 0 && path == -1));
+      }
+    EXPECT(served > 1000 && refused > 1000);
+    EXPECT(hig_gemm_bf16_plan(nullptr, 0, nullptr, nullptr, nullptr) == HIG_EINVAL && hig_gemm_plan(nullptr, 0, 0, nullptr, nullptr, nullptr) == HIG_EINVAL);
+    for (int64_t rows : {(int64_t)-1, (int64_t)0, (int64_t)2048, (int64_t)12544, (int64_t)1 << 40, INT64_MAX})
+      for (int d : {-512, 0, 256, 500, 512, 1024, INT32_MAX})
+        EXPECT((hig_gemm_bf16_lnfold_plan(rows, d, 256) | 1) == 1);
+    EXPECT(hig_gemm_bf16_lnfold_plan(12544, 512, 256) == 1 && hig_gemm_bf16_lnfold_plan(12544, 512, 128) == 0);
   }
   // ---- diagnostics pointers: set and cleared ----
   EXPECT(hig_gemm_bf16_debug_stamps(nullptr) == HIG_OK && hig_gemm_ws16_debug_stamps(nullptr) == HIG_OK &&

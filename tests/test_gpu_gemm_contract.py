@@ -3,7 +3,8 @@ element-wise bound against fp64.
 
 Every call goes through `run`, which
   - asserts that exactly the expected HIG_GEMM_PATH_* counters moved (hig_gemm_path_launches; two launches for the
-    two-pass K > 1024 form of the fp32 weight-stationary kernel);
+    two-pass K > 1024 form of the fp32 weight-stationary kernel), and that the plan entry (hig_gemm_bf16_plan /
+    hig_gemm_plan), asked before the call, named exactly those;
   - fills C (and `aux`) with a NaN pattern first and checks that every output was written;
   - puts C inside guard rows above and below, and guard columns where ldc > J, and checks they kept their bits.
 `check` then holds every element to a bound computed from the operands in fp64:
@@ -24,14 +25,11 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from hig_amd import _lib  # noqa: E402
+from gemm_dispatch_cases import (BIAS, BIAS_RES, DGELU, DISPATCH, GELU, HAS_BIAS, HAS_RES, NONE, PATHS, RES, RES_SILU, SILU,  # noqa: E402
+                                 UNSERVED, dispatch_uses_aux, plan)
 
 DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PATHS = ("TILED32", "WSP32", "TAIL32", "WGRAD_WSP32", "SPLIT32", "WSP16", "WS16", "FEWROW16", "TILED16", "SPLIT16", "WGRAD16")
-NONE, BIAS, GELU, BIAS_RES, RES, DGELU, SILU, RES_SILU = (_lib.EPI_NONE, _lib.EPI_BIAS, _lib.EPI_BIAS_GELU, _lib.EPI_BIAS_RES,
-                                                           _lib.EPI_RES, _lib.EPI_DGELU, _lib.EPI_BIAS_SILU, _lib.EPI_BIAS_RES_SILU)
-HAS_BIAS = (BIAS, GELU, BIAS_RES, SILU, RES_SILU)
-HAS_RES = (BIAS_RES, RES, DGELU, RES_SILU)
 SENTINEL = {torch.float32: (torch.int32, 0x7FC0BEEF), torch.bfloat16: (torch.int16, 0x7FD5)}   # NaN patterns
 
 # the element-wise bounds of the activation epilogues (include/hig.h, next to HIG_EPI_BIAS_GELU / _DGELU / _BIAS_SILU)
@@ -50,13 +48,18 @@ def counts():
     return [lib().hig_gemm_path_launches(getattr(_lib, "GEMM_PATH_" + n)) for n in PATHS]
 
 
-def counted(call, expect):
-    """call() -> rc; asserts rc == 0 and that exactly the path counters in `expect` ({name: launches}) moved."""
+def counted(call, expect, planned=None):
+    """call() -> rc; asserts rc == 0 and that exactly the path counters in `expect` ({name: launches}) moved.  planned:
+    (entry, descriptor) of the call where a plan entry covers it -- the plan, asked BEFORE the call, must have named exactly
+    the counters that moved."""
+    foreseen = plan(*planned) if planned else None
     before = counts()
     _lib.check(call())
     torch.cuda.synchronize()
     moved = {n: a - b for n, a, b in zip(PATHS, counts(), before) if a != b}
     assert moved == expect, "expected launches %s, got %s" % (expect, moved)
+    if planned:
+        assert foreseen[0] == 0 and foreseen[1] == moved, "the plan named %s (rc %d), the call moved %s" % (foreseen[1], foreseen[0], moved)
 
 
 def ulp16(r):
@@ -151,7 +154,7 @@ def run(entry, X, W, expect, epi=NONE, bias=None, res=None, c_f32=None, ldc=None
     else:
         d = desc16(X, W, optr, ldc_, int(c_f32), I, J, K, epi, bias, res_, aux)
         call = lambda: lib().hig_gemm_bf16(C.byref(d), _lib.stream_ptr())  # noqa: E731
-    counted(call, expect)
+    counted(call, expect, (entry, d))
     if g is not None:
         g.verify()
         out = g.out
@@ -244,56 +247,18 @@ def operands(entry, I, J, K, epi, seed, res_f32=False):
     return X, W, bias, res
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# dispatch table: (entry, I, J, K, epilogue, c_f32, res_f32, ldc) -> the path it must take.  The edges of every `_try` rule:
-# min_rows (2047 / 2048), few rows (64 / 65), K in {256, 512, 1024, 1536}, J % 128 != 0, fp32 C / residual, ldc % 8 != 0.
-# ---------------------------------------------------------------------------------------------------------------------
-DISPATCH = [
-    ("bf16", 2048, 512, 512, BIAS, 0, 0, None, {"WSP16": 1}),
-    ("bf16", 2047, 512, 512, BIAS, 0, 0, None, {"TILED16": 1}),
-    ("bf16", 2048, 512, 512, BIAS, 0, 0, 520, {"WSP16": 1}),              # guard columns, ldc % 8 == 0
-    ("bf16", 2048, 512, 512, BIAS_RES, 0, 0, 516, {"TILED16": 1}),        # ldc % 8 != 0
-    ("bf16", 2048, 512, 512, BIAS, 1, 0, None, {"TILED16": 1}),           # fp32 C
-    ("bf16", 2048, 512, 512, BIAS_RES, 0, 1, None, {"TILED16": 1}),       # fp32 residual
-    ("bf16", 2048, 384, 512, DGELU, 0, 0, None, {"WSP16": 1}),
-    ("bf16", 2048, 512, 512, GELU, 0, 0, None, {"WSP16": 1}),             # with the pre-activation `aux`
-    ("bf16", 2048, 256, 512, RES_SILU, 0, 0, None, {"WSP16": 1}),
-    ("bf16", 2048, 512, 256, GELU, 0, 0, None, {"WS16": 1}),
-    ("bf16", 2047, 512, 256, GELU, 0, 0, None, {"TILED16": 1}),
-    ("bf16", 2048, 384, 1024, BIAS_RES, 0, 0, None, {"WS16": 1}),
-    ("bf16", 3000, 512, 1536, BIAS, 0, 0, None, {"TILED16": 1}),
-    ("bf16", 2048, 200, 512, BIAS, 0, 0, None, {"TILED16": 1}),           # J % 128 != 0
-    ("bf16", 64, 512, 256, BIAS_RES, 0, 0, None, {"FEWROW16": 1}),
-    ("bf16", 65, 512, 256, BIAS_RES, 0, 0, None, {"TILED16": 1}),
-    ("bf16", 64, 512, 192, SILU, 0, 0, None, {"TILED16": 1}),             # K < 256
-    ("bf16", 40, 1024, 2048, NONE, 1, 0, None, {"FEWROW16": 1}),
-    ("bf16", 33, 96, 320, GELU, 0, 0, 104, {"FEWROW16": 1}),
-    ("f32", 2048, 512, 512, BIAS, 1, 0, None, {"WSP32": 1}),
-    ("f32", 2047, 512, 512, BIAS, 1, 0, None, {"TILED32": 1}),
-    ("f32", 2048, 512, 256, NONE, 1, 0, None, {"WSP32": 1}),
-    ("f32", 2048, 512, 1024, BIAS_RES, 1, 0, 520, {"WSP32": 1}),
-    ("f32", 2048, 512, 1536, BIAS_RES, 1, 0, None, {"WSP32": 2}),         # two passes over the reduce range
-    ("f32", 2048, 512, 1280, BIAS, 1, 0, None, {"TILED32": 1}),
-    ("f32", 2048, 200, 512, BIAS, 1, 0, None, {"TILED32": 1}),
-    ("f32", 2048, 512, 512, RES, 1, 0, 514, {"TILED32": 1}),              # ldc % 4 != 0
-    ("f32", 2048, 256, 512, GELU, 1, 0, None, {"WSP32": 1}),
-    ("f32", 2048, 256, 512, DGELU, 1, 0, None, {"WSP32": 1}),
-    ("ws", 2047, 576, 768, BIAS_RES, 1, 0, None, {"TAIL32": 1}),          # 288 64x64 tiles: the last round of 32 is cut along K
-    ("f32", 2047, 576, 768, BIAS_RES, 1, 0, None, {"TILED32": 1}),
-]
-
-
+# the dispatch table (DISPATCH) and the unserved cases (UNSERVED): tests/gemm_dispatch_cases.py, shared with tests/test_cpu_gemm_plan.py
 @pytest.mark.parametrize("entry,I,J,K,epi,c_f32,res_f32,ldc,expect", DISPATCH)
 def test_dispatch_table(entry, I, J, K, epi, c_f32, res_f32, ldc, expect):
     X, W, bias, res = operands(entry, I, J, K, epi, seed=I + 3 * J + 7 * K + epi, res_f32=res_f32)
     if epi == DGELU and entry != "bf16":   # the fp32 entry takes z through `aux`
         g = Guarded(I, J, ldc or J, torch.float32)
         d = desc32(X, W, g.ptr(), ldc or J, I, J, K, epi, None, None, res)
-        counted(lambda: lib().hig_gemm(C.byref(d), _lib.stream_ptr()), expect)
+        counted(lambda: lib().hig_gemm(C.byref(d), _lib.stream_ptr()), expect, ("f32", d))
         g.verify()
         check_gemm(g.out, X, W, DGELU, res=res, what=str(expect))
         return
-    with_aux = epi == GELU and (entry != "bf16" or "WSP16" in expect)
+    with_aux = dispatch_uses_aux(entry, epi, expect)
     out, ax = run(entry, X, W, expect, epi, bias, res, c_f32, ldc, with_aux=with_aux)
     check_gemm(out, X, W, epi, bias, res, ax, what=str(expect))
 
@@ -321,24 +286,22 @@ def test_split_forms_dispatch(I, J, R, splits, expect):
 
 
 def test_unserved_fold_and_aux_operands_raise():
-    """LayerNorm-fold operands / a bf16 `aux` on a shape no kernel that implements them serves: an error, no launch."""
-    X, W, bias, res = operands("bf16", 2047, 512, 512, BIAS_RES, seed=5)
-    gen = torch.Generator(device=DEV).manual_seed(6)
-    out = torch.empty(2047, 512, device=DEV, dtype=torch.bfloat16)
-    stats = torch.empty(2047, 4, 2, device=DEV)
-    d = desc16(X, W, out.data_ptr(), 512, 0, 2047, 512, 512, BIAS_RES, bias, res, None)
-    d.row_stats_out = stats.data_ptr()
+    """LayerNorm-fold operands / a bf16 `aux` on a shape no kernel that implements them serves (UNSERVED): an error, no launch --
+    and the plan says so beforehand."""
     before = counts()
-    assert lib().hig_gemm_bf16(C.byref(d), _lib.stream_ptr()) == -3
-    aux = torch.empty_like(out)
-    d = desc16(X, W, out.data_ptr(), 512, 0, 2047, 512, 512, GELU, bias, None, aux)
-    assert lib().hig_gemm_bf16(C.byref(d), _lib.stream_ptr()) == -3
-    X32, W32 = rnd(2048, 512, gen=gen), rnd(200, 512, gen=gen)
-    r32, b32 = rnd(2048, 200, gen=gen), rnd(200, gen=gen)
-    o32 = torch.empty(2048, 200, device=DEV)
-    d = desc32(X32, W32, o32.data_ptr(), 200, 2048, 200, 512, BIAS_RES, b32, r32, None)
-    d.row_stats_out = stats.data_ptr()
-    assert lib().hig_gemm(C.byref(d), _lib.stream_ptr()) == -3
+    for entry, I, J, K, epi, operand in UNSERVED:
+        X, W, bias, res = operands(entry, I, J, K, epi, seed=5)
+        out = torch.empty(I, J, device=DEV, dtype=torch.bfloat16 if entry == "bf16" else torch.float32)
+        extra = torch.empty(I, max(J, 8), device=DEV, dtype=torch.float32 if operand == "stats_out" else out.dtype)
+        if entry == "bf16":
+            d = desc16(X, W, out.data_ptr(), J, 0, I, J, K, epi, bias, res, extra if operand == "aux" else None)
+        else:
+            d = desc32(X, W, out.data_ptr(), J, I, J, K, epi, bias, res, None)
+        if operand == "stats_out":
+            d.row_stats_out = extra.data_ptr()
+        assert plan(entry, d)[:2] == (-3, {}), (entry, I, J, K, epi, operand)
+        call = lib().hig_gemm_bf16 if entry == "bf16" else lib().hig_gemm
+        assert call(C.byref(d), _lib.stream_ptr()) == -3, (entry, I, J, K, epi, operand)
     torch.cuda.synchronize()
     assert counts() == before
 
@@ -532,7 +495,7 @@ def test_f32_gelu_and_dgelu_over_a_dense_grid(path, I, J, K):
     g = Guarded(I, J, J, torch.float32)
     ones = torch.ones(J, K, device=DEV)
     d = desc32(X, ones, g.ptr(), J, I, J, K, DGELU, None, None, z)
-    counted(lambda: lib().hig_gemm(C.byref(d), _lib.stream_ptr()), {path: 1})
+    counted(lambda: lib().hig_gemm(C.byref(d), _lib.stream_ptr()), {path: 1}, ("f32", d))
     g.verify()
     ref = dgelu64(z.double())
     check(g.out, ref, act_bound(DGELU, z.double(), ref, False), "%s dgelu" % path)
