@@ -40,6 +40,12 @@ STORE_F32, STORE_BF16 = 0, 1
  ATTN_PATH_APPLY_STY, ATTN_PATH_APPLY_STY_WAVE64, ATTN_PATH_APPLY_BWD, ATTN_PATH_APPLY_BWD_MFMA, ATTN_PATH_CTX_BWD,
  ATTN_PATH_CTX_BWD_MFMA, ATTN_PATH_FULL_FWD, ATTN_PATH_FULL_FWD_MFMA, ATTN_PATH_FULL_BWD, ATTN_PATH_FULL_BWD_MFMA,
  ATTN_NPATHS) = range(17)
+# what hig_attn_plan is asked: the entry point, its I/O type and the operand facts it reads
+(ATTN_ENTRY_CTX, ATTN_ENTRY_APPLY, ATTN_ENTRY_APPLY_STY, ATTN_ENTRY_APPLY_BWD, ATTN_ENTRY_CTX_BWD, ATTN_ENTRY_FULL_FWD,
+ ATTN_ENTRY_FULL_BWD) = range(7)
+ATTN_IO_F32, ATTN_IO_BF16 = 0, 1
+(ATTN_FACT_IN8, ATTN_FACT_IN16, ATTN_FACT_OUT8, ATTN_FACT_OUT16, ATTN_FACT_PAR16, ATTN_FACT_OUT_I32, ATTN_FACT_OPERANDS,
+ ATTN_FACTS_ALL) = 1, 2, 4, 8, 16, 32, 64, 127
 TAB_ROWS = 7
 NORM_BLOCKS = 1024
 COLSUM_CHUNKS = 512
@@ -63,7 +69,7 @@ SYMBOLS = (
     "hig_linattn_apply_bwd_bf16", "hig_linattn_ctx_bwd_bf16", "hig_colsum_bf16", "hig_transpose_bf16_batch", "hig_transpose_bf16",
     "hig_gelu_bf16", "hig_cast_f32", "hig_cast_pad_bf16", "hig_gemm_bf16_split", "hig_gemm_bf16_split_scratch_floats", "hig_clip_adam_shadow",
     "hig_debug_marker", "hig_denoiser_fwd_text", "hig_wgrad_bf16", "hig_wgrad_bf16_scratch_floats", "hig_denoiser_fwd_x", "hig_denoiser_fwd_bf16_x",
-    "hig_gemm_bf16_plan", "hig_gemm_plan", "hig_gemm_bf16_lnfold_plan",
+    "hig_gemm_bf16_plan", "hig_gemm_plan", "hig_gemm_bf16_lnfold_plan", "hig_attn_plan",
 )
 
 
@@ -197,6 +203,7 @@ def lib():
         L.hig_gemm_bf16_plan.argtypes = [C.POINTER(Gemm16Desc), i32, pi32, pi32, pi32]
         L.hig_gemm_plan.argtypes = [C.POINTER(GemmDesc), i32, i32, pi32, pi32, pi32]
         L.hig_gemm_bf16_lnfold_plan.argtypes = [i64, i32, i32]
+        L.hig_attn_plan.argtypes = [i32] * 11 + [pi32, pi32, pi32]
         L.hig_attn_path_launches.argtypes = [i32]
         L.hig_attn_path_launches.restype = i64
         L.hig_attn_last_split.argtypes = []

@@ -16,9 +16,7 @@
 //  * head dim 8 / 16 / 32 (small test models): the VALU kernels that follow -- one workgroup = (sample, head, 64-row
 //    chunk); thread (row = tid>>2, part = tid&3) scores its row against keys {part, part+4, ...} of each staged 64-key
 //    chunk, the 4 lanes of a row combine by shuffles, probabilities cross lanes through a 64x64 LDS tile.
-#include "hig_common.h"
-
-void hig_attn_path_count(int path, int split);   // linattn.hip: one launch of the kernel of HIG_ATTN_PATH_* `path`
+#include "hig_host.h"   // the plan of every entry point (attn_plan.hip)
 
 namespace {
 
@@ -630,29 +628,13 @@ __global__ __launch_bounds__(64 * NW) void full_bwd_kv_mfma_kernel(const float* 
   }
 }
 
-// HIG_FULLATTN_VALU=1 keeps head dim 64 on the VALU kernels (A/B measurements); head dim 128 is matrix-core only
-// Waves per workgroup of the matrix-core kernels (tuning knob HIG_FULLATTN_WAVES = 2 / 4 / 8).  From the sweep in
-// profiles/r02_attn_sweep.md: 8 waves (256 rows share each staged 32-row chunk; <= 256 registers per lane, two waves
-// per SIMD) win the forward at both head dims and the backward at head dim 64; the head-dim-128 backward needs more
-// than 256 registers per lane (it spills at 8) and is fastest at 4.
-int mfma_waves(bool backward, int hd) {
-  static const int forced = [] { const char* e = getenv("HIG_FULLATTN_WAVES"); const int v = e ? atoi(e) : 0; return (v == 2 || v == 4 || v == 8) ? v : 0; }();
-  if (forced) return forced;
-  return (backward && hd == 128) ? 4 : 8;
-}
-#define FNW_SWITCH(BWD, HDIM, ...)                           \
-  switch (mfma_waves(BWD, HDIM)) {                           \
+// waves per workgroup of the matrix-core kernels: the plan's variant (full_waves, attn_plan.hip)
+#define FNW_SWITCH(WAVES, ...)                               \
+  switch (WAVES) {                                           \
     case 2: { constexpr int NWV = 2; __VA_ARGS__; } break;   \
     case 8: { constexpr int NWV = 8; __VA_ARGS__; } break;   \
     default: { constexpr int NWV = 4; __VA_ARGS__; } break;  \
   }
-bool use_mfma(int hd) {
-  static const bool valu = [] { const char* e = getenv("HIG_FULLATTN_VALU"); return e && atoi(e) != 0; }();
-  return hd == 128 || (hd == 64 && !valu);
-}
-
-bool full_hd_ok(int hd) { return hd == 8 || hd == 16 || hd == 32 || hd == 64 || hd == 128; }
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 #define FHD_SWITCH(hd, STMT)                            \
   switch (hd) {                                         \
@@ -661,6 +643,26 @@ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
     case 32: { constexpr int HDV = 32; STMT; } break;   \
     default: { constexpr int HDV = 64; STMT; } break;   \
   }
+
+uintptr_t bits(int es, int64_t ld) { return hig_low_bits(ld, es); }
+template <class... P> uintptr_t bits(int es, int64_t ld, const void* p, P... more) { return hig_low_bits(p) | bits(es, ld, more...); }
+
+// HIG_ATTN_PATH_FULL_FWD_MFMA: p.variant waves per workgroup, p.split query blocks of 32 rows per wave
+template <typename TIO>
+int launch_fwd_mfma(const hig_attn_plan_t& p, const TIO* Q, int64_t ldq, const TIO* K, const TIO* V, int64_t ldk, int32_t B, int32_t Tq,
+                    int32_t Tk, int32_t H, int32_t hd, const int64_t* qlen, const uint8_t* kpad, TIO* Y, int64_t ldy, float* lse,
+                    hipStream_t st) {
+  FNW_SWITCH(p.variant, {
+    if (hd == 128)
+      hipLaunchKernelGGL((full_fwd_mfma_kernel<128, NWV, TIO>), dim3(B * H, p.split), dim3(64 * NWV), 0, st, Q, ldq, K, V, ldk, Tq, Tk, H, qlen,
+                         kpad, Y, ldy, lse);
+    else
+      hipLaunchKernelGGL((full_fwd_mfma_kernel<64, NWV, TIO>), dim3(B * H, p.split), dim3(64 * NWV), 0, st, Q, ldq, K, V, ldk, Tq, Tk, H, qlen,
+                         kpad, Y, ldy, lse);
+  });
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
 
 }  // namespace
 
@@ -674,28 +676,13 @@ extern "C" int hig_fullattn_fwd_kpad(const float* Q, int64_t ldq, const float* K
                                      int32_t B, int32_t Tq, int32_t Tk, int32_t H, int32_t hd,
                                      const int64_t* qlen, const uint8_t* kpad, float* Y, int64_t ldy, float* lse,
                                      hig_stream_t stream) {
-  HIG_REQUIRE(Q && K && V && Y && lse && B > 0 && Tq > 0 && Tk > 0 && H > 0, "hig_fullattn_fwd: bad arguments");
-  if (!full_hd_ok(hd))
-    return hig_set_error(HIG_EUNSUPPORTED, "hig_fullattn: head dim %d not in {8,16,32,64,128}", hd);
-  HIG_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldy % 4 == 0 && al16(Q) && al16(K) && al16(V) && al16(Y),
-              "hig_fullattn_fwd: operands must be 16-byte aligned");
-  if (use_mfma(hd)) {
-    FNW_SWITCH(false, hd, {
-      const dim3 grid(B * H, (Tq + 32 * NWV - 1) / (32 * NWV));
-      if (hd == 128)
-        hipLaunchKernelGGL((full_fwd_mfma_kernel<128, NWV, float>), grid, dim3(64 * NWV), 0, hig_stream(stream), Q, ldq, K, V, ldk, Tq,
-                           Tk, H, qlen, kpad, Y, ldy, lse);
-      else
-        hipLaunchKernelGGL((full_fwd_mfma_kernel<64, NWV, float>), grid, dim3(64 * NWV), 0, hig_stream(stream), Q, ldq, K, V, ldk, Tq,
-                           Tk, H, qlen, kpad, Y, ldy, lse);
-      hig_attn_path_count(HIG_ATTN_PATH_FULL_FWD_MFMA, (int)grid.y);
-    });
-    HIG_CHECK_LAUNCH();
-    return HIG_OK;
-  }
-  FHD_SWITCH(hd, hipLaunchKernelGGL((full_fwd_kernel<HDV>), dim3(B * H, (Tq + CH - 1) / CH), dim3(256), 0,
+  hig_attn_plan_t p;
+  HIG_TRY(hig_attn_plan_entry(&p, {HIG_ATTN_ENTRY_FULL_FWD, HIG_ATTN_IO_F32, B, Tq, Tk, H, hd, false,
+                                   hig_attn_facts(Q && K && V && Y && lse, bits(4, ldq, Q) | bits(4, ldk, K, V), bits(4, ldy, Y))}));
+  if (p.path == HIG_ATTN_PATH_FULL_FWD_MFMA)
+    return launch_fwd_mfma<float>(p, Q, ldq, K, V, ldk, B, Tq, Tk, H, hd, qlen, kpad, Y, ldy, lse, hig_stream(stream));
+  FHD_SWITCH(hd, hipLaunchKernelGGL((full_fwd_kernel<HDV>), dim3(B * H, p.split), dim3(256), 0,
                                     hig_stream(stream), Q, ldq, K, V, ldk, Tq, Tk, H, qlen, kpad, Y, ldy, lse));
-  hig_attn_path_count(HIG_ATTN_PATH_FULL_FWD, (Tq + CH - 1) / CH);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -705,25 +692,11 @@ extern "C" int hig_fullattn_fwd_kpad(const float* Q, int64_t ldq, const float* K
 extern "C" int hig_fullattn_fwd_bf16(const void* Q, int64_t ldq, const void* K, const void* V, int64_t ldk, int32_t B,
                                      int32_t Tq, int32_t Tk, int32_t H, int32_t hd, const int64_t* qlen, void* Y, int64_t ldy,
                                      hig_stream_t stream) {
-  HIG_REQUIRE(Q && K && V && Y && B > 0 && Tq > 0 && Tk > 0 && H > 0, "hig_fullattn_fwd_bf16: bad arguments");
-  if (hd != 64 && hd != 128) return hig_set_error(HIG_EUNSUPPORTED, "hig_fullattn_fwd_bf16: head dim %d not in {64,128}", hd);
-  auto al8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; };
-  HIG_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldy % 4 == 0 && al8(Q) && al8(K) && al8(V) && al8(Y),
-              "hig_fullattn_fwd_bf16: operands must be 8-byte aligned");
-  const __bf16 *q = static_cast<const __bf16*>(Q), *k = static_cast<const __bf16*>(K), *v = static_cast<const __bf16*>(V);
-  __bf16* y = static_cast<__bf16*>(Y);
-  FNW_SWITCH(false, hd, {
-    const dim3 grid(B * H, (Tq + 32 * NWV - 1) / (32 * NWV));
-    if (hd == 128)
-      hipLaunchKernelGGL((full_fwd_mfma_kernel<128, NWV, __bf16>), grid, dim3(64 * NWV), 0, hig_stream(stream), q, ldq, k, v, ldk,
-                         Tq, Tk, H, qlen, (const uint8_t*)nullptr, y, ldy, (float*)nullptr);
-    else
-      hipLaunchKernelGGL((full_fwd_mfma_kernel<64, NWV, __bf16>), grid, dim3(64 * NWV), 0, hig_stream(stream), q, ldq, k, v, ldk,
-                         Tq, Tk, H, qlen, (const uint8_t*)nullptr, y, ldy, (float*)nullptr);
-    hig_attn_path_count(HIG_ATTN_PATH_FULL_FWD_MFMA, (int)grid.y);
-  });
-  HIG_CHECK_LAUNCH();
-  return HIG_OK;
+  hig_attn_plan_t p;
+  HIG_TRY(hig_attn_plan_entry(&p, {HIG_ATTN_ENTRY_FULL_FWD, HIG_ATTN_IO_BF16, B, Tq, Tk, H, hd, false,
+                                   hig_attn_facts(Q && K && V && Y, bits(2, ldq, Q) | bits(2, ldk, K, V), bits(2, ldy, Y))}));
+  return launch_fwd_mfma<__bf16>(p, static_cast<const __bf16*>(Q), ldq, static_cast<const __bf16*>(K), static_cast<const __bf16*>(V), ldk, B, Tq,
+                                 Tk, H, hd, qlen, nullptr, static_cast<__bf16*>(Y), ldy, nullptr, hig_stream(stream));
 }
 
 extern "C" int hig_fullattn_bwd(const float* dY, int64_t lddy, const float* Y, int64_t ldy, const float* Q,
@@ -731,46 +704,39 @@ extern "C" int hig_fullattn_bwd(const float* dY, int64_t lddy, const float* Y, i
                                 int32_t Tq, int32_t Tk, int32_t H, int32_t hd, const int64_t* qlen,
                                 const float* lse, float* delta, float* dQ, int64_t lddq, float* dK,
                                 float* dV, int64_t lddk, hig_stream_t stream) {
-  HIG_REQUIRE(dY && Y && Q && K && V && lse && delta && dQ && dK && dV && B > 0 && Tq > 0 && Tk > 0 && H > 0,
-              "hig_fullattn_bwd: bad arguments");
-  if (!full_hd_ok(hd))
-    return hig_set_error(HIG_EUNSUPPORTED, "hig_fullattn: head dim %d not in {8,16,32,64,128}", hd);
-  HIG_REQUIRE(lddy % 4 == 0 && ldy % 4 == 0 && ldq % 4 == 0 && ldk % 4 == 0 && lddq % 4 == 0 && lddk % 4 == 0 &&
-                  al16(dY) && al16(Y) && al16(Q) && al16(K) && al16(V) && al16(dQ) && al16(dK) && al16(dV),
-              "hig_fullattn_bwd: operands must be 16-byte aligned");
-  if (use_mfma(hd)) {
-    hipStream_t st = hig_stream(stream);
+  hig_attn_plan_t p;
+  HIG_TRY(hig_attn_plan_entry(&p, {HIG_ATTN_ENTRY_FULL_BWD, HIG_ATTN_IO_F32, B, Tq, Tk, H, hd, false,
+                                   hig_attn_facts(dY && Y && Q && K && V && lse && delta && dQ && dK && dV,
+                                                  bits(4, lddy, dY) | bits(4, ldy, Y) | bits(4, ldq, Q) | bits(4, ldk, K, V),
+                                                  bits(4, lddq, dQ) | bits(4, lddk, dK, dV))}));
+  hipStream_t st = hig_stream(stream);
+  if (p.path == HIG_ATTN_PATH_FULL_BWD_MFMA) {
+    const int waves = p.variant;
+    const dim3 gq(B * H, p.split), gk(B * H, (Tk + 32 * waves - 1) / (32 * waves));
     if (hd == 128) {
       // head dim 128: four waves, always (the key-side kernel needs more than 256 registers per lane: the 8- and 2-wave
       // instances spilled and were never selected -- profiles/r02_attn_sweep.md -- so they are not built)
       constexpr int NWV = 4;
-      const dim3 gq(B * H, (Tq + 32 * NWV - 1) / (32 * NWV)), gk(B * H, (Tk + 32 * NWV - 1) / (32 * NWV));
       hipLaunchKernelGGL((full_bwd_q_mfma_kernel<128, NWV>), gq, dim3(64 * NWV), 0, st, dY, lddy, Y, ldy, Q, ldq, K, V, ldk, Tq,
                          Tk, H, qlen, lse, delta, dQ, lddq);
       hipLaunchKernelGGL((full_bwd_kv_mfma_kernel<128, NWV>), gk, dim3(64 * NWV), 0, st, dY, lddy, Q, ldq, K, V, ldk, Tq, Tk, H,
                          qlen, lse, delta, dK, dV, lddk);
-      hig_attn_path_count(HIG_ATTN_PATH_FULL_BWD_MFMA, (int)gq.y);
     } else {
-      FNW_SWITCH(true, hd, {
-        const dim3 gq(B * H, (Tq + 32 * NWV - 1) / (32 * NWV)), gk(B * H, (Tk + 32 * NWV - 1) / (32 * NWV));
+      FNW_SWITCH(waves, {
         hipLaunchKernelGGL((full_bwd_q_mfma_kernel<64, NWV>), gq, dim3(64 * NWV), 0, st, dY, lddy, Y, ldy, Q, ldq, K, V, ldk, Tq,
                            Tk, H, qlen, lse, delta, dQ, lddq);
         hipLaunchKernelGGL((full_bwd_kv_mfma_kernel<64, NWV>), gk, dim3(64 * NWV), 0, st, dY, lddy, Q, ldq, K, V, ldk, Tq, Tk, H,
                            qlen, lse, delta, dK, dV, lddk);
-        hig_attn_path_count(HIG_ATTN_PATH_FULL_BWD_MFMA, (int)gq.y);
       });
     }
     HIG_CHECK_LAUNCH();
     return HIG_OK;
   }
-  FHD_SWITCH(hd, hipLaunchKernelGGL((full_bwd_q_kernel<HDV>), dim3(B * H, (Tq + CH - 1) / CH), dim3(256), 0,
-                                    hig_stream(stream), dY, lddy, Y, ldy, Q, ldq, K, V, ldk, Tq, Tk, H, qlen, lse,
-                                    delta, dQ, lddq));
+  FHD_SWITCH(hd, hipLaunchKernelGGL((full_bwd_q_kernel<HDV>), dim3(B * H, p.split), dim3(256), 0, st, dY, lddy, Y, ldy, Q, ldq, K, V, ldk, Tq,
+                                    Tk, H, qlen, lse, delta, dQ, lddq));
   HIG_CHECK_LAUNCH();
-  FHD_SWITCH(hd, hipLaunchKernelGGL((full_bwd_kv_kernel<HDV>), dim3(B * H, (Tk + CH - 1) / CH), dim3(256), 0,
-                                    hig_stream(stream), dY, lddy, Q, ldq, K, V, ldk, Tq, Tk, H, qlen, lse, delta,
-                                    dK, dV, lddk));
-  hig_attn_path_count(HIG_ATTN_PATH_FULL_BWD, (Tq + CH - 1) / CH);
+  FHD_SWITCH(hd, hipLaunchKernelGGL((full_bwd_kv_kernel<HDV>), dim3(B * H, (Tk + CH - 1) / CH), dim3(256), 0, st, dY, lddy, Q, ldq, K, V, ldk,
+                                    Tq, Tk, H, qlen, lse, delta, dK, dV, lddk));
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

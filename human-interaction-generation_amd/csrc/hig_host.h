@@ -132,6 +132,49 @@ int hig_with_epi(hig_epi_list<E...>, int epi, int none, F&& f) {
   (void)(((epi == E) && ((rc = f(std::integral_constant<int, E>{})), true)) || ...);
   return rc;
 }
+// ---- which kernel serves an attention call, and with which split (attn_plan.hip): decided apart from the launch ----
+// The attention switches ("Switches"), each read once per process by hig_attn_switch_values().
+struct hig_attn_switches {
+  int apply_wave;       // HIG_APPLY_WAVE: 0 keeps fp32 head dim 64 off apply_wave64_kernel
+  int fullattn_waves;   // HIG_FULLATTN_WAVES: 2 / 4 / 8 forces the waves per workgroup of the matrix-core full-attention kernels (0: the rule)
+  int fullattn_valu;    // HIG_FULLATTN_VALU: != 0 keeps head dim 64 of full attention on the VALU kernels
+};
+const hig_attn_switches& hig_attn_switch_values();
+// What a decision may depend on, and nothing else.  entry: HIG_ATTN_ENTRY_*; io: HIG_ATTN_IO_*; rows = Tq and Tk = keys for
+// full attention (Tk unused otherwise); facts: HIG_ATTN_FACT_* (include/hig.h) -- what the entry point read off its
+// operands' null-ness, low pointer bits and leading dimensions.
+struct hig_attn_call {
+  int entry, io;
+  int B, rows, Tk, H, hd;
+  bool has_scratch;
+  int facts;
+};
+// The facts of a call whose input rows (pointers and leading dimensions in bytes OR-ed together: `in`), output rows
+// (`out`) and fp32 parameter vectors (`par`) have these low bits.
+inline int hig_attn_facts(bool operands, uintptr_t in, uintptr_t out, uintptr_t par = 0, bool out_i32 = true) {
+  return (operands ? HIG_ATTN_FACT_OPERANDS : 0) | ((in & 7) ? 0 : HIG_ATTN_FACT_IN8) | ((in & 15) ? 0 : HIG_ATTN_FACT_IN16) |
+         ((out & 7) ? 0 : HIG_ATTN_FACT_OUT8) | ((out & 15) ? 0 : HIG_ATTN_FACT_OUT16) | ((par & 15) ? 0 : HIG_ATTN_FACT_PAR16) |
+         (out_i32 ? HIG_ATTN_FACT_OUT_I32 : 0);
+}
+inline uintptr_t hig_low_bits(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+inline uintptr_t hig_low_bits(int64_t ld, int elem_bytes) { return (uintptr_t)ld * (uintptr_t)elem_bytes; }
+// rc == HIG_OK: the kernel of `path` (HIG_ATTN_PATH_*) runs with `split` (what hig_attn_last_split reports: gridDim.y, the
+// number of chunks, or the strips per sample) in the instance `variant` names; else the error the entry point returns.
+// variant: full attention on the matrix cores: waves per workgroup (2 / 4 / 8); hig_linattn_apply_bwd: HIG_ATTN_VARIANT_MERGE
+// when the dA partials go to scratch and chunk_sum_kernel adds them up (0: the single partial IS dA); 0 everywhere else.
+struct hig_attn_plan_t { int rc, path, split, variant; char msg[160]; };
+#define HIG_ATTN_VARIANT_MERGE 1
+hig_attn_plan_t hig_attn_plan_for(const hig_attn_call& c, const hig_attn_switches& sw, int cus, bool big_lds_ok);
+bool hig_attn_mfma_hd(int hd);   // head dims the matrix-core linear-attention kernels are built for
+// Steps 1 - 3 of every attention entry point: plan the call for this device, refuse with the plan's error or count the launch
+// (the one place a planned call is counted).  Step 4 is the entry's switch on p->path into a launcher next to the kernel, which
+// takes the plan's split and variant and decides nothing.
+inline int hig_attn_plan_entry(hig_attn_plan_t* p, const hig_attn_call& c, bool big_lds_ok = true) {
+  *p = hig_attn_plan_for(c, hig_attn_switch_values(), hig_chip_cus(), big_lds_ok);
+  if (p->rc != HIG_OK) return hig_set_error(p->rc, "%s", p->msg);
+  hig_attn_path_count(p->path, p->split);
+  return HIG_OK;
+}
 // linattn.hip: context build of G groups of H heads in one launch (the batched text side); 1 = shape not served
 int hig_linattn_ctx_groups(const float* K, const float* V, int64_t ld, int32_t B, int32_t rows, int32_t H, int32_t G, int32_t hd,
                            float* A, int64_t a_gs, float* kstat, int64_t k_gs, hipStream_t st);

@@ -12,12 +12,7 @@
 // channel c of head h lives at column h*hd + c of the (rows, d) activation.
 #include <stdlib.h>
 
-#include "hig_common.h"
-
-int hig_chip_cus();   // hig_host.h: compute units of the current device
-// one launch of the attention kernel of `path` (HIG_ATTN_PATH_*) with gridDim.y = split: called at the launch site (below,
-// hig_attn_path_launches / hig_attn_last_split)
-void hig_attn_path_count(int path, int split);
+#include "hig_host.h"   // the plan of every entry point (attn_plan.hip), hig_attn_path_count
 
 namespace {
 
@@ -1575,8 +1570,6 @@ int allow_big_lds() {
   return rc;
 }
 
-bool hd_ok(int hd) { return hd == 8 || hd == 16 || hd == 32 || hd == 64 || hd == 128; }
-
 #define HD_SWITCH(hd, STMT)                  \
   switch (hd) {                              \
     case 8: { constexpr int HDV = 8; STMT; } break;     \
@@ -1585,6 +1578,15 @@ bool hd_ok(int hd) { return hd == 8 || hd == 16 || hd == 32 || hd == 64 || hd ==
     case 64: { constexpr int HDV = 64; STMT; } break;   \
     default: { constexpr int HDV = 128; STMT; } break;  \
   }
+// the matrix-core kernels' head dim: f(std::integral_constant<int, 64>) or f(std::integral_constant<int, 128>); HDC(c) reads it
+template <class F> void with_mfma_hd(int hd, F&& f) {
+  if (hd == 64) f(std::integral_constant<int, 64>{});
+  else f(std::integral_constant<int, 128>{});
+}
+#define HDC(c) decltype(c)::value
+
+template <typename T> uintptr_t row_bits(int64_t ld) { return hig_low_bits(ld, (int)sizeof(T)); }
+template <typename T, class... P> uintptr_t row_bits(int64_t ld, const void* p, P... more) { return hig_low_bits(p) | row_bits<T>(ld, more...); }
 
 }  // namespace
 
@@ -1594,66 +1596,37 @@ extern "C" int64_t hig_linattn_ctx_scratch_floats(int32_t B, int32_t rows, int32
 }
 
 namespace {
+// HIG_ATTN_PATH_CTX_PART (row chunks in parallel + a merge; split = the chunks) or HIG_ATTN_PATH_CTX_MFMA
 template <typename TIO>
-int linattn_ctx_t(const TIO* K, const TIO* V, int64_t ld, int32_t B, int32_t rows, int32_t H, int32_t hd,
-                  const int64_t* length, float* A, float* kstat, float* scratch, hipStream_t st, __bf16* At16 = nullptr) {
-  const int nchunk = (rows + CH - 1) / CH;
-  constexpr int ctx_walk = 1;   // (a former tuning knob, fixed at the value that won its A/B)
-  const bool walk = ctx_walk && B * H >= hig_chip_cus();   // enough (sample, head) pairs to fill the chip with walking workgroups
-  if (!walk && scratch && nchunk > 1) {
-    // row chunks in parallel + a merge: 4-5x the workgroups of the one-per-(sample, head) kernel
-    if (hd == 64) {
-      hipLaunchKernelGGL((ctx_part_mfma_kernel<64, TIO>), dim3(B * H, nchunk), dim3(256), 0, st, K, V, ld, rows, H, length,
-                         scratch);
-      hipLaunchKernelGGL(ctx_combine_kernel<64>, dim3(B * H), dim3(256), 0, st, scratch, nchunk, A, kstat, At16);
+int launch_ctx(const hig_attn_plan_t& p, const TIO* K, const TIO* V, int64_t ld, int32_t B, int32_t rows, int32_t H, int32_t hd,
+               const int64_t* length, float* A, float* kstat, float* scratch, __bf16* At16, hipStream_t st) {
+  with_mfma_hd(hd, [&](auto c) {
+    if (p.path == HIG_ATTN_PATH_CTX_PART) {
+      hipLaunchKernelGGL((ctx_part_mfma_kernel<HDC(c), TIO>), dim3(B * H, p.split), dim3(256), 0, st, K, V, ld, rows, H, length, scratch);
+      hipLaunchKernelGGL(ctx_combine_kernel<HDC(c)>, dim3(B * H), dim3(256), 0, st, scratch, p.split, A, kstat, At16);
     } else {
-      hipLaunchKernelGGL((ctx_part_mfma_kernel<128, TIO>), dim3(B * H, nchunk), dim3(256), 0, st, K, V, ld, rows, H, length,
-                         scratch);
-      hipLaunchKernelGGL(ctx_combine_kernel<128>, dim3(B * H), dim3(256), 0, st, scratch, nchunk, A, kstat, At16);
+      hipLaunchKernelGGL((ctx_mfma_kernel<HDC(c), TIO>), dim3(B * H), dim3(256), 0, st, K, V, ld, rows, H, length, A, kstat, At16, CtxGroups{H, 0, 0});
     }
-    hig_attn_path_count(HIG_ATTN_PATH_CTX_PART, nchunk);
-    HIG_CHECK_LAUNCH();
-    return HIG_OK;
-  }
-  if (hd == 64)
-    hipLaunchKernelGGL((ctx_mfma_kernel<64, TIO>), dim3(B * H), dim3(256), 0, st, K, V, ld, rows, H, length, A, kstat, At16, CtxGroups{H, 0, 0});
-  else
-    hipLaunchKernelGGL((ctx_mfma_kernel<128, TIO>), dim3(B * H), dim3(256), 0, st, K, V, ld, rows, H, length, A, kstat, At16, CtxGroups{H, 0, 0});
-  hig_attn_path_count(HIG_ATTN_PATH_CTX_MFMA, 1);
+  });
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
 
+// HIG_ATTN_PATH_APPLY_WAVE64 (exact fp32, head dim 64) or HIG_ATTN_PATH_APPLY_MFMA with split workgroups per (sample, head)
 template <typename TIO>
-int linattn_apply_t(const TIO* Q, int64_t ldq, const float* A, TIO* Y, int64_t ldy, int32_t B, int32_t rows, int32_t H,
-                    int32_t hd, hipStream_t st) {
-  // chunk-walking workgroups: enough of them to fill the chip (~4 per CU), each staging A[b,h] once
-  const int nchunk_a = (rows + CH - 1) / CH;
-  // (hd = 128 keeps 97 KB of LDS per workgroup = one per CU: fewer, longer-lived workgroups; measured with
-  // tools/attn_time.py: 61 -> 47 us at config 5, neutral at hd = 64)
+int launch_apply(const hig_attn_plan_t& p, const TIO* Q, int64_t ldq, const float* A, TIO* Y, int64_t ldy, int32_t B, int32_t rows, int32_t H,
+                 int32_t hd, hipStream_t st) {
   if constexpr (sizeof(TIO) == 4) {
-    // exact fp32, head dim 64: the wave-autonomous kernel (16-row tiles per wave, no barrier in the loop)
-    static const int wave_env = getenv("HIG_APPLY_WAVE") ? atoi(getenv("HIG_APPLY_WAVE")) : 1;   // tuning knob
-    // (short sequences keep the chunk-walking kernel: T = 91 has 6 tiles for 4 waves, 11.3 against 10.1 us at B = 64)
-    if (wave_env && hd == 64 && rows >= 128 && ldq % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Q) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
+    if (p.path == HIG_ATTN_PATH_APPLY_WAVE64) {
       hipLaunchKernelGGL(apply_wave64_kernel, dim3(B * H), dim3(256), 0, st, reinterpret_cast<const float*>(Q), ldq, A,
                          reinterpret_cast<float*>(Y), ldy, rows, H);
-      hig_attn_path_count(HIG_ATTN_PATH_APPLY_WAVE64, 1);
       HIG_CHECK_LAUNCH();
       return HIG_OK;
     }
   }
-  constexpr int apply_target = 0;   // (a former tuning knob, fixed at the value that won its A/B)
-  // (re-swept in round 2, profiles/r02_attn_sweep.md: hd = 128 at 256 / 512 / 1024 workgroups: 42.4 / 48.7 / 58.9 us)
-  const int target = apply_target > 0 ? apply_target : (hd == 128 ? 1 : 4) * hig_chip_cus();
-  int gy = (target + B * H - 1) / (B * H);
-  gy = gy < 1 ? 1 : (gy > nchunk_a ? nchunk_a : gy);
-  if (hd == 64)
-    hipLaunchKernelGGL((apply_mfma_kernel<64, TIO>), dim3(B * H, gy), dim3(256), 0, st, Q, ldq, A, Y, ldy, rows, H);
-  else
-    hipLaunchKernelGGL((apply_mfma_kernel<128, TIO>), dim3(B * H, gy), dim3(256), 0, st, Q, ldq, A, Y, ldy, rows, H);
-  hig_attn_path_count(HIG_ATTN_PATH_APPLY_MFMA, gy);
+  with_mfma_hd(hd, [&](auto c) {
+    hipLaunchKernelGGL((apply_mfma_kernel<HDC(c), TIO>), dim3(B * H, p.split), dim3(256), 0, st, Q, ldq, A, Y, ldy, rows, H);
+  });
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -1662,12 +1635,11 @@ int linattn_apply_t(const TIO* Q, int64_t ldq, const float* A, TIO* Y, int64_t l
 extern "C" int hig_linattn_ctx(const float* K, const float* V, int64_t ld, int32_t B, int32_t rows,
                                int32_t H, int32_t hd, const int64_t* length, float* A, float* kstat,
                                float* scratch, hig_stream_t stream) {
-  HIG_REQUIRE(K && V && A && kstat && B > 0 && rows > 0 && H > 0, "hig_linattn_ctx: bad arguments");
-  HIG_REQUIRE(hd_ok(hd), "hig_linattn: head dim %d not in {8,16,32,64,128}", hd);
-  if (hd == 64 || hd == 128) return linattn_ctx_t<float>(K, V, ld, B, rows, H, hd, length, A, kstat, scratch, hig_stream(stream));
+  hig_attn_plan_t p;
+  HIG_TRY(hig_attn_plan_entry(&p, {HIG_ATTN_ENTRY_CTX, HIG_ATTN_IO_F32, B, rows, 0, H, hd, scratch != nullptr, hig_attn_facts(K && V && A && kstat, 0, 0)}));
+  if (p.path != HIG_ATTN_PATH_CTX) return launch_ctx<float>(p, K, V, ld, B, rows, H, hd, length, A, kstat, scratch, nullptr, hig_stream(stream));
   HD_SWITCH(hd, hipLaunchKernelGGL((ctx_kernel<HDV>), dim3(B * H), dim3(256), 0, hig_stream(stream), K, V,
                                    ld, rows, H, length, A, kstat));
-  hig_attn_path_count(HIG_ATTN_PATH_CTX, 1);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -1678,13 +1650,11 @@ extern "C" int hig_linattn_ctx(const float* K, const float* V, int64_t ld, int32
 // caller loops over the groups instead).
 int hig_linattn_ctx_groups(const float* K, const float* V, int64_t ld, int32_t B, int32_t rows, int32_t H, int32_t G, int32_t hd,
                            float* A, int64_t a_gs, float* kstat, int64_t k_gs, hipStream_t st) {
-  if (!(hd == 64 || hd == 128) || B <= 0 || rows <= 0 || H <= 0 || G <= 0) return 1;
-  if (hd == 64)
-    hipLaunchKernelGGL((ctx_mfma_kernel<64, float>), dim3(B * H * G), dim3(256), 0, st, K, V, ld, rows, H * G, nullptr, A, kstat,
-                       nullptr, CtxGroups{H, a_gs, k_gs});
-  else
-    hipLaunchKernelGGL((ctx_mfma_kernel<128, float>), dim3(B * H * G), dim3(256), 0, st, K, V, ld, rows, H * G, nullptr, A, kstat,
-                       nullptr, CtxGroups{H, a_gs, k_gs});
+  if (!hig_attn_mfma_hd(hd) || B <= 0 || rows <= 0 || H <= 0 || G <= 0) return 1;
+  with_mfma_hd(hd, [&](auto c) {
+    hipLaunchKernelGGL((ctx_mfma_kernel<HDC(c), float>), dim3(B * H * G), dim3(256), 0, st, K, V, ld, rows, H * G, nullptr, A, kstat, nullptr,
+                       CtxGroups{H, a_gs, k_gs});
+  });
   hig_attn_path_count(HIG_ATTN_PATH_CTX_MFMA, 1);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
@@ -1692,15 +1662,11 @@ int hig_linattn_ctx_groups(const float* K, const float* V, int64_t ld, int32_t B
 
 extern "C" int hig_linattn_apply(const float* Q, int64_t ldq, const float* A, float* Y, int64_t ldy,
                                  int32_t B, int32_t rows, int32_t H, int32_t hd, hig_stream_t stream) {
-  HIG_REQUIRE(Q && A && Y && B > 0 && rows > 0 && H > 0, "hig_linattn_apply: bad arguments");
-  HIG_REQUIRE(hd_ok(hd), "hig_linattn: head dim %d not in {8,16,32,64,128}", hd);
-  HIG_REQUIRE(ldq % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Q) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(Y) & 15) == 0,
-              "hig_linattn_apply: Q/Y must be 16-byte aligned");
-  if (hd == 64 || hd == 128) return linattn_apply_t<float>(Q, ldq, A, Y, ldy, B, rows, H, hd, hig_stream(stream));
-  HD_SWITCH(hd, hipLaunchKernelGGL((apply_kernel<HDV>), dim3(B * H, (rows + CH - 1) / CH), dim3(256), 0,
-                                   hig_stream(stream), Q, ldq, A, Y, ldy, rows, H));
-  hig_attn_path_count(HIG_ATTN_PATH_APPLY, (rows + CH - 1) / CH);
+  hig_attn_plan_t p;
+  HIG_TRY(hig_attn_plan_entry(&p, {HIG_ATTN_ENTRY_APPLY, HIG_ATTN_IO_F32, B, rows, 0, H, hd, false,
+                     hig_attn_facts(Q && A && Y, row_bits<float>(ldq, Q), row_bits<float>(ldy, Y))}));
+  if (p.path != HIG_ATTN_PATH_APPLY) return launch_apply<float>(p, Q, ldq, A, Y, ldy, B, rows, H, hd, hig_stream(stream));
+  HD_SWITCH(hd, hipLaunchKernelGGL((apply_kernel<HDV>), dim3(B * H, p.split), dim3(256), 0, hig_stream(stream), Q, ldq, A, Y, ldy, rows, H));
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -1929,7 +1895,6 @@ int launch_apply_sty(const TQ* q, int64_t ldq, const float* A, const float* gamm
   } else
     hipLaunchKernelGGL((apply_sty_kernel<128, TQ, TO>), dim3(B * nblk), dim3(256), lds, st, q, ldq, A, gamma, beta, ss, ss_ld,
                        shift_off, o, ldo, rows, H, nblk);
-  hig_attn_path_count(HIG_ATTN_PATH_APPLY_STY, 1);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -2113,25 +2078,72 @@ __global__ __launch_bounds__(64 * H, 4) void apply_sty_wave64_kernel(const float
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // (a clamped, unused prefetch may still be in flight)
 }
 
-// strips per sample: enough workgroups for the 16 wave slots of each of the 256 CUs (two 8-wave or four 4-wave workgroups), then
-// the fewest strips with that many tiles each (a strip's start-up -- 16 KB of A per wave from L2 -- is paid once per workgroup).
-// B = 64, T = 196, H = 8: 7 strips of 2 tiles; B = 32: 13 strips of one.  Measured against half and twice the slots
-// (profiles/r07_notes.md): within 0.5 us at B = 32, 1 - 2 us slower at B = 64 with twice.
-constexpr int APPLY_STY_WAVE_SLOTS = 256 * 16;
+// nstrip strips of 16-row tiles per sample (the plan's split: strip_split, attn_plan.hip)
 template <int H>
 int launch_apply_sty_wave64(const float* q, int64_t ldq, const float* A, const float* gamma, const float* beta, const float* ss,
-                            int64_t ss_ld, int32_t shift_off, float* o, int64_t ldo, int32_t B, int32_t rows, hipStream_t st) {
-  const int ntile = (rows + 15) / 16;
-  int nstrip = APPLY_STY_WAVE_SLOTS / H / B;
-  nstrip = nstrip < 1 ? 1 : nstrip > ntile ? ntile : nstrip;
-  const int per = (ntile + nstrip - 1) / nstrip;
-  nstrip = (ntile + per - 1) / per;
+                            int64_t ss_ld, int32_t shift_off, float* o, int64_t ldo, int32_t B, int32_t rows, int nstrip, hipStream_t st) {
   hipLaunchKernelGGL((apply_sty_wave64_kernel<H>), dim3(B, nstrip), dim3(64 * H), 0, st, q, ldq, A, gamma, beta, ss, ss_ld, shift_off, o,
                      ldo, rows);
-  hig_attn_path_count(HIG_ATTN_PATH_APPLY_STY_WAVE64, nstrip);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
+
+// HIG_ATTN_PATH_APPLY_BWD_MFMA: split workgroups per (sample, head), each with one dA partial; HIG_ATTN_VARIANT_MERGE: the
+// partials go to scratch and chunk_sum_kernel adds them up, else the single partial is dA
+template <typename TIO>
+int launch_apply_bwd(const hig_attn_plan_t& p, const TIO* dY, int64_t lddy, const TIO* Q, int64_t ldq, const float* A, TIO* dQ, int64_t lddq,
+                     float* dA, int32_t B, int32_t rows, int32_t H, int32_t hd, float* scratch, hipStream_t st) {
+  const bool merge = p.variant & HIG_ATTN_VARIANT_MERGE;
+  if (p.path == HIG_ATTN_PATH_APPLY_BWD_MFMA) {
+    with_mfma_hd(hd, [&](auto c) {
+      hipLaunchKernelGGL((apply_bwd_mfma_kernel<HDC(c), TIO>), dim3(B * H, p.split), dim3(256), attn_bwd_lds_bytes<HDC(c)>(), st, dY, lddy, Q,
+                         ldq, A, dQ, lddq, merge ? scratch : dA, rows, H);
+    });
+  } else if constexpr (sizeof(TIO) == 4) {   // HIG_ATTN_PATH_APPLY_BWD: one workgroup and one partial per chunk
+    HD_SWITCH(hd, hipLaunchKernelGGL((apply_bwd_kernel<HDV>), dim3(B * H, p.split), dim3(256), 0, st, dY, lddy, Q, ldq, A, dQ, lddq, scratch,
+                                     rows, H));
+  }
+  HIG_CHECK_LAUNCH();
+  if (!merge) return HIG_OK;
+  const int64_t n = (int64_t)hd * hd, groups = (int64_t)B * H;
+  const int64_t want = (groups * n / 4 + 255) / 256;
+  hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)(want > 2048 ? 2048 : want)), dim3(256), 0, st, scratch, p.split, n, groups, dA);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+// HIG_ATTN_PATH_CTX_BWD_MFMA: single pass, split workgroups per (sample, head)
+template <typename TIO>
+int launch_ctx_bwd(const hig_attn_plan_t& p, const float* dA, const float* A, const TIO* K, const TIO* V, int64_t ld, const float* kstat,
+                   const int64_t* length, TIO* dK, TIO* dV, int64_t ldd, int32_t B, int32_t rows, int32_t H, int32_t hd, float* scratch,
+                   hipStream_t st) {
+  if (p.path == HIG_ATTN_PATH_CTX_BWD_MFMA) {
+    with_mfma_hd(hd, [&](auto c) {
+      hipLaunchKernelGGL((ctx_bwd_mfma_kernel<HDC(c), TIO>), dim3(B * H, p.split), dim3(256), attn_bwd_lds_bytes<HDC(c)>(), st, dA, A, K, V, ld,
+                         kstat, length, dK, dV, ldd, rows, H);
+    });
+  } else if constexpr (sizeof(TIO) == 4) {   // HIG_ATTN_PATH_CTX_BWD: two passes, one workgroup per chunk
+    HD_SWITCH(hd, hipLaunchKernelGGL((ctx_bwd_kernel<HDV>), dim3(B * H, p.split), dim3(256), 0, st, dA, K, V, ld, kstat, length, dK, dV, ldd,
+                                     rows, H, scratch));
+    HIG_CHECK_LAUNCH();
+    HD_SWITCH(hd, hipLaunchKernelGGL((ctx_bwd_finish_kernel<HDV>), dim3(B * H, p.split), dim3(256), 0, st, K, ld, kstat, length, dK, ldd, rows,
+                                     H, scratch));
+  }
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+// The backward entries: whether the device grants the head-dim-128 kernels their dynamic LDS is an input of the plan, and it is
+// asked of the device only for a head-dim-128 call whose arguments pass (as before: after the argument checks and before the
+// alignment checks, so the aligned twin of the call is the one that is asked about).
+int plan_bwd_entry(hig_attn_plan_t* p, const hig_attn_call& c) {
+  hig_attn_call aligned = c;
+  aligned.facts |= HIG_ATTN_FACT_IN8 | HIG_ATTN_FACT_IN16 | HIG_ATTN_FACT_OUT8 | HIG_ATTN_FACT_OUT16;
+  const bool would_use = c.hd == 128 && hig_attn_plan_for(aligned, hig_attn_switch_values(), hig_chip_cus(), true).rc == HIG_OK;
+  return hig_attn_plan_entry(p, c, !would_use || allow_big_lds() == 0);
+}
+// (rows + 16) ldo 4 < INT32_MAX, without overflow
+bool sty_out_i32(int64_t rows, int64_t ldo) { return rows <= 0 || ldo <= (INT32_MAX / 4) / (rows + 16); }
 
 }  // namespace
 
@@ -2140,24 +2152,18 @@ int launch_apply_sty_wave64(const float* q, int64_t ldq, const float* A, const f
 extern "C" int hig_linattn_ctx_bf16(const void* K, const void* V, int64_t ld, int32_t B, int32_t rows, int32_t H,
                                     int32_t hd, const int64_t* length, float* A, float* kstat, float* scratch,
                                     void* At16, hig_stream_t stream) {
-  HIG_REQUIRE(K && V && A && kstat && B > 0 && rows > 0 && H > 0, "hig_linattn_ctx_bf16: bad arguments");
-  if (hd != 64 && hd != 128)
-    return hig_set_error(HIG_EUNSUPPORTED, "hig_linattn: bf16 storage is built for head dim 64 / 128 (got %d)", hd);
-  HIG_REQUIRE(ld % 4 == 0 && (reinterpret_cast<uintptr_t>(K) & 7) == 0 && (reinterpret_cast<uintptr_t>(V) & 7) == 0,
-              "hig_linattn_ctx_bf16: K/V must be 8-byte aligned");
-  return linattn_ctx_t<__bf16>(static_cast<const __bf16*>(K), static_cast<const __bf16*>(V), ld, B, rows, H, hd, length, A,
-                               kstat, scratch, hig_stream(stream), static_cast<__bf16*>(At16));
+  hig_attn_plan_t p;
+  HIG_TRY(hig_attn_plan_entry(&p, {HIG_ATTN_ENTRY_CTX, HIG_ATTN_IO_BF16, B, rows, 0, H, hd, scratch != nullptr,
+                              hig_attn_facts(K && V && A && kstat, row_bits<__bf16>(ld, K, V), 0)}));
+  return launch_ctx<__bf16>(p, static_cast<const __bf16*>(K), static_cast<const __bf16*>(V), ld, B, rows, H, hd, length, A, kstat, scratch,
+                            static_cast<__bf16*>(At16), hig_stream(stream));
 }
 extern "C" int hig_linattn_apply_bf16(const void* Q, int64_t ldq, const float* A, void* Y, int64_t ldy, int32_t B,
                                       int32_t rows, int32_t H, int32_t hd, hig_stream_t stream) {
-  HIG_REQUIRE(Q && A && Y && B > 0 && rows > 0 && H > 0, "hig_linattn_apply_bf16: bad arguments");
-  if (hd != 64 && hd != 128)
-    return hig_set_error(HIG_EUNSUPPORTED, "hig_linattn: bf16 storage is built for head dim 64 / 128 (got %d)", hd);
-  HIG_REQUIRE(ldq % 4 == 0 && ldy % 8 == 0 && (reinterpret_cast<uintptr_t>(Q) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(Y) & 15) == 0,
-              "hig_linattn_apply_bf16: Q rows must be 8-byte aligned, Y rows 16-byte aligned");
-  return linattn_apply_t<__bf16>(static_cast<const __bf16*>(Q), ldq, A, static_cast<__bf16*>(Y), ldy, B, rows, H, hd,
-                                 hig_stream(stream));
+  hig_attn_plan_t p;
+  HIG_TRY(hig_attn_plan_entry(&p, {HIG_ATTN_ENTRY_APPLY, HIG_ATTN_IO_BF16, B, rows, 0, H, hd, false,
+                              hig_attn_facts(Q && A && Y, row_bits<__bf16>(ldq, Q), row_bits<__bf16>(ldy, Y))}));
+  return launch_apply<__bf16>(p, static_cast<const __bf16*>(Q), ldq, A, static_cast<__bf16*>(Y), ldy, B, rows, H, hd, hig_stream(stream));
 }
 
 extern "C" int64_t hig_linattn_bwd_scratch_floats(int32_t B, int32_t rows, int32_t H, int32_t hd) {
@@ -2169,83 +2175,21 @@ extern "C" int hig_linattn_apply_bwd(const float* dY, int64_t lddy, const float*
                                      const float* A, float* dQ, int64_t lddq, float* dA, int32_t B,
                                      int32_t rows, int32_t H, int32_t hd, float* scratch,
                                      hig_stream_t stream) {
-  HIG_REQUIRE(dY && Q && A && dQ && dA && scratch && B > 0 && rows > 0 && H > 0,
-              "hig_linattn_apply_bwd: bad arguments");
-  HIG_REQUIRE(hd_ok(hd), "hig_linattn: head dim %d not in {8,16,32,64,128}", hd);
-  HIG_REQUIRE(ldq % 4 == 0 && lddy % 4 == 0 && lddq % 4 == 0 && (reinterpret_cast<uintptr_t>(Q) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(dY) & 15) == 0 && (reinterpret_cast<uintptr_t>(dQ) & 15) == 0,
-              "hig_linattn_apply_bwd: Q/dY/dQ must be 16-byte aligned");
-  const int nchunk = (rows + CH - 1) / CH;
-  int nparts = nchunk;   // dA partials per (sample, head) that chunk_sum_kernel adds up
-  if (hd == 64 || (hd == 128 && allow_big_lds() == 0)) {
-    // chunk-walking workgroups (dA accumulated in registers across a workgroup's chunks): ~3 per CU resident
-    constexpr int tgt = 0;   // (a former tuning knob, fixed at the value that won its A/B)
-    // measured (tools/attn_time.py): one workgroup per (sample, head) walking all its chunks is fastest once
-    // B * H fills the chip (config 2: 49 -> 38 us, config 5: 135 -> 77 us) and needs no partial sums at all
-    const int target = tgt > 0 ? tgt : hig_chip_cus();
-    nparts = (target + B * H - 1) / (B * H);
-    nparts = nparts < 1 ? 1 : (nparts > nchunk ? nchunk : nparts);
-    float* part = nparts == 1 ? dA : scratch;
-    if (hd == 64)
-      hipLaunchKernelGGL(apply_bwd_mfma_kernel<64>, dim3(B * H, nparts), dim3(256), attn_bwd_lds_bytes<64>(),
-                         hig_stream(stream), dY, lddy, Q, ldq, A, dQ, lddq, part, rows, H);
-    else
-      hipLaunchKernelGGL(apply_bwd_mfma_kernel<128>, dim3(B * H, nparts), dim3(256), attn_bwd_lds_bytes<128>(),
-                         hig_stream(stream), dY, lddy, Q, ldq, A, dQ, lddq, part, rows, H);
-    hig_attn_path_count(HIG_ATTN_PATH_APPLY_BWD_MFMA, nparts);
-    if (nparts == 1) {
-      HIG_CHECK_LAUNCH();
-      return HIG_OK;
-    }
-  } else {
-    HD_SWITCH(hd, hipLaunchKernelGGL((apply_bwd_kernel<HDV>), dim3(B * H, nchunk), dim3(256), 0, hig_stream(stream),
-                                     dY, lddy, Q, ldq, A, dQ, lddq, scratch, rows, H));
-    hig_attn_path_count(HIG_ATTN_PATH_APPLY_BWD, nchunk);
-  }
-  HIG_CHECK_LAUNCH();
-  const int64_t n = (int64_t)hd * hd, groups = (int64_t)B * H;
-  const int64_t want = (groups * n / 4 + 255) / 256;
-  hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)(want > 2048 ? 2048 : want)), dim3(256), 0, hig_stream(stream),
-                     scratch, nparts, n, groups, dA);
-  HIG_CHECK_LAUNCH();
-  return HIG_OK;
+  hig_attn_plan_t p;
+  HIG_TRY(plan_bwd_entry(&p, {HIG_ATTN_ENTRY_APPLY_BWD, HIG_ATTN_IO_F32, B, rows, 0, H, hd, scratch != nullptr,
+                              hig_attn_facts(dY && Q && A && dQ && dA, row_bits<float>(ldq, Q) | row_bits<float>(lddy, dY), row_bits<float>(lddq, dQ))}));
+  return launch_apply_bwd<float>(p, dY, lddy, Q, ldq, A, dQ, lddq, dA, B, rows, H, hd, scratch, hig_stream(stream));
 }
 
 extern "C" int hig_linattn_ctx_bwd(const float* dA, const float* A, const float* K, const float* V, int64_t ld,
                                    const float* kstat, const int64_t* length, float* dK, float* dV,
                                    int64_t ldd, int32_t B, int32_t rows, int32_t H, int32_t hd,
                                    float* scratch, hig_stream_t stream) {
-  HIG_REQUIRE(dA && A && K && V && kstat && dK && dV && scratch && B > 0 && rows > 0 && H > 0,
-              "hig_linattn_ctx_bwd: bad arguments");
-  HIG_REQUIRE(hd_ok(hd), "hig_linattn: head dim %d not in {8,16,32,64,128}", hd);
-  HIG_REQUIRE(ldd % 4 == 0 && (reinterpret_cast<uintptr_t>(dK) & 15) == 0 && (reinterpret_cast<uintptr_t>(dV) & 15) == 0,
-              "hig_linattn_ctx_bwd: dK/dV must be 16-byte aligned");
-  const int nchunk = (rows + CH - 1) / CH;
-  if (hd == 64 || (hd == 128 && allow_big_lds() == 0)) {   // single pass (the column term comes from A and dA)
-    constexpr int tgt = 0;   // (a former tuning knob, fixed at the value that won its A/B)
-    const int target = tgt > 0 ? tgt : hig_chip_cus();
-    int gy = (target + B * H - 1) / (B * H);
-    gy = gy < 1 ? 1 : (gy > nchunk ? nchunk : gy);
-    if (hd == 64)
-      hipLaunchKernelGGL(ctx_bwd_mfma_kernel<64>, dim3(B * H, gy), dim3(256), attn_bwd_lds_bytes<64>(),
-                         hig_stream(stream), dA, A, K, V, ld, kstat, length, dK, dV, ldd, rows, H);
-    else
-      hipLaunchKernelGGL(ctx_bwd_mfma_kernel<128>, dim3(B * H, gy), dim3(256), attn_bwd_lds_bytes<128>(),
-                         hig_stream(stream), dA, A, K, V, ld, kstat, length, dK, dV, ldd, rows, H);
-    hig_attn_path_count(HIG_ATTN_PATH_CTX_BWD_MFMA, gy);
-    HIG_CHECK_LAUNCH();
-    return HIG_OK;
-  }
-  HD_SWITCH(hd, hipLaunchKernelGGL((ctx_bwd_kernel<HDV>), dim3(B * H, nchunk), dim3(256), 0, hig_stream(stream), dA,
-                                   K, V, ld, kstat, length, dK, dV, ldd, rows, H, scratch));
-  HIG_CHECK_LAUNCH();
-  HD_SWITCH(hd, hipLaunchKernelGGL((ctx_bwd_finish_kernel<HDV>), dim3(B * H, nchunk), dim3(256), 0,
-                                   hig_stream(stream), K, ld, kstat, length, dK, ldd, rows, H, scratch));
-  hig_attn_path_count(HIG_ATTN_PATH_CTX_BWD, nchunk);
-  HIG_CHECK_LAUNCH();
-  return HIG_OK;
+  hig_attn_plan_t p;
+  HIG_TRY(plan_bwd_entry(&p, {HIG_ATTN_ENTRY_CTX_BWD, HIG_ATTN_IO_F32, B, rows, 0, H, hd, scratch != nullptr,
+                              hig_attn_facts(dA && A && K && V && kstat && dK && dV, 0, row_bits<float>(ldd, dK, dV))}));
+  return launch_ctx_bwd<float>(p, dA, A, K, V, ld, kstat, length, dK, dV, ldd, B, rows, H, hd, scratch, hig_stream(stream));
 }
-
 
 // bf16-storage forms of the two backward kernels (training step with hig_dims.storage == HIG_STORE_BF16): dY, Q, dQ and K, V,
 // dK, dV bf16; A, dA, kstat fp32 (the hd x hd matrices and the statistics stay fp32 in this mode); the products run on the
@@ -2253,62 +2197,20 @@ extern "C" int hig_linattn_ctx_bwd(const float* dA, const float* A, const float*
 extern "C" int hig_linattn_apply_bwd_bf16(const void* dY, int64_t lddy, const void* Q, int64_t ldq, const float* A, void* dQ,
                                           int64_t lddq, float* dA, int32_t B, int32_t rows, int32_t H, int32_t hd, float* scratch,
                                           hig_stream_t stream) {
-  HIG_REQUIRE(dY && Q && A && dQ && dA && scratch && B > 0 && rows > 0 && H > 0, "hig_linattn_apply_bwd_bf16: bad arguments");
-  if (!(hd == 64 || (hd == 128 && allow_big_lds() == 0)))
-    return hig_set_error(HIG_EUNSUPPORTED, "hig_linattn_apply_bwd_bf16: head dim 64 or 128 (got %d)", hd);
-  HIG_REQUIRE(ldq % 4 == 0 && lddy % 4 == 0 && lddq % 8 == 0 && ((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(dY)) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(dQ) & 15) == 0,
-              "hig_linattn_apply_bwd_bf16: Q / dY rows must be 8-byte aligned, dQ rows 16-byte aligned");
-  const int nchunk = (rows + CH - 1) / CH;
-  constexpr int tgt16 = 0;   // (a former tuning knob, fixed at the value that won its A/B)
-  const int target16 = tgt16 > 0 ? tgt16 : hig_chip_cus();
-  int nparts = (target16 + B * H - 1) / (B * H);
-  nparts = nparts < 1 ? 1 : (nparts > nchunk ? nchunk : nparts);
-  float* part = nparts == 1 ? dA : scratch;
-  const __bf16* dy = static_cast<const __bf16*>(dY);
-  const __bf16* q = static_cast<const __bf16*>(Q);
-  __bf16* dq = static_cast<__bf16*>(dQ);
-  if (hd == 64)
-    hipLaunchKernelGGL((apply_bwd_mfma_kernel<64, __bf16>), dim3(B * H, nparts), dim3(256), attn_bwd_lds_bytes<64>(), hig_stream(stream),
-                       dy, lddy, q, ldq, A, dq, lddq, part, rows, H);
-  else
-    hipLaunchKernelGGL((apply_bwd_mfma_kernel<128, __bf16>), dim3(B * H, nparts), dim3(256), attn_bwd_lds_bytes<128>(), hig_stream(stream),
-                       dy, lddy, q, ldq, A, dq, lddq, part, rows, H);
-  hig_attn_path_count(HIG_ATTN_PATH_APPLY_BWD_MFMA, nparts);
-  HIG_CHECK_LAUNCH();
-  if (nparts == 1) return HIG_OK;
-  const int64_t n = (int64_t)hd * hd, groups = (int64_t)B * H;
-  const int64_t want = (groups * n / 4 + 255) / 256;
-  hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)(want > 2048 ? 2048 : want)), dim3(256), 0, hig_stream(stream), scratch, nparts, n,
-                     groups, dA);
-  HIG_CHECK_LAUNCH();
-  return HIG_OK;
+  hig_attn_plan_t p;
+  HIG_TRY(plan_bwd_entry(&p, {HIG_ATTN_ENTRY_APPLY_BWD, HIG_ATTN_IO_BF16, B, rows, 0, H, hd, scratch != nullptr,
+                              hig_attn_facts(dY && Q && A && dQ && dA, row_bits<__bf16>(ldq, Q) | row_bits<__bf16>(lddy, dY), row_bits<__bf16>(lddq, dQ))}));
+  return launch_apply_bwd<__bf16>(p, static_cast<const __bf16*>(dY), lddy, static_cast<const __bf16*>(Q), ldq, A, static_cast<__bf16*>(dQ), lddq,
+                                  dA, B, rows, H, hd, scratch, hig_stream(stream));
 }
 extern "C" int hig_linattn_ctx_bwd_bf16(const float* dA, const float* A, const void* K, const void* V, int64_t ld, const float* kstat,
                                         const int64_t* length, void* dK, void* dV, int64_t ldd, int32_t B, int32_t rows, int32_t H,
                                         int32_t hd, hig_stream_t stream) {
-  HIG_REQUIRE(dA && A && K && V && kstat && dK && dV && B > 0 && rows > 0 && H > 0, "hig_linattn_ctx_bwd_bf16: bad arguments");
-  if (!(hd == 64 || (hd == 128 && allow_big_lds() == 0)))
-    return hig_set_error(HIG_EUNSUPPORTED, "hig_linattn_ctx_bwd_bf16: head dim 64 or 128 (got %d)", hd);
-  HIG_REQUIRE(ld % 4 == 0 && ldd % 8 == 0 && ((reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V)) & 7) == 0 &&
-                  ((reinterpret_cast<uintptr_t>(dK) | reinterpret_cast<uintptr_t>(dV)) & 15) == 0,
-              "hig_linattn_ctx_bwd_bf16: K / V rows must be 8-byte aligned, dK / dV rows 16-byte aligned");
-  const int nchunk = (rows + CH - 1) / CH;
-  constexpr int tgt16 = 0;   // (a former tuning knob, fixed at the value that won its A/B)
-  const int target16 = tgt16 > 0 ? tgt16 : hig_chip_cus();
-  int gy = (target16 + B * H - 1) / (B * H);
-  gy = gy < 1 ? 1 : (gy > nchunk ? nchunk : gy);
-  const __bf16* k = static_cast<const __bf16*>(K);
-  const __bf16* v = static_cast<const __bf16*>(V);
-  if (hd == 64)
-    hipLaunchKernelGGL((ctx_bwd_mfma_kernel<64, __bf16>), dim3(B * H, gy), dim3(256), attn_bwd_lds_bytes<64>(), hig_stream(stream), dA, A, k, v,
-                       ld, kstat, length, static_cast<__bf16*>(dK), static_cast<__bf16*>(dV), ldd, rows, H);
-  else
-    hipLaunchKernelGGL((ctx_bwd_mfma_kernel<128, __bf16>), dim3(B * H, gy), dim3(256), attn_bwd_lds_bytes<128>(), hig_stream(stream), dA, A, k,
-                       v, ld, kstat, length, static_cast<__bf16*>(dK), static_cast<__bf16*>(dV), ldd, rows, H);
-  hig_attn_path_count(HIG_ATTN_PATH_CTX_BWD_MFMA, gy);
-  HIG_CHECK_LAUNCH();
-  return HIG_OK;
+  hig_attn_plan_t p;
+  HIG_TRY(plan_bwd_entry(&p, {HIG_ATTN_ENTRY_CTX_BWD, HIG_ATTN_IO_BF16, B, rows, 0, H, hd, false,
+                              hig_attn_facts(dA && A && K && V && kstat && dK && dV, row_bits<__bf16>(ld, K, V), row_bits<__bf16>(ldd, dK, dV))}));
+  return launch_ctx_bwd<__bf16>(p, dA, A, static_cast<const __bf16*>(K), static_cast<const __bf16*>(V), ld, kstat, length,
+                                static_cast<__bf16*>(dK), static_cast<__bf16*>(dV), ldd, B, rows, H, hd, nullptr, hig_stream(stream));
 }
 
 // Fused apply + stylization front (bf16 storage): Out = silu( LN(softmax_hd(Q) . A) * (1 + scale) + shift ), see
@@ -2317,14 +2219,10 @@ extern "C" int hig_linattn_apply_sty_bf16(const void* Q, int64_t ldq, const floa
                                           const float* beta, const float* ss, int64_t ss_ld, int32_t ss_shift_off,
                                           void* Out, int64_t ldo, int32_t B, int32_t rows, int32_t H, int32_t hd,
                                           hig_stream_t stream) {
-  HIG_REQUIRE(Q && A && gamma && beta && ss && Out && B > 0 && rows > 0, "hig_linattn_apply_sty_bf16: bad arguments");
-  if ((hd != 64 && hd != 128) || (H != 4 && H != 8))
-    return hig_set_error(HIG_EUNSUPPORTED, "hig_linattn_apply_sty_bf16: built for head dim 64 / 128 and 4 or 8 heads (got %d, %d)", hd, H);
-  HIG_REQUIRE(ldq % 8 == 0 && ldo % 8 == 0 && ss_ld % 4 == 0 && ss_shift_off % 4 == 0 &&
-                  ((reinterpret_cast<uintptr_t>(Q) & 15) | (reinterpret_cast<uintptr_t>(Out) & 15) |
-                   (reinterpret_cast<uintptr_t>(gamma) & 15) | (reinterpret_cast<uintptr_t>(beta) & 15) |
-                   (reinterpret_cast<uintptr_t>(ss) & 15)) == 0,
-              "hig_linattn_apply_sty_bf16: alignment");
+  hig_attn_plan_t p;
+  HIG_TRY(hig_attn_plan_entry(&p, {HIG_ATTN_ENTRY_APPLY_STY, HIG_ATTN_IO_BF16, B, rows, 0, H, hd, false,
+                              hig_attn_facts(Q && A && gamma && beta && ss && Out, row_bits<__bf16>(ldq, Q), row_bits<__bf16>(ldo, Out),
+                                             row_bits<float>(ss_ld, gamma, beta, ss) | row_bits<float>(ss_shift_off))}));
   return launch_apply_sty<__bf16, __bf16>(static_cast<const __bf16*>(Q), ldq, A, gamma, beta, ss, ss_ld, ss_shift_off,
                                           static_cast<__bf16*>(Out), ldo, B, rows, H, hd, hig_stream(stream));
 }
@@ -2334,25 +2232,19 @@ extern "C" int hig_linattn_apply_sty_bf16(const void* Q, int64_t ldq, const floa
 extern "C" int hig_linattn_apply_sty(const float* Q, int64_t ldq, const float* A, const float* gamma, const float* beta,
                                      const float* ss, int64_t ss_ld, int32_t ss_shift_off, float* Out, int64_t ldo,
                                      int32_t B, int32_t rows, int32_t H, int32_t hd, hig_stream_t stream) {
-  HIG_REQUIRE(Q && A && gamma && beta && ss && Out && B > 0 && rows > 0, "hig_linattn_apply_sty: bad arguments");
-  if ((hd != 64 && hd != 128) || (H != 4 && H != 8))
-    return hig_set_error(HIG_EUNSUPPORTED, "hig_linattn_apply_sty: built for head dim 64 / 128 and 4 or 8 heads (got %d, %d)", hd, H);
-  HIG_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0 && ss_ld % 4 == 0 && ss_shift_off % 4 == 0 &&
-                  ((reinterpret_cast<uintptr_t>(Q) & 15) | (reinterpret_cast<uintptr_t>(Out) & 15) |
-                   (reinterpret_cast<uintptr_t>(gamma) & 15) | (reinterpret_cast<uintptr_t>(beta) & 15) |
-                   (reinterpret_cast<uintptr_t>(ss) & 15)) == 0,
-              "hig_linattn_apply_sty: alignment");
-  if (hd == 64) {   // the wave-autonomous kernel (32-bit byte offsets into a sample's rows of Out)
-    HIG_REQUIRE(((int64_t)rows + 16) * ldo * 4 < INT32_MAX, "hig_linattn_apply_sty: a sample's output rows exceed 2 GiB");
-    return H == 8 ? launch_apply_sty_wave64<8>(Q, ldq, A, gamma, beta, ss, ss_ld, ss_shift_off, Out, ldo, B, rows, hig_stream(stream))
-                  : launch_apply_sty_wave64<4>(Q, ldq, A, gamma, beta, ss, ss_ld, ss_shift_off, Out, ldo, B, rows, hig_stream(stream));
-  }
-  return launch_apply_sty<float, float>(Q, ldq, A, gamma, beta, ss, ss_ld, ss_shift_off, Out, ldo, B, rows, H, hd,
-                                        hig_stream(stream));
+  hig_attn_plan_t p;
+  HIG_TRY(hig_attn_plan_entry(&p, {HIG_ATTN_ENTRY_APPLY_STY, HIG_ATTN_IO_F32, B, rows, 0, H, hd, false,
+                              hig_attn_facts(Q && A && gamma && beta && ss && Out, row_bits<float>(ldq, Q), row_bits<float>(ldo, Out),
+                                             row_bits<float>(ss_ld, gamma, beta, ss) | row_bits<float>(ss_shift_off),
+                                             sty_out_i32(rows, ldo))}));
+  if (p.path == HIG_ATTN_PATH_APPLY_STY)
+    return launch_apply_sty<float, float>(Q, ldq, A, gamma, beta, ss, ss_ld, ss_shift_off, Out, ldo, B, rows, H, hd, hig_stream(stream));
+  return H == 8 ? launch_apply_sty_wave64<8>(Q, ldq, A, gamma, beta, ss, ss_ld, ss_shift_off, Out, ldo, B, rows, p.split, hig_stream(stream))
+                : launch_apply_sty_wave64<4>(Q, ldq, A, gamma, beta, ss, ss_ld, ss_shift_off, Out, ldo, B, rows, p.split, hig_stream(stream));
 }
 
-// Launch counts per attention kernel (hig_attn_path_launches) and the gridDim.y of the latest counted launch
-// (hig_attn_last_split): host side, written at each launch site here and in fullattn.hip.
+// Launch counts per attention kernel (hig_attn_path_launches) and the split of the latest counted launch
+// (hig_attn_last_split): host side, written once per planned call (hig_attn_plan_entry) and by hig_linattn_ctx_groups.
 static long long g_attn_launches[HIG_ATTN_NPATHS];
 static int g_attn_last_split = 1;
 void hig_attn_path_count(int path, int split) {

@@ -646,11 +646,12 @@ int hig_gemm_plan(const hig_gemm_desc* g, int32_t has_tail_scratch, int32_t chip
 int hig_gemm_bf16_lnfold_plan(int64_t rows, int32_t d, int32_t chip_cus);
 /* Attention paths: one per kernel the linear- and full-attention entry points below (csrc/linattn.hip, csrc/fullattn.hip) can
  * launch; the fp32 and bf16-I/O instances of one kernel share a path.  hig_attn_path_launches(path) counts the launches of that
- * kernel since the library was loaded (monotonic, host side, one relaxed atomic add at the launch site; the chunk_sum_kernel
+ * kernel since the library was loaded (monotonic, host side, one relaxed atomic add per planned call; the chunk_sum_kernel
  * behind a split hig_linattn_apply_bwd is not counted); -1 for an unknown path.  hig_attn_last_split() is the gridDim.y of the
  * most recent counted launch (1 where the grid has no second dimension): how many workgroups shared one (sample, head).  Both
  * are test hooks: a test reads them around a call to prove which kernel served it and in which split regime.  The launches
- * inside hig_denoiser_*, hig_text_* and hig_eval_encoder_fwd go through the same launch sites and are counted too. */
+ * inside hig_denoiser_*, hig_text_* and hig_eval_encoder_fwd go through the same entry points and are counted too.  Which path
+ * and split a call gets is decided by its plan, apart from the launch: hig_attn_plan below answers it without launching. */
 #define HIG_ATTN_PATH_CTX 0               /* hig_linattn_ctx: ctx_kernel (head dim 8 / 16 / 32, VALU) */
 #define HIG_ATTN_PATH_CTX_MFMA 1          /* hig_linattn_ctx[_bf16]: ctx_mfma_kernel, one workgroup walks all chunks of a (sample, head) */
 #define HIG_ATTN_PATH_CTX_PART 2          /* hig_linattn_ctx[_bf16] with scratch: ctx_part_mfma_kernel + ctx_combine_kernel, counted once */
@@ -670,6 +671,42 @@ int hig_gemm_bf16_lnfold_plan(int64_t rows, int32_t d, int32_t chip_cus);
 #define HIG_ATTN_NPATHS 16
 int64_t hig_attn_path_launches(int32_t path);
 int32_t hig_attn_last_split(void);
+/* What an attention call would do, without doing it (csrc/attn_plan.hip: every entry point of linattn.hip and fullattn.hip
+ * plans, then launches what the plan names).  The return value is the code the call would return (a refusal: *path = -1,
+ * *split = 0); *path the HIG_ATTN_PATH_* whose counter would move, *split what hig_attn_last_split() would report after it,
+ * *variant the instance: the waves per workgroup (2 / 4 / 8) of the matrix-core full-attention kernels; 1 for a
+ * hig_linattn_apply_bwd whose dA partials go to scratch and are summed by chunk_sum_kernel (0: the kernel writes dA itself);
+ * 0 otherwise.  A pure function of its arguments and the environment switches (HIG_APPLY_WAVE, HIG_FULLATTN_WAVES,
+ * HIG_FULLATTN_VALU): no launch, no error message; the out pointers may be NULL.
+ *   entry, io    which entry point: HIG_ATTN_ENTRY_* with fp32 or bf16 rows (hig_linattn_ctx_bf16 = ENTRY_CTX, IO_BF16; full
+ *                attention has no bf16 backward: HIG_EINVAL)
+ *   rows, Tk     rows per sample; for full attention rows = Tq and Tk = keys per sample (ignored otherwise)
+ *   has_scratch  the call's `scratch` is not NULL
+ *   facts        bit mask of HIG_ATTN_FACT_*: what the entry point reads off its operands.  "Rows" are a pointer's low bits and
+ *                the leading dimension in bytes; "input" = the bf16 / fp32 rows the call reads (Q, K, V, dY, Y), "output" =
+ *                those it writes (Y, Out, dQ, dK, dV).  HIG_ATTN_FACTS_ALL: a dense, 16-byte aligned, complete call.
+ *   chip_cus     compute units to plan for (<= 0: the current device's)
+ *   big_lds_ok   the device grants the 135 KB of dynamic LDS the head-dim-128 matrix-core backward kernels need (on an MI355X:
+ *                1); without it fp32 falls to the VALU kernels and bf16 is HIG_EUNSUPPORTED */
+#define HIG_ATTN_ENTRY_CTX 0
+#define HIG_ATTN_ENTRY_APPLY 1
+#define HIG_ATTN_ENTRY_APPLY_STY 2
+#define HIG_ATTN_ENTRY_APPLY_BWD 3
+#define HIG_ATTN_ENTRY_CTX_BWD 4
+#define HIG_ATTN_ENTRY_FULL_FWD 5
+#define HIG_ATTN_ENTRY_FULL_BWD 6
+#define HIG_ATTN_IO_F32 0
+#define HIG_ATTN_IO_BF16 1
+#define HIG_ATTN_FACT_IN8 1        /* input rows 8-byte aligned */
+#define HIG_ATTN_FACT_IN16 2       /* ... 16-byte aligned */
+#define HIG_ATTN_FACT_OUT8 4       /* output rows 8-byte aligned */
+#define HIG_ATTN_FACT_OUT16 8      /* ... 16-byte aligned */
+#define HIG_ATTN_FACT_PAR16 16     /* hig_linattn_apply_sty: gamma, beta, ss, ss_ld and ss_shift_off 16-byte aligned */
+#define HIG_ATTN_FACT_OUT_I32 32   /* hig_linattn_apply_sty: (rows + 16) output rows of a sample stay below 2 GiB */
+#define HIG_ATTN_FACT_OPERANDS 64  /* every required operand pointer is non-NULL (scratch apart) */
+#define HIG_ATTN_FACTS_ALL 127
+int hig_attn_plan(int32_t entry, int32_t io, int32_t B, int32_t rows, int32_t Tk, int32_t H, int32_t hd, int32_t has_scratch,
+                  int32_t facts, int32_t chip_cus, int32_t big_lds_ok, int32_t* path, int32_t* split, int32_t* variant);
 int hig_wgrad16_debug_stamps(void* buf);      /* wgrad16.hip (see there): 8192 x 8 bytes */
 /* the same for hig_linattn_apply_sty_mm16: 8 stamps per workgroup (see linattn16.hip) */
 int hig_linattn16_debug_stamps(void* buf);

@@ -197,6 +197,37 @@ int main() {
         EXPECT((hig_gemm_bf16_lnfold_plan(rows, d, 256) | 1) == 1);
     EXPECT(hig_gemm_bf16_lnfold_plan(12544, 512, 256) == 1 && hig_gemm_bf16_lnfold_plan(12544, 512, 128) == 0);
   }
+  // ---- attention plan entry: a pure host function; null out-pointers, zero, negative and INT32_MAX extents, every entry x I/O x
+  // head dim x operand facts; then the entry points' own refusals (planned, so returned before any launch) ----
+  {
+    int32_t path = 0, split = 0, variant = 0;
+    const int extents[] = {-5, 0, 1, 64, 65, 196, 4096, INT32_MAX};
+    int served = 0, refused = 0;
+    for (int entry = -1; entry <= HIG_ATTN_ENTRY_FULL_BWD + 1; ++entry) for (int io = -1; io <= 2; ++io)
+      for (int hd : {-64, 0, 8, 16, 32, 48, 64, 128, 256, INT32_MAX}) for (int B : extents) for (int rows : extents) for (int H : {-1, 0, 3, 4, 8, INT32_MAX})
+        for (int facts : {0, HIG_ATTN_FACT_OPERANDS, HIG_ATTN_FACTS_ALL & ~HIG_ATTN_FACT_IN16, HIG_ATTN_FACTS_ALL, -1}) for (int cus : {1, 256, INT32_MAX})
+          for (int lds = 0; lds <= 1; ++lds) {
+            const int rc = hig_attn_plan(entry, io, B, rows, rows, H, hd, lds, facts, cus, lds, &path, &split, &variant);
+            EXPECT((rc == HIG_OK && path >= 0 && path < HIG_ATTN_NPATHS && split >= 1 && variant >= 0) || (rc < 0 && path == -1 && split == 0));
+            if (entry < 0 || entry > HIG_ATTN_ENTRY_FULL_BWD || io < 0 || io > 1 || B <= 0 || rows <= 0) EXPECT(rc == HIG_EINVAL);
+            if (facts == HIG_ATTN_FACTS_ALL) EXPECT(hig_attn_plan(entry, io, B, rows, rows, H, hd, lds, facts, cus, lds, nullptr, nullptr, nullptr) == rc);
+            rc == HIG_OK ? ++served : ++refused;
+          }
+    EXPECT(served > 1000 && refused > 1000);
+    alignas(16) static float q[64];
+    EXPECT(hig_linattn_apply(nullptr, 64, q, q, 64, 1, 1, 1, 64, nullptr) == HIG_EINVAL);
+    EXPECT(hig_linattn_apply(q, 64, q, q, 64, 1, 1, 1, 48, nullptr) == HIG_EINVAL);                                  // head dim
+    EXPECT(hig_linattn_apply(q, 64, q, q + 1, 64, 1, 1, 1, 64, nullptr) == HIG_EINVAL);                              // Y off 16 bytes
+    EXPECT(hig_linattn_apply_bf16(q, 64, q, q, 64, 1, 1, 1, 32, nullptr) == HIG_EUNSUPPORTED);
+    EXPECT(hig_linattn_ctx_bf16(q, q, 66, 1, 1, 1, 64, nullptr, q, q, nullptr, nullptr, nullptr) == HIG_EINVAL);     // ld % 4
+    EXPECT(hig_linattn_apply_bwd(q, 64, q, 64, q, q, 64, q, 1, 1, 1, 128, nullptr, nullptr) == HIG_EINVAL);          // no scratch
+    EXPECT(hig_linattn_ctx_bwd_bf16(q, q, q, q, 64, q, nullptr, q, q, INT64_MAX, 1, 1, 1, 64, nullptr) == HIG_EINVAL);
+    EXPECT(hig_linattn_apply_sty(q, 256, q, q, q, q, 512, 256, q, 256, 1, 1, 3, 64, nullptr) == HIG_EUNSUPPORTED);   // 3 heads
+    EXPECT(hig_linattn_apply_sty(q, 256, q, q, q, q, 512, 256, q, INT64_MAX - 3, 1, INT32_MAX, 4, 64, nullptr) == HIG_EINVAL);   // output rows beyond 2 GiB
+    EXPECT(hig_fullattn_fwd(q, 64, q, q, 64, 1, 1, 0, 1, 64, nullptr, q, 64, q, nullptr) == HIG_EINVAL);             // no keys
+    EXPECT(hig_fullattn_fwd_bf16(q, 64, q, q, 64, 1, 1, 1, 1, 32, nullptr, q, 64, nullptr) == HIG_EUNSUPPORTED);
+    EXPECT(hig_fullattn_bwd(q, 64, q, 64, q, 64, q, q, 64, 1, 1, 1, 1, 64, nullptr, q, q, q, 64, q, q + 2, 64, nullptr) == HIG_EINVAL);
+  }
   // ---- diagnostics pointers: set and cleared ----
   EXPECT(hig_gemm_bf16_debug_stamps(nullptr) == HIG_OK && hig_gemm_ws16_debug_stamps(nullptr) == HIG_OK &&
          hig_gemm_debug_stamps(nullptr) == HIG_OK);

@@ -52,13 +52,13 @@ def _header_constants():
 
 def test_lib_constants_mirror_the_header():
     """_lib's table slots and codes (header names without `HIG_`) hold the header's values, and every slot of the
-    parameter table, of the derived-operand tables, every GEMM path and every attention path is mirrored."""
+    parameter table, of the derived-operand tables, every GEMM path, every attention path and every code hig_attn_plan takes is mirrored."""
     consts = _header_constants()
     assert consts["HIG_EINVAL"] == -1 and consts["HIG_NLAYER"] > consts["HIG_L_INT_STY_OUT_B"] > 0, "header not parsed"
     mirrored = {n: v for n, v in vars(_lib).items() if type(v) is int and "HIG_" + n in consts}
     wrong = {n: (v, consts["HIG_" + n]) for n, v in mirrored.items() if v != consts["HIG_" + n]}
     assert not wrong, "_lib value != hig.h value: %s" % wrong
-    tables = [n for n in consts if n.startswith(("HIG_P_", "HIG_L_", "HIG_D32_", "HIG_D16_", "HIG_GEMM_PATH_", "HIG_ATTN_PATH_"))] + ["HIG_NGLOBAL", "HIG_NLAYER"]
+    tables = [n for n in consts if n.startswith(("HIG_P_", "HIG_L_", "HIG_D32_", "HIG_D16_", "HIG_GEMM_PATH_", "HIG_ATTN_PATH_", "HIG_ATTN_ENTRY_", "HIG_ATTN_IO_", "HIG_ATTN_FACT"))] + ["HIG_NGLOBAL", "HIG_NLAYER"]
     missing = [n for n in tables if n[len("HIG_"):] not in mirrored]
     assert not missing, "hig.h table slots without a _lib mirror: %s" % missing
 

@@ -1,8 +1,10 @@
 """The contract of every attention kernel (csrc/linattn.hip, csrc/fullattn.hip): which kernel served a call and in which
 split regime, that it wrote every output element and nothing around it, and an element-wise bound against fp64.
 
-Every library call goes through `counted`, which asserts that exactly the expected HIG_ATTN_PATH_* counter moved (by one) and
-holds hig_attn_last_split() to the regime the case is named for:
+Every library call goes through `counted`, which first asks the plan (hig_attn_plan with the device's CU count; the expected
+paths and regimes are the tables of tests/attn_dispatch_cases.py, which tests/test_cpu_attn_plan.py holds the plan to without a
+GPU), then asserts that exactly the planned and expected HIG_ATTN_PATH_* counter moved (by one), that hig_attn_last_split() is
+the planned split, and holds it to the regime the case is named for:
     'one'      gridDim.y == 1: one workgroup walks every chunk of a (sample, head);
     'all'      gridDim.y == number of chunks / blocks: one workgroup each;
     'partial'  strictly between: workgroups walk several chunks each AND their partial results are merged.
@@ -51,15 +53,18 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from hig_amd import _lib  # noqa: E402
+from attn_dispatch_cases import (APPLY_STY, APPLY_STY_B, APPLY_STY_T, CALLS, LIN_TABLE, MFMA_ALL, MFMA_ONE, MFMA_PART, PATHS, VALU, WAVE,  # noqa: E402
+                                 full_paths, in_regime, plan)
+import attn_dispatch_cases  # noqa: E402
 
 DEV = "cuda"
 U = 2.0 ** -24
 FLOOR = 2.0 ** -120     # products of two weights near e^-80 reach the subnormal range, which the matrix cores flush
 CH = 64                 # rows per chunk of the linear-attention kernels
-PATHS = ("CTX", "CTX_MFMA", "CTX_PART", "APPLY", "APPLY_MFMA", "APPLY_WAVE64", "APPLY_STY", "APPLY_STY_WAVE64", "APPLY_BWD",
-         "APPLY_BWD_MFMA", "CTX_BWD", "CTX_BWD_MFMA", "FULL_FWD", "FULL_FWD_MFMA", "FULL_BWD", "FULL_BWD_MFMA")
 SENTINEL = {torch.float32: (torch.int32, 0x7FC0BEEF), torch.bfloat16: (torch.int16, 0x7FD5)}   # NaN patterns
 F32, BF16 = torch.float32, torch.bfloat16
+IO = {attn_dispatch_cases.F32: F32, attn_dispatch_cases.BF16: BF16}   # the shared tables name the I/O type, this file uses the dtype
+IO_NAME = {v: k for k, v in IO.items()}
 
 
 def lib():
@@ -75,16 +80,27 @@ def counts():
     return [lib().hig_attn_path_launches(getattr(_lib, "ATTN_PATH_" + n)) for n in PATHS]
 
 
-def counted(call, path, regime, nblocks):
-    """call() -> rc; asserts rc == 0, that exactly the counter of `path` moved by one, and the split regime (see the module
-    docstring; nblocks = the chunks / blocks one (sample, head) has).  Returns the split."""
+def planned(entry, io, B, rows, H, hd, Tk=0, scratch=True):
+    """What hig_attn_plan answers for this call on the device at hand (its CU count, big dynamic LDS granted): (path, split)."""
+    rc, path, split, _ = plan(entry, IO_NAME[io], B, rows, H, hd, Tk=Tk, scratch=scratch, chip_cus=ncu(), big_lds_ok=1)
+    assert rc == 0, "the plan refuses the call (%d)" % rc
+    return path, split
+
+
+def counted(call, path, regime, nblocks, ask):
+    """call() -> rc; asks the plan first (ask = the arguments of `planned`), then asserts rc == 0, that exactly the planned
+    counter, which is that of `path`, moved by one, that hig_attn_last_split() is the planned split, and the split regime (see
+    the module docstring; nblocks = the chunks / blocks one (sample, head) has).  Returns the split."""
+    want = planned(*ask)
     before = counts()
     _lib.check(call())
     torch.cuda.synchronize()
     moved = {n: a - b for n, a, b in zip(PATHS, counts(), before) if a != b}
+    assert moved == {want[0]: 1}, "the plan named %s, the call launched %s" % (want[0], moved)
     assert moved == {path: 1}, "expected one launch of %s, got %s" % (path, moved)
     split = lib().hig_attn_last_split()
-    ok = {"one": split == 1, "all": split == nblocks, "partial": 1 < split < nblocks}[regime]
+    assert split == want[1], "the plan named split %d, the call reports %d" % (want[1], split)
+    ok = in_regime(regime, split, nblocks)
     if not ok and ncu() != 256:   # the table is written for (and never skips on) the 256 CUs of the MI355X
         pytest.skip("split %d of %d blocks: the '%s' regime of %s is not reached by this shape with %d CUs" % (split, nblocks, regime, path, ncu()))
     assert ok, "%s: split %d of %d blocks is not the '%s' regime" % (path, split, nblocks, regime)
@@ -270,7 +286,7 @@ def run_linear(B, T, H, hd, io, expect, seed=0, use_lens=True, adversarial=False
         outs = []
         for _ in range(2):
             bufs = make()
-            split = counted(lambda: call(*bufs), path, regime, nblocks)
+            split = counted(lambda: call(*bufs), path, regime, nblocks, (CALLS[entry][0], io, B, T, H, hd, 0, CALLS[entry][1]))
             outs.append([b_.verify(entry) for b_ in bufs if isinstance(b_, Guarded)])
         for a, b_ in zip(*outs):
             assert torch.equal(a, b_), "%s: two calls on the same inputs differ" % entry
@@ -345,68 +361,7 @@ def batch_for(bh, H):
 
 def regime_bh(name, H):
     """B * H of the named occupancy regime on the device at hand."""
-    n = ncu()
-    return {"few": 7 * H, "2/5": (2 * n // 5) // H * H, "half": n // 2, "ncu-H": n - H, "ncu": n, "2ncu": 2 * n, "4ncu": 4 * n}[name]
-
-
-MFMA_ONE = {"ctx_s": ("CTX_MFMA", "one"), "ctx_n": ("CTX_MFMA", "one"), "apply_bwd": ("APPLY_BWD_MFMA", "one"),
-            "ctx_bwd": ("CTX_BWD_MFMA", "one")}
-MFMA_ALL = {"ctx_s": ("CTX_PART", "all"), "ctx_n": ("CTX_MFMA", "one"), "apply_bwd": ("APPLY_BWD_MFMA", "all"),
-            "ctx_bwd": ("CTX_BWD_MFMA", "all")}
-MFMA_PART = {"ctx_s": ("CTX_PART", "all"), "ctx_n": ("CTX_MFMA", "one"), "apply_bwd": ("APPLY_BWD_MFMA", "partial"),
-             "ctx_bwd": ("CTX_BWD_MFMA", "partial")}
-VALU = {"ctx_s": ("CTX", "one"), "ctx_n": ("CTX", "one"), "apply": ("APPLY", "all"), "apply_bwd": ("APPLY_BWD", "all"),
-        "ctx_bwd": ("CTX_BWD", "all")}
-WAVE = ("APPLY_WAVE64", "one")
-
-# (id, io, hd, H, B * H regime, T, what each entry must run).  One chunk (T <= 64) is 'one' and 'all' at once; the rows say
-# 'all' for the kernels that launch a workgroup per chunk and 'one' for those that walk.
-# apply_mfma_kernel has no 'partial' row at fp32 / hd 64: rows >= 128 go to apply_wave64_kernel, and the two chunks of
-# T < 128 leave nothing strictly between 1 and 2.
-LIN_TABLE = [
-    # VALU kernels: T not a multiple of 64, H not a power of two
-    ("valu-hd8", F32, 8, 3, "few", 63, VALU), ("valu-hd16", F32, 16, 5, "few", 65, VALU), ("valu-hd32", F32, 32, 3, "few", 129, VALU),
-    ("valu-hd32-T1", F32, 32, 6, "few", 1, VALU), ("valu-hd16-T300", F32, 16, 3, "few", 300, VALU),
-    # fp32, head dim 64: few (sample, head) pairs -> one workgroup per chunk; every T edge
-    ("f32-hd64-few-T1", F32, 64, 8, "few", 1, dict(MFMA_ALL, ctx_s=("CTX_MFMA", "one"), apply=("APPLY_MFMA", "all"))),
-    ("f32-hd64-few-T63", F32, 64, 8, "few", 63, dict(MFMA_ALL, ctx_s=("CTX_MFMA", "one"), apply=("APPLY_MFMA", "all"))),
-    ("f32-hd64-few-T64", F32, 64, 4, "few", 64, dict(MFMA_ALL, ctx_s=("CTX_MFMA", "one"), apply=("APPLY_MFMA", "all"))),
-    ("f32-hd64-few-T65", F32, 64, 8, "few", 65, dict(MFMA_ALL, apply=("APPLY_MFMA", "all"))),
-    ("f32-hd64-few-T127", F32, 64, 8, "few", 127, dict(MFMA_ALL, apply=("APPLY_MFMA", "all"))),
-    ("f32-hd64-few-T128", F32, 64, 8, "few", 128, dict(MFMA_ALL, apply=WAVE)),
-    ("f32-hd64-few-T129", F32, 64, 8, "few", 129, dict(MFMA_ALL, apply=WAVE)),
-    ("f32-hd64-few-T196", F32, 64, 8, "few", 196, dict(MFMA_ALL, apply=WAVE)),
-    ("f32-hd64-few-T300", F32, 64, 8, "few", 300, dict(MFMA_ALL, apply=WAVE)),
-    # the partial walk: 5 chunks over 3 and over 2 workgroups
-    ("f32-hd64-2/5-T300", F32, 64, 2, "2/5", 300, dict(MFMA_PART, apply=WAVE)),
-    ("f32-hd64-half-T300", F32, 64, 8, "half", 300, dict(MFMA_PART, apply=WAVE)),
-    ("f32-hd64-ncu-H-T300", F32, 64, 8, "ncu-H", 300, dict(MFMA_PART, apply=WAVE)),
-    ("f32-hd64-half-T196", F32, 64, 4, "half", 196, dict(MFMA_PART, apply=WAVE)),
-    # the chip is full: one workgroup walks everything, scratch or not
-    ("f32-hd64-ncu-T196", F32, 64, 8, "ncu", 196, dict(MFMA_ONE, apply=WAVE)),
-    ("f32-hd64-2ncu-T129", F32, 64, 8, "2ncu", 129, dict(MFMA_ONE, apply=WAVE)),
-    ("f32-hd64-ncu-T127", F32, 64, 8, "ncu", 127, dict(MFMA_ONE, apply=("APPLY_MFMA", "all"))),
-    ("f32-hd64-4ncu-T65", F32, 64, 8, "4ncu", 65, dict(MFMA_ONE, apply=("APPLY_MFMA", "one"))),
-    # fp32, head dim 128 (apply_mfma_kernel aims at one workgroup per CU)
-    ("f32-hd128-few-T65", F32, 128, 4, "few", 65, dict(MFMA_ALL, apply=("APPLY_MFMA", "all"))),
-    ("f32-hd128-few-T300", F32, 128, 8, "few", 300, dict(MFMA_ALL, apply=("APPLY_MFMA", "all"))),
-    ("f32-hd128-2/5-T300", F32, 128, 2, "2/5", 300, dict(MFMA_PART, apply=("APPLY_MFMA", "partial"))),
-    ("f32-hd128-half-T300", F32, 128, 8, "half", 300, dict(MFMA_PART, apply=("APPLY_MFMA", "partial"))),
-    ("f32-hd128-ncu-H-T196", F32, 128, 4, "ncu-H", 196, dict(MFMA_PART, apply=("APPLY_MFMA", "partial"))),
-    ("f32-hd128-ncu-T129", F32, 128, 8, "ncu", 129, dict(MFMA_ONE, apply=("APPLY_MFMA", "one"))),
-    ("f32-hd128-2ncu-T128", F32, 128, 8, "2ncu", 128, dict(MFMA_ONE, apply=("APPLY_MFMA", "one"))),
-    # bf16 I/O, head dim 64 (apply_mfma_kernel aims at four workgroups per CU) and 128
-    ("bf16-hd64-few-T196", BF16, 64, 8, "few", 196, dict(MFMA_ALL, apply=("APPLY_MFMA", "all"))),
-    ("bf16-hd64-2/5-T300", BF16, 64, 2, "2/5", 300, dict(MFMA_PART, apply=("APPLY_MFMA", "all"))),
-    ("bf16-hd64-half-T300", BF16, 64, 8, "half", 300, dict(MFMA_PART, apply=("APPLY_MFMA", "all"))),
-    ("bf16-hd64-ncu-T300", BF16, 64, 8, "ncu", 300, dict(MFMA_ONE, apply=("APPLY_MFMA", "partial"))),
-    ("bf16-hd64-2ncu-T300", BF16, 64, 8, "2ncu", 300, dict(MFMA_ONE, apply=("APPLY_MFMA", "partial"))),
-    ("bf16-hd64-4ncu-T65", BF16, 64, 8, "4ncu", 65, dict(MFMA_ONE, apply=("APPLY_MFMA", "one"))),
-    ("bf16-hd128-few-T129", BF16, 128, 4, "few", 129, dict(MFMA_ALL, apply=("APPLY_MFMA", "all"))),
-    ("bf16-hd128-2/5-T300", BF16, 128, 2, "2/5", 300, dict(MFMA_PART, apply=("APPLY_MFMA", "partial"))),
-    ("bf16-hd128-half-T300", BF16, 128, 8, "half", 300, dict(MFMA_PART, apply=("APPLY_MFMA", "partial"))),
-    ("bf16-hd128-ncu-T196", BF16, 128, 8, "ncu", 196, dict(MFMA_ONE, apply=("APPLY_MFMA", "one"))),
-]
+    return attn_dispatch_cases.regime_bh(name, H, ncu())
 
 
 @pytest.mark.parametrize("case", LIN_TABLE, ids=[c[0] for c in LIN_TABLE])
@@ -416,7 +371,7 @@ def test_linear_dispatch_table(case):
     length of `lengths_for` (0, 1, 63, 64, 65, T - 1, T) is in the batch: length 0 gives A = 0, kstat = (0, 1) and zero
     gradients, rows at or beyond the length get dK = dV = 0 exactly."""
     _, io, hd, H, regime, T, expect = case
-    run_linear(batch_for(regime_bh(regime, H), H), T, H, hd, io, expect, seed=T + hd)
+    run_linear(batch_for(regime_bh(regime, H), H), T, H, hd, IO[io], expect, seed=T + hd)
 
 
 @pytest.mark.parametrize("hd,H,regime,expect", [(64, 8, "few", dict(MFMA_ALL, apply=("APPLY_MFMA", "all"))),
@@ -478,7 +433,7 @@ def test_apply_forward_does_not_depend_on_the_batch_split(io, hd, H, regime, T, 
     fn = L.hig_linattn_apply_bf16 if io == BF16 else L.hig_linattn_apply
     nchunk = (T + CH - 1) // CH
     whole = Guarded(B * T, d, io)
-    counted(lambda: fn(P(qkv), 3 * d, P(A), whole.ptr(), whole.ld, B, T, H, hd, s), apply[0], apply[1], nchunk)
+    counted(lambda: fn(P(qkv), 3 * d, P(A), whole.ptr(), whole.ld, B, T, H, hd, s), apply[0], apply[1], nchunk, ("apply", io, B, T, H, hd))
     y = whole.verify("whole")
     h = B // 2
     for lo, n in ((0, h), (h, B - h)):
@@ -488,15 +443,13 @@ def test_apply_forward_does_not_depend_on_the_batch_split(io, hd, H, regime, T, 
         assert torch.equal(part.verify("half"), y[lo * T:(lo + n) * T]), "a half of the batch differs from the whole"
 
 
-@pytest.mark.parametrize("io,hd,H,path,regime", [(F32, 64, 8, "APPLY_STY_WAVE64", None), (F32, 64, 4, "APPLY_STY_WAVE64", None),
-                                                  (F32, 128, 8, "APPLY_STY", "one"), (BF16, 64, 8, "APPLY_STY", "one"),
-                                                  (BF16, 128, 4, "APPLY_STY", "one")])
-@pytest.mark.parametrize("T", [1, 77, 196])
+@pytest.mark.parametrize("io,hd,H,path,regime", [(IO[c[0]],) + c[1:] for c in APPLY_STY])
+@pytest.mark.parametrize("T", APPLY_STY_T)
 def test_apply_sty_dispatch_and_guards(io, hd, H, path, regime, T):
     """hig_linattn_apply_sty / _bf16: which kernel runs, every output written, nothing around it (the values are held by
     test_gpu_apply_sty32.py and test_gpu_bf16_storage.py).  The strips of apply_sty_wave64_kernel are a launch-geometry
     choice, not a regime of this file: its split is only required to lie in 1 .. number of 16-row tiles."""
-    B, d, L, s = 3, H * hd, lib(), _lib.stream_ptr()
+    B, d, L, s = APPLY_STY_B, H * hd, lib(), _lib.stream_ptr()
     g = torch.Generator().manual_seed(T)
     q = (torch.randn(B * T, d, generator=g) * 2).to(DEV).to(io)
     A = (torch.randn(B, H, hd, hd, generator=g) * 0.5).to(DEV)
@@ -510,6 +463,7 @@ def test_apply_sty_dispatch_and_guards(io, hd, H, path, regime, T):
         torch.cuda.synchronize()
         assert {n: a - b for n, a, b in zip(PATHS, counts(), before) if a != b} == {path: 1}
         split = lib().hig_attn_last_split()
+        assert (path, split) == planned("apply_sty", io, B, T, H, hd), "the call did not do what its plan named"
         assert split == 1 if regime == "one" else 1 <= split <= (T + 15) // 16
         outs.append(o.verify(path))
     assert torch.equal(*outs), "two calls on the same inputs differ"
@@ -651,6 +605,7 @@ def run_full(B, Tq, Tk, H, hd, io, fwd_path, bwd_path, qlens=None, kpad=None, se
         torch.cuda.synchronize()
         assert {n: a - b_ for n, a, b_ in zip(PATHS, counts(), before) if a != b_} == {fwd_path: 1}
         split = lib().hig_attn_last_split()
+        assert (fwd_path, split) == planned("full_fwd", io, B, Tq, H, hd, Tk), "the call did not do what its plan named"
         if rows_per_wg:
             assert split == (Tq + rows_per_wg - 1) // rows_per_wg
         else:   # 32 query rows per wave, 2 / 4 / 8 waves (HIG_FULLATTN_WAVES; test_gpu_knobs.py): one of the three grids
@@ -679,6 +634,7 @@ def run_full(B, Tq, Tk, H, hd, io, fwd_path, bwd_path, qlens=None, kpad=None, se
                                           P(delta), dq.ptr(), dq.ld, dk.ptr(), dv.ptr(), dk.ld, s))
             torch.cuda.synchronize()
             assert {n: a - b_ for n, a, b_ in zip(PATHS, counts(), before) if a != b_} == {bwd_path: 1}
+            assert (bwd_path, lib().hig_attn_last_split()) == planned("full_bwd", F32, B, Tq, H, hd, Tk), "the call did not do what its plan named"
             outs.append((dq.verify("dQ"), dk.verify("dK"), dv.verify("dV")))
         for a, b_ in zip(*outs):
             assert torch.equal(a, b_), "two backward calls differ"
@@ -692,8 +648,7 @@ def run_full(B, Tq, Tk, H, hd, io, fwd_path, bwd_path, qlens=None, kpad=None, se
     print(" ".join(report))
 
 
-def paths_for(hd):
-    return ("FULL_FWD_MFMA", "FULL_BWD_MFMA") if hd >= 64 else ("FULL_FWD", "FULL_BWD")
+paths_for = full_paths
 
 
 FULL_TABLE = [
