@@ -46,6 +46,18 @@ STORE_F32, STORE_BF16 = 0, 1
 ATTN_IO_F32, ATTN_IO_BF16 = 0, 1
 (ATTN_FACT_IN8, ATTN_FACT_IN16, ATTN_FACT_OUT8, ATTN_FACT_OUT16, ATTN_FACT_PAR16, ATTN_FACT_OUT_I32, ATTN_FACT_OPERANDS,
  ATTN_FACTS_ALL) = 1, 2, 4, 8, 16, 32, 64, 127
+# what hig_denoiser_plan is asked (entry point, derived-operand facts, switches in the struct's order) and the slots it answers in
+(DN_ENTRY_TEXT32, DN_ENTRY_TEXT16, DN_ENTRY_FWD32, DN_ENTRY_FWD16, DN_ENTRY_FWD16_TRAIN, DN_ENTRY_BWD32, DN_ENTRY_BWD16) = range(7)
+DN_FACT_TABLE, DN_FACT_TEXT_GLOBALS, DN_FACT_KVALL = 1, 2, 4
+DN_SWITCHES = ("HIG_TEXT_BATCH", "HIG_TEXT_FORK", "HIG_FWD_SPLIT", "HIG_LNFOLD32", "HIG_FWD16_FORK", "HIG_CTX16", "HIG_JOINT16",
+               "HIG_FUSE_APPLY", "HIG_FUSE_OUT", "HIG_EDGE16", "HIG_BWD_OVERLAP")
+DN_SWITCH_DEFAULTS = (1, 1, -1, 1, -1, 1, 1, 2, 1, 1, -1)
+DN_NSWITCHES = 11
+(DN_PLAN_ENTRY, DN_PLAN_TEXT_BATCHED, DN_PLAN_TEXT_FORK, DN_PLAN_FUSE_APPLY, DN_PLAN_FOLD32, DN_PLAN_SPLIT, DN_PLAN_FORK_EMB,
+ DN_PLAN_FORK_TEXT, DN_PLAN_CTX_MM16, DN_PLAN_JOINT16, DN_PLAN_FUSE_MM16, DN_PLAN_FUSE_OUT, DN_PLAN_FUSE_FRONT, DN_PLAN_WGRAD_FORK,
+ DN_PLAN_EDGE16, DN_PLAN_FP, DN_PLAN_WANTS_SIDE_STREAM, DN_PLAN_NSLOTS) = range(18)
+DN_PLAN_SLOTS = ("entry", "text_batched", "text_fork", "fuse_apply", "fold32", "split", "fork_emb", "fork_text", "ctx_mm16", "joint16",
+                 "fuse_mm16", "fuse_out", "fuse_front", "wgrad_fork", "edge16", "Fp", "wants_side_stream")
 TAB_ROWS = 7
 NORM_BLOCKS = 1024
 COLSUM_CHUNKS = 512
@@ -70,6 +82,7 @@ SYMBOLS = (
     "hig_gelu_bf16", "hig_cast_f32", "hig_cast_pad_bf16", "hig_gemm_bf16_split", "hig_gemm_bf16_split_scratch_floats", "hig_clip_adam_shadow",
     "hig_debug_marker", "hig_denoiser_fwd_text", "hig_wgrad_bf16", "hig_wgrad_bf16_scratch_floats", "hig_denoiser_fwd_x", "hig_denoiser_fwd_bf16_x",
     "hig_gemm_bf16_plan", "hig_gemm_plan", "hig_gemm_bf16_lnfold_plan", "hig_attn_plan",
+    "hig_denoiser_plan", "hig_denoiser_last_schedule",
 )
 
 
@@ -204,6 +217,9 @@ def lib():
         L.hig_gemm_plan.argtypes = [C.POINTER(GemmDesc), i32, i32, pi32, pi32, pi32]
         L.hig_gemm_bf16_lnfold_plan.argtypes = [i64, i32, i32]
         L.hig_attn_plan.argtypes = [i32] * 11 + [pi32, pi32, pi32]
+        L.hig_denoiser_plan.argtypes = [C.POINTER(Dims)] + [i32] * 7 + [pi32, pi32, i32]
+        L.hig_denoiser_last_schedule.argtypes = [pi32, i32]
+        L.hig_denoiser_last_schedule.restype = i32
         L.hig_attn_path_launches.argtypes = [i32]
         L.hig_attn_path_launches.restype = i64
         L.hig_attn_last_split.argtypes = []
@@ -285,6 +301,24 @@ def last_error():
 def check(rc):
     if rc != 0:
         raise RuntimeError("libhig error %d: %s" % (rc, last_error()))
+
+
+def denoiser_plan(dims, entry, training=0, has_xf_out=0, facts=0, capturing=0, chip_cus=256, wsp32_active=1, switches=None):
+    """hig_denoiser_plan as {slot name: value}; switches: {switch name: value} over the defaults, or None for the process's."""
+    sw = None
+    if switches is not None:
+        unknown = set(switches) - set(DN_SWITCHES)
+        assert not unknown, unknown
+        sw = (C.c_int32 * DN_NSWITCHES)(*[switches.get(n, v) for n, v in zip(DN_SWITCHES, DN_SWITCH_DEFAULTS)])
+    out = (C.c_int32 * DN_PLAN_NSLOTS)()
+    check(lib().hig_denoiser_plan(C.byref(dims), entry, training, has_xf_out, facts, capturing, chip_cus, wsp32_active, sw, out, DN_PLAN_NSLOTS))
+    return dict(zip(DN_PLAN_SLOTS, out))
+
+
+def denoiser_last_schedule():
+    """What the most recent denoiser entry point on this thread ran, as {slot name: value} (None: none yet)."""
+    out = (C.c_int32 * DN_PLAN_NSLOTS)()
+    return dict(zip(DN_PLAN_SLOTS, out)) if lib().hig_denoiser_last_schedule(out, DN_PLAN_NSLOTS) >= 0 else None
 
 
 def stream_ptr():

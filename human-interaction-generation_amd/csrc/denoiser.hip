@@ -299,6 +299,13 @@ struct Derived {
 };
 inline Derived derived32_table(const Dims& D, const void* const* t) { return {t, HIG_D32_NLAYER, D.L}; }
 inline Derived derived16_table(const Dims& D, const void* const* t) { return {t, HIG_D16_NLAYER, D.L}; }
+// what a plan may know of a derived-operand table (HIG_DN_FACT_*): it was passed, and it carries the four stacked text operands
+static_assert(HIG_D32_TEXT_ZEROS == HIG_D32_TEXT_KV_W + 3 && HIG_D16_TEXT_ZEROS == HIG_D16_TEXT_KV_W + 3, "TEXT_KV_W, _KV_B, _ONES, _ZEROS contiguous");
+inline int derived_facts(const Derived& t, int text_kv_w) {
+  bool text = t.t != nullptr;
+  for (int i = 0; i < 4; ++i) text = text && t.global(text_kv_w + i);
+  return (t.t ? HIG_DN_FACT_TABLE : 0) | (text ? HIG_DN_FACT_TEXT_GLOBALS : 0);
+}
 // the fold triples are walked as `*_SA_QKV_W + 3 k`, the stylization-out fragments by their slot of the modulation table
 static_assert(HIG_D32_SA_QKV_COLSUM == HIG_D32_SA_QKV_W + 1 && HIG_D32_SA_QKV_B == HIG_D32_SA_QKV_W + 2 &&
               HIG_D32_CA_Q_W == HIG_D32_SA_QKV_W + 3 && HIG_D32_CA_Q_COLSUM == HIG_D32_SA_QKV_W + 4 &&
@@ -349,8 +356,12 @@ extern "C" int64_t hig_bwd_workspace_bytes(const hig_dims* dims) {
 
 namespace {
 struct SideStream;
+// Steps 1 and 2 of every entry point: build the call (the one place that asks whether `st` is capturing), plan it for this
+// device (denoiser_plan.hip), then obtain the library's streams where the plan wants them (*side; nullptr: none, and the plan's
+// fork fields are cleared).  Step 3 is the entry's launch sequence, which branches on plan fields only.
+hig_denoiser_plan_t plan_entry(int entry, const Dims& D, bool training, bool has_xf_out, int facts, hipStream_t st, SideStream** side = nullptr);
 int text_context_impl(const Dims& D, const void* const* params, const void* const* derived32, const float* xf_out, void* textctx,
-                      int training, hipStream_t st, hipEvent_t* layer_done);
+                      int training, bool batched, hipStream_t st, hipEvent_t* layer_done);
 }
 extern "C" int hig_text_context(const hig_dims* dims, const void* const* params, const float* xf_out,
                                 void* textctx, int training, hig_stream_t stream) {
@@ -358,22 +369,16 @@ extern "C" int hig_text_context(const hig_dims* dims, const void* const* params,
   HIG_TRY(check_dims(dims, D));
   HIG_REQUIRE(params && xf_out && textctx, "hig_text_context: null argument");
   HIG_REQUIRE(!D.bf16, "hig_text_context: bf16 storage goes through hig_text_context_bf16");
-  return text_context_impl(D, params, nullptr, xf_out, textctx, training, hig_stream(stream), nullptr);
+  const hig_denoiser_plan_t plan = plan_entry(HIG_DN_ENTRY_TEXT32, D, training, true, 0, hig_stream(stream));
+  return text_context_impl(D, params, nullptr, xf_out, textctx, training, plan.text_batched, hig_stream(stream), nullptr);
 }
 namespace {
 // layer_done (nullable): event l is recorded on `st` behind layer l's launches (hig_denoiser_fwd_text waits for it in front of
 // layer l's cross-attention)
-// Does the text side run in its batched form (one key/value GEMM + one context build for all layers)?  Inference, linear
-// attention, fp32 storage, and the caller's derived-operand table carries the stacked folded weights (HIG_D32_TEXT_*).
-bool text_batched(const Dims& D, const void* const* derived32, int training) {
-  static const int batch_env = getenv("HIG_TEXT_BATCH") ? atoi(getenv("HIG_TEXT_BATCH")) : 1;   // tuning knob
-  const Derived d32 = derived32_table(D, derived32);
-  return batch_env && !training && !D.full && !D.bf16 && d32.global(HIG_D32_TEXT_KV_W) && d32.global(HIG_D32_TEXT_KV_B) &&
-         d32.global(HIG_D32_TEXT_ONES) && d32.global(HIG_D32_TEXT_ZEROS);
-}
-// derived32 (nullable): the caller's derived-operand table (hig_denoiser_fwd_x); its HIG_D32_TEXT_* globals select the BATCHED form
+// derived32 (nullable): the caller's derived-operand table (hig_denoiser_fwd_x); `batched` (plan.text_batched): its
+// HIG_D32_TEXT_* globals serve the BATCHED form
 int text_context_impl(const Dims& D, const void* const* params, const void* const* derived32, const float* xf_out, void* textctx,
-                      int training, hipStream_t st, hipEvent_t* layer_done) {
+                      int training, bool batched, hipStream_t st, hipEvent_t* layer_done) {
   hig_stream_t stream = reinterpret_cast<hig_stream_t>(st);
   const TextLayout tl = text_layout(D, training);
   float* base = static_cast<float*>(textctx);
@@ -383,7 +388,7 @@ int text_context_impl(const Dims& D, const void* const* params, const void* cons
   // all layers stacked (derived per parameter version, models/transformer.py:_derived32) the L key/value GEMMs of B N rows
   // x K = Lt are ONE product of L 2d columns -- 77 row tiles per workgroup of the weight-stationary kernel instead of 8 launches
   // of 9.6 (K = 256: gemm_wsp32.hip), ~150 against ~300 us of chip time at config 2 (transformer.py:146,150).
-  if (text_batched(D, derived32, training)) {
+  if (batched) {
     float* xhat = base + tl.xhat;
     float* kvall = base + tl.kvall;
     const int64_t ldkv = (int64_t)D.L * 2 * D.d;
@@ -432,7 +437,7 @@ int text_context_impl(const Dims& D, const void* const* params, const void* cons
 namespace {
 
 // (the library-owned second stream of the calling thread: protocol described at WgradFork below)
-constexpr int kMaxTextLayers = 32;
+constexpr int kMaxTextLayers = HIG_MAX_TEXT_LAYERS;
 struct SideStream {
   hipStream_t s2 = nullptr;
   hipEvent_t ready = nullptr;
@@ -454,15 +459,17 @@ hipEvent_t& layer_event() {   // hig_denoiser_bwd_hooked: "layer l is enqueued" 
   return ev;
 }
 
-// HIG_BWD_OVERLAP, read once for every user below: -1 unset (each form's own default), 0 everything on the caller's stream,
-// 1 fork the weight gradients in every form (eager, captured, bf16 storage).
-int bwd_overlap_env() {
-  static const int v = getenv("HIG_BWD_OVERLAP") ? atoi(getenv("HIG_BWD_OVERLAP")) : -1;
-  return v;
+// (a failed query reads as a capture: the call then stays on the caller's stream)
+bool is_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
 }
 
-SideStream* side_stream_for_current_device(hipStream_t caller) {
-  if (bwd_overlap_env() == 0) return nullptr;
+// The library's streams of the calling thread on the current device, where a plan wants them.  nullptr: not wanted, or they
+// cannot be had (no device slot, creation failed now or before, first use under capture): the call runs in order on the
+// caller's stream.
+SideStream* side_streams(bool wanted, bool capturing) {
+  if (!wanted) return nullptr;
   SideStream* tab = side_stream_table();
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return nullptr;
@@ -471,8 +478,7 @@ SideStream* side_stream_for_current_device(hipStream_t caller) {
   if (!s.ok) {
     // first use on this thread / device.  Creating a stream is not something to do under capture: a caller that
     // captures its very first backward (no eager warm-up) simply gets the single-stream order for that graph.
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(caller, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return nullptr;
+    if (capturing) return nullptr;
     bool good = hipStreamCreateWithFlags(&s.s2, hipStreamNonBlocking) == hipSuccess;
     good = good && hipEventCreateWithFlags(&s.ready, hipEventDisableTiming) == hipSuccess;
     for (int i = 0; i < 4 && good; ++i) good = hipEventCreateWithFlags(&s.done[i], hipEventDisableTiming) == hipSuccess;
@@ -486,6 +492,35 @@ SideStream* side_stream_for_current_device(hipStream_t caller) {
   }
   return &s;
 }
+
+thread_local hig_denoiser_plan_t g_last_schedule = {-1};   // hig_denoiser_last_schedule: what the latest entry on this thread ran
+hig_denoiser_call call_of(int entry, const Dims& D, bool training, bool has_xf_out, int facts, bool capturing) {
+  return {entry, D.B, D.T, D.F, D.d, D.E, D.ff, D.L, D.H, D.hd, D.N, D.nsty, D.two, D.full, D.prec, training,
+          has_xf_out || entry == HIG_DN_ENTRY_TEXT32 || entry == HIG_DN_ENTRY_TEXT16, facts, capturing};
+}
+hig_denoiser_plan_t plan_entry(int entry, const Dims& D, bool training, bool has_xf_out, int facts, hipStream_t st, SideStream** side) {
+  const hig_denoiser_call c = call_of(entry, D, training, has_xf_out, facts, is_capturing(st));
+  hig_denoiser_plan_t p = hig_denoiser_plan_for(c, hig_denoiser_switch_values(), hig_chip_cus(), hig_gemm_wsp32_active());
+  SideStream* s = side_streams(p.wants_side_stream, c.capturing);
+  if (!s) p.text_fork = p.split = p.fork_emb = p.fork_text = p.wgrad_fork = 0;   // everything in order on the caller's stream
+  if (side) *side = s;
+  g_last_schedule = p;
+  return p;
+}
+
+// Whatever a forward has enqueued on the third stream is joined back into `st` on every exit that does not reach the success
+// path's own waits (the caller recycles `textctx` / `xf_out` / the workspace as soon as `st` gets there): disarmed on success.
+struct ThirdStreamJoin {
+  hipStream_t s3 = nullptr, st = nullptr;
+  hipEvent_t ev = nullptr;
+  bool armed = false;
+  void arm(hipStream_t s3_, hipEvent_t ev_, hipStream_t st_) { s3 = s3_; ev = ev_; st = st_; armed = true; }
+  ~ThirdStreamJoin() {
+    if (!armed) return;
+    (void)hipEventRecord(ev, s3);
+    (void)hipStreamWaitEvent(st, ev, 0);
+  }
+};
 
 }  // namespace
 
@@ -533,48 +568,31 @@ static int denoiser_fwd_impl(const hig_dims* dims, const void* const* params, co
   HIG_TRY(hig_zero_async(ws + w.gtail, HIG_GEMM_TAIL_CNT_BYTES, st));
   const TailScratchScope tail_scope(ws + w.gtail);
 
-  // The cross-attention text side (hig_denoiser_fwd_text): layer l's context matrices are first needed in front of layer l's
-  // cross-attention, a third of a layer into the forward -- its 2 L launches (key/value GEMMs over B N rows, context builds)
-  // run on a third stream next to the first layers, one event per layer (events only: eager launches; under capture, or
-  // without the library's streams, they run first on the caller's stream as hig_text_context would).
+  SideStream* side = nullptr;
+  const hig_denoiser_plan_t plan = plan_entry(HIG_DN_ENTRY_FWD32, D, training, xf_out_for_text != nullptr,
+                                              derived_facts(derived32_table(D, derived32), HIG_D32_TEXT_KV_W), st, &side);
+  // The cross-attention text side (hig_denoiser_fwd_text) on the third stream next to the first layers (plan.text_fork), one
+  // event per layer; else first on the caller's stream as hig_text_context would run it.  The last layer's own wait joins it on
+  // the success path.
   hipEvent_t* text_ev = nullptr;
-  // Whatever the text fork has enqueued on the third stream is joined back into `st` on every exit that does not reach the
-  // last layer's own wait (the caller recycles `textctx` / `xf_out` as soon as `st` gets there): disarmed on success.
-  struct TextJoin {
-    hipStream_t s3 = nullptr, st = nullptr;
-    hipEvent_t ev = nullptr;
-    bool armed = false;
-    void arm(hipStream_t s3_, hipEvent_t ev_, hipStream_t st_) { s3 = s3_; ev = ev_; st = st_; armed = true; }
-    ~TextJoin() {
-      if (!armed) return;
-      (void)hipEventRecord(ev, s3);
-      (void)hipStreamWaitEvent(st, ev, 0);
-    }
-  } text_join;
+  ThirdStreamJoin text_join;
   if (xf_out_for_text) {
-    static const int text_fork = getenv("HIG_TEXT_FORK") ? atoi(getenv("HIG_TEXT_FORK")) : 1;   // tuning knob
-    // (the batched form is two whole-chip launches: next to the first layers' GEMMs -- one workgroup per CU each -- they only take
-    // turns with them, 6.04 ms forked against 5.98 in front at config 2; it runs first on the caller's stream)
-    SideStream* ts = (text_fork && D.L <= kMaxTextLayers && !text_batched(D, derived32, training)) ? side_stream_for_current_device(st) : nullptr;
-    if (ts) {
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) ts = nullptr;
-    }
-    if (ts) {
+    if (plan.text_fork) {
       // The text side's key/value GEMMs run NEXT TO the GEMMs on `st`: they get a split-tail scratch of their own (tickets and
       // partial sums shared between two concurrent launches would hand a workgroup another GEMM's "last arriver" ticket or
       // slices: B = 32, N = 77 text rows qualify for the split tail just like the q/k/v launch beside them).
       HIG_TRY(hig_zero_async(ws + w.gtail3, HIG_GEMM_TAIL_CNT_BYTES, st));
-      if (hipEventRecord(ts->ready, st) != hipSuccess || hipStreamWaitEvent(ts->s3, ts->ready, 0) != hipSuccess)
+      if (hipEventRecord(side->ready, st) != hipSuccess || hipStreamWaitEvent(side->s3, side->ready, 0) != hipSuccess)
         return hig_set_error(HIG_EHIP, "text fork failed");
       hig_gemm_set_tail_scratch(ws + w.gtail3, HIG_GEMM_TAIL_BYTES);
-      const int rc = text_context_impl(D, params, derived32, xf_out_for_text, const_cast<void*>(textctx), training, ts->s3, ts->text_done);
+      const int rc = text_context_impl(D, params, derived32, xf_out_for_text, const_cast<void*>(textctx), training, plan.text_batched, side->s3,
+                                       side->text_done);
       hig_gemm_set_tail_scratch(ws + w.gtail, HIG_GEMM_TAIL_BYTES);
-      text_join.arm(ts->s3, ts->text_done[0], st);   // every error exit below joins the text stream first
+      text_join.arm(side->s3, side->text_done[0], st);   // every error exit below joins the text stream first
       if (rc != HIG_OK) return rc;
-      text_ev = ts->text_done;
+      text_ev = side->text_done;
     } else {
-      HIG_TRY(text_context_impl(D, params, derived32, xf_out_for_text, const_cast<void*>(textctx), training, st, nullptr));
+      HIG_TRY(text_context_impl(D, params, derived32, xf_out_for_text, const_cast<void*>(textctx), training, plan.text_batched, st, nullptr));
     }
   }
   // K0: emb = time_embed(timestep_embedding(t)) + xf_proj; all 3L scale/shift pairs in ONE GEMM
@@ -608,23 +626,11 @@ static int denoiser_fwd_impl(const hig_dims* dims, const void* const* params, co
     HIG_CHECK_LAUNCH();
     len_partner = lp;
   }
-  // inference + linear attention, head dim 64 with 4 or 8 heads: `apply` and the stylization front that follows it run as ONE
-  // kernel (hig_linattn_apply_sty -> apply_sty_wave64_kernel, linattn.hip): the (M, d) attention output y never reaches HBM, its
-  // workspace slots (y1, y2) and the statistics slots (st2, st4) are not written.  Self and cross attention of every layer.
-  // Everything else keeps the pair apply + ln_mod_silu: training (the backward reads y and the LayerNorm statistics), full
-  // attention, and head dim 128 (only the older fused kernel exists there, and it lost: 83.8 against 71.1 us per attention).
-  // The entry wants 16-byte aligned rows and parameter vectors: d and the row stride of the scale / shift table are multiples
-  // of 4 floats here (d = 64 H); the workspace slots and the parameter blocks sit at 16-byte aligned offsets (the entry checks
-  // and fails loudly, it never falls back).
-  // Measured per attention, fused against the pair (profiles/r07_notes.md): 28.2-28.7 against 31.2-31.5 us at B = 64, T = 196,
-  // 15.8-16.0 against 20.6-21.4 at B = 32 (the sampling loop), 17.0-17.8 against 21.8-22.8 at T = 91 (the two-person shape; 9.9-10.6
-  // against 12.8-13.2 at B = 32): no row threshold, unlike hig_linattn_apply's.
-  const bool fuse_apply = !training && !D.full && D.hd == 64 && (D.H == 4 || D.H == 8) && ss_ld % 4 == 0;
+  // plan.fuse_apply: `apply` and the stylization front that follows it run as ONE kernel (hig_linattn_apply_sty), self and cross
+  // attention of every layer; plan.fold32: LayerNorm folded into the projections whose derived operands the caller passed.
+  const bool fuse_apply = plan.fuse_apply, fold32 = plan.fold32;
   // One decoder layer for the samples [b0, b0 + nb) on stream `s` (every kernel of a layer is row- or sample-local, so a
   // batch range is a pointer offset).  `hin` / the returned pointer are the FULL-batch residual stream of the layer.
-  // LayerNorm fold (fp32 storage): inference only, d a multiple of 128, operands derived by the caller per parameter version
-  static const int fold_env = getenv("HIG_LNFOLD32") ? atoi(getenv("HIG_LNFOLD32")) : 1;   // tuning knob
-  const bool fold32 = fold_env && derived32 && !training && d % 128 == 0 && d <= 1024;
   const Derived d32 = derived32_table(D, derived32);
   int layer_rc = HIG_OK;   // the code of the launch that failed inside `layer` (it returns NULL then)
   auto layer = [&](int l, const float* hin_full, int b0, int nb, hipStream_t s, float* cscr) -> const float* {
@@ -755,27 +761,10 @@ static int denoiser_fwd_impl(const hig_dims* dims, const void* const* params, co
                                .epi(HIG_EPI_BIAS, P(params, HIG_P_OUT_B)).prec(D.prec).g, 1, nullptr, s);
   };
 
-  // Two halves of the batch on two streams (single-person model, enough rows): the second half runs on the library's
-  // side stream, forked after the per-sample prologue and joined before returning (events only: capturable).  An
-  // in-order stream leaves the chip idle in every kernel's tail and ramp-up; two independent chains of the same
-  // kernels fill those gaps (two whole forwards side by side: 5.85 ms each against 6.6 alone).
-  // (Round 6: with the exact-fp32 products on the weight-stationary kernel -- one workgroup per CU, every launch fills the chip
-  // by itself -- two half-batch chains no longer fit side by side, and each half pays the kernel's fixed cost on half the rows:
-  // B = 64 forward 5.85 ms split against 5.78 ms on one stream.  Unset, the split is therefore kept for the bf16 product modes
-  // and for chips where that kernel declines.)
-  static const int split_knob = getenv("HIG_FWD_SPLIT") ? atoi(getenv("HIG_FWD_SPLIT")) : -1;   // tuning knob
-  const int split_env = split_knob >= 0 ? split_knob : ((D.prec == HIG_PREC_F32 && hig_gemm_wsp32_active()) ? 0 : 1);
-  // (M >= 8192: measured at B = 64.  Half batches run other tile schedules than the whole batch -- other split-tail
-  // geometry, so sums in another order, last-bit differences (2e-7 rel-L2) -- and the B = 32 sampling step is expected to
-  // equal its captured form bit for bit (tests/test_gpu_full_size.py), so small batches stay on one stream.)
-  SideStream* side = (split_env && !D.two && D.B >= 16 && M >= 8192) ? side_stream_for_current_device(st) : nullptr;
-  if (side) {   // eager launches only: replayed from a hipGraph the two branches cost more than they gain (captured
-                // training step 21.2 -> 22.2 ms, against 20.4 -> 20.2 ms eager; forward 6.23 -> 6.10 ms eager)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) side = nullptr;
-  }
+  // plan.split: two halves of the batch on two streams, the second on the library's side stream, forked after the per-sample
+  // prologue and joined before returning (events only).
   const float* hin = ws + w.h0;
-  if (side) {
+  if (plan.split) {
     const int nbA = D.B / 2, nbB = D.B - nbA;
     HIG_TRY(hig_zero_async(ws + w.gtail2, HIG_GEMM_TAIL_CNT_BYTES, st));
     if (hipEventRecord(side->ready, st) != hipSuccess || hipStreamWaitEvent(side->s2, side->ready, 0) != hipSuccess)
@@ -942,6 +931,9 @@ struct G16 {  // small builder for bf16 gemm descriptors
 };
 
 int64_t fwd16_total(const Dims& D) { return fwd16_layout(D).total; }
+inline int derived16_facts(const Dims& D, const void* const* derived) {
+  return derived_facts(derived16_table(D, derived), HIG_D16_TEXT_KV_W) | (text16_layout(D).kvall >= 0 ? HIG_DN_FACT_KVALL : 0);
+}
 int64_t text16_total(const Dims& D) { return text16_layout(D).total; }
 
 inline const void* P16(const void* const* t, int idx) { return t[idx]; }
@@ -949,42 +941,36 @@ inline const void* PL16(const void* const* t, int l, int idx) { return t[HIG_NGL
 
 }  // namespace
 
-// Context build of the bf16-storage forward: the bf16-matrix-core kernel of linattn16.hip where it is built (head dim 64 / 128),
-// else the fp32-MFMA kernels with bf16 loads (HIG_CTX16=0 forces those).
-static int ctx16(const Dims& D, const void* K, const void* V, int64_t ld, int B, int rows, const int64_t* length, float* A,
+// Context build of the bf16-storage entries: the bf16-matrix-core kernel of linattn16.hip (mm16 = plan.ctx_mm16), else the
+// fp32-MFMA kernels with bf16 loads.
+static int ctx16(const Dims& D, bool mm16, const void* K, const void* V, int64_t ld, int B, int rows, const int64_t* length, float* A,
                  float* kstat, float* scratch, void* At16, hig_stream_t stream) {
-  static const int mm16 = getenv("HIG_CTX16") ? atoi(getenv("HIG_CTX16")) : 1;   // tuning knob
-  if (mm16 && (D.hd == 64 || D.hd == 128)) return hig_linattn_ctx_mm16(K, V, ld, B, rows, D.H, D.hd, length, A, kstat, At16, stream);
+  if (mm16) return hig_linattn_ctx_mm16(K, V, ld, B, rows, D.H, D.hd, length, A, kstat, At16, stream);
   return hig_linattn_ctx_bf16(K, V, ld, B, rows, D.H, D.hd, length, A, kstat, scratch, At16, stream);
 }
 
 // layer_done (nullable): event l is recorded on `st` behind layer l's launches (the forked form of hig_denoiser_fwd_bf16_x)
-static int text_context16_impl(const Dims& D, const void* const* params, const void* const* params16, const void* const* derived,
-                               const float* xf_out, void* textctx, hipStream_t st, hipEvent_t* layer_done);
+static int text_context16_impl(const Dims& D, const hig_denoiser_plan_t& plan, const void* const* params, const void* const* params16,
+                               const void* const* derived, const float* xf_out, void* textctx, hipStream_t st, hipEvent_t* layer_done);
 extern "C" int hig_text_context_bf16(const hig_dims* dims, const void* const* params, const void* const* params16,
                                      const float* xf_out, void* textctx, hig_stream_t stream) {
   Dims D;
   HIG_TRY(check_dims(dims, D));
   HIG_REQUIRE(D.bf16, "hig_text_context_bf16: dims->storage must be HIG_STORE_BF16");
   HIG_REQUIRE(params && params16 && xf_out && textctx, "hig_text_context_bf16: null argument");
-  return text_context16_impl(D, params, params16, nullptr, xf_out, textctx, hig_stream(stream), nullptr);
+  const hig_denoiser_plan_t plan = plan_entry(HIG_DN_ENTRY_TEXT16, D, false, true, derived16_facts(D, nullptr), hig_stream(stream));
+  return text_context16_impl(D, plan, params, params16, nullptr, xf_out, textctx, hig_stream(stream), nullptr);
 }
-// derived (nullable): the caller's derived-operand table of hig_denoiser_fwd_bf16_x; its HIG_D16_TEXT_* globals select the
-// BATCHED form (text_context_impl above: one key/value GEMM over the stacked text_norm-folded bf16 weights of all layers, one
-// context build over L H heads)
-static bool text16_batched(const Dims& D, const void* const* derived) {
-  static const int batch_env = getenv("HIG_TEXT_BATCH") ? atoi(getenv("HIG_TEXT_BATCH")) : 1;   // tuning knob
-  const Derived d16 = derived16_table(D, derived);
-  return batch_env && !D.full && d16.global(HIG_D16_TEXT_KV_W) && d16.global(HIG_D16_TEXT_KV_B) && d16.global(HIG_D16_TEXT_ONES) &&
-         d16.global(HIG_D16_TEXT_ZEROS);
-}
-static int text_context16_impl(const Dims& D, const void* const* params, const void* const* params16, const void* const* derived,
-                               const float* xf_out, void* textctx, hipStream_t st, hipEvent_t* layer_done) {
+// derived (nullable): the caller's derived-operand table of hig_denoiser_fwd_bf16_x; plan.text_batched: its HIG_D16_TEXT_* globals
+// serve the BATCHED form (text_context_impl above: one key/value GEMM over the stacked text_norm-folded bf16 weights of all
+// layers, one context build over L H heads)
+static int text_context16_impl(const Dims& D, const hig_denoiser_plan_t& plan, const void* const* params, const void* const* params16,
+                               const void* const* derived, const float* xf_out, void* textctx, hipStream_t st, hipEvent_t* layer_done) {
   const Text16Layout tl = text16_layout(D);
   char* base = static_cast<char*>(textctx);
   hig_stream_t stream = reinterpret_cast<hig_stream_t>(st);
   void* xfn = base + tl.xfn;
-  if (text16_batched(D, derived) && tl.kvall >= 0) {
+  if (plan.text_batched) {
     char* kvall = base + tl.kvall;
     const int64_t ldkv = (int64_t)D.L * 2 * D.d;
     const Derived d16 = derived16_table(D, derived);
@@ -1003,7 +989,7 @@ static int text_context16_impl(const Dims& D, const void* const* params, const v
       if (rc != HIG_OK) {   // (head dim not on the bf16 matrix-core kernel: one launch per layer)
         float* Ac = reinterpret_cast<float*>(base + tl.layer0 + tl.lstride * l + tl.Ac);
         float* kstc = reinterpret_cast<float*>(base + tl.layer0 + tl.lstride * l + tl.kstc);
-        HIG_TRY(ctx16(D, Kall + (int64_t)l * D.d * 2, Vall + (int64_t)l * D.d * 2, ldkv, D.B, D.N, nullptr, Ac, kstc,
+        HIG_TRY(ctx16(D, plan.ctx_mm16, Kall + (int64_t)l * D.d * 2, Vall + (int64_t)l * D.d * 2, ldkv, D.B, D.N, nullptr, Ac, kstc,
                       reinterpret_cast<float*>(base + tl.cscr), base + tl.layer0 + tl.lstride * l + tl.Atc, stream));
       }
       if (layer_done && hipEventRecord(layer_done[l], st) != hipSuccess) return hig_set_error(HIG_EHIP, "hipEventRecord failed");
@@ -1020,7 +1006,7 @@ static int text_context16_impl(const Dims& D, const void* const* params, const v
     HIG_TRY(hig_gemm16_launch(G16(xfn, D.Lt, PL16(params16, l, HIG_L_CA_KV_W), D.Lt, kv, 2 * D.d, D.Mt, 2 * D.d, D.Lt)
                                   .epi(HIG_EPI_BIAS, PL(params, l, HIG_L_CA_KV_B)).g, st));
     if (!D.full)
-      HIG_TRY(ctx16(D, kv, kv + (int64_t)D.d * 2, 2 * D.d, D.B, D.N, nullptr, Ac, kstc,
+      HIG_TRY(ctx16(D, plan.ctx_mm16, kv, kv + (int64_t)D.d * 2, 2 * D.d, D.B, D.N, nullptr, Ac, kstc,
                     reinterpret_cast<float*>(base + tl.cscr), base + tl.layer0 + tl.lstride * l + tl.Atc, stream));
     if (layer_done && hipEventRecord(layer_done[l], st) != hipSuccess) return hig_set_error(HIG_EHIP, "hipEventRecord failed");
   }
@@ -1061,57 +1047,38 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
   const int64_t ss_ld = (int64_t)D.nsty * D.L * 2 * d;
   float* ss = reinterpret_cast<float*>(ws + w.ss);
 
-  // Everything that hangs off the B conditioning rows instead of the M frame rows -- the embedding chain (its last GEMM reads
-  // every stylization block's (2 d, E) weight: 604 MB at the config-5 shape, HBM-bound) and the cross-attention text side --
-  // is first needed a few launches into layer 0 / in front of layer l's cross-attention.  Launched eagerly with the library's
-  // streams available, both run on the third stream next to the frame-row launches (events only; HIG_FWD16_FORK=0, a capture
-  // in progress or no side streams: everything in order on the caller's stream).
-  // Measured (tools/fwd16_fork.sh, same call, per-call text: off / text / both): config 2 B = 64 1.718 / 1.667 / 1.657-1.672 ms,
-  // B = 32 1.158 / 1.134 / 1.121; config-5 shape 4.83 / 4.71 / 4.66-4.70; with the text side cached, forking the embedding
-  // chain alone COSTS 2-6 % at config 2 (its 35 us of launches are shorter than the two event waits they add): it is forked
-  // only when its modulation weight is large (>= 256 MB: the d = 1024 models).
-  static const int fork_knob = getenv("HIG_FWD16_FORK") ? atoi(getenv("HIG_FWD16_FORK")) : -1;   // tuning knob: bit 0 embedding chain, bit 1 text side
-  // (round 6: the BATCHED text side -- three launches, two of them chip-wide -- is faster in front of the frame-row launches than
-  // next to them: B = 64 1.488 against 1.540 ms, per-layer form 1.539 forked / 1.603 in front; not forked by default)
-  const bool batched_text = xf_out_for_text && text16_batched(D, derived);
+  // Everything that hangs off the B conditioning rows instead of the M frame rows -- the embedding chain and the cross-attention
+  // text side -- is first needed a few launches into layer 0 / in front of layer l's cross-attention: where the plan forks them
+  // (fork_emb, fork_text) they run on the third stream next to the frame-row launches (events only), else in order on the
+  // caller's stream.
+  SideStream* fs = nullptr;
+  const hig_denoiser_plan_t plan = plan_entry(HIG_DN_ENTRY_FWD16, D, false, xf_out_for_text != nullptr, derived16_facts(D, derived), st, &fs);
   const Derived d16 = derived16_table(D, derived);
-  const int fork_env = fork_knob >= 0 ? fork_knob : ((batched_text ? 0 : 2) | (((int64_t)E * ss_ld * 2 >= (256ll << 20)) ? 1 : 0));
-  SideStream* fs = (fork_env && D.L < kMaxTextLayers) ? side_stream_for_current_device(st) : nullptr;
-  if (fs) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) fs = nullptr;
-  }
-  const bool fork_emb = fs && (fork_env & 1), fork_text = fs && (fork_env & 2) && xf_out_for_text;
-  if (fork_emb || fork_text)
+  const bool fork_emb = plan.fork_emb, fork_text = plan.fork_text;
+  ThirdStreamJoin join_side;   // whatever was enqueued on the third stream is joined before an error leaves
+  if (fork_emb || fork_text) {
     if (hipEventRecord(fs->ready, st) != hipSuccess || hipStreamWaitEvent(fs->s3, fs->ready, 0) != hipSuccess)
       return hig_set_error(HIG_EHIP, "forward fork failed");
+    join_side.arm(fs->s3, fs->text_done[kMaxTextLayers - 1], st);
+  }
   hipStream_t se = fork_emb ? fs->s3 : st;
   hig_stream_t hse = reinterpret_cast<hig_stream_t>(se);
   hipEvent_t emb_ev = fork_emb ? fs->text_done[kMaxTextLayers - 1] : nullptr;
-  // whatever was enqueued on the third stream is joined before an error leaves
-  auto join_side = [&](int rc) -> int {
-    if (fork_emb || fork_text) {
-      (void)hipEventRecord(fs->text_done[kMaxTextLayers - 1], fs->s3);
-      (void)hipStreamWaitEvent(st, fs->text_done[kMaxTextLayers - 1], 0);
-    }
-    return rc;
-  };
-#define HIG_TRY_SIDE(expr) do { const int rc_ = (expr); if (rc_ != HIG_OK) return join_side(rc_); } while (0)
 
   // K0: emb = time_embed(timestep_embedding(t)) + xf_proj; only silu(emb) is consumed (by every stylization block):
   //     te -> silu(Lin0) -> silu(Lin2 + xf_proj) -> ONE GEMM for all 3L (scale, shift) pairs      (transformer.py:345-349,415,81-83)
-  HIG_TRY_SIDE(hig_timestep_embedding_bf16(t, D.B, d, ws + w.te16, hse));
-  HIG_TRY_SIDE(hig_gemm16_launch(G16(ws + w.te16, d, P16(params16, HIG_P_TE0_W), d, ws + w.teh16, E, D.B, E, d)
-                                     .epi(HIG_EPI_BIAS_SILU, P(params, HIG_P_TE0_B)).g, se));
-  HIG_TRY_SIDE(hig_gemm16_launch(G16(ws + w.teh16, E, P16(params16, HIG_P_TE2_W), E, ws + w.semb16, E, D.B, E, E)
-                                     .epi(HIG_EPI_BIAS_RES_SILU, P(params, HIG_P_TE2_B)).res32(xf_proj, E).g, se));
-  HIG_TRY_SIDE(hig_gemm16_launch(G16(ws + w.semb16, E, P16(params16, HIG_P_STY_EMB_W), E, ss, ss_ld, D.B, ss_ld, E)
-                                     .epi(HIG_EPI_BIAS, P(params, HIG_P_STY_EMB_B)).out32().g, se));
-  if (fork_emb && hipEventRecord(emb_ev, se) != hipSuccess) return join_side(hig_set_error(HIG_EHIP, "hipEventRecord failed"));
+  HIG_TRY(hig_timestep_embedding_bf16(t, D.B, d, ws + w.te16, hse));
+  HIG_TRY(hig_gemm16_launch(G16(ws + w.te16, d, P16(params16, HIG_P_TE0_W), d, ws + w.teh16, E, D.B, E, d)
+                                .epi(HIG_EPI_BIAS_SILU, P(params, HIG_P_TE0_B)).g, se));
+  HIG_TRY(hig_gemm16_launch(G16(ws + w.teh16, E, P16(params16, HIG_P_TE2_W), E, ws + w.semb16, E, D.B, E, E)
+                                .epi(HIG_EPI_BIAS_RES_SILU, P(params, HIG_P_TE2_B)).res32(xf_proj, E).g, se));
+  HIG_TRY(hig_gemm16_launch(G16(ws + w.semb16, E, P16(params16, HIG_P_STY_EMB_W), E, ss, ss_ld, D.B, ss_ld, E)
+                                .epi(HIG_EPI_BIAS, P(params, HIG_P_STY_EMB_B)).out32().g, se));
+  if (fork_emb && hipEventRecord(emb_ev, se) != hipSuccess) return hig_set_error(HIG_EHIP, "hipEventRecord failed");
   hipEvent_t* text_ev = nullptr;
   if (xf_out_for_text) {
-    HIG_TRY_SIDE(text_context16_impl(D, params, params16, derived, xf_out_for_text, const_cast<void*>(textctx), fork_text ? fs->s3 : st,
-                                     fork_text ? fs->text_done : nullptr));
+    HIG_TRY(text_context16_impl(D, plan, params, params16, derived, xf_out_for_text, const_cast<void*>(textctx), fork_text ? fs->s3 : st,
+                                fork_text ? fs->text_done : nullptr));
     if (fork_text) text_ev = fs->text_done;
   }
   bool emb_joined = !fork_emb;
@@ -1120,12 +1087,10 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
     emb_joined = true;
     return hipStreamWaitEvent(st, emb_ev, 0) == hipSuccess ? HIG_OK : hig_set_error(HIG_EHIP, "embedding join failed");
   };
-  auto frame_rows = [&]() -> int {
   // K1: h0 = joint_embed(x) + sequence_embedding[:T]: fp32 operands (x is the fp32 DDPM state, F = 150 rows are not
   //     16-byte aligned), result rounded once into the bf16 residual stream
-  static const int joint16 = getenv("HIG_JOINT16") ? atoi(getenv("HIG_JOINT16")) : 1;   // tuning knob
-  if (joint16 && d % 128 == 0 && D.F <= 512) {
-    // own kernel pair (weight padded / rounded to bf16, x rounded in LDS, bf16 MFMA): 31 -> ~8 us at B = 32
+  if (plan.joint16) {
+    // own kernel pair (weight padded / rounded to bf16, x rounded in LDS, bf16 MFMA)
     if (d16.global(HIG_D16_JOINT_W))   // (weight padded / rounded once, next to the caller's bf16 shadow)
       HIG_TRY(hig_joint_embed_bf16_w(x, M, D.F, d16.global(HIG_D16_JOINT_W), P(params, HIG_P_JOINT_B), P(params, HIG_P_SEQ_EMB), d, D.T,
                                      D.two ? 1 : 0, ws + w.h, d, d, stream));
@@ -1198,23 +1163,10 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
     HIG_TRY(hig_ln_bf16(y, 0, d, M, d, PL(params, l, norm_w), PL(params, l, norm_b), ssl, ss_ld, d, D.T, a, d, stream));
     return sty_out(l, out_w, out_b);
   };
-  // attention output -> stylization block.  With 4 or 8 heads the `y = q A` product, the LayerNorm, the modulation and
-  // the SiLU are ONE kernel (y never leaves the chip); otherwise apply + row kernel.
-  // (opt-in: measured equal at B = 64 and 4 % slower at B = 32 -- its fp32 MFMAs serialise 128 per wave behind poorly
-  // coalesced query loads; profiles/r02_notes.md)
-  // HIG_FUSE_APPLY: 2 (default) = the bf16-matrix-core kernel of linattn16.hip where it is built (head dim 64), 1 = the
-  // fp32-MFMA fused kernel, 0 = apply + row kernel
-  static const int fuse_env = getenv("HIG_FUSE_APPLY") ? atoi(getenv("HIG_FUSE_APPLY")) : 2;   // tuning knob
-  const bool fuse_mm16 = fuse_env == 2 && (D.hd == 64 || D.hd == 128) && (D.H == 4 || D.H == 8);
-  const bool fuse_apply = (fuse_env == 1 || fuse_mm16) && (D.H == 4 || D.H == 8);
-  // hig_attn_out16 / hig_rows_out16 (a whole stylization block as one launch) for the small batches: there the launches are
-  // bound by the per-launch floor (~4.4 us) and a fetch-bound projection.  Two of their workgroups (one per 32 rows of a sample)
-  // are resident per CU; same-call A/B, forward, fused vs not: B = 32 (224 workgroups) 0.996 vs 1.097 ms, B = 40 1.221 vs
-  // 1.262, B = 64 (448) 1.521 vs 1.614, B = 73 1.640 vs 1.733, B = 96 (672) 2.067 vs 2.100, B = 128 (896) 2.512 vs 2.516,
-  // B = 256 4.393 vs 4.377: used up to 3 workgroups per CU (768).  HIG_FUSE_OUT=0 switches it off, n >= 2 moves the limit to n per CU.
-  static const int fuse_out_env = getenv("HIG_FUSE_OUT") ? atoi(getenv("HIG_FUSE_OUT")) : 1;   // tuning knob
-  const bool fuse_out = fuse_out_env && fuse_mm16 && d == 512 && D.hd == 64 && D.H == 8 &&
-                        (int64_t)((D.T + 31) / 32) * D.B <= (int64_t)hig_chip_cus() * (fuse_out_env >= 2 ? fuse_out_env : 3);
+  // attention output -> stylization block.  plan.fuse_apply: the `y = q A` product, the LayerNorm, the modulation and the SiLU
+  // are ONE kernel (y never leaves the chip; fuse_mm16: the bf16-matrix-core one of linattn16.hip), otherwise apply + row kernel.
+  // plan.fuse_out: hig_attn_out16 / hig_rows_out16, a whole stylization block as one launch, where the caller derived its fragment.
+  const bool fuse_mm16 = plan.fuse_mm16, fuse_apply = plan.fuse_apply, fuse_out = plan.fuse_out;
   auto attend = [&](int l, int slot, const void* q, int64_t ldq, const float* ctx, const void* ctx_t16, int norm_w, int norm_b,
                     int out_w, int out_b) -> int {
     HIG_TRY(need_emb());
@@ -1248,7 +1200,7 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
                                     length, y, d, stream));
       HIG_TRY(stylize(l, 0, HIG_L_SA_STY_NORM_W, HIG_L_SA_STY_NORM_B, HIG_L_SA_STY_OUT_W, HIG_L_SA_STY_OUT_B));
     } else {
-      HIG_TRY(ctx16(D, qkv + (int64_t)d * 2, qkv + (int64_t)2 * d * 2, 3 * d, D.B, D.T, length, A1, kst1, cscr, ws + w.At1, stream));
+      HIG_TRY(ctx16(D, plan.ctx_mm16, qkv + (int64_t)d * 2, qkv + (int64_t)2 * d * 2, 3 * d, D.B, D.T, length, A1, kst1, cscr, ws + w.At1, stream));
       HIG_TRY(attend(l, 0, qkv, 3 * d, A1, ws + w.At1, HIG_L_SA_STY_NORM_W, HIG_L_SA_STY_NORM_B, HIG_L_SA_STY_OUT_W, HIG_L_SA_STY_OUT_B));
     }
     // ---- cross attention to the text context (transformer.py:135-155) ----
@@ -1268,7 +1220,7 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
       // stream, key / value from the partner's (same LayerNorm on both), key softmax masked with the consumer's length
       HIG_TRY(ln_proj(l, 2, HIG_L_INT_NORM_W, HIG_L_INT_NORM_B, HIG_L_INT_QKV_W, HIG_L_INT_QKV_B, qkv, 3 * d));
       want_stats = false;                        // (the interaction stylization block: no folded consumer behind it)
-      HIG_TRY(ctx16(D, qkv + (int64_t)d * 2, qkv + (int64_t)2 * d * 2, 3 * d, D.B, D.T, len_partner, A1, kst1, cscr,
+      HIG_TRY(ctx16(D, plan.ctx_mm16, qkv + (int64_t)d * 2, qkv + (int64_t)2 * d * 2, 3 * d, D.B, D.T, len_partner, A1, kst1, cscr,
                     fuse_mm16 ? ws + w.At1 : nullptr, stream));
       const int64_t halfA = (int64_t)Bp * D.H * D.hd * D.hd, halfM = (int64_t)Bp * D.T;
       const void* wfrag = fuse_out ? d16.layer(l, HIG_D16_INT_STY_OUT_FRAG) : nullptr;
@@ -1323,11 +1275,8 @@ static int denoiser_fwd16_impl(const hig_dims* dims, const void* const* params, 
   if (D.two)  // init-pose rows go through out2 instead (interaction_transformer.py:613-614)
     HIG_TRY(hig_gemm16_launch(G16(h, (int64_t)D.T * d, P16(params16, HIG_P_OUT2_W), d, out, (int64_t)D.T * D.F, D.B, D.F, d)
                                   .epi(HIG_EPI_BIAS, P(params, HIG_P_OUT2_B)).out32().g, st));
+  join_side.armed = false;   // (the layers waited for the embedding chain and for every layer's text event)
   return HIG_OK;
-  };
-  const int rc = frame_rows();
-  return rc == HIG_OK ? rc : join_side(rc);
-#undef HIG_TRY_SIDE
 }
 
 namespace {
@@ -1343,7 +1292,7 @@ namespace {
 //   (dh ping/pong, t1, t2, tff, dqkv, dkv) is next overwritten at least two requests later (walk of the layer loop
 //   in DESIGN.md section 4), and the saved forward activations are never written during backward;
 //   join = the caller's stream waits for the last done event.
-// HIG_BWD_OVERLAP=0 keeps everything on the caller's stream.
+// Whether a backward forks is its plan's wgrad_fork (denoiser_plan.hip); `side` == nullptr keeps everything on the caller's stream.
 struct WgradFork {
   SideStream* side;
   hipStream_t main;
@@ -1448,14 +1397,10 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
   HIG_TRY(hig_zero_async(b + bw.gtail, HIG_GEMM_TAIL_CNT_BYTES, st));
   const TailScratchScope tail_scope(b + bw.gtail);
 
-  // Eager launches: the weight gradients go to the second stream.  Under stream capture they stay on the caller's (unless
-  // HIG_BWD_OVERLAP=1): the replayed graph did not turn the fork into overlap -- config 2, captured fp32 step 21.6-21.7 ms forked
-  // against 21.2 on one stream, while eager launches gain a millisecond from it (20.4 against 21.3).
-  const int fork_env = bwd_overlap_env();
-  hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap_status) != hipSuccess) cap_status = hipStreamCaptureStatusNone;
-  const bool want_fork = fork_env == 1 || (fork_env != 0 && cap_status == hipStreamCaptureStatusNone);
-  WgradFork fork(want_fork ? side_stream_for_current_device(st) : nullptr, st);
+  // plan.wgrad_fork: the weight gradients go to the second stream (`side` is non-null exactly then)
+  SideStream* side = nullptr;
+  plan_entry(HIG_DN_ENTRY_BWD32, D, true, false, 0, st, &side);
+  WgradFork fork(side, st);
   hig_stream_t wstream = reinterpret_cast<hig_stream_t>(fork.stream());
   auto wgrad_on = [&](G gd) -> int {  // X, Y both reduce-slow; split over the reduce rows
     const int s = wgrad_splits(gd.g.I, gd.g.J, gd.g.R, bw.slab_floats, gd.g.prec);
@@ -1904,6 +1849,7 @@ extern "C" int hig_text_context_bf16_train(const hig_dims* dims, const void* con
   const Text16TLayout tl = text16t_layout(D);
   char* base = static_cast<char*>(textctx);
   hipStream_t st = hig_stream(stream);
+  const hig_denoiser_plan_t plan = plan_entry(HIG_DN_ENTRY_TEXT16, D, true, true, 0, st);   // (the training form is never batched)
   for (int l = 0; l < D.L; ++l) {
     char* lb = base + tl.layer0 + tl.lstride * l;
     // text_norm of THIS layer, [key; value] projection, softmax over the N tokens, A_c = k^T v   (transformer.py:146-152)
@@ -1911,7 +1857,7 @@ extern "C" int hig_text_context_bf16_train(const hig_dims* dims, const void* con
                         lb + tl.xfn, D.Lt, stream));
     HIG_TRY(hig_gemm16_launch(G16(lb + tl.xfn, D.Lt, PL16(params16, l, HIG_L_CA_KV_W), D.Lt, lb + tl.kv, 2 * D.d, D.Mt, 2 * D.d, D.Lt)
                                   .epi(HIG_EPI_BIAS, PL(params, l, HIG_L_CA_KV_B)).g, st));
-    HIG_TRY(ctx16(D, lb + tl.kv, lb + tl.kv + (int64_t)D.d * 2, 2 * D.d, D.B, D.N, nullptr, reinterpret_cast<float*>(lb + tl.Ac),
+    HIG_TRY(ctx16(D, plan.ctx_mm16, lb + tl.kv, lb + tl.kv + (int64_t)D.d * 2, 2 * D.d, D.B, D.N, nullptr, reinterpret_cast<float*>(lb + tl.Ac),
                   reinterpret_cast<float*>(lb + tl.kstc), reinterpret_cast<float*>(base + tl.cscr), lb + tl.Atc, stream));
   }
   return HIG_OK;
@@ -1929,6 +1875,7 @@ extern "C" int hig_denoiser_fwd_bf16_train(const hig_dims* dims, const void* con
   char* ws = static_cast<char*>(workspace);
   const char* tc = static_cast<const char*>(textctx);
   hipStream_t st = hig_stream(stream);
+  const hig_denoiser_plan_t plan = plan_entry(HIG_DN_ENTRY_FWD16_TRAIN, D, true, false, 0, st);
   const int d = D.d, E = D.E;
   const int64_t M = D.M;
   const int64_t ss_ld = (int64_t)D.nsty * D.L * 2 * d;
@@ -1980,8 +1927,7 @@ extern "C" int hig_denoiser_fwd_bf16_train(const hig_dims* dims, const void* con
   for (int l = 0; l < D.L; ++l) {
     char* lb = ws + w.layer0 + w.lstride * l;
     const float* ssl = ss + (int64_t)(D.nsty * l) * 2 * d;
-    static const int fuse_env = getenv("HIG_FUSE_APPLY") ? atoi(getenv("HIG_FUSE_APPLY")) : 2;   // tuning knob (as the inference forward)
-    const bool fuse_front = fuse_env == 2 && (D.hd == 64 || D.hd == 128) && (D.H == 4 || D.H == 8);
+    const bool fuse_front = plan.fuse_front;
     // one stylization block: h_out = h_in + Lin_out( silu( LN(y) (1 + scale) + shift ) )     (transformer.py:81-86)
     auto sty_out = [&](const void* a, const void* h_in, void* h_out, int out_w, int out_b) -> int {
       return hig_gemm16_launch(G16(a, d, PL16(params16, l, out_w), d, h_out, d, M, d, d).epi(HIG_EPI_BIAS_RES, PL(params, l, out_b)).res16(h_in, d).g, st);
@@ -2007,7 +1953,7 @@ extern "C" int hig_denoiser_fwd_bf16_train(const hig_dims* dims, const void* con
     HIG_TRY(hig_gemm16_launch(G16(lb + w.xn1, d, PL16(params16, l, HIG_L_SA_QKV_W), d, lb + w.qkv, 3 * d, M, 3 * d, d)
                                   .epi(HIG_EPI_BIAS, PL(params, l, HIG_L_SA_QKV_B)).g, st));
     char* qkv = lb + w.qkv;
-    HIG_TRY(ctx16(D, qkv + (int64_t)d * 2, qkv + (int64_t)2 * d * 2, 3 * d, D.B, D.T, length, reinterpret_cast<float*>(lb + w.A1),
+    HIG_TRY(ctx16(D, plan.ctx_mm16, qkv + (int64_t)d * 2, qkv + (int64_t)2 * d * 2, 3 * d, D.B, D.T, length, reinterpret_cast<float*>(lb + w.A1),
                   reinterpret_cast<float*>(lb + w.kst1), reinterpret_cast<float*>(ws + w.cscr), lb + w.At1, stream));
     HIG_TRY(attn_front(0, qkv, 3 * d, reinterpret_cast<const float*>(lb + w.A1), lb + w.At1, lb + w.y1, lb + w.a1, HIG_L_SA_STY_NORM_W, HIG_L_SA_STY_NORM_B, 0, D.B));
     HIG_TRY(sty_out(lb + w.a1, hin, lb + w.h1, HIG_L_SA_STY_OUT_W, HIG_L_SA_STY_OUT_B));
@@ -2027,7 +1973,7 @@ extern "C" int hig_denoiser_fwd_bf16_train(const hig_dims* dims, const void* con
                                     .epi(HIG_EPI_BIAS, PL(params, l, HIG_L_INT_QKV_B)).g, st));
       char* iqkv = lb + w.iqkv;
       float* Ai = reinterpret_cast<float*>(lb + w.Ai);
-      HIG_TRY(ctx16(D, iqkv + (int64_t)d * 2, iqkv + (int64_t)2 * d * 2, 3 * d, D.B, D.T, len_partner, Ai, reinterpret_cast<float*>(lb + w.ksti),
+      HIG_TRY(ctx16(D, plan.ctx_mm16, iqkv + (int64_t)d * 2, iqkv + (int64_t)2 * d * 2, 3 * d, D.B, D.T, len_partner, Ai, reinterpret_cast<float*>(lb + w.ksti),
                     reinterpret_cast<float*>(ws + w.cscr), lb + w.Ati, stream));
       const int64_t halfA = (int64_t)Bp * D.H * D.hd * D.hd;
       // (person 1's queries against person 2's context and vice versa: the halves of A / At swapped)
@@ -2122,13 +2068,10 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
   const float* ssf = reinterpret_cast<const float*>(ws + w.ss);
   char* tA = b + bw.tA;
 
-  // bf16 storage: the weight gradients stay on the caller's stream unless HIG_BWD_OVERLAP=1 asks for the fork.  The kernels of
-  // this mode are one-workgroup-per-CU designs (gemm_wsp16: 159 KB of LDS, wgrad16x: 128 KB + twelve waves): two of them cannot
-  // share a CU, so a weight gradient on the second stream delays the workgroups of the data-gradient GEMM CU by CU instead of
-  // filling idle slots -- config 2, captured step: 7.27 ms on one stream, 7.40 forked (7.72 with the LayerNorm reductions
-  // forked as well).  The fp32 step keeps the fork (tiled kernels, several workgroups per CU: 20.4 vs 21.4 ms eager).
-  const int fork16 = bwd_overlap_env() == 1;
-  WgradFork fork(fork16 ? side_stream_for_current_device(st) : nullptr, st);
+  // plan.wgrad_fork: the weight gradients go to the second stream (`side` is non-null exactly then; bf16 storage: only on request)
+  SideStream* side = nullptr;
+  const hig_denoiser_plan_t plan = plan_entry(HIG_DN_ENTRY_BWD16, D, true, false, 0, st, &side);
+  WgradFork fork(side, st);
   // dW[n][k] = sum_m dC[m][n] act[m][k] (+ the bias gradient = column sums of dC): both operands transposed to
   // reduce-contiguous bf16 (n_out x Mp), (k_in x Mp), then the split-R bf16 GEMM into the fp32 gradient.  Everything on the
   // weight-gradient stream (protocol: WgradFork).
@@ -2225,19 +2168,17 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
   };
 
   // ---- output projection ---------------------------------------------------------------------------------------------------
-  // The F-wide edges on the bf16 matrix kernels too (HIG_EDGE16=0: the fp32 kernels on fp32 copies, as before): d(out) and x
-  // are rounded to bf16 rows padded to Fp = F rounded up to 32 (hig_cast_pad_bf16), the data gradient d(h_L) = d(out) W_out is a
-  // bf16 GEMM over Fp (W_out^T padded with zero columns), the two weight gradients run on wgrad16 into padded fp32 scratch
-  // and are copied into place.  Scratch: the first of the two (M, d) fp32 buffers the fp32 path needs.
+  // plan.edge16: the F-wide edges on the bf16 matrix kernels too (else the fp32 kernels on fp32 copies): d(out) and x are rounded
+  // to bf16 rows padded to Fp (hig_cast_pad_bf16), the data gradient d(h_L) = d(out) W_out is a bf16 GEMM over Fp (W_out^T padded
+  // with zero columns), the two weight gradients run on wgrad16 into padded fp32 scratch and are copied into place.  Scratch
+  // (hig_edge16_layout): the first of the two (M, d) fp32 buffers the fp32 path needs.
   const char* hL = ws + w.layer0 + w.lstride * (D.L - 1) + w.h3;
   char* dh = b + bw.dhA;
   char* dh_alt = b + bw.dhB;
-  static const int edge16_env = getenv("HIG_EDGE16") ? atoi(getenv("HIG_EDGE16")) : 1;   // tuning knob
-  const int Fp = (F + 31) / 32 * 32;
-  auto up256 = [](int64_t v) { return (v + 255) / 256 * 256; };
-  const int64_t e_dout = 0, e_x = e_dout + up256(M * Fp * 2), e_wot = e_x + up256(M * Fp * 2), e_dwo = e_wot + up256((int64_t)d * Fp * 2),
-                e_dwj = e_dwo + up256((int64_t)Fp * d * 4), e_dbo = e_dwj + up256((int64_t)d * Fp * 4), e_end = e_dbo + up256((int64_t)Fp * 4);
-  const bool edge16 = edge16_env && d % 8 == 0 && e_end <= M * d * 4 && M * (int64_t)Fp < (1ll << 30);
+  const bool edge16 = plan.edge16;
+  const int Fp = plan.Fp;
+  const hig_edge16_offsets e = hig_edge16_layout(M, Fp, d);
+  const int64_t e_dout = e.dout, e_x = e.x, e_wot = e.wot, e_dwo = e.dwo, e_dwj = e.dwj, e_dbo = e.dbo;
   char* edgeb = reinterpret_cast<char*>(f32a);
   // weight gradient on wgrad16 into a padded scratch, then the real rows / columns into the gradient (weight-gradient stream)
   auto wgrad_edge = [&](const void* dC, int n_out, const void* act, int k_in, float* scratch, float* sbias, float* out, int out_rows, int out_cols,
@@ -2501,4 +2442,25 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
   HIG_TRY(hig_colsum(dte_h, E, D.B, E, GP(grads, HIG_P_TE0_B), colp, stream));
   HIG_TRY(hig_gemm_launch(G(dte_h, E, 1, te, d, 1, GP(grads, HIG_P_TE0_W), d, E, d, D.B).g, 1, nullptr, st));
   return HIG_OK;
+}
+
+// ---- the schedule of a call, asked apart from running it (include/hig.h) ----
+extern "C" int hig_denoiser_plan(const hig_dims* dims, int32_t entry, int32_t training, int32_t has_xf_out, int32_t derived_facts, int32_t capturing,
+                                 int32_t chip_cus, int32_t wsp32_active, const int32_t* switches, int32_t* out, int32_t n_out) {
+  Dims D;
+  HIG_TRY(check_dims(dims, D));
+  const bool bf16_entry = entry == HIG_DN_ENTRY_TEXT16 || entry == HIG_DN_ENTRY_FWD16 || entry == HIG_DN_ENTRY_FWD16_TRAIN || entry == HIG_DN_ENTRY_BWD16;
+  if (entry < 0 || entry > HIG_DN_ENTRY_BWD16 || bf16_entry != (D.bf16 != 0))
+    return hig_set_error(HIG_EINVAL, "hig_denoiser_plan: no entry point %d with storage=%d", entry, D.bf16);
+  hig_denoiser_switches sw = hig_denoiser_switch_values();
+  if (switches) memcpy(&sw, switches, sizeof(sw));
+  const hig_denoiser_plan_t p = hig_denoiser_plan_for(call_of(entry, D, training != 0, has_xf_out != 0, derived_facts, capturing != 0), sw,
+                                                      chip_cus > 0 ? chip_cus : hig_chip_cus(), wsp32_active != 0);
+  if (out && n_out > 0) memcpy(out, &p, sizeof(int32_t) * (size_t)(n_out < HIG_DN_PLAN_NSLOTS ? n_out : HIG_DN_PLAN_NSLOTS));
+  return HIG_OK;
+}
+extern "C" int32_t hig_denoiser_last_schedule(int32_t* out, int32_t n_out) {
+  const hig_denoiser_plan_t& p = g_last_schedule;
+  if (p.entry >= 0 && out && n_out > 0) memcpy(out, &p, sizeof(int32_t) * (size_t)(n_out < HIG_DN_PLAN_NSLOTS ? n_out : HIG_DN_PLAN_NSLOTS));
+  return p.entry;
 }

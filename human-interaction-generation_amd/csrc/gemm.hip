@@ -1122,7 +1122,7 @@ int gemm_dispatch(const hig_gemm_desc& g, int splits, float* slabs, hipStream_t 
 // from `scratch` (deterministic slab reduction), which also applies bias / residual.
 // EPI_BIAS / EPI_BIAS_RES, reduce-contiguous operands, dense C; falls back to the plain launch when that does not apply.
 int hig_gemm_few_rows(const hig_gemm_desc& g, float* scratch, int64_t scratch_floats, hipStream_t st) {
-  static const int enabled = getenv("HIG_FEW_ROWS_SPLIT") ? atoi(getenv("HIG_FEW_ROWS_SPLIT")) : 1;   // tuning knob
+  const int enabled = hig_gemm_switch_values().few_rows_split;   // HIG_FEW_ROWS_SPLIT
   const int64_t out = (int64_t)g.I * g.J;
   const bool ok = enabled && scratch && g.I > 0 && g.I <= 64 && g.x_rs == 0 && g.y_rs == 0 && g.ldc == g.J && g.J % 4 == 0 &&
                   (g.epi == HIG_EPI_BIAS || g.epi == HIG_EPI_BIAS_RES) && g.bias &&

@@ -214,6 +214,7 @@ const hig_gemm_switches& hig_gemm_switch_values() {
       env_int(getenv("HIG_F32_WSP"), 1),         // 0: gemm_wsp32 (and wgrad_wsp32) off
       env_int(getenv("HIG_GEMM_TILE"), -1),      // 0 .. 3: force the tiled fp32 kernel's tile
       env_int(getenv("HIG_GEMM_TAIL"), 1),       // 0: no split tail
+      env_int(getenv("HIG_FEW_ROWS_SPLIT"), 1),  // 0: the few-row GEMMs unsplit
   };
   return sw;
 }

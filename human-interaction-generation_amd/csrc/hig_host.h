@@ -59,6 +59,7 @@ int hig_reduce_slabs(const float* slabs, int splits, int64_t slab, int64_t n, fl
 struct hig_gemm_switches {
   int wsp16, ws16, ws_rows, ws_nwj, lnfold, lnfold1024, fewrow16, tile16;   // HIG_BF16_WSP, _WS, _WS_ROWS, _WS_NWJ, HIG_LNFOLD, HIG_LNFOLD1024, HIG_BF16_FEWROW, _TILE
   int wsp32, tile32, tail32;                                                // HIG_F32_WSP, HIG_GEMM_TILE, HIG_GEMM_TAIL
+  int few_rows_split;                                                       // HIG_FEW_ROWS_SPLIT (hig_gemm_few_rows)
 };
 const hig_gemm_switches& hig_gemm_switch_values();
 // rc == HIG_OK: `launches` launches of the kernel of `path` (HIG_GEMM_PATH_*; -1 and 0 launches: an empty problem) in the
@@ -174,6 +175,53 @@ inline int hig_attn_plan_entry(hig_attn_plan_t* p, const hig_attn_call& c, bool 
   if (p->rc != HIG_OK) return hig_set_error(p->rc, "%s", p->msg);
   hig_attn_path_count(p->path, p->split);
   return HIG_OK;
+}
+// ---- how a denoiser call is scheduled (denoiser_plan.hip): decided apart from its launch sequence ----
+// The denoiser switches ("Switches"), each read once per process by hig_denoiser_switch_values().  The order is
+// that of hig_denoiser_plan's `switches` array (include/hig.h).
+struct hig_denoiser_switches {
+  int32_t text_batch, text_fork, fwd_split, lnfold32, fwd16_fork, ctx16, joint16, fuse_apply, fuse_out, edge16, bwd_overlap;
+};
+static_assert(sizeof(hig_denoiser_switches) == HIG_DN_NSWITCHES * sizeof(int32_t), "one int32 per switch, in the documented order");
+const hig_denoiser_switches& hig_denoiser_switch_values();
+// What a decision may depend on, and nothing else.  entry: HIG_DN_ENTRY_*; the checked extents of the call's dims; facts:
+// HIG_DN_FACT_* (what the entry point read off its derived-operand table); capturing: the caller's stream is under capture.
+struct hig_denoiser_call {
+  int entry;
+  int B, T, F, d, E, ff, L, H, hd, N, nsty, two, full, prec;
+  bool training, has_xf_out;
+  int facts;
+  bool capturing;
+};
+// Named 0 / 1 answers (Fp: the padded feature count of edge16) in the order of the HIG_DN_PLAN_* slots; what an entry does not
+// decide stays 0.  The fork fields (text_fork, split, fork_emb, fork_text, wgrad_fork) say what the call wants: the entry point
+// clears them when the library's streams cannot be had.
+struct hig_denoiser_plan_t {
+  int32_t entry;
+  int32_t text_batched, text_fork, fuse_apply, fold32, split;        // fp32 forward / text context (text_batched, fuse_apply: bf16 too)
+  int32_t fork_emb, fork_text, ctx_mm16, joint16, fuse_mm16, fuse_out;   // bf16 forward / text context
+  int32_t fuse_front;                                                 // bf16 training forward
+  int32_t wgrad_fork;                                                 // backward
+  int32_t edge16, Fp;                                                 // bf16 backward
+  int32_t wants_side_stream;                                          // the entry asks for the library's streams at all
+};
+static_assert(sizeof(hig_denoiser_plan_t) == HIG_DN_PLAN_NSLOTS * sizeof(int32_t), "one int32 per HIG_DN_PLAN_* slot");
+hig_denoiser_plan_t hig_denoiser_plan_for(const hig_denoiser_call& c, const hig_denoiser_switches& sw, int cus, bool wsp32_active);
+constexpr int HIG_MAX_TEXT_LAYERS = 32;   // per-layer events of the forked text side (denoiser.hip: SideStream)
+// Byte offsets of the bf16 backward's padded edge operands in its first (M, d) fp32 buffer: d(out) and x as bf16 (M, Fp),
+// W_out^T as bf16 (d, Fp), the padded fp32 gradients of W_out (Fp, d) and W_joint (d, Fp), the padded bias gradient.
+struct hig_edge16_offsets { int64_t dout, x, wot, dwo, dwj, dbo, end; };
+inline hig_edge16_offsets hig_edge16_layout(int64_t M, int64_t Fp, int d) {
+  auto up256 = [](int64_t v) { return (v + 255) / 256 * 256; };
+  hig_edge16_offsets e;
+  e.dout = 0;
+  e.x = e.dout + up256(M * Fp * 2);
+  e.wot = e.x + up256(M * Fp * 2);
+  e.dwo = e.wot + up256((int64_t)d * Fp * 2);
+  e.dwj = e.dwo + up256(Fp * d * 4);
+  e.dbo = e.dwj + up256((int64_t)d * Fp * 4);
+  e.end = e.dbo + up256(Fp * 4);
+  return e;
 }
 // linattn.hip: context build of G groups of H heads in one launch (the batched text side); 1 = shape not served
 int hig_linattn_ctx_groups(const float* K, const float* V, int64_t ld, int32_t B, int32_t rows, int32_t H, int32_t G, int32_t hd,

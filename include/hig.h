@@ -707,6 +707,66 @@ int32_t hig_attn_last_split(void);
 #define HIG_ATTN_FACTS_ALL 127
 int hig_attn_plan(int32_t entry, int32_t io, int32_t B, int32_t rows, int32_t Tk, int32_t H, int32_t hd, int32_t has_scratch,
                   int32_t facts, int32_t chip_cus, int32_t big_lds_ok, int32_t* path, int32_t* split, int32_t* variant);
+/* How a denoiser call would be scheduled, without running it (csrc/denoiser_plan.hip: every entry point of csrc/denoiser.hip
+ * plans, then runs its launch sequence branching on the plan).  hig_denoiser_plan writes the first min(n_out,
+ * HIG_DN_PLAN_NSLOTS) slots of the plan to `out` (NULL: nothing is written) and returns HIG_OK, the error of the dims check, or
+ * HIG_EINVAL for an unknown entry or one that does not take dims->storage.  A pure function of its arguments: no launch, no
+ * stream asked for.
+ *   entry          HIG_DN_ENTRY_*: which entry point (hig_denoiser_fwd / _fwd_text / _fwd_x = FWD32, hig_denoiser_fwd_bf16[_x] =
+ *                  FWD16, hig_text_context_bf16_train = TEXT16 with training, the hooked backwards = BWD32 / BWD16)
+ *   training       the call's `training` argument (FWD32, TEXT32; 1 for hig_text_context_bf16_train)
+ *   has_xf_out     the text side is computed inside the forward call (xf_out != NULL); the text-context entries imply it
+ *   derived_facts  bit mask of HIG_DN_FACT_*: what the entry point reads off its derived-operand table
+ *   capturing      the caller's stream is being captured into a graph
+ *   chip_cus       compute units to plan for (<= 0: the current device's)
+ *   wsp32_active   the fp32 weight-stationary GEMM serves this process (on: MI355X in SPX mode unless HIG_F32_WSP=0)
+ *   switches       NULL: the process's environment switches; else HIG_DN_NSWITCHES values in the order HIG_TEXT_BATCH,
+ *                  HIG_TEXT_FORK, HIG_FWD_SPLIT, HIG_LNFOLD32, HIG_FWD16_FORK, HIG_CTX16, HIG_JOINT16, HIG_FUSE_APPLY, HIG_FUSE_OUT,
+ *                  HIG_EDGE16, HIG_BWD_OVERLAP (unset: 1, 1, -1, 1, -1, 1, 1, 2, 1, 1, -1)
+ * Plan slots (0 / 1 unless said; a slot an entry does not decide is 0):
+ *   fp32 forward and text context: TEXT_BATCHED (one key/value GEMM + one context build for all layers), TEXT_FORK (text side on
+ *     the third stream), FUSE_APPLY (apply + stylization front as one kernel), FOLD32 (LayerNorm folded into the projections whose
+ *     derived slots are present), SPLIT (batch halved over two streams)
+ *   bf16 forward and text context: TEXT_BATCHED, FORK_EMB / FORK_TEXT (embedding chain / text side on the third stream), CTX_MM16
+ *     (context builds on the bf16 matrix cores), JOINT16, FUSE_APPLY, FUSE_MM16, FUSE_OUT (a stylization block as one launch)
+ *   bf16 training forward: FUSE_FRONT, CTX_MM16
+ *   backward: WGRAD_FORK (weight gradients on the second stream); bf16: EDGE16 and FP (the padded F it runs over, 0 without)
+ *   every entry: ENTRY (the code asked; -1 unknown), WANTS_SIDE_STREAM (the call asks for the library's streams)
+ * hig_denoiser_last_schedule is a test hook like hig_attn_last_split: the plan the most recent denoiser entry point on this thread
+ * ran, in the same slots, its fork slots as left after the library's streams were or were not obtained; returns that entry's
+ * HIG_DN_ENTRY_* (-1, nothing written: none yet). */
+#define HIG_DN_ENTRY_TEXT32 0
+#define HIG_DN_ENTRY_TEXT16 1
+#define HIG_DN_ENTRY_FWD32 2
+#define HIG_DN_ENTRY_FWD16 3
+#define HIG_DN_ENTRY_FWD16_TRAIN 4
+#define HIG_DN_ENTRY_BWD32 5
+#define HIG_DN_ENTRY_BWD16 6
+#define HIG_DN_FACT_TABLE 1          /* a derived-operand table was passed */
+#define HIG_DN_FACT_TEXT_GLOBALS 2   /* its four HIG_D32_TEXT_* / HIG_D16_TEXT_* globals are non-NULL */
+#define HIG_DN_FACT_KVALL 4          /* bf16: the text-context layout has the slot of the batched key/value projections */
+#define HIG_DN_NSWITCHES 11
+#define HIG_DN_PLAN_ENTRY 0
+#define HIG_DN_PLAN_TEXT_BATCHED 1
+#define HIG_DN_PLAN_TEXT_FORK 2
+#define HIG_DN_PLAN_FUSE_APPLY 3
+#define HIG_DN_PLAN_FOLD32 4
+#define HIG_DN_PLAN_SPLIT 5
+#define HIG_DN_PLAN_FORK_EMB 6
+#define HIG_DN_PLAN_FORK_TEXT 7
+#define HIG_DN_PLAN_CTX_MM16 8
+#define HIG_DN_PLAN_JOINT16 9
+#define HIG_DN_PLAN_FUSE_MM16 10
+#define HIG_DN_PLAN_FUSE_OUT 11
+#define HIG_DN_PLAN_FUSE_FRONT 12
+#define HIG_DN_PLAN_WGRAD_FORK 13
+#define HIG_DN_PLAN_EDGE16 14
+#define HIG_DN_PLAN_FP 15
+#define HIG_DN_PLAN_WANTS_SIDE_STREAM 16
+#define HIG_DN_PLAN_NSLOTS 17
+int hig_denoiser_plan(const hig_dims* dims, int32_t entry, int32_t training, int32_t has_xf_out, int32_t derived_facts, int32_t capturing,
+                      int32_t chip_cus, int32_t wsp32_active, const int32_t* switches, int32_t* out, int32_t n_out);
+int32_t hig_denoiser_last_schedule(int32_t* out, int32_t n_out);
 int hig_wgrad16_debug_stamps(void* buf);      /* wgrad16.hip (see there): 8192 x 8 bytes */
 /* the same for hig_linattn_apply_sty_mm16: 8 stamps per workgroup (see linattn16.hip) */
 int hig_linattn16_debug_stamps(void* buf);

@@ -228,6 +228,64 @@ int main() {
     EXPECT(hig_fullattn_fwd_bf16(q, 64, q, q, 64, 1, 1, 1, 1, 32, nullptr, q, 64, nullptr) == HIG_EUNSUPPORTED);
     EXPECT(hig_fullattn_bwd(q, 64, q, 64, q, 64, q, q, 64, 1, 1, 1, 1, 64, nullptr, q, q, q, 64, q, q + 2, 64, nullptr) == HIG_EINVAL);
   }
+  // ---- denoiser plan entry: a pure host function behind the dims check; every entry code from -1 to one past the last, extents
+  // 0, 1, the thresholds +- 1 and INT32_MAX, every switch at -1, 0, 1, 2 and 1000, `out` NULL and n_out too small ----
+  {
+    const int NS = HIG_DN_PLAN_NSLOTS, CANARY = 0x5a5a5a5a;
+    int32_t out[HIG_DN_PLAN_NSLOTS + 1];
+    long served = 0, refused = 0;
+    const int32_t dflt[HIG_DN_NSWITCHES] = {1, 1, -1, 1, -1, 1, 1, 2, 1, 1, -1};
+    auto ask = [&](const hig_dims& D, int entry, int flags, int facts, int cus, const int32_t* sw, int n_out) {
+      for (int i = 0; i <= NS; ++i) out[i] = CANARY;
+      const int rc = hig_denoiser_plan(&D, entry, flags & 1, (flags >> 1) & 1, facts, (flags >> 2) & 1, cus, (flags >> 3) & 1, sw, out, n_out);
+      const int wrote = rc == HIG_OK ? (n_out < 0 ? 0 : n_out > NS ? NS : n_out) : 0;
+      for (int i = wrote; i <= NS; ++i) EXPECT(out[i] == CANARY);
+      if (rc != HIG_OK) { EXPECT(rc < 0); ++refused; return rc; }
+      ++served;
+      EXPECT(hig_denoiser_plan(&D, entry, flags & 1, (flags >> 1) & 1, facts, (flags >> 2) & 1, cus, (flags >> 3) & 1, sw, nullptr, n_out) == HIG_OK);
+      if (wrote == NS) {
+        EXPECT(out[HIG_DN_PLAN_ENTRY] == entry && out[HIG_DN_PLAN_FP] >= 0 && out[HIG_DN_PLAN_FP] % 32 == 0 && (out[HIG_DN_PLAN_FP] > 0) == out[HIG_DN_PLAN_EDGE16]);
+        for (int i = 1; i < NS; ++i) if (i != HIG_DN_PLAN_FP) EXPECT(out[i] == 0 || out[i] == 1);
+        const int forks = out[HIG_DN_PLAN_TEXT_FORK] | out[HIG_DN_PLAN_SPLIT] | out[HIG_DN_PLAN_FORK_EMB] | out[HIG_DN_PLAN_FORK_TEXT] | out[HIG_DN_PLAN_WGRAD_FORK];
+        EXPECT(!forks || out[HIG_DN_PLAN_WANTS_SIDE_STREAM]);
+      }
+      return rc;
+    };
+    const int ext[] = {0, 1, 15, 16, 17, 31, 32, 33, 511, 512, 513, 8191, 8192, 8193, INT32_MAX};
+    for (int entry = -1; entry <= HIG_DN_ENTRY_BWD16 + 1; ++entry) for (int storage = 0; storage <= 1; ++storage)
+      for (int B : ext) for (int T : ext) for (int L : {0, 1, 31, 32, 33, INT32_MAX}) for (int F : {0, 150, 513, INT32_MAX}) for (int d : {0, 64, 512, 1024, INT32_MAX})
+        for (int flags = 0; flags < 16; flags += 1 + (B & 1)) {
+          hig_dims D = dims(B, T, F, d, 8, 1024, L, (T & 1) ? 0 : (B & 2), storage, 0, flags % 3);
+          D.num_frames = INT32_MAX;
+          const int rc = ask(D, entry, flags, (flags * 3 + (L & 7)) & 7, (flags & 4) ? 128 : 256, nullptr, NS);
+          if (entry < 0 || entry > HIG_DN_ENTRY_BWD16 || B <= 0 || T <= 0 || L <= 0 || F <= 0 || d <= 0 || d > 1024) EXPECT(rc < 0);
+        }
+    const hig_dims shapes16[] = {dims(32, 196, 150, 512, 8, 1024, 8, 0, 1, 0, 0), dims(96, 256, 150, 512, 8, 1024, 8, 0, 1, 0, 0), dims(97, 256, 150, 512, 8, 1024, 8, 0, 1, 0, 0),
+                                 dims(32, 300, 150, 1024, 8, 1024, 12, 0, 1, 0, 0), dims(64, 91, 263, 512, 8, 1024, 8, 1, 1, 0, 0), dims(1, 583, 150, 512, 8, 1024, 8, 0, 1, 0, 0)};
+    const hig_dims shapes32[] = {dims(64, 196, 150, 512, 8, 1024, 8, 0, 0, 0, 0), dims(16, 512, 150, 256, 4, 512, 2, 0, 0, 0, 1), dims(16, 511, 150, 256, 4, 512, 33, 0, 0, 0, 2),
+                                 dims(64, 91, 263, 512, 8, 1024, 8, 1, 0, 0, 0), dims(2, 196, 150, 512, 8, 1024, 8, 0, 0, 1, 0)};
+    for (int entry = 0; entry <= HIG_DN_ENTRY_BWD16; ++entry) {
+      const bool bf = entry == HIG_DN_ENTRY_TEXT16 || entry == HIG_DN_ENTRY_FWD16 || entry == HIG_DN_ENTRY_FWD16_TRAIN || entry == HIG_DN_ENTRY_BWD16;
+      for (int s = 0; s < (bf ? 6 : 5); ++s) for (int flags = 0; flags < 16; ++flags) for (int facts = 0; facts < 8; ++facts) for (int cus : {1, 128, 256, INT32_MAX}) {
+        const hig_dims& D = bf ? shapes16[s] : shapes32[s];
+        for (int k = 0; k < HIG_DN_NSWITCHES; ++k) for (int v : {-1, 0, 1, 2, 1000, INT32_MAX, INT32_MIN}) {
+          int32_t sw[HIG_DN_NSWITCHES];
+          memcpy(sw, dflt, sizeof(sw));
+          sw[k] = v;
+          EXPECT(ask(D, entry, flags, facts, cus, sw, NS) == HIG_OK);
+        }
+        for (int v : {-1, 0, 1, 2, 1000}) {
+          int32_t sw[HIG_DN_NSWITCHES];
+          for (int k = 0; k < HIG_DN_NSWITCHES; ++k) sw[k] = v;
+          EXPECT(ask(D, entry, flags, facts, cus, sw, NS) == HIG_OK);
+        }
+        for (int n_out : {INT32_MIN, -1, 0, 1, NS - 1, NS + 1, INT32_MAX}) EXPECT(ask(D, entry, flags, facts, cus, dflt, n_out) == HIG_OK);
+      }
+    }
+    EXPECT(served > 1000 && refused > 1000);
+    EXPECT(hig_denoiser_plan(nullptr, 0, 0, 0, 0, 0, 256, 1, nullptr, out, NS) == HIG_EINVAL);
+    EXPECT(hig_denoiser_last_schedule(out, NS) == -1 && hig_denoiser_last_schedule(nullptr, 0) == -1);       // no entry point has run here
+  }
   // ---- diagnostics pointers: set and cleared ----
   EXPECT(hig_gemm_bf16_debug_stamps(nullptr) == HIG_OK && hig_gemm_ws16_debug_stamps(nullptr) == HIG_OK &&
          hig_gemm_debug_stamps(nullptr) == HIG_OK);

@@ -2,7 +2,8 @@
 once per process), over a pass that touches every path they select between: the results must stay at the rounding level of the
 path -- a switch chooses between two implementations of the same arithmetic, never between two results.  The diagnostic
 switches whose builds are wrong by construction (HIG_BF16_DBG, HIG_BF16_WSP_DBG, HIG_F32_WSP_DBG: timing ablations; HIG_POISON) are not
-flipped."""
+flipped.  That a flipped denoiser switch still changes the schedule -- which this digest cannot see -- is held by
+tests/test_cpu_denoiser_plan.py."""
 import json
 import os
 import subprocess
