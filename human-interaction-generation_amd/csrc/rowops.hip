@@ -968,8 +968,8 @@ extern "C" int hig_ln_bwd(const float* da, int64_t ldda, const float* x, int64_t
                           int32_t n, int32_t rows_per_sample, float* dgamma, float* dbeta,
                           float* dss, int64_t dss_ld, float* partial, hig_stream_t stream) {
   HIG_REQUIRE(da && x && stats && gamma && beta && dx && partial, "hig_ln_bwd: null argument");
-  HIG_REQUIRE(n % 4 == 0 && n <= 1024 && ldda % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0,
-              "hig_ln_bwd: n must be a multiple of 4 and <= 1024 (got %d)", n);
+  HIG_REQUIRE(n > 0 && n % 4 == 0 && n <= 1024 && ldda % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && (!res || ldr % 4 == 0),
+              "hig_ln_bwd: n and the leading dimensions must be multiples of 4, 0 < n <= 1024 (got %d)", n);
   HIG_REQUIRE(rows_per_sample > 0 && rows % rows_per_sample == 0, "hig_ln_bwd: rows %% rows_per_sample");
   HIG_REQUIRE(!mod_silu || (ss && dss), "hig_ln_bwd: modulation needs ss / dss");
   if (rows == 0) return HIG_OK;

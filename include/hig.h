@@ -925,7 +925,9 @@ int hig_fullattn_bwd(const float* dY, int64_t lddy, const float* Y, int64_t ldy,
 
 /* Backward of y = [silu](LN(x)*(1+scale)+shift) w.r.t. x for upstream gradient da, plus the
  * reductions for gamma/beta (over all rows) and scale/shift (per sample):
- *   dx = (res ? res : 0) + LNbwd(...).  partial: [rows/rows_per_sample * splits][4][n]. */
+ *   dx = (res ? res : 0) + LNbwd(...).  partial: [rows/rows_per_sample * splits][4][n].
+ * 0 < n <= 1024; n, ldda, ldx, lddx and (with res) ldr multiples of 4.  dgamma / dbeta: each nullable on its own
+ * (that reduction is then not launched); dss is written whenever mod_silu is set. */
 int hig_ln_bwd(const float* da, int64_t ldda, const float* x, int64_t ldx, const float* stats,
                const float* gamma, const float* beta, const float* ss, int64_t ss_ld,
                int32_t ss_shift_off, int32_t mod_silu, const float* res, int64_t ldr,
@@ -975,7 +977,8 @@ int hig_p_sample_step(const float* x, const float* eps, const float* z, const in
 /* t[b] -= 1 on the device (the sampling loop's step counter, graph-replayable). */
 int hig_dec_timesteps(int64_t* t, int32_t B, hig_stream_t s);
 /* DDPMTrainer.backward_G (ddpm_trainer.py:172-178): loss = sum_bt mask*mean_f (p-t)^2 / sum mask
- * with mask[b][t] = t < length[b];  dpred = d loss / d pred.  scratch: 2*B floats + loss. */
+ * with mask[b][t] = t < length[b];  dpred = d loss / d pred.  scratch: HIG_NORM_BLOCKS floats
+ * (one partial sum per workgroup, at most HIG_NORM_BLOCKS - 1 of them, and sum(mask) behind them). */
 int hig_masked_mse(const float* pred, const float* target, const int64_t* length, int32_t B,
                    int32_t T, int32_t F, float* loss /* device scalar */, float* dpred,
                    float* scratch, hig_stream_t s);
