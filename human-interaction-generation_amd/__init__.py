@@ -9,8 +9,8 @@ Putting this directory itself on sys.path gives the reference's own import layou
 """
 from . import _lib  # noqa: F401
 from .models import (GaussianDiffusion, MotionConsistencyEvalModel, MotionEncoder,  # noqa: F401
-                     MotionInteractionTransformer, MotionTransformer)
+                     MotionInteractionTransformer, MotionTransformer, SpacedDiffusion, space_timesteps)
 from .trainers import DDPMMulTrainer, DDPMTrainer  # noqa: F401
 
 __all__ = ["MotionTransformer", "MotionInteractionTransformer", "MotionEncoder", "MotionConsistencyEvalModel",
-           "GaussianDiffusion", "DDPMTrainer", "DDPMMulTrainer"]
+           "GaussianDiffusion", "SpacedDiffusion", "space_timesteps", "DDPMTrainer", "DDPMMulTrainer"]

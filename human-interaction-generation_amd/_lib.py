@@ -59,6 +59,7 @@ DN_NSWITCHES = 11
 DN_PLAN_SLOTS = ("entry", "text_batched", "text_fork", "fuse_apply", "fold32", "split", "fork_emb", "fork_text", "ctx_mm16", "joint16",
                  "fuse_mm16", "fuse_out", "fuse_front", "wgrad_fork", "edge16", "Fp", "wants_side_stream")
 TAB_ROWS = 7
+DDIM_TAB_ROWS = 4
 NORM_BLOCKS = 1024
 COLSUM_CHUNKS = 512
 
@@ -83,6 +84,8 @@ SYMBOLS = (
     "hig_debug_marker", "hig_denoiser_fwd_text", "hig_wgrad_bf16", "hig_wgrad_bf16_scratch_floats", "hig_denoiser_fwd_x", "hig_denoiser_fwd_bf16_x",
     "hig_gemm_bf16_plan", "hig_gemm_plan", "hig_gemm_bf16_lnfold_plan", "hig_attn_plan",
     "hig_denoiser_plan", "hig_denoiser_last_schedule",
+    # few-step sampling
+    "hig_ddim_step", "hig_advance_timesteps",
 )
 
 
@@ -197,6 +200,8 @@ def lib():
         L.hig_q_sample.argtypes = [vp, vp, vp, vp, i32, i32, i64, vp, vp]
         L.hig_p_sample_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, vp, vp, vp]
         L.hig_dec_timesteps.argtypes = [vp, i32, vp]
+        L.hig_ddim_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, f32, i32, vp, vp, vp]
+        L.hig_advance_timesteps.argtypes = [vp, vp, i32, i32, vp, vp]
         L.hig_masked_mse.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
         L.hig_pair_mse.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
         L.hig_sumsq_partial.argtypes = [vp, i64, f32, vp, vp]

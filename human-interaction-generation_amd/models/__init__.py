@@ -2,7 +2,8 @@
 from .evaluation_models import MotionConsistencyEvalModel, MotionEncoder
 from .gaussian_diffusion import GaussianDiffusion
 from .interaction_transformer import MotionInteractionTransformer
+from .spaced_diffusion import SpacedDiffusion, space_timesteps
 from .transformer import MotionTransformer
 
 __all__ = ["MotionTransformer", "MotionInteractionTransformer", "MotionEncoder", "MotionConsistencyEvalModel",
-           "GaussianDiffusion"]
+           "GaussianDiffusion", "SpacedDiffusion", "space_timesteps"]

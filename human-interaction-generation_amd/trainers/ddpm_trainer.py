@@ -26,6 +26,7 @@ from torch.nn.utils import clip_grad_norm_
 from .. import _lib
 from ..models.gaussian_diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType,
                                          create_named_schedule_sampler, get_named_beta_schedule)
+from ..models.spaced_diffusion import SpacedDiffusion, space_timesteps
 from ..parallel import (FlatGradAllReduce, OverlappedGradAllReduce, ShardedSampler, broadcast_flat, broadcast_parameters,
                         exchange_active)
 
@@ -79,6 +80,7 @@ class DDPMTrainer(object):
         if args.is_train:
             self.mse_criterion = torch.nn.MSELoss(reduction='none')
         self._fused = None
+        self._few_step = None          # set_sampler: (SpacedDiffusion, method, eta), or None = the full chain
         self.to(self.device)
 
     # ---- small helpers the reference exposes as static methods ----------------------------------------------
@@ -183,15 +185,43 @@ class DDPMTrainer(object):
                 p.grad.copy_(v)
 
     # ---- sampling ----------------------------------------------------------------------------------------------
+    def set_sampler(self, steps=None, method="ddpm", eta=0.0):
+        """How `generate` samples.  steps=None: the full ancestral chain of `self.diffusion` (the default).  Otherwise
+        `steps` of the diffusion_steps training steps (space_timesteps), walked by the ancestral update (method="ddpm")
+        or by DDIM with the given eta (method="ddim"; eta = 0 is deterministic).  Training always uses self.diffusion."""
+        if method not in ("ddpm", "ddim"):
+            raise ValueError("set_sampler: method must be 'ddpm' or 'ddim', got %r" % (method,))
+        eta = float(eta)
+        if not 0.0 <= eta < float("inf"):
+            raise ValueError("set_sampler: eta must be a finite number >= 0, got %r" % (eta,))
+        if steps is None:
+            self._few_step = None
+            return
+        spaced = SpacedDiffusion(space_timesteps(self.diffusion_steps, steps), betas=self.diffusion.betas,
+                                 model_mean_type=self.diffusion.model_mean_type,
+                                 model_var_type=self.diffusion.model_var_type, loss_type=self.diffusion.loss_type,
+                                 rescale_timesteps=self.diffusion.rescale_timesteps)
+        self._few_step = (spaced, method, eta)
+
+    def _sample_loop(self, shape, model_kwargs):
+        """The sampling loop `set_sampler` chose, with the arguments every reference tool passes."""
+        if self._few_step is None:
+            return self.diffusion.p_sample_loop(self.encoder, shape, clip_denoised=False, progress=True,
+                                                model_kwargs=model_kwargs)
+        spaced, method, eta = self._few_step
+        if method == "ddim":
+            return spaced.ddim_sample_loop(self.encoder, shape, clip_denoised=False, progress=True,
+                                           model_kwargs=model_kwargs, eta=eta)
+        return spaced.p_sample_loop(self.encoder, shape, clip_denoised=False, progress=True, model_kwargs=model_kwargs)
+
     def generate_batch(self, caption, m_lens, dim_pose):
-        """One chunk of captions -> (B, T, dim_pose) samples: text encoded once, then the 1000-step loop (captured
-        as a hipGraph by GaussianDiffusion); T = longest requested length, capped at num_frames (:121-150)."""
+        """One chunk of captions -> (B, T, dim_pose) samples: text encoded once, then the sampling loop (the 1000-step
+        chain unless set_sampler chose a shorter one; captured as a hipGraph by the diffusion object); T = longest
+        requested length, capped at num_frames (:121-150)."""
         core = _core(self.encoder)
         xf_proj, xf_out = core.encode_text(caption, self.device)
         T = min(int(m_lens.max()), core.num_frames)
-        return self.diffusion.p_sample_loop(self.encoder, (len(caption), T, dim_pose), clip_denoised=False,
-                                            progress=True,
-                                            model_kwargs=dict(xf_proj=xf_proj, xf_out=xf_out, length=m_lens))
+        return self._sample_loop((len(caption), T, dim_pose), dict(xf_proj=xf_proj, xf_out=xf_out, length=m_lens))
 
     def generate(self, caption, m_lens, dim_pose, batch_size=1024):
         """All captions in chunks of `batch_size` -> python list of (T_chunk, dim_pose) tensors (:152-170)."""

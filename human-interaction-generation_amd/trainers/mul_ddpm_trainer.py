@@ -152,8 +152,7 @@ class DDPMMulTrainer(DDPMTrainer):
             B = len(caption)
             xf_proj, xf_out = core.encode_text(caption, self.device)
             kwargs = {'xf_proj': xf_proj, 'xf_out': xf_out, 'length': m_lens}
-        return self.diffusion.p_sample_loop(self.encoder, (B, T, dim_pose), clip_denoised=False,
-                                            progress=True, model_kwargs=kwargs)
+        return self._sample_loop((B, T, dim_pose), kwargs)
 
     def generate(self, caption1, caption2, m_lens, dim_pose, batch_size=512):
         """mul_ddpm_trainer.py:201-221 -> list of [motion1, motion2] per pair."""
