@@ -86,6 +86,8 @@ SYMBOLS = (
     "hig_denoiser_plan", "hig_denoiser_last_schedule",
     # few-step sampling
     "hig_ddim_step", "hig_advance_timesteps",
+    # known-region conditioning
+    "hig_impose_known",
 )
 
 
@@ -202,6 +204,7 @@ def lib():
         L.hig_dec_timesteps.argtypes = [vp, i32, vp]
         L.hig_ddim_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, f32, i32, vp, vp, vp]
         L.hig_advance_timesteps.argtypes = [vp, vp, i32, i32, vp, vp]
+        L.hig_impose_known.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i64, vp]
         L.hig_masked_mse.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
         L.hig_pair_mse.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
         L.hig_sumsq_partial.argtypes = [vp, i64, f32, vp, vp]

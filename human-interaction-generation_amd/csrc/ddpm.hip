@@ -123,6 +123,59 @@ __global__ void advance_t_kernel(int64_t* __restrict__ t, const int64_t* __restr
   }
 }
 
+// ---- known-region conditioning (gaussian_diffusion.py:636-640, pre_seq: the known part noised to level t and written over x) ----
+// x[i] = sqrt_ac[t] known[i] + sqrt_1m_ac[t] z[i] where mask[i] != 0, untouched elsewhere.  A select: the value of an
+// unmasked lane is never computed from known / z (they may hold NaN there) and x keeps its bits.  The masked value has the
+// bits of q_sample_kernel's: there hipcc pairs the two products into one v_pk_mul_f32 and adds them, nothing fused; here,
+// four elements at a time, it would fuse some lanes and not others, so contraction is off and the three roundings are spelled out.
+struct impose_coef { float a, b; };
+
+__device__ __forceinline__ impose_coef impose_coef_at(const float* __restrict__ tab, int nsteps, int64_t t) {
+  const int tt = t < 0 ? 0 : (t >= nsteps ? nsteps - 1 : (int)t);   // (a step outside the table reads its nearest row)
+  impose_coef c;
+  c.a = tab[T_SQRT_AC * nsteps + tt];
+  c.b = tab[T_SQRT_1M_AC * nsteps + tt];
+  return c;
+}
+
+__device__ __forceinline__ float impose_elem(const impose_coef& c, float known, float z) {
+#pragma clang fp contract(off)
+  const float p = c.a * known, q = c.b * z;
+  return p + q;
+}
+
+// n4 groups of four elements (float4 of x / known / z, one 32-bit word of mask), then the scalar rest [4 n4, total); the host
+// passes n4 = 0 when x, known or z is not 16-byte aligned or mask not 4-byte aligned.  A group whose four mask bytes are zero
+// loads nothing else and stores nothing; a group that straddles a sample boundary looks its coefficients up per element.
+__global__ __launch_bounds__(256) void impose_known_kernel(float* x, const float* __restrict__ known,
+                                                           const uint8_t* __restrict__ mask, const float* __restrict__ z,
+                                                           const int64_t* __restrict__ t, const float* __restrict__ tab,
+                                                           int nsteps, int64_t per_sample, int64_t total, int64_t n4) {
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = tid; i < n4; i += stride) {
+    const uint32_t m = reinterpret_cast<const uint32_t*>(mask)[i];
+    if (m == 0) continue;
+    const float4 xv = reinterpret_cast<const float4*>(x)[i], kv = reinterpret_cast<const float4*>(known)[i];
+    const float4 zv = reinterpret_cast<const float4*>(z)[i];
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ks[4] = {kv.x, kv.y, kv.z, kv.w}, zs[4] = {zv.x, zv.y, zv.z, zv.w};
+    float o[4];
+    const int64_t s0 = (4 * i) / per_sample, s3 = (4 * i + 3) / per_sample;
+    if (s0 == s3) {
+      const impose_coef c = impose_coef_at(tab, nsteps, t[s0]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = ((m >> (8 * k)) & 0xffu) ? impose_elem(c, ks[k], zs[k]) : xs[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        o[k] = ((m >> (8 * k)) & 0xffu) ? impose_elem(impose_coef_at(tab, nsteps, t[(4 * i + k) / per_sample]), ks[k], zs[k])
+                                        : xs[k];
+    }
+    reinterpret_cast<float4*>(x)[i] = make_float4(o[0], o[1], o[2], o[3]);
+  }
+  for (int64_t i = 4 * n4 + tid; i < total; i += stride)
+    if (mask[i]) x[i] = impose_elem(impose_coef_at(tab, nsteps, t[i / per_sample]), known[i], z[i]);
+}
+
 // One wave per (b, t) row: row mean of squared error, masked; dpred written in the same pass.
 __global__ __launch_bounds__(256) void masked_mse_kernel(const float* __restrict__ pred,
                                                          const float* __restrict__ target,
@@ -411,6 +464,19 @@ extern "C" int hig_ddim_step(const float* x, const float* eps, const float* z, c
   hipLaunchKernelGGL(ddim_step_kernel, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, eps,
                      eta == 0.0f ? nullptr : z, t, tab, nsteps, per_sample, total, n4, eta, clip_denoised ? 1 : 0, x_prev,
                      pred_xstart);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_impose_known(float* x, const float* known, const uint8_t* mask, const float* z, const int64_t* t,
+                                const float* tab, int32_t nsteps, int32_t B, int64_t per_sample, hig_stream_t s) {
+  HIG_REQUIRE(x && known && mask && z && t && tab && B > 0 && per_sample > 0 && nsteps > 0, "hig_impose_known: bad arguments");
+  const int64_t total = (int64_t)B * per_sample;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(known) | reinterpret_cast<uintptr_t>(z);
+  const int64_t n4 = (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0 ? total / 4 : 0;
+  const int64_t work = n4 > total - 4 * n4 ? n4 : total - 4 * n4;
+  hipLaunchKernelGGL(impose_known_kernel, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, known, mask, z, t, tab,
+                     nsteps, per_sample, total, n4);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

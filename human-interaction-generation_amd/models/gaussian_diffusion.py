@@ -15,6 +15,11 @@ variance, the cosine schedule, q_mean_variance, the eps <-> x0 <-> x_{t-1} conve
 arithmetic on whatever device the tensors live on; only the trainers' combination takes the HIP kernels.  Not built
 (no reference tool reaches them): learned variances and the KL / VLB losses that train them, DDIM, cond_fn guidance --
 the enums keep their member names and those paths raise NotImplementedError instead of silently running something else.
+
+Known-region conditioning (replacement-style in-painting, gaussian_diffusion.py:636-647): before every denoising step the known
+part of the motion is noised to the current level and written over the state.  The primitive is a `known` tensor of the
+sample's shape plus an element mask (`known_mask`), one hig_impose_known launch on fp32 ROCm tensors; the reference's
+`pre_seq` (the first Fp features of every frame) is a special case of it, its `transl_req` stays tensor arithmetic.
 """
 import enum
 import math
@@ -113,6 +118,49 @@ _TAB_ORDER = ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod", "sqrt_reci
 
 def _unwrap(model):
     return getattr(model, "module", model)
+
+
+def _known_args(shape, known, known_mask, pre_seq, transl_req=None):
+    """Checks the conditioning arguments of one sampling call against the sample's shape (B, T, F).  Returns (known,
+    known_mask) with the mask expanded to the shape as a contiguous uint8 tensor on known's device, or (None, None) when
+    neither was given.  ValueError: one of the pair without the other, known together with pre_seq, shapes that do not fit, a
+    mask that is neither bool nor uint8, transl_req at B > 2 (the reference's coefficient expand fails there)."""
+    shape = tuple(shape)
+    if (known is None) != (known_mask is None):
+        raise ValueError("known and known_mask go together: got %s without %s"
+                         % (("known", "known_mask") if known_mask is None else ("known_mask", "known")))
+    if known is not None and pre_seq is not None:
+        raise ValueError("known / known_mask and pre_seq are two forms of the same conditioning: give one of them")
+    if pre_seq is not None:
+        ps = tuple(pre_seq.shape)
+        if len(shape) != 3 or len(ps) != 3 or ps[:2] != shape[:2] or not 1 <= ps[2] <= shape[2]:
+            raise ValueError("pre_seq must be (B, T, Fp) with Fp <= F for a sample of shape %r, got %r" % (shape, ps))
+    if transl_req is not None and shape[0] > 2:
+        raise ValueError("transl_req works for a batch of 1 or 2 only (the reference expands a (B,) coefficient to the 2 "
+                         "frames it sets), got B = %d" % shape[0])
+    if known is None:
+        return None, None
+    if tuple(known.shape) != shape:
+        raise ValueError("known must have the sample's shape %r, got %r" % (shape, tuple(known.shape)))
+    known_mask = th.as_tensor(known_mask)
+    if known_mask.dtype not in (th.bool, th.uint8):
+        raise ValueError("known_mask must be bool or uint8, got %s" % known_mask.dtype)
+    try:
+        full = th.broadcast_to(known_mask, shape)
+    except RuntimeError:
+        raise ValueError("known_mask of shape %r does not broadcast to the sample's shape %r"
+                         % (tuple(known_mask.shape), shape)) from None
+    return known, full.to(device=known.device, dtype=th.uint8).contiguous()
+
+
+def _pre_seq_as_known(pre_seq, shape, device):
+    """The reference's pre_seq as the primitive: known[:, :, :Fp] = pre_seq, the mask on features < Fp."""
+    Fp = pre_seq.shape[2]
+    known = th.zeros(*shape, device=device, dtype=th.float32)
+    known[:, :, :Fp] = pre_seq.to(device)
+    mask = th.zeros(*shape, device=device, dtype=th.uint8)
+    mask[:, :, :Fp] = 1
+    return known, mask
 
 
 class GaussianDiffusion:
@@ -254,17 +302,64 @@ class GaussianDiffusion:
     def _is_trainer_branch(self, clip_denoised, denoised_fn, cond_fn, pre_seq, transl_req):
         return (self.model_mean_type == ModelMeanType.EPSILON
                 and self.model_var_type == ModelVarType.FIXED_SMALL and not clip_denoised
-                and denoised_fn is None and cond_fn is None and pre_seq is None and transl_req is None
-                and not self.rescale_timesteps)
+                and denoised_fn is None and cond_fn is None and transl_req is None
+                and not self.rescale_timesteps)      # (pre_seq / known: imposed before the step, whichever branch follows)
+
+    # ---- known-region conditioning ---------------------------------------------------------
+    def _q_sample_ops(self, x_start, t, noise):
+        """q_sample as tensor arithmetic in the reference's operation order, whatever the device."""
+        return (_extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
+                + _extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
+
+    def _launch_impose(self, x, known, mask, z, t):
+        """ONE hig_impose_known launch on x in place (through a contiguous copy when x is a strided view)."""
+        xc = x if x.is_contiguous() else x.contiguous()
+        kc, zc, t64, tab = known.contiguous(), z.contiguous(), t.long().contiguous(), self.device_table(x.device)
+        B = xc.shape[0]
+        _lib.check(_lib.lib().hig_impose_known(_lib.ptr(xc), _lib.ptr(kc), _lib.ptr(mask), _lib.ptr(zc), _lib.ptr(t64),
+                                              _lib.ptr(tab), self.num_timesteps, B, xc.numel() // B, _lib.stream_ptr()))
+        if xc is not x:
+            x.copy_(xc)
+
+    def _impose(self, x, t, known, known_mask, pre_seq, transl_req=None):
+        """x <- the known part noised to level t, in place, where it is known (gaussian_diffusion.py:636-647); `t` indexes this
+        object's own schedule.  The draws are the reference's: randn_like(pre_seq) [or randn_like(known)], then randn(2) per
+        transl_req item.  fp32 ROCm tensors: one hig_impose_known launch; anything else: tensor arithmetic in the
+        reference's operation order (a select, so NaN in known off the mask reaches nothing).  transl_req is always tensor
+        arithmetic."""
+        if pre_seq is not None:
+            Fp = pre_seq.shape[2]
+            noise = th.randn_like(pre_seq)
+            if self._fused_ok(x, pre_seq, noise):
+                kf, mask = _pre_seq_as_known(pre_seq, x.shape, x.device)
+                z = th.zeros_like(kf)
+                z[:, :, :Fp] = noise
+                self._launch_impose(x, kf, mask, z, t)
+            else:
+                x[:, :, :Fp] = self._q_sample_ops(pre_seq, t, noise)
+        elif known is not None:
+            noise = th.randn_like(known)
+            if self._fused_ok(x, known, noise) and known_mask.is_cuda:
+                self._launch_impose(x, known, known_mask, noise, t)
+            else:
+                x.copy_(th.where(known_mask.to(x.device).bool(), self._q_sample_ops(known, t, noise).to(x.dtype), x))
+        if transl_req is not None:
+            for item in transl_req:
+                noise = th.randn(2).type_as(x)
+                transl = th.Tensor(item[1:]).type_as(x)
+                x[:, :2, item[0]] = self._q_sample_ops(transl, t, noise)
 
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, pre_seq=None,
-                 transl_req=None, model_kwargs=None):
+                 transl_req=None, model_kwargs=None, known=None, known_mask=None):
         """gaussian_diffusion.py:606-666.  On the trainers' branch the whole update
-        (x0-hat, posterior mean, noise) is ONE kernel; other branches use tensor ops."""
-        if pre_seq is not None or transl_req is not None:
-            raise NotImplementedError("pre_seq / transl_req conditioning is never used by the reference tools")
+        (x0-hat, posterior mean, noise) is ONE kernel; other branches use tensor ops.
+        pre_seq (B, T, Fp) / transl_req [[j, v0, v1], ...] as in the reference, or known (B, T, F) + known_mask (bool / uint8,
+        broadcastable): the known part, noised to level t, is written INTO THE CALLER'S x before the model sees it."""
         if cond_fn is not None:
             raise NotImplementedError("cond_fn guidance is never used by the reference tools")
+        known, known_mask = _known_args(x.shape, known, known_mask, pre_seq, transl_req)
+        if known is not None or pre_seq is not None or transl_req is not None:
+            self._impose(x, t, known, known_mask, pre_seq, transl_req)
         if self._is_trainer_branch(clip_denoised, denoised_fn, cond_fn, pre_seq, transl_req) and self._fused_ok(x):
             eps = model(x, t, **(model_kwargs or {}))
             noise = th.randn_like(x)
@@ -284,28 +379,33 @@ class GaussianDiffusion:
         return {"sample": sample, "pred_xstart": out["pred_xstart"]}
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                      model_kwargs=None, device=None, pre_seq=None, transl_req=None, progress=False):
-        """gaussian_diffusion.py:668-716."""
+                      model_kwargs=None, device=None, pre_seq=None, transl_req=None, progress=False, known=None,
+                      known_mask=None):
+        """gaussian_diffusion.py:668-716.  pre_seq / transl_req / known + known_mask: see p_sample; the captured loop takes
+        pre_seq and known (one more launch per step), a call with transl_req runs eagerly."""
         core = _unwrap(model)
         if (self.use_hip_graph and hasattr(core, "_launch_forward") and model_kwargs is not None
                 and model_kwargs.get("xf_proj") is not None and model_kwargs.get("xf_out") is not None
                 and self._is_trainer_branch(clip_denoised, denoised_fn, cond_fn, pre_seq, transl_req)):
-            return self._p_sample_loop_graph(core, shape, noise, model_kwargs, device)
+            known, known_mask = _known_args(shape, known, known_mask, pre_seq)
+            return self._p_sample_loop_graph(core, shape, noise, model_kwargs, device, known, known_mask, pre_seq)
         final = None
         for sample in self.p_sample_loop_progressive(
                 model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                 cond_fn=cond_fn, model_kwargs=model_kwargs, device=device, pre_seq=pre_seq,
-                transl_req=transl_req, progress=progress):
+                transl_req=transl_req, progress=progress, known=known, known_mask=known_mask):
             final = sample
         return final["sample"]
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                   cond_fn=None, model_kwargs=None, device=None, pre_seq=None,
-                                  transl_req=None, progress=False):
+                                  transl_req=None, progress=False, known=None, known_mask=None):
         """gaussian_diffusion.py:718-769: t = N-1 ... 0, fresh noise every step, no_grad."""
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
+        known, known_mask = _known_args(shape, known, known_mask, pre_seq, transl_req)    # (the mask is expanded once)
+        cond = {} if known is None else dict(known=known.to(device), known_mask=known_mask.to(device))
         img = noise if noise is not None else th.randn(*shape, device=device)
         indices = list(range(self.num_timesteps))[::-1]
         if progress:
@@ -316,17 +416,21 @@ class GaussianDiffusion:
             with th.no_grad():
                 out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                     cond_fn=cond_fn, model_kwargs=model_kwargs, pre_seq=pre_seq,
-                                    transl_req=transl_req)
+                                    transl_req=transl_req, **cond)
                 yield out
                 img = out["sample"]
 
-    def _p_sample_loop_graph(self, core, shape, noise, model_kwargs, device):
+    def _p_sample_loop_graph(self, core, shape, noise, model_kwargs, device, known=None, known_mask=None, pre_seq=None):
         """The 1000-step loop as ONE captured hipGraph replayed num_timesteps times.
 
         Captured per step: denoiser forward (text context hoisted: it is step-invariant), fresh
         Gaussian noise (torch's graph-safe Philox), the fused x_{t-1} update in place, and the
         device-side `t -= 1`.  Nothing crosses PCIe inside the loop (the reference does ~8 H2D
-        copies and B device syncs per step)."""
+        copies and B device syncs per step).
+
+        With known + known_mask (or pre_seq, turned into that pair) the step opens with the imposition:
+        zz.normal_() -> hig_impose_known(img, known, mask, zk, t_dev) -> forward -> update with z -> dec, where zk and z are
+        the two halves of ONE buffer drawn by a single normal_(): a conditioned step has one launch more, not two."""
         if device is None:
             device = next(core.parameters()).device
         B = shape[0]
@@ -341,14 +445,29 @@ class GaussianDiffusion:
             else:
                 length = th.as_tensor(length).to(device).long().contiguous()
             t_dev = th.full((B,), self.num_timesteps - 1, dtype=th.int64, device=device)
-            z = th.zeros_like(img)
             tab = self.device_table(device)
             L = _lib.lib()
             per = img.numel() // B
+            if pre_seq is not None:
+                known, known_mask = _pre_seq_as_known(pre_seq.float(), img.shape, device)
+            cond = known is not None
+            if cond:
+                known = known.to(device).float().contiguous()
+                known_mask = known_mask.to(device).contiguous()
+                zz = th.zeros(2, *img.shape, device=device)
+                zk, z = zz[0], zz[1]
+            else:
+                z = th.zeros_like(img)
 
             def step():
+                if cond:
+                    if not self._debug_zero_noise:
+                        zz.normal_()
+                    _lib.check(L.hig_impose_known(_lib.ptr(img), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
+                                                  _lib.ptr(t_dev), _lib.ptr(tab), self.num_timesteps, B, per,
+                                                  _lib.stream_ptr()))
                 eps, _ = core._launch_forward(img, t_dev, length, xf_proj, xf_out, training=False)
-                if not self._debug_zero_noise:
+                if not cond and not self._debug_zero_noise:
                     z.normal_()
                 _lib.check(L.hig_p_sample_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(z), _lib.ptr(t_dev),
                                                _lib.ptr(tab), self.num_timesteps, B, per, _lib.ptr(img),

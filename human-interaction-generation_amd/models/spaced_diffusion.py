@@ -11,7 +11,11 @@
     mapped step, noise (no noise node at all when eta == 0), the update in place, hig_advance_timesteps.  The graph lives for
     one call: it reads the text context the warm-up step built for THIS call's xf_out.
 
-`GaussianDiffusion` itself is unchanged (its four DDIM names still raise); `SpacedDiffusion(space_timesteps(N, N), ...)` is
+  * Every sampler takes known-region conditioning (`known` + `known_mask`; the ancestral family also the reference's `pre_seq`
+    / `transl_req`): the known part, noised to the level of this object's own step t, is written over the state before each
+    model call -- hig_impose_known, one more launch in front of the captured step.
+
+`GaussianDiffusion`'s four DDIM names still raise; `SpacedDiffusion(space_timesteps(N, N), ...)` is
 the unstrided DDIM sampler.
 """
 import numbers
@@ -20,7 +24,8 @@ import numpy as np
 import torch as th
 
 from .. import _lib
-from .gaussian_diffusion import GaussianDiffusion, ModelMeanType, _extract_into_tensor, _unwrap
+from .gaussian_diffusion import (GaussianDiffusion, ModelMeanType, _extract_into_tensor, _known_args, _pre_seq_as_known,
+                                 _unwrap)
 
 _DDIM_TAB_ORDER = ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "alphas_cumprod", "alphas_cumprod_prev")
 
@@ -118,13 +123,20 @@ class SpacedDiffusion(GaussianDiffusion):
         return (self.model_mean_type == ModelMeanType.EPSILON and denoised_fn is None and cond_fn is None
                 and not self.rescale_timesteps)
 
-    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0):
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0,
+                    known=None, known_mask=None):
         """gaussian_diffusion.py:771-819.  For fp32 ROCm tensors on the eps-prediction branch the whole update is ONE kernel
         (either value of clip_denoised); everything else is tensor arithmetic.  The fused path draws no noise at eta == 0
         (z is never read there), the tensor-op path draws it always, as the reference does: after an eta == 0 call the
-        generator's state therefore depends on which path ran, the sample does not."""
+        generator's state therefore depends on which path ran, the sample does not.
+        known + known_mask: the known part, noised to level t with a fresh randn_like(known), is written into the caller's x
+        first (as p_sample does).  A conditioned step therefore draws noise at eta == 0 too: it is no longer a pure function
+        of x."""
         if cond_fn is not None:
             raise NotImplementedError("cond_fn guidance is never used by the reference tools")
+        known, known_mask = _known_args(x.shape, known, known_mask, None)
+        if known is not None:
+            self._impose(x, t, known, known_mask, None)
         if self._ddim_fused_ok(denoised_fn, cond_fn) and self._fused_ok(x):
             eps = self._wrap(model)(x, t, **(model_kwargs or {}))
             noise = th.randn_like(x).contiguous() if eta != 0 else None
@@ -161,24 +173,30 @@ class SpacedDiffusion(GaussianDiffusion):
         return {"sample": mean_pred, "pred_xstart": out["pred_xstart"]}
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                         model_kwargs=None, device=None, progress=False, eta=0.0):
-        """gaussian_diffusion.py:859-891."""
+                         model_kwargs=None, device=None, progress=False, eta=0.0, known=None, known_mask=None):
+        """gaussian_diffusion.py:859-891.  With known + known_mask every step first writes the noised known part over the
+        state; the noise of that imposition is fresh every step, so a conditioned loop at eta == 0 is NOT a pure function of
+        its start (the unconditioned one is)."""
         core = _unwrap(model)
         if self._graph_ok(core, model_kwargs) and self._ddim_fused_ok(denoised_fn, cond_fn):
-            return self._spaced_loop_graph(core, shape, noise, model_kwargs, device, "ddim", float(eta), clip_denoised)
+            known, known_mask = _known_args(shape, known, known_mask, None)
+            return self._spaced_loop_graph(core, shape, noise, model_kwargs, device, "ddim", float(eta), clip_denoised,
+                                           known, known_mask)
         final = None
         for sample in self.ddim_sample_loop_progressive(
                 model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                model_kwargs=model_kwargs, device=device, progress=progress, eta=eta):
+                model_kwargs=model_kwargs, device=device, progress=progress, eta=eta, known=known, known_mask=known_mask):
             final = sample
         return final["sample"]
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                                     model_kwargs=None, device=None, progress=False, eta=0.0):
+                                     model_kwargs=None, device=None, progress=False, eta=0.0, known=None, known_mask=None):
         """gaussian_diffusion.py:893-941: t = K-1 ... 0, no_grad."""
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
+        known, known_mask = _known_args(shape, known, known_mask, None)    # (the mask is expanded once)
+        cond = {} if known is None else dict(known=known.to(device), known_mask=known_mask.to(device))
         img = noise if noise is not None else th.randn(*shape, device=device)
         indices = list(range(self.num_timesteps))[::-1]
         if progress:
@@ -188,7 +206,7 @@ class SpacedDiffusion(GaussianDiffusion):
             t = th.tensor([i] * shape[0], device=device)
             with th.no_grad():
                 out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                       cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta)
+                                       cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta, **cond)
                 yield out
                 img = out["sample"]
 
@@ -198,24 +216,36 @@ class SpacedDiffusion(GaussianDiffusion):
                 and model_kwargs.get("xf_proj") is not None and model_kwargs.get("xf_out") is not None)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                      model_kwargs=None, device=None, pre_seq=None, transl_req=None, progress=False):
-        """The ancestral chain over the K kept steps; captured under the base class's conditions."""
+                      model_kwargs=None, device=None, pre_seq=None, transl_req=None, progress=False, known=None,
+                      known_mask=None):
+        """The ancestral chain over the K kept steps; captured under the base class's conditions (pre_seq and known +
+        known_mask stay on the captured path, transl_req runs eagerly)."""
         core = _unwrap(model)
         if (self._graph_ok(core, model_kwargs)
                 and self._is_trainer_branch(clip_denoised, denoised_fn, cond_fn, pre_seq, transl_req)):
-            return self._spaced_loop_graph(core, shape, noise, model_kwargs, device, "ddpm", 0.0, False)
+            known, known_mask = _known_args(shape, known, known_mask, pre_seq)
+            return self._spaced_loop_graph(core, shape, noise, model_kwargs, device, "ddpm", 0.0, False, known, known_mask,
+                                           pre_seq)
         final = None
         for sample in self.p_sample_loop_progressive(
                 model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                model_kwargs=model_kwargs, device=device, pre_seq=pre_seq, transl_req=transl_req, progress=progress):
+                model_kwargs=model_kwargs, device=device, pre_seq=pre_seq, transl_req=transl_req, progress=progress,
+                known=known, known_mask=known_mask):
             final = sample
         return final["sample"]
 
-    def _spaced_loop_graph(self, core, shape, noise, model_kwargs, device, method, eta, clip_denoised):
+    def _spaced_loop_graph(self, core, shape, noise, model_kwargs, device, method, eta, clip_denoised, known=None,
+                           known_mask=None, pre_seq=None):
         """One captured step replayed num_timesteps times: denoiser forward at the ORIGINAL timestep (t_model), fresh noise
         (ancestral, or DDIM with eta > 0: at eta == 0 the graph has no noise node and the update gets z = NULL), the update in
         place, then hig_advance_timesteps (t -= 1, t_model = map[t]).  The warm-up step outside the graph builds the text
-        context of this call's xf_out, whose buffer the captured forward reads: the graph is not kept beyond the call."""
+        context of this call's xf_out, whose buffer the captured forward reads: the graph is not kept beyond the call.
+        With known + known_mask (or pre_seq, turned into that pair) the step becomes
+            zz.normal_() -> hig_impose_known(img, known, mask, zk, t_dev, device_table) -> forward -> update with z -> advance
+        The imposition reads t_dev, the index into this object's own K-column table, not t_model.  zk (and z, where the update
+        needs one) are parts of ONE buffer drawn by a single normal_(): a conditioned step has one launch more than an
+        unconditioned one with noise, two more at DDIM eta == 0 -- which now draws noise and is no longer a pure function of
+        its start."""
         if device is None:
             device = next(core.parameters()).device
         K, B = self.num_timesteps, shape[0]
@@ -234,14 +264,29 @@ class SpacedDiffusion(GaussianDiffusion):
             t_model = th.full((B,), self.timestep_map[K - 1], dtype=th.int64, device=device)
             ddim = method == "ddim"
             needs_z = not ddim or eta != 0
-            z = th.zeros_like(img) if needs_z else None
             tab = self.ddim_table(device) if ddim else self.device_table(device)
             L = _lib.lib()
             per = img.numel() // B
+            if pre_seq is not None:
+                known, known_mask = _pre_seq_as_known(pre_seq.float(), img.shape, device)
+            cond = known is not None
+            if cond:
+                known = known.to(device).float().contiguous()
+                known_mask = known_mask.to(device).contiguous()
+                qtab = self.device_table(device)
+                zz = th.zeros(2 if needs_z else 1, *img.shape, device=device)
+                zk, z = zz[0], (zz[1] if needs_z else None)
+            else:
+                z = th.zeros_like(img) if needs_z else None
 
             def step():
+                if cond:
+                    if not self._debug_zero_noise:
+                        zz.normal_()
+                    _lib.check(L.hig_impose_known(_lib.ptr(img), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
+                                                  _lib.ptr(t_dev), _lib.ptr(qtab), K, B, per, _lib.stream_ptr()))
                 eps, _ = core._launch_forward(img, t_model, length, xf_proj, xf_out, training=False)
-                if needs_z and not self._debug_zero_noise:
+                if needs_z and not cond and not self._debug_zero_noise:
                     z.normal_()
                 if ddim:
                     _lib.check(L.hig_ddim_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(z), _lib.ptr(t_dev), _lib.ptr(tab), K, B,

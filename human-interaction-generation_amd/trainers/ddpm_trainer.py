@@ -203,33 +203,54 @@ class DDPMTrainer(object):
                                  rescale_timesteps=self.diffusion.rescale_timesteps)
         self._few_step = (spaced, method, eta)
 
-    def _sample_loop(self, shape, model_kwargs):
-        """The sampling loop `set_sampler` chose, with the arguments every reference tool passes."""
+    def _sample_loop(self, shape, model_kwargs, known=None, known_mask=None):
+        """The sampling loop `set_sampler` chose, with the arguments every reference tool passes; known + known_mask (see
+        GaussianDiffusion.p_sample) go to whichever loop that is."""
+        cond = {} if known is None and known_mask is None else dict(known=known, known_mask=known_mask)
         if self._few_step is None:
             return self.diffusion.p_sample_loop(self.encoder, shape, clip_denoised=False, progress=True,
-                                                model_kwargs=model_kwargs)
+                                                model_kwargs=model_kwargs, **cond)
         spaced, method, eta = self._few_step
         if method == "ddim":
             return spaced.ddim_sample_loop(self.encoder, shape, clip_denoised=False, progress=True,
-                                           model_kwargs=model_kwargs, eta=eta)
-        return spaced.p_sample_loop(self.encoder, shape, clip_denoised=False, progress=True, model_kwargs=model_kwargs)
+                                           model_kwargs=model_kwargs, eta=eta, **cond)
+        return spaced.p_sample_loop(self.encoder, shape, clip_denoised=False, progress=True, model_kwargs=model_kwargs,
+                                    **cond)
 
-    def generate_batch(self, caption, m_lens, dim_pose):
+    def _known_for(self, known, known_mask, T):
+        """The conditioning pair of one model batch (B, >= T, F) on the device, the mask expanded to known's shape, both cut to
+        T frames.  One of the pair alone is passed on as it is: the diffusion object refuses it."""
+        if known is None or known_mask is None:
+            return known, known_mask
+        known = torch.as_tensor(known).to(self.device).float()
+        known_mask = torch.broadcast_to(torch.as_tensor(known_mask).to(self.device), known.shape)
+        return known[:, :T], known_mask[:, :T]
+
+    def generate_batch(self, caption, m_lens, dim_pose, known=None, known_mask=None):
         """One chunk of captions -> (B, T, dim_pose) samples: text encoded once, then the sampling loop (the 1000-step
         chain unless set_sampler chose a shorter one; captured as a hipGraph by the diffusion object); T = longest
-        requested length, capped at num_frames (:121-150)."""
+        requested length, capped at num_frames (:121-150).  known (B, >= T, dim_pose) + known_mask (bool / uint8,
+        broadcastable to it): the part of the motion that is given, imposed before every step; both are cut to T frames."""
         core = _core(self.encoder)
         xf_proj, xf_out = core.encode_text(caption, self.device)
         T = min(int(m_lens.max()), core.num_frames)
-        return self._sample_loop((len(caption), T, dim_pose), dict(xf_proj=xf_proj, xf_out=xf_out, length=m_lens))
+        known, known_mask = self._known_for(known, known_mask, T)
+        return self._sample_loop((len(caption), T, dim_pose), dict(xf_proj=xf_proj, xf_out=xf_out, length=m_lens),
+                                 known, known_mask)
 
-    def generate(self, caption, m_lens, dim_pose, batch_size=1024):
-        """All captions in chunks of `batch_size` -> python list of (T_chunk, dim_pose) tensors (:152-170)."""
+    def generate(self, caption, m_lens, dim_pose, batch_size=1024, known=None, known_mask=None):
+        """All captions in chunks of `batch_size` -> python list of (T_chunk, dim_pose) tensors (:152-170).  known (N, T,
+        dim_pose) + known_mask: sliced per chunk, cut to the chunk's T."""
         self.encoder.eval()
+        if known is not None and known_mask is not None:
+            known = torch.as_tensor(known)
+            known_mask = torch.broadcast_to(torch.as_tensor(known_mask), known.shape)
         samples = []
         for lo in range(0, len(caption), batch_size):
             hi = min(len(caption), lo + batch_size)
-            samples.extend(self.generate_batch(caption[lo:hi], m_lens[lo:hi], dim_pose).unbind(0))
+            k = known if known is None else known[lo:hi]
+            km = known_mask if known_mask is None or known is None else known_mask[lo:hi]
+            samples.extend(self.generate_batch(caption[lo:hi], m_lens[lo:hi], dim_pose, known=k, known_mask=km).unbind(0))
         return samples
 
     # ---- checkpoints (keys: opt_encoder / ep / total_it / encoder, ddpm_trainer.py:200-218) ---------------------

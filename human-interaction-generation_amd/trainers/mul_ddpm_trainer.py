@@ -138,11 +138,18 @@ class DDPMMulTrainer(DDPMTrainer):
         return step(x_start.contiguous(), t, cur_len, noise=noise, clip_out=clip_out, eot=eot)
 
     # ---- sampling ---------------------------------------------------------------------------
-    def generate_batch(self, caption1, caption2, m_lens, dim_pose):
-        """mul_ddpm_trainer.py:163-199."""
+    def generate_batch(self, caption1, caption2, m_lens, dim_pose, known=None, known_mask=None):
+        """mul_ddpm_trainer.py:163-199.  known + known_mask: (2, pairs, T, F) (person, pair), or already in the model batch's
+        layout (2 pairs, T, F) = person 1 of all pairs, then person 2; cut to this chunk's T."""
         m_lens = torch.cat([m_lens, m_lens], dim=0)
         core = _core(self.encoder)
         T = min(int(m_lens.max()), core.num_frames)
+        if known is not None and known_mask is not None:
+            known = torch.as_tensor(known)
+            known_mask = torch.broadcast_to(torch.as_tensor(known_mask), known.shape)
+            if known.dim() == 4:
+                known, known_mask = known.flatten(0, 1), known_mask.flatten(0, 1)
+        known, known_mask = self._known_for(known, known_mask, T)
         if self.cap_id:
             caption = [torch.as_tensor(caption1).view(-1), torch.as_tensor(caption2).view(-1)]
             B = len(caption1) + len(caption2)
@@ -152,11 +159,16 @@ class DDPMMulTrainer(DDPMTrainer):
             B = len(caption)
             xf_proj, xf_out = core.encode_text(caption, self.device)
             kwargs = {'xf_proj': xf_proj, 'xf_out': xf_out, 'length': m_lens}
-        return self._sample_loop((B, T, dim_pose), kwargs)
+        return self._sample_loop((B, T, dim_pose), kwargs, known, known_mask)
 
-    def generate(self, caption1, caption2, m_lens, dim_pose, batch_size=512):
-        """mul_ddpm_trainer.py:201-221 -> list of [motion1, motion2] per pair."""
+    def generate(self, caption1, caption2, m_lens, dim_pose, batch_size=512, known=None, known_mask=None):
+        """mul_ddpm_trainer.py:201-221 -> list of [motion1, motion2] per pair.  known + known_mask: (2, N, T, F) (person,
+        pair), sliced per chunk.  Reaction generation: known[0] = person 1's motion, known_mask[0] = frames < length,
+        known_mask[1] = 0."""
         N = len(caption1)
+        if known is not None and known_mask is not None:
+            known = torch.as_tensor(known)
+            known_mask = torch.broadcast_to(torch.as_tensor(known_mask), known.shape)
         cur_idx = 0
         self.encoder.eval()
         all_output = []
@@ -167,7 +179,9 @@ class DDPMMulTrainer(DDPMTrainer):
             # kept, so chunked generation gives the same conditioning as upstream
             batch_caption2 = caption2[cur_idx:] if end == N else caption1[cur_idx:end]
             batch_m_lens = m_lens[cur_idx:end]
-            output = self.generate_batch(batch_caption1, batch_caption2, batch_m_lens, dim_pose)
+            k = known if known is None else known[:, cur_idx:end]
+            km = known_mask if known_mask is None or known is None else known_mask[:, cur_idx:end]
+            output = self.generate_batch(batch_caption1, batch_caption2, batch_m_lens, dim_pose, known=k, known_mask=km)
             B = len(batch_caption1)
             motion1, motion2 = output[:B], output[B:]
             for i in range(B):

@@ -998,6 +998,20 @@ int hig_ddim_step(const float* x, const float* eps, const float* z /* nullable i
 /* t[b] -= 1, then t_model[b] = map[max(t[b], 0)] (map: nsteps int64 entries, the original timestep of each kept step), one
  * launch: the counter of the strided loops.  After the last step t = -1 and t_model = map[0], which nobody reads. */
 int hig_advance_timesteps(int64_t* t, const int64_t* map, int32_t nsteps, int32_t B, int64_t* t_model, hig_stream_t s);
+/* Known-region conditioning (the reference's pre_seq, gaussian_diffusion.py:636-640, as a known tensor plus an element mask):
+ * for every element i of sample b = i / per_sample
+ *   mask[i] != 0:  x[i] = tab[sqrt_alphas_cumprod][t[b]] * known[i] + tab[sqrt_one_minus_alphas_cumprod][t[b]] * z[i]
+ *   mask[i] == 0:  x[i] keeps its bits, and known[i] / z[i] are never used (they may hold NaN)
+ * in place, one launch.  A select, not a blend; any nonzero mask byte means "known".  `tab` is the HIG_TAB_ROWS x nsteps table
+ * of hig_q_sample; t is per sample (0 <= t[b] < nsteps; a value outside reads the nearest row).  x, known, z: B * per_sample
+ * floats, mask: as many bytes; none of known / mask / z may overlap x.  Vector path (float4 + one mask word per group) when
+ * x, known and z are 16-byte and mask 4-byte aligned, scalar otherwise: the same bits.  A group of four whose mask bytes are
+ * all zero reads neither known nor z and stores nothing.  No allocation, no synchronisation, nothing read back: capturable.
+ * Refused with HIG_EINVAL, nothing written: a NULL x / known / mask / z / t / tab, B, per_sample or nsteps <= 0.
+ * Bound: the masked value is what hig_q_sample computes for the same operands, bit for bit -- two products and a sum in
+ * fp32, so with u = 2^-24 and the table's entries taken as exact it is within 2 u (|a known| + |b z|) of its fp64 value. */
+int hig_impose_known(float* x, const float* known, const uint8_t* mask, const float* z, const int64_t* t,
+                     const float* tab, int32_t nsteps, int32_t B, int64_t per_sample, hig_stream_t s);
 /* DDPMTrainer.backward_G (ddpm_trainer.py:172-178): loss = sum_bt mask*mean_f (p-t)^2 / sum mask
  * with mask[b][t] = t < length[b];  dpred = d loss / d pred.  scratch: HIG_NORM_BLOCKS floats
  * (one partial sum per workgroup, at most HIG_NORM_BLOCKS - 1 of them, and sum(mask) behind them). */

@@ -2,7 +2,11 @@
 1000-step chain through plain GaussianDiffusion (the path every earlier commit has) next to SpacedDiffusion's strided ancestral
 and DDIM (eta = 0) loops at K = 1000 / 100 / 50 / 20, with fp32 and with bf16 storage.
 
-    python tools/few_step_time.py [--repeats 5] [--ks 1000,100,50,20] [--out FILE]
+    python tools/few_step_time.py [--repeats 5] [--ks 1000,100,50,20] [--out FILE] [--known]
+
+--known: what known-region conditioning adds to a step.  Instead of the list above, every K gets its strided ancestral and DDIM
+(eta = 0) loops twice, unconditioned (the path without hig_impose_known, launch for launch the parent commit's) and with the
+first half of the frames known (`known` + `known_mask`), alternating in the same run.
 
 Per loop and repeat it reports
   * call_ms    host clock around one whole call, between device synchronisations: warm-up step, capture and K replays (text
@@ -98,6 +102,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--ks", default="1000,100,50,20")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--known", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("few_step_time.py needs the MI355X")
@@ -110,19 +115,25 @@ def main():
           "length": torch.full((c["B"],), c["T"], dtype=torch.int64, device=dev)}
     shape = (c["B"], c["T"], c["F"])
     x0 = torch.randn(*shape, generator=g).to(dev)
-    loops = [("GaussianDiffusion ddpm", N, lambda: hig_amd.GaussianDiffusion(**diffusion_args()), "p")]
+    known = torch.randn(*shape, generator=g).to(dev)
+    known_mask = torch.zeros(shape, dtype=torch.bool, device=dev)
+    known_mask[:, :c["T"] // 2] = True
+    loops = [] if a.known else [("GaussianDiffusion ddpm", N, lambda: hig_amd.GaussianDiffusion(**diffusion_args()), "p")]
     for k in (int(v) for v in a.ks.split(",")):
         for name, kind in (("ddpm", "p"), ("ddim eta=0", "d")):
-            loops.append(("SpacedDiffusion %s" % name, k,
-                          lambda k=k: hig_amd.SpacedDiffusion(hig_amd.space_timesteps(N, k), **diffusion_args()), kind))
+            for tag, suffix in (("", ""), (" + known", "k")) if a.known else (("", ""),):
+                loops.append(("SpacedDiffusion %s%s" % (name, tag), k,
+                              lambda k=k: hig_amd.SpacedDiffusion(hig_amd.space_timesteps(N, k), **diffusion_args()),
+                              kind + suffix))
     results = []
     for storage in ("f32", "bf16"):
         model.precision, model.storage = ("bf16", "bf16") if storage == "bf16" else ("f32", "f32")
 
         def caller(gd, kind):
-            if kind == "p":
-                return lambda: gd.p_sample_loop(model, shape, noise=x0, clip_denoised=False, model_kwargs=kw)
-            return lambda: gd.ddim_sample_loop(model, shape, noise=x0, clip_denoised=False, model_kwargs=kw, eta=0.0)
+            cond = dict(known=known, known_mask=known_mask) if kind.endswith("k") else {}
+            if kind[0] == "p":
+                return lambda: gd.p_sample_loop(model, shape, noise=x0, clip_denoised=False, model_kwargs=kw, **cond)
+            return lambda: gd.ddim_sample_loop(model, shape, noise=x0, clip_denoised=False, model_kwargs=kw, eta=0.0, **cond)
 
         calls = [(name, k, caller(make(), kind)) for name, k, make, kind in loops]
         firsts = [timed_call(call, k) for _, k, call in calls]
@@ -138,7 +149,7 @@ def main():
                 vals = [r[key] for r in rep]
                 row[key] = dict(median=statistics.median(vals), min=min(vals), max=max(vals))
             results.append(row)
-            print("%-5s %-26s K=%-4d first call %8.1f ms (setup %4.1f %%) | call %8.1f ms [%8.1f .. %8.1f]  step %7.1f us "
+            print("%-5s %-34s K=%-4d first call %8.1f ms (setup %4.1f %%) | call %8.1f ms [%8.1f .. %8.1f]  step %7.1f us "
                   "[%7.1f .. %7.1f]  setup %4.1f %% [%4.1f .. %4.1f]" % (
                       storage, name, k, first["call_ms"], 100 * first["setup"], row["call_ms"]["median"], row["call_ms"]["min"],
                       row["call_ms"]["max"], row["step_us"]["median"], row["step_us"]["min"], row["step_us"]["max"],
