@@ -10,7 +10,7 @@ Putting this directory itself on sys.path gives the reference's own import layou
 from . import _lib  # noqa: F401
 from .models import (GaussianDiffusion, MotionConsistencyEvalModel, MotionEncoder,  # noqa: F401
                      MotionInteractionTransformer, MotionTransformer, SpacedDiffusion, space_timesteps)
-from .trainers import DDPMMulTrainer, DDPMTrainer  # noqa: F401
+from .trainers import DDPMMulTrainer, DDPMTrainer, EvalModelTrainer  # noqa: F401
 
 __all__ = ["MotionTransformer", "MotionInteractionTransformer", "MotionEncoder", "MotionConsistencyEvalModel",
-           "GaussianDiffusion", "SpacedDiffusion", "space_timesteps", "DDPMTrainer", "DDPMMulTrainer"]
+           "GaussianDiffusion", "SpacedDiffusion", "space_timesteps", "DDPMTrainer", "DDPMMulTrainer", "EvalModelTrainer"]

@@ -88,6 +88,9 @@ SYMBOLS = (
     "hig_ddim_step", "hig_advance_timesteps",
     # known-region conditioning
     "hig_impose_known",
+    # training the evaluation classifiers
+    "hig_fullattn_bwd_kpad", "hig_softmax_xent", "hig_eval_encoder_train_workspace_bytes", "hig_eval_encoder_bwd_workspace_bytes",
+    "hig_eval_encoder_fwd_train", "hig_eval_encoder_bwd",
 )
 
 
@@ -267,6 +270,13 @@ def lib():
         L.hig_eval_encoder_workspace_bytes.restype = i64
         L.hig_eval_encoder_workspace_bytes.argtypes = [C.POINTER(EvalDims)]
         L.hig_eval_encoder_fwd.argtypes = [C.POINTER(EvalDims)] + [vp] * 8
+        L.hig_fullattn_bwd_kpad.argtypes = L.hig_fullattn_bwd.argtypes[:-1] + [vp, vp]
+        for fn in ("hig_eval_encoder_train_workspace_bytes", "hig_eval_encoder_bwd_workspace_bytes"):
+            getattr(L, fn).restype = i64
+            getattr(L, fn).argtypes = [C.POINTER(EvalDims)]
+        L.hig_eval_encoder_fwd_train.argtypes = [C.POINTER(EvalDims)] + [vp] * 8
+        L.hig_eval_encoder_bwd.argtypes = [C.POINTER(EvalDims)] + [vp] * 10
+        L.hig_softmax_xent.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
         L.hig_layernorm.argtypes = [vp, i64, i64, i32, vp, vp, vp, i64, vp, vp]
         L.hig_gather_rows.argtypes = [vp, i64, i32, i32, vp, i32, vp, i64, vp]
         L.hig_scatter_add_rows.argtypes = [vp, i64, i32, i32, vp, i32, vp, i64, vp]

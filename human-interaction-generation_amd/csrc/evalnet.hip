@@ -1,7 +1,9 @@
 // Evaluator feature extraction: forward of the reference's two scoring classifiers,
 // MotionEncoder (codes/models/interaction_transformer.py:641-741) and MotionConsistencyEvalModel
 // (:743-829), as they are called by EvaluatorModelWrapper.get_motion_embeddings
-// (codes/datasets/evaluator.py:479-493) -- inference only.
+// (codes/datasets/evaluator.py:479-493), and their training step (tools/train_evaluation_model.py,
+// tools/train_consistency_evaluation_model.py): the same forward with every layer's activations kept, its adjoint, and
+// nn.CrossEntropyLoss.
 //
 //   h[b] = [cls_input?] ++ embed(x1[b]) ++ embed(x2[b])            (S = cls + 2T tokens)
 //   embed(x)[0] = joint_embed2(x[0, :4]);  embed(x)[t>=1] = joint_embed1(x[t]) + sequence_embedding[t-1]
@@ -10,7 +12,8 @@
 //   MotionEncoder: o = out2(h[token 0 of a person]) / out1(h[other tokens]);
 //                  feature = sum_valid o / #valid;  logits = fin_proj(feature)
 //   Consistency:   logits = cls_output(h[cls token])
-// Host code + two small row kernels; the GEMMs, LayerNorm and attention are the shared ones.
+// Host code + a few small row kernels; the GEMMs, LayerNorm and attention are the shared ones, and the backward of a layer is
+// the text head's (hig_enc_layer_bwd, hig_host.h).
 #include "hig_common.h"
 #include "hig_host.h"
 
@@ -109,6 +112,281 @@ __global__ __launch_bounds__(256) void masked_mean_kernel(const float* __restric
   feat[(int64_t)b * d + c] = acc / (float)(2 * len);
 }
 
+
+// ---- training ---------------------------------------------------------------------------------------------------------
+// Forward workspace (floats): the inference prefix, then one activation block per layer (as the text head's training layout).
+struct ETrain {
+  int64_t emb, h, kpad, o, feat, layer0, lstride;
+  int64_t qkv, lse, att, r1, st1, x1, z, f, r2, st2, x2;
+  int64_t total;
+};
+ETrain etrain_layout(const EDims& D) {
+  ETrain w;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { int64_t r = o; o += al(n); return r; };
+  w.emb = take((int64_t)2 * D.B * D.T * D.d);
+  w.h = take(D.M * D.d);
+  w.kpad = take((D.M + 3) / 4);
+  w.o = take(D.cls ? 0 : D.M * D.d);
+  w.feat = take((int64_t)D.B * D.d);
+  w.layer0 = o;
+  o = 0;
+  w.qkv = take(D.M * 3 * D.d);
+  w.lse = take((int64_t)D.B * D.H * D.S);
+  w.att = take(D.M * D.d);
+  w.r1 = take(D.M * D.d);
+  w.st1 = take(D.M * 2);
+  w.x1 = take(D.M * D.d);
+  w.z = take(D.M * D.ff);
+  w.f = take(D.M * D.ff);
+  w.r2 = take(D.M * D.d);
+  w.st2 = take(D.M * 2);
+  w.x2 = take(D.M * D.d);
+  w.lstride = o;
+  w.total = w.layer0 + o * D.L;
+  return w;
+}
+
+struct EBwd {
+  int64_t dA, dB, dC, dff, dqkv, delta, wT, slabs, slab_floats, colpart, lnpart;
+  int64_t dft, g, gn, g2, pool1, pool2, u1, u2;   // MotionEncoder head, (B, d) each
+  int64_t xcat, dmove, dinit, postmp;             // embedding
+  int64_t total;
+};
+EBwd ebwd_layout(const EDims& D) {
+  EBwd w;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { int64_t r = o; o += al(n); return r; };
+  const int64_t d = D.d, Bd = (int64_t)D.B * d, R = (int64_t)2 * D.B * D.T;
+  w.dA = take(D.M * d);
+  w.dB = take(D.M * d);
+  w.dC = take(D.M * d);
+  w.dff = take(D.M * D.ff);
+  w.dqkv = take(D.M * 3 * d);
+  w.delta = take((int64_t)D.B * D.H * D.S);
+  int64_t big = 3 * d * d;
+  if ((int64_t)D.ff * d > big) big = (int64_t)D.ff * d;
+  if ((int64_t)d * D.F > big) big = (int64_t)d * D.F;
+  w.wT = take(big);
+  w.slab_floats = big * 16 > (int64_t)1536 * 128 * 128 ? big * 16 : (int64_t)1536 * 128 * 128;
+  w.slabs = take(w.slab_floats);
+  int64_t colp = 0;
+  const int64_t uses[][2] = {{D.M, 3 * d}, {D.M, D.ff}, {D.B, D.C}, {D.B, d}, {R, d}, {2 * D.B, (int64_t)D.T * d}};
+  for (auto& u : uses) {
+    const int64_t v = (int64_t)hig_colsum_chunks(u[0]) * u[1];
+    colp = v > colp ? v : colp;
+  }
+  w.colpart = take(colp);
+  w.lnpart = take(hig_ln_bwd_partial_floats(D.M, D.d, D.S));
+  w.dft = take(Bd); w.g = take(Bd); w.gn = take(Bd); w.g2 = take(Bd);
+  w.pool1 = take(Bd); w.pool2 = take(Bd); w.u1 = take(Bd); w.u2 = take(Bd);
+  w.xcat = take(R * D.F);
+  w.dmove = take(R * d);
+  w.dinit = take((int64_t)2 * D.B * d);
+  w.postmp = take((int64_t)D.T * d);
+  w.total = o;
+  return w;
+}
+
+inline float* EG(void* const* t, int idx) { return static_cast<float*>(t[idx]); }
+
+__device__ __forceinline__ int clamp_len(const int64_t* length, int b, int T) {
+  int64_t len = length[b];
+  if (len > T) len = T;
+  if (len < 0) len = 0;
+  return (int)len;
+}
+
+// The MotionEncoder's masked mean is linear in h: with g[b] = d(feature)[b] / (2 len_b),
+//   d(out1.weight) = g^T pool1, d(out1.bias) = sum_b 2 (len_b - 1) g[b]    pool1[b] = sum of h over the valid tokens t >= 1 of both persons
+//   d(out2.weight) = g^T pool2, d(out2.bias) = sum_b 2 g[b]                pool2[b] = h of the two init-pose tokens
+//   d(h)[b][s] = g[b] . out2.weight on a valid init-pose token, g[b] . out1.weight on any other valid token, 0 on a padded one
+// so the (M, d) gradient of o is never written.
+__global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ h, const int64_t* __restrict__ length,
+                                                   float* __restrict__ pool1, float* __restrict__ pool2, int T, int d) {
+  const int b = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+  if (c >= d) return;
+  const int len = clamp_len(length, b, T);
+  const float* hb = h + (int64_t)b * 2 * T * d + c;
+  float a1 = 0.f, a2 = 0.f;
+  for (int p = 0; p < 2; ++p) {
+    if (len > 0) a2 += hb[(int64_t)p * T * d];
+    for (int t = 1; t < len; ++t) a1 += hb[((int64_t)p * T + t) * d];
+  }
+  pool1[(int64_t)b * d + c] = a1;
+  pool2[(int64_t)b * d + c] = a2;
+}
+__global__ __launch_bounds__(256) void head_scale_kernel(const float* __restrict__ dft, const int64_t* __restrict__ length,
+                                                         float* __restrict__ g, float* __restrict__ gn, float* __restrict__ g2,
+                                                         int T, int d) {
+  const int b = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+  if (c >= d) return;
+  const int len = clamp_len(length, b, T);
+  const int64_t i = (int64_t)b * d + c;
+  const float v = len > 0 ? dft[i] / (float)(2 * len) : 0.f;
+  g[i] = v;
+  gn[i] = (float)(len > 0 ? 2 * (len - 1) : 0) * v;
+  g2[i] = len > 0 ? 2.f * v : 0.f;
+}
+// d(h) rows of the MotionEncoder (cls == 0): grid = M rows
+__global__ __launch_bounds__(128) void unpool_kernel(const float* __restrict__ u1, const float* __restrict__ u2,
+                                                     const int64_t* __restrict__ length, float* __restrict__ dh, int T, int d) {
+  const int S = 2 * T;
+  const int64_t row = blockIdx.x;
+  const int b = (int)(row / S), t = (int)(row % S) % T;
+  const bool valid = t < clamp_len(length, b, T);
+  const float* src = (t == 0 ? u2 : u1) + (int64_t)b * d;
+  float* dst = dh + row * d;
+  for (int c = 4 * threadIdx.x; c < d; c += 4 * 128)
+    *reinterpret_cast<float4*>(dst + c) = valid ? *reinterpret_cast<const float4*>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// Adjoint of assemble_kernel: row (p, b, t) of the per-person blocks takes row (b, cls + p T + t) of d(h); the init-pose rows
+// (t = 0: joint_embed2, no positional term) go to dinit (p, b) and leave zeros behind, so that the joint_embed1 /
+// sequence_embedding adjoints see the motion rows only.  grid = 2 B T rows
+__global__ __launch_bounds__(128) void unassemble_kernel(const float* __restrict__ dh, float* __restrict__ dmove,
+                                                         float* __restrict__ dinit, int B, int T, int d, int cls) {
+  const int S = cls + 2 * T;
+  const int64_t row = blockIdx.x;
+  const int t = (int)(row % T), pb = (int)(row / T), p = pb / B, b = pb % B;
+  const float* src = dh + ((int64_t)b * S + cls + (int64_t)p * T + t) * d;
+  float* dst = dmove + row * d;
+  float* ini = dinit + (int64_t)pb * d;
+  for (int c = 4 * threadIdx.x; c < d; c += 4 * 128) {
+    const float4 v = *reinterpret_cast<const float4*>(src + c);
+    if (t == 0) {
+      *reinterpret_cast<float4*>(ini + c) = v;
+      *reinterpret_cast<float4*>(dst + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      *reinterpret_cast<float4*>(dst + c) = v;
+    }
+  }
+}
+
+// nn.CrossEntropyLoss(): one workgroup of four waves, wave w takes rows w, w + 4, ...; a row's maximum, sum and argmax are
+// wave reductions, the loss is summed per wave in row order and the four partial sums in a fixed order: no atomics.
+__device__ __forceinline__ int wave_min_int(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const int u = __shfl_xor(v, o, 64);
+    v = u < v ? u : v;
+  }
+  return v;
+}
+__global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                           int B, int C, float* __restrict__ loss, float* __restrict__ dlogits,
+                                                           int64_t* __restrict__ pred) {
+  __shared__ float s_part[4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float invB = 1.0f / (float)B;
+  float acc = 0.f;
+  for (int b = wave; b < B; b += 4) {
+    const float* row = logits + (int64_t)b * C;
+    float mx = -INFINITY;
+    int arg = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) {
+      const float v = row[c];
+      if (v > mx) { mx = v; arg = c; }
+    }
+    const float wm = wave_max(mx);
+    arg = wave_min_int(mx == wm ? arg : 0x7fffffff);   // the first index that holds the maximum
+    float se = 0.f;
+    for (int c = lane; c < C; c += 64) se += expf(row[c] - wm);
+    se = wave_sum(se);
+    const int64_t lab = labels[b];
+    const bool ok = lab >= 0 && lab < C;
+    acc += (wm + logf(se)) - (ok ? row[lab] : 0.f);
+    if (dlogits) {
+      float* drow = dlogits + (int64_t)b * C;
+      for (int c = lane; c < C; c += 64) drow[c] = (expf(row[c] - wm) / se - ((ok && c == (int)lab) ? 1.f : 0.f)) * invB;
+    }
+    if (pred && lane == 0) pred[b] = arg < C ? arg : 0;
+  }
+  if (lane == 0) s_part[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) *loss = ((s_part[0] + s_part[1]) + (s_part[2] + s_part[3])) * invB;
+}
+
+// what both training entry points ask of a table (parameters or gradients) before the first launch
+int check_train(const EDims& D, const void* const* params, const char* who) {
+  if (D.prec != HIG_PREC_F32)
+    return hig_set_error(HIG_EUNSUPPORTED, "%s: training the evaluation classifiers runs exact-fp32 products only (prec f32)", who);
+  HIG_REQUIRE(EP(params, HIG_EV_SEQ_EMB) && EP(params, HIG_EV_JOINT1_W) && EP(params, HIG_EV_JOINT1_B) && EP(params, HIG_EV_JOINT2_W) &&
+                  EP(params, HIG_EV_JOINT2_B) && EP(params, HIG_EV_HEAD_W) && EP(params, HIG_EV_HEAD_B),
+              "%s: missing embedding / head slots", who);
+  if (D.cls)
+    HIG_REQUIRE(EP(params, HIG_EV_CLS_IN), "%s: consistency model needs cls_input", who);
+  else
+    HIG_REQUIRE(EP(params, HIG_EV_OUT1_W) && EP(params, HIG_EV_OUT1_B) && EP(params, HIG_EV_OUT2_W) && EP(params, HIG_EV_OUT2_B),
+                "%s: MotionEncoder needs out1 / out2", who);
+  for (int l = 0; l < D.L; ++l)
+    for (int i = 0; i < HIG_TL_NLAYER; ++i) HIG_REQUIRE(EPL(params, l, i), "%s: layer %d lacks slot %d", who, l, i);
+  return HIG_OK;
+}
+
+// The forward both entry points launch; they differ in where a layer's activations live (layer_of(l)) and in whether the GELU
+// pre-activation is kept (z != NULL).  o: (M, d) scratch of the MotionEncoder head; feat: where its pooled feature goes.
+struct EFwdLayer {
+  float *qkv, *lse, *att, *r1, *st1, *x1, *z, *f, *r2, *st2, *x2;
+};
+template <class LayerOf>
+int eval_forward(const EDims& D, const void* const* params, const float* x1, const float* x2, const int64_t* length,
+                 float* logits, float* emb, float* h, uint8_t* kpad, float* o, float* feat, int prec, LayerOf layer_of,
+                 hig_stream_t stream) {
+  hipStream_t st = hig_stream(stream);
+  const int d = D.d, ff = D.ff, T = D.T, S = D.S;
+  const int64_t M = D.M, BT = (int64_t)D.B * T;
+  // per-person embeddings: every row through joint_embed1 (+ sequence_embedding[t-1]), then the init-pose rows
+  // (t = 0) overwritten with joint_embed2 of their first 4 features (:717-720 / :814-817)
+  const float* xs[2] = {x1, x2};
+  for (int p = 0; p < 2; ++p) {
+    float* e = emb + p * BT * d;
+    G ge(xs[p], D.F, 0, EP(params, HIG_EV_JOINT1_W), D.F, 0, e, d, BT, d, D.F);
+    ge.epi(HIG_EPI_BIAS_POS, EP(params, HIG_EV_JOINT1_B)).pos(EP(params, HIG_EV_SEQ_EMB), d, T).prec(prec);
+    ge.g.pos_shift = 1;
+    HIG_TRY(hig_gemm_launch(ge.g, 1, nullptr, st));
+    HIG_TRY(hig_gemm_launch(G(xs[p], (int64_t)T * D.F, 0, EP(params, HIG_EV_JOINT2_W), 4, 0, e, (int64_t)T * d, D.B, d, 4)
+                                .epi(HIG_EPI_BIAS, EP(params, HIG_EV_JOINT2_B)).g, 1, nullptr, st));
+  }
+  hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)M), dim3(128), 0, st, emb, EP(params, HIG_EV_CLS_IN), length, h, kpad, D.B,
+                     T, d, D.cls);
+  HIG_CHECK_LAUNCH();
+
+  const float* xin = h;
+  for (int l = 0; l < D.L; ++l) {
+    const EFwdLayer a = layer_of(l);
+    HIG_TRY(hig_gemm_launch(G(xin, d, 0, EPL(params, l, HIG_TL_IN_W), d, 0, a.qkv, 3 * d, M, 3 * d, d)
+                                .epi(HIG_EPI_BIAS, EPL(params, l, HIG_TL_IN_B)).prec(prec).g, 1, nullptr, st));
+    HIG_TRY(hig_fullattn_fwd_kpad(a.qkv, 3 * d, a.qkv + d, a.qkv + 2 * d, 3 * d, D.B, S, S, D.H, D.hd, nullptr, kpad, a.att, d,
+                                  a.lse, stream));
+    HIG_TRY(hig_gemm_launch(G(a.att, d, 0, EPL(params, l, HIG_TL_OUT_W), d, 0, a.r1, d, M, d, d)
+                                .epi(HIG_EPI_BIAS_RES, EPL(params, l, HIG_TL_OUT_B)).res(xin, d).prec(prec).g, 1, nullptr, st));
+    HIG_TRY(hig_layernorm(a.r1, d, M, d, EPL(params, l, HIG_TL_N1_W), EPL(params, l, HIG_TL_N1_B), a.x1, d, a.st1, stream));
+    G g1(a.x1, d, 0, EPL(params, l, HIG_TL_FF1_W), d, 0, a.f, ff, M, ff, d);
+    g1.epi(HIG_EPI_BIAS_GELU, EPL(params, l, HIG_TL_FF1_B)).prec(prec);
+    if (a.z) g1.aux(a.z, ff);
+    HIG_TRY(hig_gemm_launch(g1.g, 1, nullptr, st));
+    HIG_TRY(hig_gemm_launch(G(a.f, ff, 0, EPL(params, l, HIG_TL_FF2_W), ff, 0, a.r2, d, M, d, ff)
+                                .epi(HIG_EPI_BIAS_RES, EPL(params, l, HIG_TL_FF2_B)).res(a.x1, d).prec(prec).g, 1, nullptr, st));
+    HIG_TRY(hig_layernorm(a.r2, d, M, d, EPL(params, l, HIG_TL_N2_W), EPL(params, l, HIG_TL_N2_B), a.x2, d, a.st2, stream));
+    xin = a.x2;
+  }
+
+  if (D.cls) {  // logits from the [cls] token's row of each pair
+    return hig_gemm_launch(G(xin, (int64_t)S * d, 0, EP(params, HIG_EV_HEAD_W), d, 0, logits, D.C, D.B, D.C, d)
+                               .epi(HIG_EPI_BIAS, EP(params, HIG_EV_HEAD_B)).g, 1, nullptr, st);
+  }
+  HIG_TRY(hig_gemm_launch(G(xin, d, 0, EP(params, HIG_EV_OUT1_W), d, 0, o, d, M, d, d)
+                              .epi(HIG_EPI_BIAS, EP(params, HIG_EV_OUT1_B)).prec(prec).g, 1, nullptr, st));
+  for (int p = 0; p < 2; ++p)
+    HIG_TRY(hig_gemm_launch(G(xin + (int64_t)p * T * d, (int64_t)S * d, 0, EP(params, HIG_EV_OUT2_W), d, 0,
+                              o + (int64_t)p * T * d, (int64_t)S * d, D.B, d, d)
+                                .epi(HIG_EPI_BIAS, EP(params, HIG_EV_OUT2_B)).g, 1, nullptr, st));
+  hipLaunchKernelGGL(masked_mean_kernel, dim3(D.B, (d + 255) / 256), dim3(256), 0, st, o, length, feat, T, D.cls, d);
+  HIG_CHECK_LAUNCH();
+  return hig_gemm_launch(G(feat, d, 0, EP(params, HIG_EV_HEAD_W), d, 0, logits, D.C, D.B, D.C, d)
+                             .epi(HIG_EPI_BIAS, EP(params, HIG_EV_HEAD_B)).g, 1, nullptr, st);
+}
+
 }  // namespace
 
 extern "C" int64_t hig_eval_encoder_workspace_bytes(const hig_eval_dims* dims) {
@@ -132,65 +410,138 @@ extern "C" int hig_eval_encoder_fwd(const hig_eval_dims* dims, const void* const
     HIG_REQUIRE(EP(params, HIG_EV_OUT1_W) && EP(params, HIG_EV_OUT2_W), "hig_eval_encoder_fwd: MotionEncoder needs out1 / out2");
   const EWs w = ews_layout(D);
   float* ws = static_cast<float*>(workspace);
+  // one activation block, the layer output ping-ponging between xa and xb so that a layer never overwrites its own input; the
+  // head's o reuses r1
+  auto layer_of = [&](int l) {
+    return EFwdLayer{ws + w.qkv, ws + w.lse, ws + w.att, ws + w.r1, ws + w.st, ws + w.x1, nullptr, ws + w.f, ws + w.r2, ws + w.st,
+                     ws + ((l & 1) ? w.xb : w.xa)};
+  };
+  return eval_forward(D, params, x1, x2, length, logits, ws + w.emb, ws + w.h, reinterpret_cast<uint8_t*>(ws + w.kpad), ws + w.r1,
+                      feature ? feature : ws + w.feat, D.prec, layer_of, stream);
+}
+
+extern "C" int64_t hig_eval_encoder_train_workspace_bytes(const hig_eval_dims* dims) {
+  EDims D;
+  if (check_edims(dims, D) != HIG_OK) return -1;
+  return etrain_layout(D).total * 4;
+}
+extern "C" int64_t hig_eval_encoder_bwd_workspace_bytes(const hig_eval_dims* dims) {
+  EDims D;
+  if (check_edims(dims, D) != HIG_OK) return -1;
+  return ebwd_layout(D).total * 4;
+}
+
+extern "C" int hig_eval_encoder_fwd_train(const hig_eval_dims* dims, const void* const* params, const float* x1,
+                                          const float* x2, const int64_t* length, float* logits, float* feature,
+                                          void* workspace, hig_stream_t stream) {
+  EDims D;
+  HIG_TRY(check_edims(dims, D));
+  HIG_REQUIRE(params && x1 && x2 && length && logits && workspace, "hig_eval_encoder_fwd_train: null argument");
+  HIG_TRY(check_train(D, params, "hig_eval_encoder_fwd_train"));
+  const ETrain w = etrain_layout(D);
+  float* ws = static_cast<float*>(workspace);
+  auto layer_of = [&](int l) {   // one block per layer, the GELU pre-activation z kept
+    float* lb = ws + w.layer0 + w.lstride * l;
+    return EFwdLayer{lb + w.qkv, lb + w.lse, lb + w.att, lb + w.r1, lb + w.st1, lb + w.x1, lb + w.z, lb + w.f, lb + w.r2, lb + w.st2,
+                     lb + w.x2};
+  };
+  // the pooled feature is kept in the workspace (the backward's fin_proj weight gradient reads it) and copied out
+  HIG_TRY(eval_forward(D, params, x1, x2, length, logits, ws + w.emb, ws + w.h, reinterpret_cast<uint8_t*>(ws + w.kpad), ws + w.o,
+                       ws + w.feat, HIG_PREC_F32, layer_of, stream));
+  if (!D.cls && feature) HIG_TRY(hig_copy_async(feature, ws + w.feat, (int64_t)D.B * D.d * 4, hig_stream(stream)));
+  return HIG_OK;
+}
+
+extern "C" int hig_eval_encoder_bwd(const hig_eval_dims* dims, const void* const* params, const float* x1, const float* x2,
+                                    const int64_t* length, const void* workspace, const float* dlogits,
+                                    const float* dfeature, void* const* grads, void* bwd_workspace, hig_stream_t stream) {
+  EDims D;
+  HIG_TRY(check_edims(dims, D));
+  HIG_REQUIRE(params && x1 && x2 && length && workspace && dlogits && grads && bwd_workspace, "hig_eval_encoder_bwd: null argument");
+  HIG_TRY(check_train(D, params, "hig_eval_encoder_bwd"));
+  HIG_TRY(check_train(D, grads, "hig_eval_encoder_bwd (gradient table)"));
+  HIG_REQUIRE(!(D.cls && dfeature), "hig_eval_encoder_bwd: the consistency model has no feature output");
+  const ETrain w = etrain_layout(D);
+  const EBwd bw = ebwd_layout(D);
+  const float* ws = static_cast<const float*>(workspace);
+  float* b = static_cast<float*>(bwd_workspace);
   hipStream_t st = hig_stream(stream);
-  const int d = D.d, ff = D.ff, T = D.T, S = D.S;
+  const int d = D.d, T = D.T, S = D.S, C = D.C, F = D.F;
   const int64_t M = D.M, BT = (int64_t)D.B * T;
-  uint8_t* kpad = reinterpret_cast<uint8_t*>(ws + w.kpad);
+  const uint8_t* kpad = reinterpret_cast<const uint8_t*>(ws + w.kpad);
+  EncBwd e;
+  e.B = D.B; e.S = S; e.n = d; e.ff = D.ff; e.H = D.H; e.hd = D.hd; e.prec = HIG_PREC_F32; e.M = M;
+  e.slabs = b + bw.slabs; e.slab_floats = bw.slab_floats;
+  e.colp = b + bw.colpart; e.lnp = b + bw.lnpart; e.wT = b + bw.wT; e.tA = nullptr; e.tB = nullptr;   // (tA / tB: bf16 product modes only)
+  e.dff = b + bw.dff; e.dqkv = b + bw.dqkv; e.delta = b + bw.delta;
+  e.stream = stream;
 
-  // per-person embeddings: every row through joint_embed1 (+ sequence_embedding[t-1]), then the init-pose rows
-  // (t = 0) overwritten with joint_embed2 of their first 4 features (:717-720 / :814-817)
-  const float* xs[2] = {x1, x2};
-  for (int p = 0; p < 2; ++p) {
-    float* e = ws + w.emb + p * BT * d;
-    G ge(xs[p], D.F, 0, EP(params, HIG_EV_JOINT1_W), D.F, 0, e, d, BT, d, D.F);
-    ge.epi(HIG_EPI_BIAS_POS, EP(params, HIG_EV_JOINT1_B)).pos(EP(params, HIG_EV_SEQ_EMB), d, T).prec(D.prec);
-    ge.g.pos_shift = 1;
-    HIG_TRY(hig_gemm_launch(ge.g, 1, nullptr, st));
-    HIG_TRY(hig_gemm_launch(G(xs[p], (int64_t)T * D.F, 0, EP(params, HIG_EV_JOINT2_W), 4, 0, e, (int64_t)T * d, D.B, d, 4)
-                                .epi(HIG_EPI_BIAS, EP(params, HIG_EV_JOINT2_B)).g, 1, nullptr, st));
+  float* dA = b + bw.dA;
+  float* dB = b + bw.dB;
+  float* dC = b + bw.dC;
+  const float* xL = ws + w.layer0 + w.lstride * (D.L - 1) + w.x2;
+  // ---- head: d(h of the last layer) into dB ---------------------------------------------------------------------------
+  HIG_TRY(e.colsum(dlogits, C, D.B, C, EG(grads, HIG_EV_HEAD_B)));
+  if (D.cls) {
+    // logits = cls_output(h[b][0])
+    HIG_TRY(hig_gemm_launch(G(dlogits, C, 1, xL, (int64_t)S * d, 1, EG(grads, HIG_EV_HEAD_W), d, C, d, D.B).g, 1, nullptr, st));
+    HIG_TRY(hig_zero_async(dB, M * d * 4, st));
+    HIG_TRY(hig_gemm_launch(G(dlogits, C, 0, EP(params, HIG_EV_HEAD_W), d, 1, dB, (int64_t)S * d, D.B, d, C).g, 1, nullptr, st));
+  } else {
+    HIG_TRY(hig_gemm_launch(G(dlogits, C, 1, ws + w.feat, d, 1, EG(grads, HIG_EV_HEAD_W), d, C, d, D.B).g, 1, nullptr, st));
+    // d(feature) total = upstream + dlogits . fin_proj.weight
+    G gf(dlogits, C, 0, EP(params, HIG_EV_HEAD_W), d, 1, b + bw.dft, d, D.B, d, C);
+    if (dfeature) gf.epi(HIG_EPI_RES).res(dfeature, d);
+    HIG_TRY(hig_gemm_launch(gf.g, 1, nullptr, st));
+    const dim3 gb(D.B, (d + 255) / 256);
+    hipLaunchKernelGGL(head_scale_kernel, gb, dim3(256), 0, st, b + bw.dft, length, b + bw.g, b + bw.gn, b + bw.g2, T, d);
+    HIG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(pool_kernel, gb, dim3(256), 0, st, xL, length, b + bw.pool1, b + bw.pool2, T, d);
+    HIG_CHECK_LAUNCH();
+    HIG_TRY(hig_gemm_launch(G(b + bw.g, d, 1, b + bw.pool1, d, 1, EG(grads, HIG_EV_OUT1_W), d, d, d, D.B).g, 1, nullptr, st));
+    HIG_TRY(hig_gemm_launch(G(b + bw.g, d, 1, b + bw.pool2, d, 1, EG(grads, HIG_EV_OUT2_W), d, d, d, D.B).g, 1, nullptr, st));
+    HIG_TRY(e.colsum(b + bw.gn, d, D.B, d, EG(grads, HIG_EV_OUT1_B)));
+    HIG_TRY(e.colsum(b + bw.g2, d, D.B, d, EG(grads, HIG_EV_OUT2_B)));
+    HIG_TRY(hig_gemm_launch(G(b + bw.g, d, 0, EP(params, HIG_EV_OUT1_W), d, 1, b + bw.u1, d, D.B, d, d).g, 1, nullptr, st));
+    HIG_TRY(hig_gemm_launch(G(b + bw.g, d, 0, EP(params, HIG_EV_OUT2_W), d, 1, b + bw.u2, d, D.B, d, d).g, 1, nullptr, st));
+    hipLaunchKernelGGL(unpool_kernel, dim3((unsigned)M), dim3(128), 0, st, b + bw.u1, b + bw.u2, length, dB, T, d);
+    HIG_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)M), dim3(128), 0, st, ws + w.emb, EP(params, HIG_EV_CLS_IN), length,
-                     ws + w.h, kpad, D.B, T, d, D.cls);
+  // ---- layers ------------------------------------------------------------------------------------------------------------
+  float* dh = dB;
+  for (int l = D.L - 1; l >= 0; --l) {
+    const float* lb = ws + w.layer0 + w.lstride * l;
+    const float* xin = l == 0 ? ws + w.h : ws + w.layer0 + w.lstride * (l - 1) + w.x2;
+    const EncLayerAct a = {lb + w.qkv, lb + w.lse, lb + w.att, lb + w.r1, lb + w.st1, lb + w.x1, lb + w.z, lb + w.f, lb + w.r2, lb + w.st2};
+    HIG_TRY(hig_enc_layer_bwd(e, params + HIG_EV_NGLOBAL + l * HIG_TL_NLAYER, grads + HIG_EV_NGLOBAL + l * HIG_TL_NLAYER, a, xin, kpad, dh, dA,
+                              dC));
+  }
+  // ---- embedding -----------------------------------------------------------------------------------------------------------
+  if (D.cls) HIG_TRY(e.colsum(dh, (int64_t)S * d, D.B, d, EG(grads, HIG_EV_CLS_IN)));   // the [cls] rows, summed over the batch
+  float* dmove = b + bw.dmove;
+  float* dinit = b + bw.dinit;
+  float* xcat = b + bw.xcat;
+  hipLaunchKernelGGL(unassemble_kernel, dim3((unsigned)(2 * BT)), dim3(128), 0, st, dh, dmove, dinit, D.B, T, d, D.cls);
   HIG_CHECK_LAUNCH();
+  HIG_TRY(hig_copy_async(xcat, x1, BT * F * 4, st));
+  HIG_TRY(hig_copy_async(xcat + BT * F, x2, BT * F * 4, st));
+  // joint_embed2: the init-pose rows (t = 0), first 4 features
+  HIG_TRY(e.colsum(dinit, d, 2 * D.B, d, EG(grads, HIG_EV_JOINT2_B)));
+  HIG_TRY(e.wgrad(G(dinit, d, 1, xcat, (int64_t)T * F, 1, EG(grads, HIG_EV_JOINT2_W), 4, d, 4, 2 * D.B)));
+  // joint_embed1: the rows t >= 1 (the forward overwrote its t = 0 rows: they are zero in dmove)
+  HIG_TRY(e.colsum(dmove, d, 2 * BT, d, EG(grads, HIG_EV_JOINT1_B)));
+  HIG_TRY(e.wgrad(G(dmove, d, 1, xcat, F, 1, EG(grads, HIG_EV_JOINT1_W), F, d, F, 2 * BT)));
+  // d(sequence_embedding)[t - 1] = sum over persons and samples of row t: column sums of dmove viewed as (2 B, T d), row 0 dropped
+  // (the table's rows at or beyond T - 1 were never read: the caller zeroes their gradient, include/hig.h)
+  HIG_TRY(e.colsum(dmove, (int64_t)T * d, 2 * D.B, T * d, b + bw.postmp));
+  HIG_TRY(hig_copy_async(EG(grads, HIG_EV_SEQ_EMB), b + bw.postmp + d, (int64_t)(T - 1) * d * 4, st));
+  return HIG_OK;
+}
 
-  const float* xin = ws + w.h;
-  for (int l = 0; l < D.L; ++l) {
-    float* xout = ws + ((l & 1) ? w.xb : w.xa);
-    HIG_TRY(hig_gemm_launch(G(xin, d, 0, EPL(params, l, HIG_TL_IN_W), d, 0, ws + w.qkv, 3 * d, M, 3 * d, d)
-                                .epi(HIG_EPI_BIAS, EPL(params, l, HIG_TL_IN_B)).prec(D.prec).g, 1, nullptr, st));
-    HIG_TRY(hig_fullattn_fwd_kpad(ws + w.qkv, 3 * d, ws + w.qkv + d, ws + w.qkv + 2 * d, 3 * d, D.B, S, S, D.H, D.hd,
-                                  nullptr, kpad, ws + w.att, d, ws + w.lse, stream));
-    HIG_TRY(hig_gemm_launch(G(ws + w.att, d, 0, EPL(params, l, HIG_TL_OUT_W), d, 0, ws + w.r1, d, M, d, d)
-                                .epi(HIG_EPI_BIAS_RES, EPL(params, l, HIG_TL_OUT_B)).res(xin, d).prec(D.prec).g,
-                            1, nullptr, st));
-    HIG_TRY(hig_layernorm(ws + w.r1, d, M, d, EPL(params, l, HIG_TL_N1_W), EPL(params, l, HIG_TL_N1_B), ws + w.x1, d,
-                          ws + w.st, stream));
-    HIG_TRY(hig_gemm_launch(G(ws + w.x1, d, 0, EPL(params, l, HIG_TL_FF1_W), d, 0, ws + w.f, ff, M, ff, d)
-                                .epi(HIG_EPI_BIAS_GELU, EPL(params, l, HIG_TL_FF1_B)).prec(D.prec).g, 1, nullptr, st));
-    HIG_TRY(hig_gemm_launch(G(ws + w.f, ff, 0, EPL(params, l, HIG_TL_FF2_W), ff, 0, ws + w.r2, d, M, d, ff)
-                                .epi(HIG_EPI_BIAS_RES, EPL(params, l, HIG_TL_FF2_B)).res(ws + w.x1, d).prec(D.prec).g,
-                            1, nullptr, st));
-    HIG_TRY(hig_layernorm(ws + w.r2, d, M, d, EPL(params, l, HIG_TL_N2_W), EPL(params, l, HIG_TL_N2_B), xout, d,
-                          ws + w.st, stream));
-    xin = xout;
-  }
-
-  if (D.cls) {  // logits from the [cls] token's row of each pair
-    HIG_TRY(hig_gemm_launch(G(xin, (int64_t)S * d, 0, EP(params, HIG_EV_HEAD_W), d, 0, logits, D.C, D.B, D.C, d)
-                                .epi(HIG_EPI_BIAS, EP(params, HIG_EV_HEAD_B)).g, 1, nullptr, st));
-    return HIG_OK;
-  }
-  float* o = ws + w.r1;
-  HIG_TRY(hig_gemm_launch(G(xin, d, 0, EP(params, HIG_EV_OUT1_W), d, 0, o, d, M, d, d)
-                              .epi(HIG_EPI_BIAS, EP(params, HIG_EV_OUT1_B)).prec(D.prec).g, 1, nullptr, st));
-  for (int p = 0; p < 2; ++p)
-    HIG_TRY(hig_gemm_launch(G(xin + (int64_t)p * T * d, (int64_t)S * d, 0, EP(params, HIG_EV_OUT2_W), d, 0,
-                              o + (int64_t)p * T * d, (int64_t)S * d, D.B, d, d)
-                                .epi(HIG_EPI_BIAS, EP(params, HIG_EV_OUT2_B)).g, 1, nullptr, st));
-  float* feat = feature ? feature : ws + w.feat;
-  hipLaunchKernelGGL(masked_mean_kernel, dim3(D.B, (d + 255) / 256), dim3(256), 0, st, o, length, feat, T, D.cls, d);
+extern "C" int hig_softmax_xent(const float* logits, const int64_t* labels, int32_t B, int32_t C, float* loss, float* dlogits,
+                                int64_t* pred, hig_stream_t stream) {
+  HIG_REQUIRE(logits && labels && loss && B > 0 && C > 0 && C <= 1024, "hig_softmax_xent: bad arguments (0 < C <= 1024)");
+  hipLaunchKernelGGL(softmax_xent_kernel, dim3(1), dim3(256), 0, hig_stream(stream), logits, labels, B, C, loss, dlogits, pred);
   HIG_CHECK_LAUNCH();
-  HIG_TRY(hig_gemm_launch(G(feat, d, 0, EP(params, HIG_EV_HEAD_W), d, 0, logits, D.C, D.B, D.C, d)
-                              .epi(HIG_EPI_BIAS, EP(params, HIG_EV_HEAD_B)).g, 1, nullptr, st));
   return HIG_OK;
 }

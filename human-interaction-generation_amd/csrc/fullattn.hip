@@ -160,6 +160,7 @@ __global__ __launch_bounds__(256) void full_bwd_q_kernel(const float* __restrict
                                                          const float* __restrict__ K,
                                                          const float* __restrict__ V, int64_t ldk, int Tq,
                                                          int Tk, int H, const int64_t* __restrict__ qlen,
+                                                         const uint8_t* __restrict__ kpad,
                                                          const float* __restrict__ lse,
                                                          float* __restrict__ delta, float* __restrict__ dQ,
                                                          int64_t lddq) {
@@ -188,6 +189,7 @@ __global__ __launch_bounds__(256) void full_bwd_q_kernel(const float* __restrict
   if (nvalid && part == 0) delta[(int64_t)blockIdx.x * Tq + n] = dl;
   const float* Kb = K + (int64_t)b * Tk * ldk + h * HD;
   const float* Vb = V + (int64_t)b * Tk * ldk + h * HD;
+  const uint8_t* pad = kpad ? kpad + (int64_t)b * Tk : nullptr;  // 1 = not a key: its probability is exactly 0
   float acc[PER];
 #pragma unroll
   for (int e = 0; e < PER; ++e) acc[e] = 0.f;
@@ -200,7 +202,9 @@ __global__ __launch_bounds__(256) void full_bwd_q_kernel(const float* __restrict
     for (int j = 0; j < 16; ++j) {
       const int ml = 4 * j + part;
       float ds = 0.f;
-      if (kc + ml < Tk && nvalid) {
+      // (the key byte straight from global memory, one per thread and key: staging the chunk's bytes in LDS next to K / V
+      // measured slower without a mask -- +1.2 % instead of +0.8 % at hd 32, +4 % instead of +0.7 % at hd 8, B = 4)
+      if (kc + ml < Tk && nvalid && !(pad && pad[kc + ml])) {
         const float s = dot_row<HD>(q, sK + ml * LDP) / sq + addc;
         const float p = __expf(s - my_lse);
         ds = p * (dot_row<HD>(dy, sV + ml * LDP) - dl) / sq;
@@ -227,6 +231,7 @@ __global__ __launch_bounds__(256) void full_bwd_kv_kernel(const float* __restric
                                                           const float* __restrict__ K,
                                                           const float* __restrict__ V, int64_t ldk, int Tq,
                                                           int Tk, int H, const int64_t* __restrict__ qlen,
+                                                          const uint8_t* __restrict__ kpad,
                                                           const float* __restrict__ lse,
                                                           const float* __restrict__ delta,
                                                           float* __restrict__ dK, float* __restrict__ dV,
@@ -246,6 +251,8 @@ __global__ __launch_bounds__(256) void full_bwd_kv_kernel(const float* __restric
   const int64_t rowk = (int64_t)b * Tk + (mvalid ? m : 0);
   load_row<HD>(K + rowk * ldk + h * HD, k, mvalid);
   load_row<HD>(V + rowk * ldk + h * HD, v, mvalid);
+  // the thread's own key byte, read once: a padded key has p = dS = 0 for every query, so its dK / dV rows are exact zeros
+  const bool kvalid = mvalid && !(kpad && kpad[rowk]);
   const float* Qb = Q + (int64_t)b * Tq * ldq + h * HD;
   const float* Db = dY + (int64_t)b * Tq * lddy + h * HD;
   float dk[PER], dv[PER];
@@ -266,7 +273,7 @@ __global__ __launch_bounds__(256) void full_bwd_kv_kernel(const float* __restric
     for (int j = 0; j < 16; ++j) {
       const int nl = 4 * j + part;
       float p = 0.f, ds = 0.f;
-      if (qc + nl < Tq && mvalid) {
+      if (qc + nl < Tq && kvalid) {
         const float s = dot_row<HD>(k, sQ + nl * LDP) / sq + s_addc[nl];
         p = __expf(s - s_lse[nl]);
         ds = p * (dot_row<HD>(v, sD + nl * LDP) - s_delta[nl]) / sq;
@@ -493,11 +500,13 @@ __global__ __launch_bounds__(64 * NW) void full_bwd_q_mfma_kernel(const float* _
                                                               const float* __restrict__ K, const float* __restrict__ V,
                                                               int64_t ldk, int Tq, int Tk, int H,
                                                               const int64_t* __restrict__ qlen,
+                                                              const uint8_t* __restrict__ kpad,
                                                               const float* __restrict__ lse, float* __restrict__ delta,
                                                               float* __restrict__ dQ, int64_t lddq) {
   constexpr int LDK = HD + 8, LDV = HD + 4, NCB = HD / 32;
   __shared__ __attribute__((aligned(16))) float sK[MC * LDK];
   __shared__ __attribute__((aligned(16))) float sV[MC * LDV];
+  __shared__ __attribute__((aligned(16))) int s_key[MC];   // 1: a key of this sample (inside Tk and not padded)
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, g = lane >> 5;
   const int b = blockIdx.x / H, h = blockIdx.x % H;
   const int q0 = blockIdx.y * (32 * NW) + wave * 32, n = q0 + lr;
@@ -522,6 +531,7 @@ __global__ __launch_bounds__(64 * NW) void full_bwd_q_mfma_kernel(const float* _
   if (nvalid && g == 0) delta[(int64_t)blockIdx.x * Tq + n] = dl;
   const float* Kb = K + (int64_t)b * Tk * ldk + h * HD;
   const float* Vb = V + (int64_t)b * Tk * ldk + h * HD;
+  const uint8_t* pad = kpad ? kpad + (int64_t)b * Tk : nullptr;
   f32x16 dq[NCB];
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb)
@@ -534,6 +544,7 @@ __global__ __launch_bounds__(64 * NW) void full_bwd_q_mfma_kernel(const float* _
     __syncthreads();
     put32<HD, LDK, NW>(ck, sK);
     put32<HD, LDV, NW>(cv, sV);
+    if (tid < MC) s_key[tid] = (kc + tid < Tk && !(pad && pad[kc + tid])) ? 1 : 0;
     __syncthreads();
     if (kc + MC < Tk) {
       fetch32<HD, NW>(Kb, ldk, kc + MC, Tk, ck);
@@ -544,10 +555,15 @@ __global__ __launch_bounds__(64 * NW) void full_bwd_q_mfma_kernel(const float* _
     const f32x16 dp = rows_dot<HD, LDV>(sV, dyf, lr, g);
     f32x16 ds;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int key = kc + 8 * (i / 4) + 4 * g + (i % 4);
-      const float pr = key < Tk ? __expf(st[i] * isq + addc - my_lse) : 0.f;
-      ds[i] = pr * (dp[i] - dl) * isq;
+    for (int q = 0; q < 4; ++q) {
+      const int4 k4 = *reinterpret_cast<const int4*>(s_key + 8 * q + 4 * g);
+      const int kv4[4] = {k4.x, k4.y, k4.z, k4.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int i = 4 * q + e;
+        const float pr = kv4[e] ? __expf(st[i] * isq + addc - my_lse) : 0.f;
+        ds[i] = pr * (dp[i] - dl) * isq;
+      }
     }
     cols_acc<HD, LDK>(sK, ds, dq, lr, g);
   }
@@ -561,6 +577,7 @@ __global__ __launch_bounds__(64 * NW) void full_bwd_kv_mfma_kernel(const float* 
                                                                const float* __restrict__ K, const float* __restrict__ V,
                                                                int64_t ldk, int Tq, int Tk, int H,
                                                                const int64_t* __restrict__ qlen,
+                                                               const uint8_t* __restrict__ kpad,
                                                                const float* __restrict__ lse,
                                                                const float* __restrict__ delta, float* __restrict__ dK,
                                                                float* __restrict__ dV, int64_t lddk) {
@@ -574,9 +591,12 @@ __global__ __launch_bounds__(64 * NW) void full_bwd_kv_mfma_kernel(const float* 
   const bool wactive = m0 < Tk, mvalid = m < Tk;
   const float isq = HD == 64 ? 0.125f : 0.08838834764831845f;   // 1 / sqrt(HD)
   const int64_t rowk = (int64_t)b * Tk + (mvalid ? m : 0);
+  // the lane's own key byte, read once.  A padded key is treated like a key past Tk (zero K / V rows; whatever the products
+  // give stays in this lane's own column of dK / dV) and its rows are stored as exact zeros at the end.
+  const bool kvalid = mvalid && !(kpad && kpad[rowk]);
   float kf[HD / 8][4], vf[HD / 8][4];
-  load_half_row<HD>(K + rowk * ldk + h * HD, kf, mvalid, g);
-  load_half_row<HD>(V + rowk * ldk + h * HD, vf, mvalid, g);
+  load_half_row<HD>(K + rowk * ldk + h * HD, kf, kvalid, g);
+  load_half_row<HD>(V + rowk * ldk + h * HD, vf, kvalid, g);
   const float* Qb = Q + (int64_t)b * Tq * ldq + h * HD;
   const float* Db = dY + (int64_t)b * Tq * lddy + h * HD;
   f32x16 dk[NCB], dv[NCB];
@@ -623,6 +643,12 @@ __global__ __launch_bounds__(64 * NW) void full_bwd_kv_mfma_kernel(const float* 
     cols_acc<HD, LD>(sQ, ds, dk, lr, g);
   }
   if (mvalid) {
+    if (!kvalid) {
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) dk[cb][e] = dv[cb][e] = 0.f;
+    }
     store_cols<HD>(dK + ((int64_t)b * Tk + m) * lddk + h * HD, dk, 1.0f, g);
     store_cols<HD>(dV + ((int64_t)b * Tk + m) * lddk + h * HD, dv, 1.0f, g);
   }
@@ -704,6 +730,17 @@ extern "C" int hig_fullattn_bwd(const float* dY, int64_t lddy, const float* Y, i
                                 int32_t Tq, int32_t Tk, int32_t H, int32_t hd, const int64_t* qlen,
                                 const float* lse, float* delta, float* dQ, int64_t lddq, float* dK,
                                 float* dV, int64_t lddk, hig_stream_t stream) {
+  return hig_fullattn_bwd_kpad(dY, lddy, Y, ldy, Q, ldq, K, V, ldk, B, Tq, Tk, H, hd, qlen, lse, delta, dQ, lddq, dK, dV, lddk,
+                               nullptr, stream);
+}
+
+// The same backward under torch's key-padding mask (kpad (B, Tk), 1 = not a key; NULL = none): a padded key's probability is
+// exactly 0 -- nothing from it in dQ, exact zeros in its dK / dV rows.  The mask changes no launch geometry.
+extern "C" int hig_fullattn_bwd_kpad(const float* dY, int64_t lddy, const float* Y, int64_t ldy, const float* Q,
+                                     int64_t ldq, const float* K, const float* V, int64_t ldk, int32_t B,
+                                     int32_t Tq, int32_t Tk, int32_t H, int32_t hd, const int64_t* qlen,
+                                     const float* lse, float* delta, float* dQ, int64_t lddq, float* dK,
+                                     float* dV, int64_t lddk, const uint8_t* kpad, hig_stream_t stream) {
   hig_attn_plan_t p;
   HIG_TRY(hig_attn_plan_entry(&p, {HIG_ATTN_ENTRY_FULL_BWD, HIG_ATTN_IO_F32, B, Tq, Tk, H, hd, false,
                                    hig_attn_facts(dY && Y && Q && K && V && lse && delta && dQ && dK && dV,
@@ -718,25 +755,25 @@ extern "C" int hig_fullattn_bwd(const float* dY, int64_t lddy, const float* Y, i
       // instances spilled and were never selected -- profiles/r02_attn_sweep.md -- so they are not built)
       constexpr int NWV = 4;
       hipLaunchKernelGGL((full_bwd_q_mfma_kernel<128, NWV>), gq, dim3(64 * NWV), 0, st, dY, lddy, Y, ldy, Q, ldq, K, V, ldk, Tq,
-                         Tk, H, qlen, lse, delta, dQ, lddq);
+                         Tk, H, qlen, kpad, lse, delta, dQ, lddq);
       hipLaunchKernelGGL((full_bwd_kv_mfma_kernel<128, NWV>), gk, dim3(64 * NWV), 0, st, dY, lddy, Q, ldq, K, V, ldk, Tq, Tk, H,
-                         qlen, lse, delta, dK, dV, lddk);
+                         qlen, kpad, lse, delta, dK, dV, lddk);
     } else {
       FNW_SWITCH(waves, {
         hipLaunchKernelGGL((full_bwd_q_mfma_kernel<64, NWV>), gq, dim3(64 * NWV), 0, st, dY, lddy, Y, ldy, Q, ldq, K, V, ldk, Tq,
-                           Tk, H, qlen, lse, delta, dQ, lddq);
+                           Tk, H, qlen, kpad, lse, delta, dQ, lddq);
         hipLaunchKernelGGL((full_bwd_kv_mfma_kernel<64, NWV>), gk, dim3(64 * NWV), 0, st, dY, lddy, Q, ldq, K, V, ldk, Tq, Tk, H,
-                           qlen, lse, delta, dK, dV, lddk);
+                           qlen, kpad, lse, delta, dK, dV, lddk);
       });
     }
     HIG_CHECK_LAUNCH();
     return HIG_OK;
   }
   FHD_SWITCH(hd, hipLaunchKernelGGL((full_bwd_q_kernel<HDV>), dim3(B * H, p.split), dim3(256), 0, st, dY, lddy, Y, ldy, Q, ldq, K, V, ldk, Tq,
-                                    Tk, H, qlen, lse, delta, dQ, lddq));
+                                    Tk, H, qlen, kpad, lse, delta, dQ, lddq));
   HIG_CHECK_LAUNCH();
   FHD_SWITCH(hd, hipLaunchKernelGGL((full_bwd_kv_kernel<HDV>), dim3(B * H, (Tk + CH - 1) / CH), dim3(256), 0, st, dY, lddy, Q, ldq, K, V, ldk,
-                                    Tq, Tk, H, qlen, lse, delta, dK, dV, lddk));
+                                    Tq, Tk, H, qlen, kpad, lse, delta, dK, dV, lddk));
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

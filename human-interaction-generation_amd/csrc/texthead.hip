@@ -189,45 +189,13 @@ extern "C" int hig_text_head_bwd(const hig_text_dims* dims, const void* const* p
   hipStream_t st = hig_stream(stream);
   const int Lt = D.Lt, ff = D.ff, E = D.E;
   const int64_t M = D.M;
-  float* slabs = b + bw.slabs;
-  float* colp = b + bw.colpart;
-  float* lnp = b + bw.lnpart;
-  float* wT = b + bw.wT;
-
-  auto wgrad = [&](G gd) -> int {
-    const int s = wgrad_splits(gd.g.I, gd.g.J, gd.g.R, bw.slab_floats, gd.g.prec);
-    return hig_gemm_launch(gd.g, s, slabs, st);
-  };
-  // dW[n][k] = sum_m dC[m][n] * act[m][k]; bf16 product modes transpose both operands first
-  // dbias = column sums of dC (the bias gradient): from the wgrad GEMM itself in the exact-fp32 path
-  auto wgrad_act = [&](const float* dC, int n_out, const float* act, int k_in, float* out, int64_t rows,
-                       float* dbias) -> int {
-    if (D.prec != HIG_PREC_F32 && rows % 32 == 0) {
-      float* ta = b + bw.tA;
-      float* tb = b + bw.tB;
-      HIG_TRY(hig_colsum(dC, n_out, rows, n_out, dbias, colp, stream));
-      HIG_TRY(hig_transpose(dC, n_out, (int)rows, n_out, ta, rows, nullptr, nullptr, nullptr, stream));
-      HIG_TRY(hig_transpose(act, k_in, (int)rows, k_in, tb, rows, nullptr, nullptr, nullptr, stream));
-      return wgrad(G(ta, rows, 0, tb, rows, 0, out, k_in, n_out, k_in, rows).prec(D.prec));
-    }
-    G gd(dC, n_out, 1, act, k_in, 1, out, k_in, n_out, k_in, rows);
-    if (n_out % 4 == 0) gd.xsum(dbias);
-    else HIG_TRY(hig_colsum(dC, n_out, rows, n_out, dbias, colp, stream));
-    return wgrad(gd);
-  };
-  // dX = dC . W with W (out_f, in_f) transposed first, so both operands are reduce-contiguous
-  auto dgrad = [&](const float* dC, const float* W, int out_f, int in_f, int64_t rows, float* dX, int epi,
-                   const float* res, float* aux) -> int {
-    HIG_TRY(hig_transpose(W, in_f, out_f, in_f, wT, out_f, nullptr, nullptr, nullptr, stream));
-    G gd(dC, out_f, 0, wT, out_f, 0, dX, in_f, rows, in_f, out_f);
-    gd.prec(D.prec);
-    if (epi == HIG_EPI_RES) gd.epi(HIG_EPI_RES).res(res, in_f);
-    if (epi == HIG_EPI_DGELU) gd.epi(HIG_EPI_DGELU).aux(aux, in_f);
-    return hig_gemm_launch(gd.g, 1, nullptr, st);
-  };
-  auto colsum = [&](const float* src, int64_t ld, int64_t rows, int n, float* dst) -> int {
-    return hig_colsum(src, ld, rows, n, dst, colp, stream);
-  };
+  EncBwd e;
+  e.B = D.B; e.S = D.N; e.n = Lt; e.ff = ff; e.H = D.H; e.hd = D.hd; e.prec = D.prec; e.M = M;
+  e.slabs = b + bw.slabs; e.slab_floats = bw.slab_floats;
+  e.colp = b + bw.colpart; e.lnp = b + bw.lnpart; e.wT = b + bw.wT; e.tA = b + bw.tA; e.tB = b + bw.tB;
+  e.dff = b + bw.dff; e.dqkv = b + bw.dqkv; e.delta = b + bw.delta;
+  e.stream = stream;
+  float* lnp = e.lnp;
 
   float* dA = b + bw.dA;
   float* dB = b + bw.dB;
@@ -239,7 +207,7 @@ extern "C" int hig_text_head_bwd(const hig_text_dims* dims, const void* const* p
     HIG_TRY(hig_zero_async(dA, (size_t)M * Lt * 4, st));
   }
   if (dxf_proj) {
-    HIG_TRY(colsum(dxf_proj, E, D.B, E, TG(grads, HIG_T_PROJ_B)));
+    HIG_TRY(e.colsum(dxf_proj, E, D.B, E, TG(grads, HIG_T_PROJ_B)));
     HIG_TRY(hig_gemm_launch(G(dxf_proj, E, 1, ws + w.gath, Lt, 1, TG(grads, HIG_T_PROJ_W), Lt, E, Lt, D.B).g, 1, nullptr, st));
     HIG_TRY(hig_gemm_launch(G(dxf_proj, E, 0, TP(params, HIG_T_PROJ_W), Lt, 1, b + bw.dgath, Lt, D.B, Lt, E).g, 1, nullptr, st));
     HIG_TRY(hig_scatter_add_rows(b + bw.dgath, Lt, D.B, D.N, eot, Lt, dA, Lt, stream));
@@ -257,37 +225,14 @@ extern "C" int hig_text_head_bwd(const hig_text_dims* dims, const void* const* p
   for (int l = D.L - 1; l >= 0; --l) {
     const float* lb = ws + w.layer0 + w.lstride * l;
     const float* xin = l == 0 ? (D.pre ? ws + w.x0 : clip_out) : ws + w.layer0 + w.lstride * (l - 1) + w.x2;
-    // norm2: x2 = LN(r2)
-    HIG_TRY(hig_ln_bwd(d, Lt, lb + w.r2, Lt, lb + w.st2, TPL(params, l, HIG_TL_N2_W), TPL(params, l, HIG_TL_N2_B), nullptr,
-                       0, 0, 0, nullptr, 0, t1, Lt, M, Lt, D.N, TGL(grads, l, HIG_TL_N2_W), TGL(grads, l, HIG_TL_N2_B),
-                       nullptr, 0, lnp, stream));
-    const float* dr2 = t1;
-    // r2 = x1 + linear2(gelu(z)),  z = linear1(x1)
-    HIG_TRY(wgrad_act(dr2, Lt, lb + w.f, ff, TGL(grads, l, HIG_TL_FF2_W), M, TGL(grads, l, HIG_TL_FF2_B)));
-    HIG_TRY(dgrad(dr2, TPL(params, l, HIG_TL_FF2_W), Lt, ff, M, b + bw.dff, HIG_EPI_DGELU, nullptr,
-                  const_cast<float*>(lb + w.z)));
-    const float* dz = b + bw.dff;
-    HIG_TRY(wgrad_act(dz, ff, lb + w.x1, Lt, TGL(grads, l, HIG_TL_FF1_W), M, TGL(grads, l, HIG_TL_FF1_B)));
-    HIG_TRY(dgrad(dz, TPL(params, l, HIG_TL_FF1_W), ff, Lt, M, t2, HIG_EPI_RES, dr2, nullptr));  // t2 = d(x1)
-    // norm1: x1 = LN(r1)
-    HIG_TRY(hig_ln_bwd(t2, Lt, lb + w.r1, Lt, lb + w.st1, TPL(params, l, HIG_TL_N1_W), TPL(params, l, HIG_TL_N1_B), nullptr,
-                       0, 0, 0, nullptr, 0, t1, Lt, M, Lt, D.N, TGL(grads, l, HIG_TL_N1_W), TGL(grads, l, HIG_TL_N1_B),
-                       nullptr, 0, lnp, stream));
-    const float* dr1 = t1;
-    // r1 = xin + out_proj(att)
-    HIG_TRY(wgrad_act(dr1, Lt, lb + w.att, Lt, TGL(grads, l, HIG_TL_OUT_W), M, TGL(grads, l, HIG_TL_OUT_B)));
-    HIG_TRY(dgrad(dr1, TPL(params, l, HIG_TL_OUT_W), Lt, Lt, M, t2, HIG_EPI_NONE, nullptr, nullptr));  // t2 = d(att)
-    float* dqkv = b + bw.dqkv;
-    HIG_TRY(hig_fullattn_bwd(t2, Lt, lb + w.att, Lt, lb + w.qkv, 3 * Lt, lb + w.qkv + Lt, lb + w.qkv + 2 * Lt, 3 * Lt, D.B,
-                             D.N, D.N, D.H, D.hd, nullptr, lb + w.lse, b + bw.delta, dqkv, 3 * Lt, dqkv + Lt,
-                             dqkv + 2 * Lt, 3 * Lt, stream));
-    HIG_TRY(wgrad_act(dqkv, 3 * Lt, xin, Lt, TGL(grads, l, HIG_TL_IN_W), M, TGL(grads, l, HIG_TL_IN_B)));
-    HIG_TRY(dgrad(dqkv, TPL(params, l, HIG_TL_IN_W), 3 * Lt, Lt, M, d, HIG_EPI_RES, dr1, nullptr));   // d = d(xin)
+    const EncLayerAct a = {lb + w.qkv, lb + w.lse, lb + w.att, lb + w.r1, lb + w.st1, lb + w.x1, lb + w.z, lb + w.f, lb + w.r2, lb + w.st2};
+    HIG_TRY(hig_enc_layer_bwd(e, params + HIG_T_NGLOBAL + l * HIG_TL_NLAYER, grads + HIG_T_NGLOBAL + l * HIG_TL_NLAYER, a, xin, nullptr, d, t1,
+                              t2));
   }
   // ---- text_pre_proj -----------------------------------------------------------------------
   if (D.pre) {
-    HIG_TRY(wgrad_act(d, Lt, clip_out, D.W, TG(grads, HIG_T_PRE_W), M, TG(grads, HIG_T_PRE_B)));
-    if (dclip) HIG_TRY(dgrad(d, TP(params, HIG_T_PRE_W), Lt, D.W, M, dclip, HIG_EPI_NONE, nullptr, nullptr));
+    HIG_TRY(e.wgrad_act(d, Lt, clip_out, D.W, TG(grads, HIG_T_PRE_W), M, TG(grads, HIG_T_PRE_B)));
+    if (dclip) HIG_TRY(e.dgrad(d, TP(params, HIG_T_PRE_W), Lt, D.W, M, dclip, HIG_EPI_NONE, nullptr, nullptr));
   } else if (dclip) {
     HIG_TRY(hig_copy_async(dclip, d, (size_t)M * Lt * 4, st));
   }

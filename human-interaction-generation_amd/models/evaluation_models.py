@@ -4,10 +4,18 @@ feature that FID / diversity / multimodality are computed on -- and `MotionConsi
 (:743-829) -- real/fake logits from a learned [cls] token.  Same constructors, attributes,
 state-dict keys (checkpoints `best_eval_model.pth` load with strict=True) and call signatures.
 
-Inference only, which is how the reference's evaluation uses them (EvaluatorModelWrapper,
-codes/datasets/evaluator.py:468-493: `.eval()`, under no_grad); training the classifiers
-(tools/train_evaluation_model.py) is out of scope.  The whole forward is ONE C-ABI call,
+By default inference only, which is how the reference's evaluation uses them (EvaluatorModelWrapper,
+codes/datasets/evaluator.py:468-493: `.eval()`, under no_grad): the whole forward is ONE C-ABI call,
 `hig_eval_encoder_fwd` (include/hig.h, csrc/evalnet.hip); there is no CPU fallback.
+
+Built with `trainable=True` they also train, the way the reference's tools/train_evaluation_model.py and
+tools/train_consistency_evaluation_model.py train them: under enabled gradients `forward` is a
+`torch.autograd.Function` over `hig_eval_encoder_fwd_train` / `hig_eval_encoder_bwd`, so
+`pred, _ = encoder(m1, m2, length=m_lens); lossFn(pred, class_id).backward(); opt.step()` runs unchanged
+(`MotionEncoder`'s feature output is differentiable too; the inputs are not).  `time_embed.*` and
+`init_pos_embedding` take no part in the forward and get no gradient (`.grad` stays None), as in the
+reference.  Training runs exact-fp32 products only (precision "f32"); `trainers.EvalModelTrainer` is the
+loop, with the whole step as four C-ABI calls.
 """
 import ctypes as C
 import os
@@ -18,9 +26,60 @@ from torch import nn
 from .. import _lib
 from .transformer import _WorkspacePool, zero_module
 
-__all__ = ["MotionEncoder", "MotionConsistencyEvalModel"]
+__all__ = ["MotionEncoder", "MotionConsistencyEvalModel", "softmax_xent"]
 
 _PREC = {"f32": _lib.PREC_F32, "bf16x3": _lib.PREC_BF16X3, "bf16": _lib.PREC_BF16}
+
+
+def softmax_xent(logits, labels, want_dlogits=True, loss=None):
+    """nn.CrossEntropyLoss() (mean) of fp32 device logits (B, C) in one launch of `hig_softmax_xent`:
+    -> (loss (device scalar, no host sync), dlogits = (softmax - onehot) / B or None, pred = row argmax (B) int64).
+    A label outside [0, C) is refused here, on the host, when `labels` is a host tensor or a sequence; device labels are
+    the caller's to have checked (checking them here would be a host sync per step)."""
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError("softmax_xent: logits must be fp32 (B, C), got %s %s" % (logits.dtype, tuple(logits.shape)))
+    B, Cn = logits.shape
+    if not (B > 0 and 0 < Cn <= 1024):
+        raise ValueError("softmax_xent: B > 0 and 0 < C <= 1024 (got B=%d C=%d)" % (B, Cn))
+    labels = torch.as_tensor(labels)
+    if labels.numel() != B or labels.dtype.is_floating_point:
+        raise ValueError("softmax_xent: labels must be %d integer class indices" % B)
+    if not labels.is_cuda:
+        if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= Cn):
+            raise ValueError("softmax_xent: label outside [0, %d)" % Cn)
+    if not logits.is_cuda:
+        raise RuntimeError("softmax_xent: ROCm device tensors required (no CPU fallback)")
+    labels = labels.detach().to(logits.device, torch.int64).view(-1).contiguous()
+    logits = logits.detach().contiguous()
+    dev = logits.device
+    loss = torch.empty((), device=dev, dtype=torch.float32) if loss is None else loss
+    dlogits = torch.empty_like(logits) if want_dlogits else None
+    pred = torch.empty(B, device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().hig_softmax_xent(_lib.ptr(logits), _lib.ptr(labels), B, Cn, _lib.ptr(loss),
+                                               _lib.ptr(dlogits), _lib.ptr(pred), _lib.stream_ptr()))
+    return loss, dlogits, pred
+
+
+class _EvalTrainFn(torch.autograd.Function):
+    """Autograd boundary of the `trainable=True` classifiers: forward = hig_eval_encoder_fwd_train, backward =
+    hig_eval_encoder_bwd.  The parameters ride along as inputs so that autograd routes their gradients."""
+
+    @staticmethod
+    def forward(ctx, model, x1, x2, length, class_num, *params):
+        logits, feature, saved = model._launch_train(x1, x2, length, class_num)
+        ctx.model, ctx.saved = model, saved
+        ctx.set_materialize_grads(False)
+        return (logits, feature) if feature is not None else logits
+
+    @staticmethod
+    def backward(ctx, dlogits, dfeature=None):
+        if ctx.saved is None:
+            raise RuntimeError("%s: backward through this forward a second time -- its activations went back to the "
+                               "workspace pool after the first (retain_graph is not supported)" % type(ctx.model).__name__)
+        saved, ctx.saved = ctx.saved, None
+        grads = ctx.model._launch_bwd(saved, dlogits, dfeature)
+        return (None,) * 5 + tuple(grads)
 
 
 class _EvalEncoderBase(nn.Module):
@@ -48,6 +107,7 @@ class _EvalEncoderBase(nn.Module):
         self.sequence_embedding = nn.Parameter(torch.randn(num_frames, latent_dim))
         self.init_pos_embedding = nn.Parameter(torch.randn(1, latent_dim))
         self.precision = kargs.get("precision", os.environ.get("HIG_PREC", "f32"))
+        self.trainable = bool(kargs.get("trainable", False))
         self._pool = _WorkspacePool()
 
     def _build_trunk(self):
@@ -65,13 +125,26 @@ class _EvalEncoderBase(nn.Module):
     def _globals(self):
         raise NotImplementedError
 
-    def _table(self):
+    def _slots(self):
         ps = list(self._globals())
         for layer in self.motionTransEncoder.layers:
             a = layer.self_attn
             ps += [a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
                    layer.norm1.weight, layer.norm1.bias, layer.linear1.weight, layer.linear1.bias,
                    layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias]
+        return ps
+
+    def trained_parameters(self):
+        """The parameters the forward uses, in table order: what training gives a gradient (everything but
+        `time_embed.*` and `init_pos_embedding`)."""
+        return [p for p in self._slots() if p is not None]
+
+    def _table(self, tensors=None):
+        """The C table of the parameters, or of `tensors`: one tensor per trained parameter, in table order (gradients)."""
+        ps = self._slots()
+        if tensors is not None:
+            it = iter(tensors)
+            ps = [None if p is None else next(it) for p in ps]
         arr = (C.c_void_p * len(ps))()
         for i, p in enumerate(ps):
             if p is None:
@@ -88,22 +161,21 @@ class _EvalEncoderBase(nn.Module):
         return (torch.arange(T)[None, :] < length[:, None]).float()
 
     def _launch(self, x1, x2, length, class_num, want_feature):
+        if self.trainable and torch.is_grad_enabled():
+            if x1.requires_grad or x2.requires_grad:
+                raise ValueError("%s: there is no gradient for x1 / x2 -- detach the inputs" % type(self).__name__)
+            self._check_shapes(x1, x2, length, ValueError)
+            if not (x1.is_cuda and x2.is_cuda):
+                raise RuntimeError("%s.forward: ROCm device tensors required (no CPU fallback)" % type(self).__name__)
+            out = _EvalTrainFn.apply(self, x1, x2, length, class_num, *self.trained_parameters())
+            return out if want_feature else (out, None)
         if not (x1.is_cuda and x2.is_cuda):
             raise RuntimeError("%s.forward: ROCm device tensors required (no CPU fallback)" % type(self).__name__)
         if torch.is_grad_enabled() and self.training:
             raise NotImplementedError("%s: inference only -- call .eval() / torch.no_grad() like the reference's "
                                       "EvaluatorModelWrapper does" % type(self).__name__)
-        B, T, F_ = x1.shape
-        assert x2.shape == x1.shape and F_ == self.input_feats and 2 <= T <= self.num_frames + 1
-        if length is None:
-            raise ValueError("length is required (the reference indexes it unconditionally)")
-        dev = x1.device
-        x1 = x1.detach().float().contiguous()
-        x2 = x2.detach().float().contiguous()
-        length = torch.as_tensor(length).detach().to(dev, torch.int64).view(-1).contiguous()
-        assert length.numel() == B
-        dims = _lib.EvalDims(B=B, T=T, F=F_, d=self.latent_dim, H=self.num_heads, ff=self.ff_size,
-                             L=self.num_layers, C=class_num, cls=self._cls_token, prec=_PREC[self.precision])
+        x1, x2, length, dims = self._prepare(x1, x2, length, class_num)
+        B, dev = x1.shape[0], x1.device
         L = _lib.lib()
         nbytes = L.hig_eval_encoder_workspace_bytes(C.byref(dims))
         if nbytes < 0:
@@ -117,6 +189,85 @@ class _EvalEncoderBase(nn.Module):
                                               _lib.ptr(logits), _lib.ptr(feature), _lib.ptr(ws), _lib.stream_ptr()))
         self._pool.give("eval_ws", ws, dev)   # stream-ordered reuse: the next call launches behind this one
         return logits, feature
+
+    def _check_shapes(self, x1, x2, length, shape_error):
+        if x1.dim() != 3 or x2.shape != x1.shape or x1.shape[2] != self.input_feats or not 2 <= x1.shape[1] <= self.num_frames + 1:
+            raise shape_error("%s: x1, x2 must both be (B, T, %d) with 2 <= T <= %d, got %s and %s"
+                              % (type(self).__name__, self.input_feats, self.num_frames + 1, tuple(x1.shape), tuple(x2.shape)))
+        if length is None:
+            raise ValueError("length is required (the reference indexes it unconditionally)")
+        if torch.as_tensor(length).numel() != x1.shape[0]:
+            raise shape_error("%s: length must hold one entry per pair (%d)" % (type(self).__name__, x1.shape[0]))
+
+    def _prepare(self, x1, x2, length, class_num, shape_error=AssertionError):
+        self._check_shapes(x1, x2, length, shape_error)
+        B, T, F_ = x1.shape
+        dev = x1.device
+        x1 = x1.detach().float().contiguous()
+        x2 = x2.detach().float().contiguous()
+        length = torch.as_tensor(length).detach().to(dev, torch.int64).view(-1).contiguous()
+        dims = _lib.EvalDims(B=B, T=T, F=F_, d=self.latent_dim, H=self.num_heads, ff=self.ff_size,
+                             L=self.num_layers, C=class_num, cls=self._cls_token, prec=_PREC[self.precision])
+        return x1, x2, length, dims
+
+    def _launch_train(self, x1, x2, length, class_num):
+        """hig_eval_encoder_fwd_train -> (logits, feature or None, what the backward needs).  The activation workspace is
+        held until `_launch_bwd` (or `_release`) returns it to the pool."""
+        if not (x1.is_cuda and x2.is_cuda):
+            raise RuntimeError("%s.forward: ROCm device tensors required (no CPU fallback)" % type(self).__name__)
+        if self.precision != "f32":
+            raise NotImplementedError("%s: training runs exact-fp32 products only (precision='f32'), not %r"
+                                      % (type(self).__name__, self.precision))
+        x1, x2, length, dims = self._prepare(x1, x2, length, class_num, shape_error=ValueError)
+        B, dev = x1.shape[0], x1.device
+        L = _lib.lib()
+        nbytes = L.hig_eval_encoder_train_workspace_bytes(C.byref(dims))
+        if nbytes < 0:
+            raise RuntimeError("libhig: " + _lib.last_error())
+        ws = self._pool.take("eval_train_ws", nbytes, dev)
+        logits = torch.empty(B, class_num, device=dev, dtype=torch.float32)
+        feature = None if self._cls_token else torch.empty(B, self.latent_dim, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(L.hig_eval_encoder_fwd_train(C.byref(dims), self._table(), _lib.ptr(x1), _lib.ptr(x2), _lib.ptr(length),
+                                                    _lib.ptr(logits), _lib.ptr(feature), _lib.ptr(ws), _lib.stream_ptr()))
+        return logits, feature, (dims, x1, x2, length, ws, [p._version for p in self.trained_parameters()])
+
+    def _release(self, saved):
+        self._pool.give("eval_train_ws", saved[4], saved[4].device)
+
+    def _launch_bwd(self, saved, dlogits, dfeature, grads=None):
+        """hig_eval_encoder_bwd.  grads: one fp32 device tensor per trained parameter (table order) to write into; None
+        allocates them.  The kernel sequence writes rows [0, T - 1) of sequence_embedding's gradient, the rows the forward read;
+        the rows behind them are zeroed here on every call (T may change from one batch to the next).  Returns the list.  The
+        activation workspace goes back to the pool whether or not the call succeeds."""
+        try:
+            return self._bwd(saved, dlogits, dfeature, grads)
+        finally:
+            self._release(saved)
+
+    def _bwd(self, saved, dlogits, dfeature, grads):
+        dims, x1, x2, length, ws, versions = saved
+        dev = x1.device
+        ps = self.trained_parameters()
+        if versions != [p._version for p in ps]:
+            raise RuntimeError("%s: a parameter was modified in place between forward and backward; the kept activations "
+                               "no longer belong to it" % type(self).__name__)
+        if grads is None:
+            grads = [torch.empty_like(p) for p in ps]
+        grads[0][dims.T - 1:].zero_()          # sequence_embedding is the table's first slot (HIG_EV_SEQ_EMB)
+        if dlogits is None:
+            dlogits = torch.zeros(dims.B, dims.C, device=dev, dtype=torch.float32)
+        dlogits = dlogits.detach().float().contiguous()
+        if dfeature is not None:
+            dfeature = dfeature.detach().float().contiguous()
+        L = _lib.lib()
+        bws = self._pool.take("eval_bwd_ws", L.hig_eval_encoder_bwd_workspace_bytes(C.byref(dims)), dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.hig_eval_encoder_bwd(C.byref(dims), self._table(), _lib.ptr(x1), _lib.ptr(x2), _lib.ptr(length),
+                                              _lib.ptr(ws), _lib.ptr(dlogits), _lib.ptr(dfeature), self._table(grads),
+                                              _lib.ptr(bws), _lib.stream_ptr()))
+        self._pool.give("eval_bwd_ws", bws, dev)
+        return grads
 
 
 class MotionEncoder(_EvalEncoderBase):

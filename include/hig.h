@@ -427,8 +427,8 @@ int hig_text_head_bwd(const hig_text_dims* dims, const void* const* params, cons
  * Evaluator feature extraction: the two classifiers that score generated pairs,
  * `MotionEncoder` (interaction_transformer.py:641-741: class logits + the pooled feature FID /
  * diversity are computed on) and `MotionConsistencyEvalModel` (:743-829: real/fake logits from a
- * learned [cls] token).  Inference only (the reference calls them under no_grad,
- * datasets/evaluator.py:479-493).  Both embed each person like the two-person denoiser (token 0 =
+ * learned [cls] token).  hig_eval_encoder_fwd is the inference forward (the reference's evaluation calls them under no_grad,
+ * datasets/evaluator.py:479-493); the training pair follows it.  Both embed each person like the two-person denoiser (token 0 =
  * joint_embed2 of the init-pose row's first 4 features, token t >= 1 = joint_embed1 +
  * sequence_embedding[t-1]), put the two persons one after the other on the token axis
  * ([cls,] person 1's T tokens, person 2's T tokens), run a post-norm nn.TransformerEncoder with
@@ -462,6 +462,31 @@ int64_t hig_eval_encoder_workspace_bytes(const hig_eval_dims* dims);
 int hig_eval_encoder_fwd(const hig_eval_dims* dims, const void* const* params, const float* x1,
                          const float* x2, const int64_t* length, float* logits, float* feature,
                          void* workspace, hig_stream_t stream);
+/* Training the two classifiers (the reference's tools/train_evaluation_model.py and
+ * tools/train_consistency_evaluation_model.py).  hig_eval_encoder_fwd_train is hig_eval_encoder_fwd with every layer's
+ * activations (and the GELU pre-activation) kept in `workspace` (hig_eval_encoder_train_workspace_bytes) for
+ * hig_eval_encoder_bwd, which takes d(logits) (B, C) and, for the MotionEncoder, an optional upstream d(feature) (B, d), and
+ * WRITES (never accumulates) every parameter gradient through `grads`, a table laid out like `params`; a NULL slot there
+ * must be a slot the model does not have.  Of sequence_embedding's gradient the call writes rows [0, T - 1), the ones the
+ * forward read; the table's length is not among the dims, so the rows behind them are the caller's to zero before every call
+ * whose T is smaller than that of the call before (a call with a larger T has written them; the Python wrapper zeroes them on
+ * every call).  There is no gradient for x1 / x2.  Padded tokens are never keys and reach no output: their rows carry an exact-zero gradient through every
+ * layer.  Exact-fp32 products only (prec == HIG_PREC_F32).  No allocation, no synchronisation, everything on `stream`. */
+int64_t hig_eval_encoder_train_workspace_bytes(const hig_eval_dims* dims);
+int64_t hig_eval_encoder_bwd_workspace_bytes(const hig_eval_dims* dims);
+int hig_eval_encoder_fwd_train(const hig_eval_dims* dims, const void* const* params, const float* x1,
+                               const float* x2, const int64_t* length, float* logits, float* feature,
+                               void* workspace, hig_stream_t stream);
+int hig_eval_encoder_bwd(const hig_eval_dims* dims, const void* const* params, const float* x1, const float* x2,
+                         const int64_t* length, const void* workspace, const float* dlogits,
+                         const float* dfeature /* nullable */, void* const* grads, void* bwd_workspace,
+                         hig_stream_t stream);
+/* nn.CrossEntropyLoss() (mean reduction) over logits (B, C), C <= 1024, in one launch, deterministic (no float atomics):
+ *   loss = mean_b (lse_b - logits[b][label_b]);  dlogits = (softmax - onehot) / B (nullable);  pred[b] = first argmax of row b
+ * (nullable).  A label outside [0, C) is the caller's error (the Python wrapper refuses it); the kernel then reads nothing out
+ * of bounds: that row adds lse_b alone to the loss and has no one-hot term. */
+int hig_softmax_xent(const float* logits, const int64_t* labels, int32_t B, int32_t C, float* loss /* device scalar */,
+                     float* dlogits, int64_t* pred, hig_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Input pipeline: batch assembly from a device-resident bank of motions.
@@ -922,6 +947,15 @@ int hig_fullattn_bwd(const float* dY, int64_t lddy, const float* Y, int64_t ldy,
                      int32_t Tk, int32_t H, int32_t hd, const int64_t* qlen, const float* lse,
                      float* delta, float* dQ, int64_t lddq, float* dK, float* dV, int64_t lddk,
                      hig_stream_t stream);
+/* hig_fullattn_bwd under the key-padding mask of hig_fullattn_fwd_kpad (kpad (B, Tk) bytes, non-zero = not a key; NULL =
+ * none, and then this IS hig_fullattn_bwd, bit for bit).  A padded key's probability is exactly 0: it adds nothing to dQ, and
+ * its dK / dV rows are written as exact zeros.  Same plan, same launch geometry, same path counters.  A sample whose keys are
+ * ALL padded is outside the contract, as in the forward. */
+int hig_fullattn_bwd_kpad(const float* dY, int64_t lddy, const float* Y, int64_t ldy, const float* Q,
+                          int64_t ldq, const float* K, const float* V, int64_t ldk, int32_t B, int32_t Tq,
+                          int32_t Tk, int32_t H, int32_t hd, const int64_t* qlen, const float* lse,
+                          float* delta, float* dQ, int64_t lddq, float* dK, float* dV, int64_t lddk,
+                          const uint8_t* kpad, hig_stream_t stream);
 
 /* Backward of y = [silu](LN(x)*(1+scale)+shift) w.r.t. x for upstream gradient da, plus the
  * reductions for gamma/beta (over all rows) and scale/shift (per sample):
