@@ -8,9 +8,10 @@ Putting this directory itself on sys.path gives the reference's own import layou
 (`from models.transformer import MotionTransformer`, `from trainers.ddpm_trainer import DDPMTrainer`).
 """
 from . import _lib  # noqa: F401
-from .models import (GaussianDiffusion, MotionConsistencyEvalModel, MotionEncoder,  # noqa: F401
+from .models import (ClassifierFreeGuidedModel, GaussianDiffusion, MotionConsistencyEvalModel, MotionEncoder,  # noqa: F401
                      MotionInteractionTransformer, MotionTransformer, SpacedDiffusion, space_timesteps)
 from .trainers import DDPMMulTrainer, DDPMTrainer, EvalModelTrainer  # noqa: F401
 
 __all__ = ["MotionTransformer", "MotionInteractionTransformer", "MotionEncoder", "MotionConsistencyEvalModel",
-           "GaussianDiffusion", "SpacedDiffusion", "space_timesteps", "DDPMTrainer", "DDPMMulTrainer", "EvalModelTrainer"]
+           "GaussianDiffusion", "SpacedDiffusion", "space_timesteps", "DDPMTrainer", "DDPMMulTrainer", "EvalModelTrainer",
+           "ClassifierFreeGuidedModel"]

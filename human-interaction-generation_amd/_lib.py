@@ -88,6 +88,8 @@ SYMBOLS = (
     "hig_ddim_step", "hig_advance_timesteps",
     # known-region conditioning
     "hig_impose_known",
+    # classifier-free guidance
+    "hig_cfg_combine", "hig_p_sample_step_cfg", "hig_ddim_step_cfg", "hig_impose_known_cfg",
     # training the evaluation classifiers
     "hig_fullattn_bwd_kpad", "hig_softmax_xent", "hig_eval_encoder_train_workspace_bytes", "hig_eval_encoder_bwd_workspace_bytes",
     "hig_eval_encoder_fwd_train", "hig_eval_encoder_bwd",
@@ -208,6 +210,10 @@ def lib():
         L.hig_ddim_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, f32, i32, vp, vp, vp]
         L.hig_advance_timesteps.argtypes = [vp, vp, i32, i32, vp, vp]
         L.hig_impose_known.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i64, vp]
+        L.hig_cfg_combine.argtypes = [vp, f32, i32, i32, i64, vp, vp]
+        L.hig_p_sample_step_cfg.argtypes = [vp, vp, f32, vp, vp, vp, i32, i32, i32, i64, vp, vp]
+        L.hig_ddim_step_cfg.argtypes = [vp, vp, f32, vp, vp, vp, i32, i32, i32, i64, f32, i32, vp, vp]
+        L.hig_impose_known_cfg.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, vp]
         L.hig_masked_mse.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
         L.hig_pair_mse.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
         L.hig_sumsq_partial.argtypes = [vp, i64, f32, vp, vp]

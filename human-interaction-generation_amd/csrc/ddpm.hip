@@ -20,22 +20,119 @@ __global__ void q_sample_kernel(const float* __restrict__ x0, const float* __res
   }
 }
 
-__global__ void p_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+// ---- classifier-free guidance: the stacked layout of include/hig.h ----
+// B samples in blocks of `group`: block g holds its conditional rows, then its unconditional rows, so element i of the B-row
+// view (sample b = i / per_sample, g = b / group) has its conditional copy at i + g gp and its unconditional copy gp further,
+// gp = group * per_sample.  The row of t that goes with it is (conditional offset) / per_sample.  Every kernel below is ONE
+// template over `CFG`: the unguided instance indexes with the identity and never sees scale / gp, the guided one reads eps
+// through cfg_eps and stores the new state to both copies; what follows the combine is the same code for both.
+template <bool CFG> __device__ __forceinline__ int64_t cfg_cond(int64_t i, int64_t gp) {
+  if constexpr (CFG) return i + (i / gp) * gp;
+  return i;
+}
+
+// eps_g = eps_u + s (eps_c - eps_u): a difference, a product, a sum, nothing fused.
+__device__ __forceinline__ float cfg_eps(float ec, float eu, float s) {
+#pragma clang fp contract(off)
+  const float d = ec - eu;
+  const float sd = s * d;
+  return eu + sd;
+}
+
+template <bool CFG> __device__ __forceinline__ float eps_at(const float* __restrict__ eps, int64_t oc, int64_t gp, float s) {
+  if constexpr (CFG) return cfg_eps(eps[oc], eps[oc + gp], s);
+  return eps[oc];
+}
+
+template <bool CFG> __device__ __forceinline__ float4 eps4_at(const float* __restrict__ eps, int64_t oc, int64_t gp, float s) {
+  const float4 c = *reinterpret_cast<const float4*>(eps + oc);
+  if constexpr (CFG) {
+    const float4 u = *reinterpret_cast<const float4*>(eps + oc + gp);
+    return make_float4(cfg_eps(c.x, u.x, s), cfg_eps(c.y, u.y, s), cfg_eps(c.z, u.z, s), cfg_eps(c.w, u.w, s));
+  }
+  return c;
+}
+
+__global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restrict__ eps2, float scale, int64_t gp, int64_t total,
+                                                          int64_t n4, float* __restrict__ out) {
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = tid; i < n4; i += stride)
+    reinterpret_cast<float4*>(out)[i] = eps4_at<true>(eps2, cfg_cond<true>(4 * i, gp), gp, scale);
+  for (int64_t i = 4 * n4 + tid; i < total; i += stride) out[i] = eps_at<true>(eps2, cfg_cond<true>(i, gp), gp, scale);
+}
+
+// The ancestral update.  Same operation order as the reference: x0 = a*x - b*eps; mean = c1*x0 + c2*x; x_prev = mean +
+// [t != 0] sd z, with the three fusions the compiler has always made here written out (x0 = fma(a, x, -(b eps)), mean =
+// fma(c1, x0, c2 x), x_prev = fma([t != 0] sd, z, mean)) so that the float4 and the scalar path of the guided instance cannot
+// be contracted differently.
+struct p_coef { float a, b, c1, c2, nzsd; };
+
+__device__ __forceinline__ p_coef p_coef_at(const float* __restrict__ tab, int nsteps, int tt) {
+  p_coef c;
+  c.a = tab[T_SQRT_RECIP_AC * nsteps + tt];
+  c.b = tab[T_SQRT_RECIPM1_AC * nsteps + tt];
+  c.c1 = tab[T_COEF1 * nsteps + tt];
+  c.c2 = tab[T_COEF2 * nsteps + tt];
+  const float nz = tt != 0 ? 1.0f : 0.0f;
+  const float sd = expf(0.5f * tab[T_LOGVAR * nsteps + tt]);
+  c.nzsd = nz * sd;
+  return c;
+}
+
+__device__ __forceinline__ float p_elem(const p_coef& c, float xi, float e, float z, float* x0_out) {
+#pragma clang fp contract(off)
+  const float be = c.b * e;
+  const float x0 = __builtin_fmaf(c.a, xi, -be);
+  const float cx = c.c2 * xi;
+  const float mean = __builtin_fmaf(c.c1, x0, cx);
+  *x0_out = x0;
+  return __builtin_fmaf(c.nzsd, z, mean);
+}
+
+// Unguided: x, eps, z, x_prev, pred_xstart are B rows and the loop is the scalar stream it has always been.  Guided: x ==
+// x_prev is the stacked state (read at the conditional copy, stored to both), eps the stacked model output, t the stacked
+// step vector; z and pred_xstart stay B rows.  n4 float4 groups first (the host passes 0 unless every pointer is 16-byte
+// aligned and gp % 4 == 0, which keeps a group inside one block of the layout), then the scalar rest.
+template <bool CFG>
+__global__ void p_step_kernel(const float* x, const float* __restrict__ eps,
                               const float* __restrict__ z, const int64_t* __restrict__ t,
                               const float* __restrict__ tab, int nsteps, int64_t per_sample,
-                              int64_t total, float* __restrict__ x_prev,
+                              int64_t total, int64_t n4, float scale, int64_t gp, float* x_prev,
                               float* __restrict__ pred_xstart) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int tt = (int)t[i / per_sample];
-    const float xi = x[i];
-    // same operation order as the reference: x0 = a*x - b*eps; mean = c1*x0 + c2*x
-    const float x0 = tab[T_SQRT_RECIP_AC * nsteps + tt] * xi - tab[T_SQRT_RECIPM1_AC * nsteps + tt] * eps[i];
-    const float mean = tab[T_COEF1 * nsteps + tt] * x0 + tab[T_COEF2 * nsteps + tt] * xi;
-    const float nz = tt != 0 ? 1.0f : 0.0f;
-    const float sd = expf(0.5f * tab[T_LOGVAR * nsteps + tt]);
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t first = tid;
+  if constexpr (CFG) {
+    for (int64_t i = tid; i < n4; i += stride) {
+      const int64_t oc = cfg_cond<true>(4 * i, gp);
+      const float4 xv = *reinterpret_cast<const float4*>(x + oc), ev = eps4_at<true>(eps, oc, gp, scale);
+      const float4 zv = reinterpret_cast<const float4*>(z)[i];
+      const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w}, zs[4] = {zv.x, zv.y, zv.z, zv.w};
+      float o[4], p[4];
+      const int64_t s0 = oc / per_sample, s3 = (oc + 3) / per_sample;
+      if (s0 == s3) {
+        const p_coef c = p_coef_at(tab, nsteps, (int)t[s0]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = p_elem(c, xs[k], es[k], zs[k], &p[k]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          o[k] = p_elem(p_coef_at(tab, nsteps, (int)t[(oc + k) / per_sample]), xs[k], es[k], zs[k], &p[k]);
+      }
+      if (pred_xstart) reinterpret_cast<float4*>(pred_xstart)[i] = make_float4(p[0], p[1], p[2], p[3]);
+      const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+      *reinterpret_cast<float4*>(x_prev + oc) = ov;
+      *reinterpret_cast<float4*>(x_prev + oc + gp) = ov;
+    }
+    first = 4 * n4 + tid;
+  }
+  for (int64_t i = first; i < total; i += stride) {
+    const int64_t oc = cfg_cond<CFG>(i, gp);
+    const int tt = (int)t[oc / per_sample];
+    float x0;
+    const float o = p_elem(p_coef_at(tab, nsteps, tt), x[oc], eps_at<CFG>(eps, oc, gp, scale), z[i], &x0);
     if (pred_xstart) pred_xstart[i] = x0;
-    x_prev[i] = mean + nz * sd * z[i];
+    x_prev[oc] = o;
+    if constexpr (CFG) x_prev[oc + gp] = o;
   }
 }
 
@@ -79,19 +176,22 @@ __device__ __forceinline__ float ddim_elem(const ddim_coef& c, float x, float e,
 
 // x_prev may alias x (every element is read before its own store), so neither is __restrict__.  n4 float4 groups, then the
 // scalar rest [4 n4, total); the host passes n4 = 0 when a pointer is not 16-byte aligned.  A float4 that straddles a sample
-// boundary looks its coefficients up per element.
+// boundary looks its coefficients up per element.  Guided (see cfg_cond): x == x_prev is the stacked state, read at the
+// conditional copy and stored to both; eps and t are stacked; z and pred_xstart are B rows.
+template <bool CFG>
 __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const float* __restrict__ eps,
                                                         const float* __restrict__ z, const int64_t* __restrict__ t,
                                                         const float* __restrict__ tab, int nsteps, int64_t per_sample,
-                                                        int64_t total, int64_t n4, float eta, int clip, float* x_prev,
-                                                        float* __restrict__ pred_xstart) {
+                                                        int64_t total, int64_t n4, float eta, int clip, float scale, int64_t gp,
+                                                        float* x_prev, float* __restrict__ pred_xstart) {
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = tid; i < n4; i += stride) {
-    const float4 xv = reinterpret_cast<const float4*>(x)[i], ev = reinterpret_cast<const float4*>(eps)[i];
+    const int64_t oc = cfg_cond<CFG>(4 * i, gp);
+    const float4 xv = *reinterpret_cast<const float4*>(x + oc), ev = eps4_at<CFG>(eps, oc, gp, scale);
     const float4 zv = z ? reinterpret_cast<const float4*>(z)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w}, zs[4] = {zv.x, zv.y, zv.z, zv.w};
     float o[4], p[4];
-    const int64_t s0 = (4 * i) / per_sample, s3 = (4 * i + 3) / per_sample;
+    const int64_t s0 = oc / per_sample, s3 = (oc + 3) / per_sample;
     if (s0 == s3) {
       const ddim_coef c = ddim_coef_at(tab, nsteps, t[s0], eta);
 #pragma unroll
@@ -99,16 +199,21 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const fl
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        o[k] = ddim_elem(ddim_coef_at(tab, nsteps, t[(4 * i + k) / per_sample], eta), xs[k], es[k], zs[k], clip, &p[k]);
+        o[k] = ddim_elem(ddim_coef_at(tab, nsteps, t[(oc + k) / per_sample], eta), xs[k], es[k], zs[k], clip, &p[k]);
     }
     if (pred_xstart) reinterpret_cast<float4*>(pred_xstart)[i] = make_float4(p[0], p[1], p[2], p[3]);
-    reinterpret_cast<float4*>(x_prev)[i] = make_float4(o[0], o[1], o[2], o[3]);
+    const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(x_prev + oc) = ov;
+    if constexpr (CFG) *reinterpret_cast<float4*>(x_prev + oc + gp) = ov;
   }
   for (int64_t i = 4 * n4 + tid; i < total; i += stride) {
+    const int64_t oc = cfg_cond<CFG>(i, gp);
     float p;
-    const float o = ddim_elem(ddim_coef_at(tab, nsteps, t[i / per_sample], eta), x[i], eps[i], z ? z[i] : 0.f, clip, &p);
+    const float o = ddim_elem(ddim_coef_at(tab, nsteps, t[oc / per_sample], eta), x[oc], eps_at<CFG>(eps, oc, gp, scale),
+                              z ? z[i] : 0.f, clip, &p);
     if (pred_xstart) pred_xstart[i] = p;
-    x_prev[i] = o;
+    x_prev[oc] = o;
+    if constexpr (CFG) x_prev[oc + gp] = o;
   }
 }
 
@@ -147,19 +252,24 @@ __device__ __forceinline__ float impose_elem(const impose_coef& c, float known, 
 // n4 groups of four elements (float4 of x / known / z, one 32-bit word of mask), then the scalar rest [4 n4, total); the host
 // passes n4 = 0 when x, known or z is not 16-byte aligned or mask not 4-byte aligned.  A group whose four mask bytes are zero
 // loads nothing else and stores nothing; a group that straddles a sample boundary looks its coefficients up per element.
+// Guided (see cfg_cond): x is the stacked state and t the stacked step vector; known, mask and z are B rows.  The selected
+// value goes to both copies, and a lane off the mask keeps the bits of each copy (the unconditional copy is loaded for that
+// in a partly masked group only).
+template <bool CFG>
 __global__ __launch_bounds__(256) void impose_known_kernel(float* x, const float* __restrict__ known,
                                                            const uint8_t* __restrict__ mask, const float* __restrict__ z,
                                                            const int64_t* __restrict__ t, const float* __restrict__ tab,
-                                                           int nsteps, int64_t per_sample, int64_t total, int64_t n4) {
+                                                           int nsteps, int64_t per_sample, int64_t total, int64_t n4, int64_t gp) {
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = tid; i < n4; i += stride) {
     const uint32_t m = reinterpret_cast<const uint32_t*>(mask)[i];
     if (m == 0) continue;
-    const float4 xv = reinterpret_cast<const float4*>(x)[i], kv = reinterpret_cast<const float4*>(known)[i];
+    const int64_t oc = cfg_cond<CFG>(4 * i, gp);
+    const float4 xv = *reinterpret_cast<const float4*>(x + oc), kv = reinterpret_cast<const float4*>(known)[i];
     const float4 zv = reinterpret_cast<const float4*>(z)[i];
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ks[4] = {kv.x, kv.y, kv.z, kv.w}, zs[4] = {zv.x, zv.y, zv.z, zv.w};
     float o[4];
-    const int64_t s0 = (4 * i) / per_sample, s3 = (4 * i + 3) / per_sample;
+    const int64_t s0 = oc / per_sample, s3 = (oc + 3) / per_sample;
     if (s0 == s3) {
       const impose_coef c = impose_coef_at(tab, nsteps, t[s0]);
 #pragma unroll
@@ -167,13 +277,28 @@ __global__ __launch_bounds__(256) void impose_known_kernel(float* x, const float
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        o[k] = ((m >> (8 * k)) & 0xffu) ? impose_elem(impose_coef_at(tab, nsteps, t[(4 * i + k) / per_sample]), ks[k], zs[k])
+        o[k] = ((m >> (8 * k)) & 0xffu) ? impose_elem(impose_coef_at(tab, nsteps, t[(oc + k) / per_sample]), ks[k], zs[k])
                                         : xs[k];
     }
-    reinterpret_cast<float4*>(x)[i] = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(x + oc) = make_float4(o[0], o[1], o[2], o[3]);
+    if constexpr (CFG) {
+      float u[4] = {o[0], o[1], o[2], o[3]};
+      if ((m & 0xffu) == 0 || (m & 0xff00u) == 0 || (m & 0xff0000u) == 0 || (m & 0xff000000u) == 0) {
+        const float4 uv = *reinterpret_cast<const float4*>(x + oc + gp);
+        const float us[4] = {uv.x, uv.y, uv.z, uv.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) u[k] = ((m >> (8 * k)) & 0xffu) ? o[k] : us[k];
+      }
+      *reinterpret_cast<float4*>(x + oc + gp) = make_float4(u[0], u[1], u[2], u[3]);
+    }
   }
   for (int64_t i = 4 * n4 + tid; i < total; i += stride)
-    if (mask[i]) x[i] = impose_elem(impose_coef_at(tab, nsteps, t[i / per_sample]), known[i], z[i]);
+    if (mask[i]) {
+      const int64_t oc = cfg_cond<CFG>(i, gp);
+      const float v = impose_elem(impose_coef_at(tab, nsteps, t[oc / per_sample]), known[i], z[i]);
+      x[oc] = v;
+      if constexpr (CFG) x[oc + gp] = v;
+    }
 }
 
 // One wave per (b, t) row: row mean of squared error, masked; dpred written in the same pass.
@@ -436,8 +561,75 @@ extern "C" int hig_p_sample_step(const float* x, const float* eps, const float* 
                                  float* x_prev, float* pred_xstart, hig_stream_t s) {
   HIG_REQUIRE(x && eps && z && t && tab && x_prev && B > 0 && per_sample > 0, "hig_p_sample_step: bad arguments");
   const int64_t total = (int64_t)B * per_sample;
-  hipLaunchKernelGGL(p_step_kernel, dim3(stream_blocks(total)), dim3(256), 0, hig_stream(s), x, eps, z, t,
-                     tab, nsteps, per_sample, total, x_prev, pred_xstart);
+  hipLaunchKernelGGL(p_step_kernel<false>, dim3(stream_blocks(total)), dim3(256), 0, hig_stream(s), x, eps, z, t,
+                     tab, nsteps, per_sample, total, (int64_t)0, 0.0f, (int64_t)0, x_prev, pred_xstart);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+// ---- classifier-free guidance: the entries over the stacked layout (cfg_cond) ----
+namespace {
+bool cfg_shape_ok(float scale, int32_t nsteps, int32_t B, int32_t group, int64_t per_sample) {
+  return nsteps > 0 && B > 0 && group > 0 && per_sample > 0 && B % group == 0 && fabsf(scale) <= 3.402823466e+38f;   // (NaN fails)
+}
+// float4 groups of the B-row view: all of them when every base pointer is 16-byte aligned and a group of four cannot leave
+// its block of the layout (gp % 4 == 0, which makes total a multiple of 4 as well), none otherwise.
+int64_t cfg_n4(uintptr_t bits, int64_t gp, int64_t total) { return (bits & 15) == 0 && gp % 4 == 0 ? total / 4 : 0; }
+int64_t cfg_work(int64_t n4, int64_t total) { return n4 > total - 4 * n4 ? n4 : total - 4 * n4; }
+}  // namespace
+
+extern "C" int hig_cfg_combine(const float* eps2, float scale, int32_t B, int32_t group, int64_t per_sample, float* eps_out,
+                               hig_stream_t s) {
+  HIG_REQUIRE(eps2 && eps_out && cfg_shape_ok(scale, 1, B, group, per_sample), "hig_cfg_combine: bad arguments");
+  const int64_t total = (int64_t)B * per_sample, gp = (int64_t)group * per_sample;
+  const int64_t n4 = cfg_n4(reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(eps_out), gp, total);
+  hipLaunchKernelGGL(cfg_combine_kernel, dim3(stream_blocks(cfg_work(n4, total))), dim3(256), 0, hig_stream(s), eps2, scale, gp,
+                     total, n4, eps_out);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_p_sample_step_cfg(float* xx, const float* eps2, float scale, const float* z, const int64_t* t2,
+                                     const float* tab, int32_t nsteps, int32_t B, int32_t group, int64_t per_sample,
+                                     float* pred_xstart, hig_stream_t s) {
+  HIG_REQUIRE(xx && eps2 && z && t2 && tab && cfg_shape_ok(scale, nsteps, B, group, per_sample),
+              "hig_p_sample_step_cfg: bad arguments");
+  const int64_t total = (int64_t)B * per_sample, gp = (int64_t)group * per_sample;
+  const int64_t n4 = cfg_n4(reinterpret_cast<uintptr_t>(xx) | reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(z) |
+                                reinterpret_cast<uintptr_t>(pred_xstart), gp, total);
+  hipLaunchKernelGGL(p_step_kernel<true>, dim3(stream_blocks(cfg_work(n4, total))), dim3(256), 0, hig_stream(s), xx, eps2, z, t2,
+                     tab, nsteps, per_sample, total, n4, scale, gp, xx, pred_xstart);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_ddim_step_cfg(float* xx, const float* eps2, float scale, const float* z, const int64_t* t2, const float* tab,
+                                 int32_t nsteps, int32_t B, int32_t group, int64_t per_sample, float eta, int32_t clip_denoised,
+                                 float* pred_xstart, hig_stream_t s) {
+  HIG_REQUIRE(xx && eps2 && t2 && tab && cfg_shape_ok(scale, nsteps, B, group, per_sample), "hig_ddim_step_cfg: bad arguments");
+  HIG_REQUIRE(eta >= 0.0f && eta <= 3.402823466e+38f, "hig_ddim_step_cfg: eta must be a finite number >= 0 (got %g)", (double)eta);
+  HIG_REQUIRE(z || eta == 0.0f, "hig_ddim_step_cfg: z may be NULL only when eta == 0");
+  const int64_t total = (int64_t)B * per_sample, gp = (int64_t)group * per_sample;
+  const int64_t n4 = cfg_n4(reinterpret_cast<uintptr_t>(xx) | reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(z) |
+                                reinterpret_cast<uintptr_t>(pred_xstart), gp, total);
+  // eta == 0 never reads z (sigma = 0 multiplies a literal zero instead)
+  hipLaunchKernelGGL(ddim_step_kernel<true>, dim3(stream_blocks(cfg_work(n4, total))), dim3(256), 0, hig_stream(s), xx, eps2,
+                     eta == 0.0f ? nullptr : z, t2, tab, nsteps, per_sample, total, n4, eta, clip_denoised ? 1 : 0, scale, gp, xx,
+                     pred_xstart);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_impose_known_cfg(float* xx, const float* known, const uint8_t* mask, const float* z, const int64_t* t2,
+                                    const float* tab, int32_t nsteps, int32_t B, int32_t group, int64_t per_sample,
+                                    hig_stream_t s) {
+  HIG_REQUIRE(xx && known && mask && z && t2 && tab && cfg_shape_ok(0.0f, nsteps, B, group, per_sample),
+              "hig_impose_known_cfg: bad arguments");
+  const int64_t total = (int64_t)B * per_sample, gp = (int64_t)group * per_sample;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(xx) | reinterpret_cast<uintptr_t>(known) | reinterpret_cast<uintptr_t>(z);
+  const int64_t n4 = (reinterpret_cast<uintptr_t>(mask) & 3) == 0 ? cfg_n4(bits, gp, total) : 0;
+  hipLaunchKernelGGL(impose_known_kernel<true>, dim3(stream_blocks(cfg_work(n4, total))), dim3(256), 0, hig_stream(s), xx, known,
+                     mask, z, t2, tab, nsteps, per_sample, total, n4, gp);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -461,9 +653,9 @@ extern "C" int hig_ddim_step(const float* x, const float* eps, const float* z, c
   const int64_t n4 = (bits & 15) == 0 ? total / 4 : 0;
   const int64_t work = n4 > total - 4 * n4 ? n4 : total - 4 * n4;
   // eta == 0 never reads z (sigma = 0 multiplies a literal zero instead)
-  hipLaunchKernelGGL(ddim_step_kernel, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, eps,
-                     eta == 0.0f ? nullptr : z, t, tab, nsteps, per_sample, total, n4, eta, clip_denoised ? 1 : 0, x_prev,
-                     pred_xstart);
+  hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, eps,
+                     eta == 0.0f ? nullptr : z, t, tab, nsteps, per_sample, total, n4, eta, clip_denoised ? 1 : 0, 0.0f, (int64_t)0,
+                     x_prev, pred_xstart);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -475,8 +667,8 @@ extern "C" int hig_impose_known(float* x, const float* known, const uint8_t* mas
   const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(known) | reinterpret_cast<uintptr_t>(z);
   const int64_t n4 = (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0 ? total / 4 : 0;
   const int64_t work = n4 > total - 4 * n4 ? n4 : total - 4 * n4;
-  hipLaunchKernelGGL(impose_known_kernel, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, known, mask, z, t, tab,
-                     nsteps, per_sample, total, n4);
+  hipLaunchKernelGGL(impose_known_kernel<false>, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, known, mask, z, t,
+                     tab, nsteps, per_sample, total, n4, (int64_t)0);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

@@ -20,6 +20,10 @@ Known-region conditioning (replacement-style in-painting, gaussian_diffusion.py:
 part of the motion is noised to the current level and written over the state.  The primitive is a `known` tensor of the
 sample's shape plus an element mask (`known_mask`), one hig_impose_known launch on fp32 ROCm tensors; the reference's
 `pre_seq` (the first Fp features of every frame) is a special case of it, its `transl_req` stays tensor arithmetic.
+
+Classifier-free guidance (not in the reference): a model wrapped in models/guidance.py's ClassifierFreeGuidedModel runs through
+every sampler as any callable does; the captured loop keeps it (it is not stripped like a DDP wrapper) and runs the step on the
+stacked batch with hig_impose_known_cfg / hig_p_sample_step_cfg.  cond_fn (classifier guidance) still raises.
 """
 import enum
 import math
@@ -29,6 +33,7 @@ import numpy as np
 import torch as th
 
 from .. import _lib
+from .guidance import ClassifierFreeGuidedModel, split_rows, stack_rows
 
 
 def create_named_schedule_sampler(name, diffusion):
@@ -118,6 +123,28 @@ _TAB_ORDER = ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod", "sqrt_reci
 
 def _unwrap(model):
     return getattr(model, "module", model)
+
+
+def _guided(model, model_kwargs):
+    """(core, cfg) of a sampling call's model.  A ClassifierFreeGuidedModel around a model of ours with precomputed text on
+    both branches is kept, not stripped: cfg = (scale, group or None, unconditional xf_proj, xf_out) and core = the model under
+    it, whose captured loop then runs on the stacked batch.  Anything else: cfg None and core = the unwrapped model (a guided
+    model that cannot be captured has no _launch_forward of its own, so it runs eagerly through its __call__)."""
+    if isinstance(model, ClassifierFreeGuidedModel):
+        u = model.uncond_kwargs
+        if (hasattr(model.core(), "_launch_forward") and u.get("xf_proj") is not None and u.get("xf_out") is not None
+                and set(u) <= {"xf_proj", "xf_out"} and model_kwargs is not None
+                and all(model_kwargs.get(k) is None for k in ("text",))):
+            return model.core(), model
+        return model, None
+    return _unwrap(model), None
+
+
+def _stacked_inputs(cfg, B, xf_proj, xf_out, length):
+    """(group, xf_proj, xf_out, length) of a guided captured loop, the three tensors in the stacked layout (2 B rows)."""
+    group = cfg.group_for(B)
+    kw = cfg.stacked_kwargs(dict(xf_proj=xf_proj, xf_out=xf_out, length=length), group)
+    return group, kw["xf_proj"].float().contiguous(), kw["xf_out"].float().contiguous(), kw["length"].contiguous()
 
 
 def _known_args(shape, known, known_mask, pre_seq, transl_req=None):
@@ -383,12 +410,12 @@ class GaussianDiffusion:
                       known_mask=None):
         """gaussian_diffusion.py:668-716.  pre_seq / transl_req / known + known_mask: see p_sample; the captured loop takes
         pre_seq and known (one more launch per step), a call with transl_req runs eagerly."""
-        core = _unwrap(model)
+        core, cfg = _guided(model, model_kwargs)
         if (self.use_hip_graph and hasattr(core, "_launch_forward") and model_kwargs is not None
                 and model_kwargs.get("xf_proj") is not None and model_kwargs.get("xf_out") is not None
                 and self._is_trainer_branch(clip_denoised, denoised_fn, cond_fn, pre_seq, transl_req)):
             known, known_mask = _known_args(shape, known, known_mask, pre_seq)
-            return self._p_sample_loop_graph(core, shape, noise, model_kwargs, device, known, known_mask, pre_seq)
+            return self._p_sample_loop_graph(core, shape, noise, model_kwargs, device, known, known_mask, pre_seq, cfg)
         final = None
         for sample in self.p_sample_loop_progressive(
                 model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
@@ -420,7 +447,8 @@ class GaussianDiffusion:
                 yield out
                 img = out["sample"]
 
-    def _p_sample_loop_graph(self, core, shape, noise, model_kwargs, device, known=None, known_mask=None, pre_seq=None):
+    def _p_sample_loop_graph(self, core, shape, noise, model_kwargs, device, known=None, known_mask=None, pre_seq=None,
+                             cfg=None):
         """The 1000-step loop as ONE captured hipGraph replayed num_timesteps times.
 
         Captured per step: denoiser forward (text context hoisted: it is step-invariant), fresh
@@ -430,7 +458,12 @@ class GaussianDiffusion:
 
         With known + known_mask (or pre_seq, turned into that pair) the step opens with the imposition:
         zz.normal_() -> hig_impose_known(img, known, mask, zk, t_dev) -> forward -> update with z -> dec, where zk and z are
-        the two halves of ONE buffer drawn by a single normal_(): a conditioned step has one launch more, not two."""
+        the two halves of ONE buffer drawn by a single normal_(): a conditioned step has one launch more, not two.
+
+        cfg (a ClassifierFreeGuidedModel around `core`): the state, the step vector and the text inputs are kept in the stacked
+        layout of models/guidance.py (2 B rows, the two rows of a sample equal), the forward runs once at 2 B, and
+        hig_impose_known_cfg / hig_p_sample_step_cfg take the place of the unguided kernels: the same number of launches, noise
+        for B rows, and the B conditional rows returned."""
         if device is None:
             device = next(core.parameters()).device
         B = shape[0]
@@ -444,7 +477,13 @@ class GaussianDiffusion:
                 length = th.full((B,), shape[1], dtype=th.int64, device=device)
             else:
                 length = th.as_tensor(length).to(device).long().contiguous()
-            t_dev = th.full((B,), self.num_timesteps - 1, dtype=th.int64, device=device)
+            if cfg is not None:
+                group, xf_proj, xf_out, length = _stacked_inputs(cfg, B, xf_proj, xf_out, length)
+                state = stack_rows(img, img, group).contiguous()
+            else:
+                state = img
+            rows = state.shape[0]
+            t_dev = th.full((rows,), self.num_timesteps - 1, dtype=th.int64, device=device)
             tab = self.device_table(device)
             L = _lib.lib()
             per = img.numel() // B
@@ -463,25 +502,35 @@ class GaussianDiffusion:
                 if cond:
                     if not self._debug_zero_noise:
                         zz.normal_()
-                    _lib.check(L.hig_impose_known(_lib.ptr(img), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
-                                                  _lib.ptr(t_dev), _lib.ptr(tab), self.num_timesteps, B, per,
-                                                  _lib.stream_ptr()))
-                eps, _ = core._launch_forward(img, t_dev, length, xf_proj, xf_out, training=False)
+                    if cfg is not None:
+                        _lib.check(L.hig_impose_known_cfg(_lib.ptr(state), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
+                                                          _lib.ptr(t_dev), _lib.ptr(tab), self.num_timesteps, B, group, per,
+                                                          _lib.stream_ptr()))
+                    else:
+                        _lib.check(L.hig_impose_known(_lib.ptr(img), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
+                                                      _lib.ptr(t_dev), _lib.ptr(tab), self.num_timesteps, B, per,
+                                                      _lib.stream_ptr()))
+                eps, _ = core._launch_forward(state, t_dev, length, xf_proj, xf_out, training=False)
                 if not cond and not self._debug_zero_noise:
                     z.normal_()
-                _lib.check(L.hig_p_sample_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(z), _lib.ptr(t_dev),
-                                               _lib.ptr(tab), self.num_timesteps, B, per, _lib.ptr(img),
-                                               None, _lib.stream_ptr()))
-                _lib.check(L.hig_dec_timesteps(_lib.ptr(t_dev), B, _lib.stream_ptr()))
+                if cfg is not None:
+                    _lib.check(L.hig_p_sample_step_cfg(_lib.ptr(state), _lib.ptr(eps), cfg.scale, _lib.ptr(z), _lib.ptr(t_dev),
+                                                       _lib.ptr(tab), self.num_timesteps, B, group, per, None,
+                                                       _lib.stream_ptr()))
+                else:
+                    _lib.check(L.hig_p_sample_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(z), _lib.ptr(t_dev),
+                                                   _lib.ptr(tab), self.num_timesteps, B, per, _lib.ptr(img),
+                                                   None, _lib.stream_ptr()))
+                _lib.check(L.hig_dec_timesteps(_lib.ptr(t_dev), rows, _lib.stream_ptr()))
 
             # warm-up on a side stream (allocations, text context), then undo its effect
-            img0 = img.clone()
+            img0 = state.clone()
             s = th.cuda.Stream()
             s.wait_stream(th.cuda.current_stream())
             with th.cuda.stream(s):
                 step()
             th.cuda.current_stream().wait_stream(s)
-            img.copy_(img0)
+            state.copy_(img0)
             t_dev.fill_(self.num_timesteps - 1)
             graph = th.cuda.CUDAGraph()
             with th.cuda.graph(graph, capture_error_mode="thread_local"):
@@ -489,7 +538,7 @@ class GaussianDiffusion:
             # capture does not execute: state is still (img0, N-1)
             for _ in range(self.num_timesteps):
                 graph.replay()
-        return img
+        return state if cfg is None else split_rows(state, group)[0].contiguous()
 
     # ---- training ---------------------------------------------------------------------------
     def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, forward_twice=False):

@@ -24,8 +24,9 @@ import numpy as np
 import torch as th
 
 from .. import _lib
-from .gaussian_diffusion import (GaussianDiffusion, ModelMeanType, _extract_into_tensor, _known_args, _pre_seq_as_known,
-                                 _unwrap)
+from .gaussian_diffusion import (GaussianDiffusion, ModelMeanType, _extract_into_tensor, _guided, _known_args,
+                                 _pre_seq_as_known, _stacked_inputs)
+from .guidance import split_rows, stack_rows
 
 _DDIM_TAB_ORDER = ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "alphas_cumprod", "alphas_cumprod_prev")
 
@@ -177,11 +178,11 @@ class SpacedDiffusion(GaussianDiffusion):
         """gaussian_diffusion.py:859-891.  With known + known_mask every step first writes the noised known part over the
         state; the noise of that imposition is fresh every step, so a conditioned loop at eta == 0 is NOT a pure function of
         its start (the unconditioned one is)."""
-        core = _unwrap(model)
+        core, cfg = _guided(model, model_kwargs)
         if self._graph_ok(core, model_kwargs) and self._ddim_fused_ok(denoised_fn, cond_fn):
             known, known_mask = _known_args(shape, known, known_mask, None)
             return self._spaced_loop_graph(core, shape, noise, model_kwargs, device, "ddim", float(eta), clip_denoised,
-                                           known, known_mask)
+                                           known, known_mask, cfg=cfg)
         final = None
         for sample in self.ddim_sample_loop_progressive(
                 model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
@@ -220,12 +221,12 @@ class SpacedDiffusion(GaussianDiffusion):
                       known_mask=None):
         """The ancestral chain over the K kept steps; captured under the base class's conditions (pre_seq and known +
         known_mask stay on the captured path, transl_req runs eagerly)."""
-        core = _unwrap(model)
+        core, cfg = _guided(model, model_kwargs)
         if (self._graph_ok(core, model_kwargs)
                 and self._is_trainer_branch(clip_denoised, denoised_fn, cond_fn, pre_seq, transl_req)):
             known, known_mask = _known_args(shape, known, known_mask, pre_seq)
             return self._spaced_loop_graph(core, shape, noise, model_kwargs, device, "ddpm", 0.0, False, known, known_mask,
-                                           pre_seq)
+                                           pre_seq, cfg)
         final = None
         for sample in self.p_sample_loop_progressive(
                 model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
@@ -235,7 +236,7 @@ class SpacedDiffusion(GaussianDiffusion):
         return final["sample"]
 
     def _spaced_loop_graph(self, core, shape, noise, model_kwargs, device, method, eta, clip_denoised, known=None,
-                           known_mask=None, pre_seq=None):
+                           known_mask=None, pre_seq=None, cfg=None):
         """One captured step replayed num_timesteps times: denoiser forward at the ORIGINAL timestep (t_model), fresh noise
         (ancestral, or DDIM with eta > 0: at eta == 0 the graph has no noise node and the update gets z = NULL), the update in
         place, then hig_advance_timesteps (t -= 1, t_model = map[t]).  The warm-up step outside the graph builds the text
@@ -245,7 +246,11 @@ class SpacedDiffusion(GaussianDiffusion):
         The imposition reads t_dev, the index into this object's own K-column table, not t_model.  zk (and z, where the update
         needs one) are parts of ONE buffer drawn by a single normal_(): a conditioned step has one launch more than an
         unconditioned one with noise, two more at DDIM eta == 0 -- which now draws noise and is no longer a pure function of
-        its start."""
+        its start.
+        cfg (a ClassifierFreeGuidedModel around `core`): the state, both step vectors and the text inputs are kept in the stacked
+        layout of models/guidance.py (2 B rows, the two rows of a sample equal); the forward runs once at 2 B and
+        hig_impose_known_cfg / hig_ddim_step_cfg / hig_p_sample_step_cfg take the place of the unguided kernels, the counter
+        advances 2 B entries: launch for launch the unguided step, noise for B rows, the B conditional rows returned."""
         if device is None:
             device = next(core.parameters()).device
         K, B = self.num_timesteps, shape[0]
@@ -259,9 +264,15 @@ class SpacedDiffusion(GaussianDiffusion):
                 length = th.full((B,), shape[1], dtype=th.int64, device=device)
             else:
                 length = th.as_tensor(length).to(device).long().contiguous()
+            if cfg is not None:
+                group, xf_proj, xf_out, length = _stacked_inputs(cfg, B, xf_proj, xf_out, length)
+                state = stack_rows(img, img, group).contiguous()
+            else:
+                state = img
+            rows = state.shape[0]
             tmap = self.device_map(device)
-            t_dev = th.full((B,), K - 1, dtype=th.int64, device=device)
-            t_model = th.full((B,), self.timestep_map[K - 1], dtype=th.int64, device=device)
+            t_dev = th.full((rows,), K - 1, dtype=th.int64, device=device)
+            t_model = th.full((rows,), self.timestep_map[K - 1], dtype=th.int64, device=device)
             ddim = method == "ddim"
             needs_z = not ddim or eta != 0
             tab = self.ddim_table(device) if ddim else self.device_table(device)
@@ -283,28 +294,39 @@ class SpacedDiffusion(GaussianDiffusion):
                 if cond:
                     if not self._debug_zero_noise:
                         zz.normal_()
-                    _lib.check(L.hig_impose_known(_lib.ptr(img), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
-                                                  _lib.ptr(t_dev), _lib.ptr(qtab), K, B, per, _lib.stream_ptr()))
-                eps, _ = core._launch_forward(img, t_model, length, xf_proj, xf_out, training=False)
+                    if cfg is not None:
+                        _lib.check(L.hig_impose_known_cfg(_lib.ptr(state), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
+                                                          _lib.ptr(t_dev), _lib.ptr(qtab), K, B, group, per, _lib.stream_ptr()))
+                    else:
+                        _lib.check(L.hig_impose_known(_lib.ptr(img), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
+                                                      _lib.ptr(t_dev), _lib.ptr(qtab), K, B, per, _lib.stream_ptr()))
+                eps, _ = core._launch_forward(state, t_model, length, xf_proj, xf_out, training=False)
                 if needs_z and not cond and not self._debug_zero_noise:
                     z.normal_()
-                if ddim:
+                if cfg is not None and ddim:
+                    _lib.check(L.hig_ddim_step_cfg(_lib.ptr(state), _lib.ptr(eps), cfg.scale, _lib.ptr(z), _lib.ptr(t_dev),
+                                                   _lib.ptr(tab), K, B, group, per, eta, int(bool(clip_denoised)), None,
+                                                   _lib.stream_ptr()))
+                elif cfg is not None:
+                    _lib.check(L.hig_p_sample_step_cfg(_lib.ptr(state), _lib.ptr(eps), cfg.scale, _lib.ptr(z), _lib.ptr(t_dev),
+                                                       _lib.ptr(tab), K, B, group, per, None, _lib.stream_ptr()))
+                elif ddim:
                     _lib.check(L.hig_ddim_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(z), _lib.ptr(t_dev), _lib.ptr(tab), K, B,
                                                per, eta, int(bool(clip_denoised)), _lib.ptr(img), None, _lib.stream_ptr()))
                 else:
                     _lib.check(L.hig_p_sample_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(z), _lib.ptr(t_dev), _lib.ptr(tab),
                                                    K, B, per, _lib.ptr(img), None, _lib.stream_ptr()))
-                _lib.check(L.hig_advance_timesteps(_lib.ptr(t_dev), _lib.ptr(tmap), K, B, _lib.ptr(t_model),
+                _lib.check(L.hig_advance_timesteps(_lib.ptr(t_dev), _lib.ptr(tmap), K, rows, _lib.ptr(t_model),
                                                    _lib.stream_ptr()))
 
             # warm-up on a side stream (allocations, text context), then undo its effect
-            img0 = img.clone()
+            img0 = state.clone()
             s = th.cuda.Stream()
             s.wait_stream(th.cuda.current_stream())
             with th.cuda.stream(s):
                 step()
             th.cuda.current_stream().wait_stream(s)
-            img.copy_(img0)
+            state.copy_(img0)
             t_dev.fill_(K - 1)
             t_model.fill_(self.timestep_map[K - 1])
             graph = th.cuda.CUDAGraph()
@@ -313,4 +335,4 @@ class SpacedDiffusion(GaussianDiffusion):
             # capture does not execute: state is still (img0, K-1)
             for _ in range(K):
                 graph.replay()
-        return img
+        return state if cfg is None else split_rows(state, group)[0].contiguous()

@@ -26,6 +26,7 @@ from torch.nn.utils import clip_grad_norm_
 from .. import _lib
 from ..models.gaussian_diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType,
                                          create_named_schedule_sampler, get_named_beta_schedule)
+from ..models.guidance import ClassifierFreeGuidedModel, check_scale
 from ..models.spaced_diffusion import SpacedDiffusion, space_timesteps
 from ..parallel import (FlatGradAllReduce, OverlappedGradAllReduce, ShardedSampler, broadcast_flat, broadcast_parameters,
                         exchange_active)
@@ -81,6 +82,7 @@ class DDPMTrainer(object):
             self.mse_criterion = torch.nn.MSELoss(reduction='none')
         self._fused = None
         self._few_step = None          # set_sampler: (SpacedDiffusion, method, eta), or None = the full chain
+        self._guidance_scale = None    # set_sampler: the classifier-free guidance scale, or None = unguided
         self.to(self.device)
 
     # ---- small helpers the reference exposes as static methods ----------------------------------------------
@@ -116,11 +118,32 @@ class DDPMTrainer(object):
         cur_len = torch.tensor([min(T, int(n)) for n in m_lens], dtype=torch.int64).to(self.device)
         return caption, x_start, cur_len
 
+    # ---- caption dropout (classifier-free guidance needs a model that also runs on the empty caption) ------------
+    def _caption_keep(self, n):
+        """None at opt.cond_drop_prob == 0 (no random number is drawn: existing runs keep their random stream); otherwise a
+        list of n bools from ONE torch.rand(n) on the CPU generator: False = this caption is replaced by ""."""
+        p = float(getattr(self.opt, "cond_drop_prob", 0.0))
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("opt.cond_drop_prob must lie in [0, 1], got %r" % (p,))
+        if p == 0.0:
+            return None
+        if getattr(self.opt, "cap_id", False):
+            raise NotImplementedError("cond_drop_prob: cap_id models take class embeddings, not captions -- there is no empty "
+                                      "caption to drop to")
+        return (torch.rand(n) >= p).tolist()
+
+    def _drop_captions(self, caption):
+        keep = self._caption_keep(len(caption))
+        if keep is None:
+            return caption
+        return [c if k else "" for c, k in zip(caption, keep)]
+
     # ---- the reference's step: forward() then update() --------------------------------------------------------
     def forward(self, batch_data, eval_mode=False):
         """Noises the batch at sampled timesteps and runs the denoiser (ddpm_trainer.py:97-119); leaves
         `real_noise`, `fake_noise`, `src_mask` for `backward_G`."""
         caption, x_start, cur_len = self._stage_batch(batch_data)
+        caption = self._drop_captions(caption)
         self.caption, self.motions = caption, x_start
         t, _unit_weights = self.sampler.sample(x_start.shape[0], x_start.device)
         terms = self.diffusion.training_losses(model=self.encoder, x_start=x_start, t=t,
@@ -185,15 +208,22 @@ class DDPMTrainer(object):
                 p.grad.copy_(v)
 
     # ---- sampling ----------------------------------------------------------------------------------------------
-    def set_sampler(self, steps=None, method="ddpm", eta=0.0):
+    def set_sampler(self, steps=None, method="ddpm", eta=0.0, guidance_scale=None):
         """How `generate` samples.  steps=None: the full ancestral chain of `self.diffusion` (the default).  Otherwise
         `steps` of the diffusion_steps training steps (space_timesteps), walked by the ancestral update (method="ddpm")
-        or by DDIM with the given eta (method="ddim"; eta = 0 is deterministic).  Training always uses self.diffusion."""
+        or by DDIM with the given eta (method="ddim"; eta = 0 is deterministic).  Training always uses self.diffusion.
+        guidance_scale: classifier-free guidance, eps_u + s (eps_c - eps_u) with the empty caption as the unconditional
+        branch (train with opt.cond_drop_prob > 0); kept independently of `steps`, so it applies to the full chain too.
+        None or 1.0: unguided, launch for launch the loop without it.  ValueError unless it is a finite number."""
         if method not in ("ddpm", "ddim"):
             raise ValueError("set_sampler: method must be 'ddpm' or 'ddim', got %r" % (method,))
         eta = float(eta)
         if not 0.0 <= eta < float("inf"):
             raise ValueError("set_sampler: eta must be a finite number >= 0, got %r" % (eta,))
+        scale = None if guidance_scale is None else check_scale(guidance_scale, "set_sampler")
+        if scale is not None and scale != 1.0 and getattr(self, "cap_id", False):
+            raise NotImplementedError("guidance on a cap_id model: it takes class embeddings, there is no empty caption")
+        self._guidance_scale = None if scale == 1.0 else scale
         if steps is None:
             self._few_step = None
             return
@@ -207,15 +237,31 @@ class DDPMTrainer(object):
         """The sampling loop `set_sampler` chose, with the arguments every reference tool passes; known + known_mask (see
         GaussianDiffusion.p_sample) go to whichever loop that is."""
         cond = {} if known is None and known_mask is None else dict(known=known, known_mask=known_mask)
+        model = self._guided_encoder(shape[0])
         if self._few_step is None:
-            return self.diffusion.p_sample_loop(self.encoder, shape, clip_denoised=False, progress=True,
+            return self.diffusion.p_sample_loop(model, shape, clip_denoised=False, progress=True,
                                                 model_kwargs=model_kwargs, **cond)
         spaced, method, eta = self._few_step
         if method == "ddim":
-            return spaced.ddim_sample_loop(self.encoder, shape, clip_denoised=False, progress=True,
+            return spaced.ddim_sample_loop(model, shape, clip_denoised=False, progress=True,
                                            model_kwargs=model_kwargs, eta=eta, **cond)
-        return spaced.p_sample_loop(self.encoder, shape, clip_denoised=False, progress=True, model_kwargs=model_kwargs,
+        return spaced.p_sample_loop(model, shape, clip_denoised=False, progress=True, model_kwargs=model_kwargs,
                                     **cond)
+
+    def _guidance_group(self, B):
+        """Rows per block of the stacked layout (models/guidance.py): the whole batch here, pairs in the two-person trainer."""
+        return B
+
+    def _guided_encoder(self, B):
+        """The encoder itself without guidance; with a scale, the encoder under a ClassifierFreeGuidedModel whose
+        unconditional branch is the empty caption, encoded once and expanded to the batch."""
+        if getattr(self, "_guidance_scale", None) is None:
+            return self.encoder
+        if getattr(self, "cap_id", False):
+            raise NotImplementedError("guidance on a cap_id model: it takes class embeddings, there is no empty caption")
+        xf_proj, xf_out = _core(self.encoder).encode_text([""], self.device)
+        uncond = dict(xf_proj=xf_proj.expand(B, *xf_proj.shape[1:]), xf_out=xf_out.expand(B, *xf_out.shape[1:]))
+        return ClassifierFreeGuidedModel(self.encoder, self._guidance_scale, uncond, group=self._guidance_group(B))
 
     def _known_for(self, known, known_mask, T):
         """The conditioning pair of one model batch (B, >= T, F) on the device, the mask expanded to known's shape, both cut to
@@ -554,6 +600,7 @@ class DDPMTrainer(object):
         faster than the replayed graph at every batch size since the backward runs on two streams), or
         train_step_captured with captured=True (two graph launches per step, no other host work)."""
         caption, x_start, cur_len = self._stage_batch(batch_data)
+        caption = self._drop_captions(caption)
         t, _ = self.sampler.sample(x_start.shape[0], x_start.device)
         clip_out, eot = self.clip_inputs(caption)
         step = self.train_step_captured if captured else self.train_step_fused

@@ -35,11 +35,23 @@ class DDPMMulTrainer(DDPMTrainer):
         cur_len = torch.LongTensor([min(T, int(m_len)) for m_len in m_lens]).to(self.device)
         return caption, list(caption1), list(caption2), x_start, cur_len, motion1.shape[0], T
 
+    def _drop_pair_captions(self, caption1, caption2):
+        """Caption dropout per PAIR: one draw blanks both captions of a pair, in every ordering the PIT loss builds from them."""
+        keep = self._caption_keep(len(caption1))
+        if keep is None:
+            return caption1, caption2
+        return ([c if k else "" for c, k in zip(caption1, keep)], [c if k else "" for c, k in zip(caption2, keep)])
+
+    def _guidance_group(self, B):
+        return B // 2 if self.multi else B
+
     def forward(self, batch_data, eval_mode=False):
         """mul_ddpm_trainer.py:90-161."""
         if not self.multi:
             return super().forward(batch_data, eval_mode)
         caption, caption1, caption2, x_start, cur_len, B, T = self._pair_inputs(batch_data)
+        caption1, caption2 = self._drop_pair_captions(caption1, caption2)
+        caption = caption1 + caption2
         t, _ = self.sampler.sample(B, x_start.device)
         t = torch.cat([t, t], dim=0)
         if not self.with_label:
@@ -128,6 +140,8 @@ class DDPMMulTrainer(DDPMTrainer):
         if not self.multi:
             return super().train_fused_batch(batch_data, captured, noise)
         caption, caption1, caption2, x_start, cur_len, B, T = self._pair_inputs(batch_data)
+        caption1, caption2 = self._drop_pair_captions(caption1, caption2)
+        caption = caption1 + caption2
         if not self.with_label:
             caption = caption + caption2 + caption1
         t, _ = self.sampler.sample(B, x_start.device)

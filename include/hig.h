@@ -1046,6 +1046,46 @@ int hig_advance_timesteps(int64_t* t, const int64_t* map, int32_t nsteps, int32_
  * fp32, so with u = 2^-24 and the table's entries taken as exact it is within 2 u (|a known| + |b z|) of its fp64 value. */
 int hig_impose_known(float* x, const float* known, const uint8_t* mask, const float* z, const int64_t* t,
                      const float* tab, int32_t nsteps, int32_t B, int64_t per_sample, hig_stream_t s);
+/* Classifier-free guidance: eps_g = eps_u + s (eps_c - eps_u), the conditional and the unconditional noise estimate of ONE
+ * model call on a stacked batch.  Stacked layout (fixed here; models/guidance.py builds it): for B samples and a `group` with
+ * B % group == 0, sample b has its
+ *   conditional row    rc = 2 (b / group) group + b % group
+ *   unconditional row  ru = rc + group
+ * in a buffer of 2 B rows.  group = B is [cond; uncond], what the single-person model uses.  The two-person model uses group =
+ * pairs, [p1 cond, p1 uncond, p2 cond, p2 uncond], so that row i still meets row i + half in the interaction attention.
+ * In the four entries below xx (the state), eps2 (the model output) and t2 (int64) are stacked -- 2 B rows / entries, t2 read at
+ * rc -- while z, known, mask, pred_xstart and eps_out are B rows; scale is s, by value.  The state's two rows per sample are
+ * equal on entry (only rc is read) and equal on return (both are stored: two stores, no copy kernel).
+ *   hig_cfg_combine        eps_out[b] = eps_g                                         (the eager / wrapper path)
+ *   hig_p_sample_step_cfg  the update of hig_p_sample_step on eps_g, in place on xx; pred_xstart may be NULL
+ *   hig_ddim_step_cfg      the update of hig_ddim_step on eps_g, in place on xx; z may be NULL exactly when eta == 0 and is
+ *                          then never read; pred_xstart may be NULL
+ *   hig_impose_known_cfg   the select of hig_impose_known written to both rows: where mask != 0 the value hig_impose_known
+ *                          computes (bit for bit), where mask == 0 each row keeps its own bits and known / z are never read
+ * Each guided kernel and its unguided counterpart are one template over a flag: after the combine the arithmetic is the
+ * unguided kernel's, operation for operation.  float4 path when every base pointer is 16-byte aligned (mask: 4-byte) and
+ * group * per_sample % 4 == 0, scalar otherwise: the same bits.  Grid-stride loops; no allocation, no synchronisation, nothing
+ * read back: capturable.  Refused with HIG_EINVAL, nothing written: a NULL required pointer, B, group, per_sample or nsteps
+ * <= 0, B % group != 0, a scale that is NaN or infinite, and whatever the unguided entry refuses (z NULL with eta > 0, eta
+ * negative, NaN or infinite).
+ * Bound, u = 2^-24, the table's fp32 entries taken as exact.  eps_g takes three fp32 roundings (the difference d = eps_c -
+ * eps_u, the product s d, the sum), nothing fused: it is within
+ *   e_g = u (|s| |d| + |s d| + |eps_g|)
+ * of its fp64 value.  That error is carried through the step's own derivation: it enters x0 = a x - b eps_g multiplied by
+ * b = sqrt_recipm1_alphas_cumprod,
+ *   e_x0 = 2 u (|a x| + |b eps_g|) + b e_g      (pred_xstart is within e_x0)
+ * and from there x_prev is within the bound stated for hig_ddim_step (resp. |c1| e_x0 + 2 u (|c1 x0| + |c2 x|) + 3 u |sd z| +
+ * u (|mean| + |sd z|) for hig_p_sample_step) with this e_x0 in place of the unguided one.  At eps_u == eps_c, d = 0 and eps_g
+ * = eps_u exactly: the guided step then returns the unguided step's bits.  tests/cfg_bounds.py derives every term. */
+int hig_cfg_combine(const float* eps2, float scale, int32_t B, int32_t group, int64_t per_sample, float* eps_out, hig_stream_t s);
+int hig_p_sample_step_cfg(float* xx, const float* eps2, float scale, const float* z, const int64_t* t2, const float* tab,
+                          int32_t nsteps, int32_t B, int32_t group, int64_t per_sample, float* pred_xstart /* nullable */,
+                          hig_stream_t s);
+int hig_ddim_step_cfg(float* xx, const float* eps2, float scale, const float* z /* nullable iff eta == 0 */, const int64_t* t2,
+                      const float* tab, int32_t nsteps, int32_t B, int32_t group, int64_t per_sample, float eta,
+                      int32_t clip_denoised, float* pred_xstart /* nullable */, hig_stream_t s);
+int hig_impose_known_cfg(float* xx, const float* known, const uint8_t* mask, const float* z, const int64_t* t2, const float* tab,
+                         int32_t nsteps, int32_t B, int32_t group, int64_t per_sample, hig_stream_t s);
 /* DDPMTrainer.backward_G (ddpm_trainer.py:172-178): loss = sum_bt mask*mean_f (p-t)^2 / sum mask
  * with mask[b][t] = t < length[b];  dpred = d loss / d pred.  scratch: HIG_NORM_BLOCKS floats
  * (one partial sum per workgroup, at most HIG_NORM_BLOCKS - 1 of them, and sum(mask) behind them). */

@@ -2,11 +2,17 @@
 1000-step chain through plain GaussianDiffusion (the path every earlier commit has) next to SpacedDiffusion's strided ancestral
 and DDIM (eta = 0) loops at K = 1000 / 100 / 50 / 20, with fp32 and with bf16 storage.
 
-    python tools/few_step_time.py [--repeats 5] [--ks 1000,100,50,20] [--out FILE] [--known]
+    python tools/few_step_time.py [--repeats 5] [--ks 1000,100,50,20] [--out FILE] [--known | --guided]
 
 --known: what known-region conditioning adds to a step.  Instead of the list above, every K gets its strided ancestral and DDIM
 (eta = 0) loops twice, unconditioned (the path without hig_impose_known, launch for launch the parent commit's) and with the
 first half of the frames known (`known` + `known_mask`), alternating in the same run.
+
+--guided: what classifier-free guidance costs a step.  Every K gets its strided ancestral and DDIM (eta = 0) loops three times,
+alternating in the same run: guided at B (ClassifierFreeGuidedModel, scale 2.5: the stacked 2 B forward and the _cfg kernels),
+unguided at B (the path without guidance, launch for launch the parent commit's) and unguided at 2 B (the same forward the
+guided step runs, next to the unguided update kernels).  The summary lines at the end give guided / (2 x unguided at B) and
+guided - unguided at 2 B per storage and sampler.
 
 Per loop and repeat it reports
   * call_ms    host clock around one whole call, between device synchronisations: warm-up step, capture and K replays (text
@@ -103,7 +109,10 @@ def main():
     ap.add_argument("--ks", default="1000,100,50,20")
     ap.add_argument("--out", default=None)
     ap.add_argument("--known", action="store_true")
+    ap.add_argument("--guided", action="store_true")
     a = ap.parse_args()
+    if a.known and a.guided:
+        raise SystemExit("--known and --guided are two different comparisons: give one of them")
     if not torch.cuda.is_available():
         raise SystemExit("few_step_time.py needs the MI355X")
     dev = torch.device("cuda:0")
@@ -118,10 +127,14 @@ def main():
     known = torch.randn(*shape, generator=g).to(dev)
     known_mask = torch.zeros(shape, dtype=torch.bool, device=dev)
     known_mask[:, :c["T"] // 2] = True
-    loops = [] if a.known else [("GaussianDiffusion ddpm", N, lambda: hig_amd.GaussianDiffusion(**diffusion_args()), "p")]
+    un = {"xf_proj": torch.randn(c["B"], 4 * c["d"], generator=g).to(dev), "xf_out": torch.randn(c["B"], c["N"], c["Lt"], generator=g).to(dev)}
+    kw2 = {k: torch.cat([v, un.get(k, v)]) for k, v in kw.items()}       # the unguided loop at 2 B: the guided forward's inputs
+    shape2, x02 = (2 * c["B"],) + shape[1:], torch.cat([x0, x0])
+    loops = [] if a.known or a.guided else [("GaussianDiffusion ddpm", N, lambda: hig_amd.GaussianDiffusion(**diffusion_args()), "p")]
+    variants = (("", ""), (" + known", "k")) if a.known else ((" guided", "g"), ("", ""), (" at 2B", "2")) if a.guided else (("", ""),)
     for k in (int(v) for v in a.ks.split(",")):
         for name, kind in (("ddpm", "p"), ("ddim eta=0", "d")):
-            for tag, suffix in (("", ""), (" + known", "k")) if a.known else (("", ""),):
+            for tag, suffix in variants:
                 loops.append(("SpacedDiffusion %s%s" % (name, tag), k,
                               lambda k=k: hig_amd.SpacedDiffusion(hig_amd.space_timesteps(N, k), **diffusion_args()),
                               kind + suffix))
@@ -131,9 +144,11 @@ def main():
 
         def caller(gd, kind):
             cond = dict(known=known, known_mask=known_mask) if kind.endswith("k") else {}
+            mdl = hig_amd.ClassifierFreeGuidedModel(model, 2.5, un) if kind.endswith("g") else model
+            sh, start, mk = (shape2, x02, kw2) if kind.endswith("2") else (shape, x0, kw)
             if kind[0] == "p":
-                return lambda: gd.p_sample_loop(model, shape, noise=x0, clip_denoised=False, model_kwargs=kw, **cond)
-            return lambda: gd.ddim_sample_loop(model, shape, noise=x0, clip_denoised=False, model_kwargs=kw, eta=0.0, **cond)
+                return lambda: gd.p_sample_loop(mdl, sh, noise=start, clip_denoised=False, model_kwargs=mk, **cond)
+            return lambda: gd.ddim_sample_loop(mdl, sh, noise=start, clip_denoised=False, model_kwargs=mk, eta=0.0, **cond)
 
         calls = [(name, k, caller(make(), kind)) for name, k, make, kind in loops]
         firsts = [timed_call(call, k) for _, k, call in calls]
@@ -154,6 +169,17 @@ def main():
                       storage, name, k, first["call_ms"], 100 * first["setup"], row["call_ms"]["median"], row["call_ms"]["min"],
                       row["call_ms"]["max"], row["step_us"]["median"], row["step_us"]["min"], row["step_us"]["max"],
                       100 * row["setup"]["median"], 100 * row["setup"]["min"], 100 * row["setup"]["max"]), flush=True)
+    if a.guided:
+        by = {(r["storage"], r["loop"], r["K"]): r["step_us"] for r in results}
+        for (storage, loop, k), g_us in by.items():
+            if not loop.endswith(" guided"):
+                continue
+            base = loop[:-len(" guided")]
+            b_us, b2_us = by[(storage, base, k)], by[(storage, base + " at 2B", k)]
+            print("GUIDED %-5s %-26s K=%-4d guided %7.1f us  unguided at B %7.1f us [%7.1f .. %7.1f]  at 2B %7.1f us  "
+                  "guided / (2 x at B) %.3f  guided - at 2B %+6.1f us" % (
+                      storage, base, k, g_us["median"], b_us["median"], b_us["min"], b_us["max"], b2_us["median"],
+                      g_us["median"] / (2 * b_us["median"]), g_us["median"] - b2_us["median"]), flush=True)
     lines = [json.dumps(r) for r in results]
     print("\n".join(lines))
     if a.out:
