@@ -9,9 +9,10 @@ Putting this directory itself on sys.path gives the reference's own import layou
 """
 from . import _lib  # noqa: F401
 from .models import (ClassifierFreeGuidedModel, GaussianDiffusion, MotionConsistencyEvalModel, MotionEncoder,  # noqa: F401
-                     MotionInteractionTransformer, MotionTransformer, SpacedDiffusion, space_timesteps)
+                     MotionInteractionTransformer, MotionTransformer, SpacedDiffusion, space_timesteps,
+                     space_timesteps_logsnr)
 from .trainers import DDPMMulTrainer, DDPMTrainer, EvalModelTrainer  # noqa: F401
 
 __all__ = ["MotionTransformer", "MotionInteractionTransformer", "MotionEncoder", "MotionConsistencyEvalModel",
-           "GaussianDiffusion", "SpacedDiffusion", "space_timesteps", "DDPMTrainer", "DDPMMulTrainer", "EvalModelTrainer",
-           "ClassifierFreeGuidedModel"]
+           "GaussianDiffusion", "SpacedDiffusion", "space_timesteps", "space_timesteps_logsnr", "DDPMTrainer", "DDPMMulTrainer",
+           "EvalModelTrainer", "ClassifierFreeGuidedModel"]

@@ -60,6 +60,7 @@ DN_PLAN_SLOTS = ("entry", "text_batched", "text_fork", "fuse_apply", "fold32", "
                  "fuse_mm16", "fuse_out", "fuse_front", "wgrad_fork", "edge16", "Fp", "wants_side_stream")
 TAB_ROWS = 7
 DDIM_TAB_ROWS = 4
+DPM_TAB_ROWS = 5
 NORM_BLOCKS = 1024
 COLSUM_CHUNKS = 512
 
@@ -86,6 +87,8 @@ SYMBOLS = (
     "hig_denoiser_plan", "hig_denoiser_last_schedule",
     # few-step sampling
     "hig_ddim_step", "hig_advance_timesteps",
+    # second-order few-step sampling
+    "hig_dpm2m_step", "hig_dpm2m_step_cfg",
     # known-region conditioning
     "hig_impose_known",
     # classifier-free guidance
@@ -209,6 +212,8 @@ def lib():
         L.hig_dec_timesteps.argtypes = [vp, i32, vp]
         L.hig_ddim_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, f32, i32, vp, vp, vp]
         L.hig_advance_timesteps.argtypes = [vp, vp, i32, i32, vp, vp]
+        L.hig_dpm2m_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, i32, vp]
+        L.hig_dpm2m_step_cfg.argtypes = [vp, vp, f32, vp, vp, vp, i32, i32, i32, i64, i32, vp]
         L.hig_impose_known.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i64, vp]
         L.hig_cfg_combine.argtypes = [vp, f32, i32, i32, i64, vp, vp]
         L.hig_p_sample_step_cfg.argtypes = [vp, vp, f32, vp, vp, vp, i32, i32, i32, i64, vp, vp]

@@ -217,6 +217,86 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const fl
   }
 }
 
+// ---- second-order few-step sampling: the DPM-Solver++(2M) update, data prediction, multistep ----
+// tab: HIG_DPM_TAB_ROWS x nsteps (include/hig.h): a, b of the x0 estimate and the three coefficients of the linear update, which
+// the host computes per kept step in fp64.  x0 = a x - b eps [clamped]; r = c_x x + c_0 x0; r += c_1 hist only where c_1 != 0
+// (the first step has no history, the last one is first order by definition: hist may hold anything there, NaN included);
+// hist = x0 always.  Two products and a difference, two products and a sum, a product and a sum: nothing fused.
+enum { M_A = 0, M_B, M_CX, M_C0, M_C1 };
+
+struct dpm_coef { float a, b, cx, c0, c1; };
+
+__device__ __forceinline__ dpm_coef dpm_coef_at(const float* __restrict__ tab, int nsteps, int64_t t) {
+  const int tt = t < 0 ? 0 : (t >= nsteps ? nsteps - 1 : (int)t);   // (a step outside the table reads its nearest row)
+  dpm_coef c;
+  c.a = tab[M_A * nsteps + tt];
+  c.b = tab[M_B * nsteps + tt];
+  c.cx = tab[M_CX * nsteps + tt];
+  c.c0 = tab[M_C0 * nsteps + tt];
+  c.c1 = tab[M_C1 * nsteps + tt];
+  return c;
+}
+
+// h is used only where c.c1 != 0 (the caller loads it only there and passes 0 otherwise).  Returns x_prev.
+__device__ __forceinline__ float dpm_elem(const dpm_coef& c, float x, float e, float h, int clip, float* x0_out) {
+#pragma clang fp contract(off)
+  const float ax = c.a * x, be = c.b * e;
+  float x0 = ax - be;
+  if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+  const float px = c.cx * x, p0 = c.c0 * x0;
+  float r = px + p0;
+  if (c.c1 != 0.0f) {
+    const float ph = c.c1 * h;
+    r = r + ph;
+  }
+  *x0_out = x0;
+  return r;
+}
+
+// In place on x and on hist.  n4 float4 groups, then the scalar rest [4 n4, total); the host passes n4 = 0 when a pointer is not
+// 16-byte aligned.  A float4 that straddles a sample boundary looks its coefficients (and its history) up per element.  Guided
+// (see cfg_cond): x is the stacked state, read at the conditional copy and stored to both; eps and t are stacked; hist is B rows.
+template <bool CFG>
+__global__ __launch_bounds__(256) void dpm2m_step_kernel(float* x, const float* __restrict__ eps, float* __restrict__ hist,
+                                                         const int64_t* __restrict__ t, const float* __restrict__ tab,
+                                                         int nsteps, int64_t per_sample, int64_t total, int64_t n4, int clip,
+                                                         float scale, int64_t gp) {
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = tid; i < n4; i += stride) {
+    const int64_t oc = cfg_cond<CFG>(4 * i, gp);
+    const float4 xv = *reinterpret_cast<const float4*>(x + oc), ev = eps4_at<CFG>(eps, oc, gp, scale);
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
+    float o[4], p[4];
+    const int64_t s0 = oc / per_sample, s3 = (oc + 3) / per_sample;
+    if (s0 == s3) {
+      const dpm_coef c = dpm_coef_at(tab, nsteps, t[s0]);
+      const float4 hv = c.c1 != 0.0f ? reinterpret_cast<const float4*>(hist)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float hs[4] = {hv.x, hv.y, hv.z, hv.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = dpm_elem(c, xs[k], es[k], hs[k], clip, &p[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const dpm_coef c = dpm_coef_at(tab, nsteps, t[(oc + k) / per_sample]);
+        o[k] = dpm_elem(c, xs[k], es[k], c.c1 != 0.0f ? hist[4 * i + k] : 0.f, clip, &p[k]);
+      }
+    }
+    reinterpret_cast<float4*>(hist)[i] = make_float4(p[0], p[1], p[2], p[3]);
+    const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(x + oc) = ov;
+    if constexpr (CFG) *reinterpret_cast<float4*>(x + oc + gp) = ov;
+  }
+  for (int64_t i = 4 * n4 + tid; i < total; i += stride) {
+    const int64_t oc = cfg_cond<CFG>(i, gp);
+    const dpm_coef c = dpm_coef_at(tab, nsteps, t[oc / per_sample]);
+    float p;
+    const float o = dpm_elem(c, x[oc], eps_at<CFG>(eps, oc, gp, scale), c.c1 != 0.0f ? hist[i] : 0.f, clip, &p);
+    hist[i] = p;
+    x[oc] = o;
+    if constexpr (CFG) x[oc + gp] = o;
+  }
+}
+
 // t[b] -= 1; t_model[b] = map[t[b]] with the index held inside the map (after the last step t = -1 reads map[0]).
 __global__ void advance_t_kernel(int64_t* __restrict__ t, const int64_t* __restrict__ map, int nsteps, int B,
                                  int64_t* __restrict__ t_model) {
@@ -656,6 +736,33 @@ extern "C" int hig_ddim_step(const float* x, const float* eps, const float* z, c
   hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, eps,
                      eta == 0.0f ? nullptr : z, t, tab, nsteps, per_sample, total, n4, eta, clip_denoised ? 1 : 0, 0.0f, (int64_t)0,
                      x_prev, pred_xstart);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_dpm2m_step(float* x, const float* eps, float* hist, const int64_t* t, const float* tab, int32_t nsteps,
+                              int32_t B, int64_t per_sample, int32_t clip_denoised, hig_stream_t s) {
+  HIG_REQUIRE(x && eps && hist && t && tab && B > 0 && per_sample > 0 && nsteps > 0, "hig_dpm2m_step: bad arguments");
+  const int64_t total = (int64_t)B * per_sample;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(hist);
+  const int64_t n4 = (bits & 15) == 0 ? total / 4 : 0;
+  const int64_t work = n4 > total - 4 * n4 ? n4 : total - 4 * n4;
+  hipLaunchKernelGGL(dpm2m_step_kernel<false>, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, eps, hist, t, tab, nsteps,
+                     per_sample, total, n4, clip_denoised ? 1 : 0, 0.0f, (int64_t)0);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_dpm2m_step_cfg(float* xx, const float* eps2, float scale, float* hist, const int64_t* t2, const float* tab,
+                                  int32_t nsteps, int32_t B, int32_t group, int64_t per_sample, int32_t clip_denoised,
+                                  hig_stream_t s) {
+  HIG_REQUIRE(xx && eps2 && hist && t2 && tab && cfg_shape_ok(scale, nsteps, B, group, per_sample),
+              "hig_dpm2m_step_cfg: bad arguments");
+  const int64_t total = (int64_t)B * per_sample, gp = (int64_t)group * per_sample;
+  const int64_t n4 = cfg_n4(reinterpret_cast<uintptr_t>(xx) | reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(hist),
+                            gp, total);
+  hipLaunchKernelGGL(dpm2m_step_kernel<true>, dim3(stream_blocks(cfg_work(n4, total))), dim3(256), 0, hig_stream(s), xx, eps2, hist,
+                     t2, tab, nsteps, per_sample, total, n4, clip_denoised ? 1 : 0, scale, gp);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

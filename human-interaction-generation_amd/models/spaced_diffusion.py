@@ -15,6 +15,15 @@
     / `transl_req`): the known part, noised to the level of this object's own step t, is written over the state before each
     model call -- hig_impose_known, one more launch in front of the captured step.
 
+  * `space_timesteps_logsnr` picks the K steps uniformly in log-SNR, lam = log(sqrt(abar) / sqrt(1 - abar)), instead of
+    uniformly in t, and `dpm_solver_sample` / `dpm_solver_sample_loop` walk them with DPM-Solver++(2M): the x0 estimate of the
+    step before is kept and extrapolated, which makes the update second order in the log-SNR step at no further model call.
+    The update is linear, x_prev = c_x x + c_0 x0_i + c_1 x0_(i+1), its coefficients are computed per kept step in fp64 on the
+    host (`dpm_solver_coefficients`), and for fp32 ROCm tensors it is one kernel, hig_dpm2m_step, in place on the state and the
+    history.  The two belong together: on the uniform-in-t selection the last steps are huge in log-SNR and the extrapolation
+    overshoots there.  order=1 is DDIM at eta = 0 in other arithmetic.  The captured loop is the same single step replayed K
+    times (method "dpmpp2m"): no noise node, one history buffer of B rows.
+
 `GaussianDiffusion`'s four DDIM names still raise; `SpacedDiffusion(space_timesteps(N, N), ...)` is
 the unstrided DDIM sampler.
 """
@@ -42,6 +51,41 @@ def space_timesteps(num_timesteps, k):
     if not 2 <= k <= n:
         raise ValueError("space_timesteps: need 2 <= k <= num_timesteps, got k = %d of %d" % (k, n))
     return [(2 * i * (n - 1) + (k - 1)) // (2 * (k - 1)) for i in range(k)]
+
+
+def space_timesteps_logsnr(betas, k):
+    """The K original timesteps a K-step sampler keeps out of N = len(betas), uniform in log-SNR: with abar = cumprod(1 -
+    betas) and lam[t] = 0.5 log(abar[t] / (1 - abar[t])) (fp64, strictly decreasing in t), t_i is the index of the lam entry
+    nearest linspace(lam[0], lam[N-1], K)[i], a tie going to the lower t; then t_i = max(t_i, t_(i-1) + 1), so that duplicates
+    near t = 0 move up.  Where lam falls steeply at the far end as well (the cosine schedule; K near N) that bump runs past
+    N - 1; then, and only then, the mirror image follows: t_(K-1) = N - 1 and t_i = min(t_i, t_(i+1) - 1), so that duplicates
+    near t = N - 1 move down.  Strictly increasing from 0 to N - 1 for every valid K.  ValueError: K no integer or outside 2 <= K
+    <= N, betas not 1-D, a schedule whose log-SNR is not finite and strictly decreasing."""
+    b = np.array(betas, dtype=np.float64)
+    if b.ndim != 1:
+        raise ValueError("space_timesteps_logsnr: betas must be 1-D, got shape %r" % (b.shape,))
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+        raise ValueError("space_timesteps_logsnr: k must be an integer, got %r" % (k,))
+    n, k = int(b.shape[0]), int(k)
+    if not 2 <= k <= n:
+        raise ValueError("space_timesteps_logsnr: need 2 <= k <= len(betas), got k = %d of %d" % (k, n))
+    abar = np.cumprod(1.0 - b)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lam = 0.5 * np.log(abar / (1.0 - abar))
+    if not (np.isfinite(lam).all() and (np.diff(lam) < 0).all()):
+        raise ValueError("space_timesteps_logsnr: the log-SNR of this schedule is not finite and strictly decreasing")
+    steps = []
+    for target in np.linspace(lam[0], lam[n - 1], k):
+        t = int(np.argmin(np.abs(lam - target)))      # (argmin returns the first of equal minima: the lower t)
+        steps.append(t if not steps else max(t, steps[-1] + 1))
+    if steps[-1] > n - 1:
+        steps[-1] = n - 1
+        for i in range(k - 2, -1, -1):
+            steps[i] = min(steps[i], steps[i + 1] - 1)
+    if steps[0] != 0 or steps[-1] != n - 1 or any(b2 <= a for a, b2 in zip(steps, steps[1:])):
+        raise ValueError("space_timesteps_logsnr: %d steps uniform in log-SNR do not fit this schedule of %d (got %d .. %d)"
+                         % (k, n, steps[0], steps[-1]))
+    return steps
 
 
 class _MappedModel:
@@ -77,6 +121,7 @@ class SpacedDiffusion(GaussianDiffusion):
                          loss_type=loss_type, rescale_timesteps=rescale_timesteps)
         self._dev_maps = {}
         self._dev_ddim_tabs = {}
+        self._dev_dpm_tabs = {}
 
     # ---- what the model sees ----------------------------------------------------------------
     def device_map(self, device):
@@ -211,6 +256,127 @@ class SpacedDiffusion(GaussianDiffusion):
                 yield out
                 img = out["sample"]
 
+    # ---- DPM-Solver++(2M) -------------------------------------------------------------------
+    def dpm_solver_coefficients(self, order=2):
+        """(HIG_DPM_TAB_ROWS, K) fp64: rows a, b (the x0 estimate, x0 = a x - b eps) and c_x, c_0, c_1 of the update
+        x_prev = c_x x + c_0 x0_i + c_1 x0_(i+1) of kept step i.  With al = sqrt(abar_i), sg = sqrt(1 - abar_i), lam = log(al /
+        sg), the same three of the target level (alphas_cumprod_prev: alp, sgp, lamp) and h = lamp - lam:
+            x_prev = (sgp / sg) x + alp (1 - e^-h) D,   D = x0_i                                       first order
+                                                        D = (1 + 1 / (2 r)) x0_i - (1 / (2 r)) x0_(i+1)   second order
+        r = (lam_i - lam_(i+1)) / h.  First order at i = K - 1 (no history yet) and at i = 0, where the target is sigma = 0, h
+        is infinite and x_prev = x0_0: c_x = 0, c_0 = 1, c_1 = 0 exactly.  order=1: c_1 = 0 everywhere, DDIM at eta = 0."""
+        if order not in (1, 2):
+            raise ValueError("dpm_solver: order must be 1 or 2, got %r" % (order,))
+        K = self.num_timesteps
+        ac, acp = self.alphas_cumprod, self.alphas_cumprod_prev
+        al, sg = np.sqrt(ac), np.sqrt(1.0 - ac)
+        lam = np.log(al / sg)
+        out = np.zeros((_lib.DPM_TAB_ROWS, K), dtype=np.float64)
+        out[0], out[1] = self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod
+        out[3, 0] = 1.0
+        for i in range(1, K):
+            alp, sgp = np.sqrt(acp[i]), np.sqrt(1.0 - acp[i])
+            h = np.log(alp / sgp) - lam[i]
+            base = alp * -np.expm1(-h)
+            out[2, i] = sgp / sg[i]
+            if order == 2 and i < K - 1:
+                half_inv_r = 0.5 * h / (lam[i] - lam[i + 1])
+                out[3, i], out[4, i] = base * (1.0 + half_inv_r), -base * half_inv_r
+            else:
+                out[3, i] = base
+        return out
+
+    def dpm_solver_table(self, device, order=2):
+        """(5, num_timesteps) fp32 table of hig_dpm2m_step (HIG_DPM_TAB_ROWS): dpm_solver_coefficients rounded once, built once
+        per device and per order."""
+        key = (str(device), int(order))
+        if key not in self._dev_dpm_tabs:
+            tab = self.dpm_solver_coefficients(order).astype(np.float32)
+            self._dev_dpm_tabs[key] = th.from_numpy(tab).to(device).contiguous()
+        return self._dev_dpm_tabs[key]
+
+    def dpm_solver_sample(self, model, x, t, prev_xstart=None, order=2, clip_denoised=True, denoised_fn=None,
+                          model_kwargs=None, known=None, known_mask=None, cond_fn=None):
+        """One DPM-Solver++(2M) step: {"sample", "pred_xstart"}; pred_xstart (after denoised_fn and the clamp, as
+        p_mean_variance processes it) is what the next call takes as `prev_xstart`.  prev_xstart=None forces first order for
+        this call; otherwise the coefficients decide per sample (first order at t = K - 1 and at t = 0, where prev_xstart is
+        not read and may hold anything).  For fp32 ROCm tensors on the eps-prediction branch without denoised_fn the update is
+        ONE kernel (hig_dpm2m_step, on copies: the caller's x and prev_xstart are left alone); everything else is tensor
+        arithmetic in the same operation order.  known + known_mask: as ddim_sample, written into the caller's x first."""
+        if cond_fn is not None:
+            raise NotImplementedError("cond_fn guidance is never used by the reference tools")
+        if prev_xstart is None:
+            order = 1
+        coef = self.dpm_solver_coefficients(order)                         # (validates order)
+        if prev_xstart is not None and tuple(prev_xstart.shape) != tuple(x.shape):
+            raise ValueError("dpm_solver_sample: prev_xstart must have x's shape %r, got %r"
+                             % (tuple(x.shape), tuple(prev_xstart.shape)))
+        known, known_mask = _known_args(x.shape, known, known_mask, None)
+        if known is not None:
+            self._impose(x, t, known, known_mask, None)
+        if (self._ddim_fused_ok(denoised_fn, cond_fn) and self._fused_ok(x)
+                and (prev_xstart is None or self._fused_ok(prev_xstart))):
+            eps = self._wrap(model)(x, t, **(model_kwargs or {}))
+            sample, ec = x.contiguous().clone(), eps.float().contiguous()
+            hist = th.empty_like(sample) if prev_xstart is None else prev_xstart.contiguous().clone()
+            B = sample.shape[0]
+            t64, tab = t.long().contiguous(), self.dpm_solver_table(sample.device, order)   # (alive until the launch is enqueued)
+            _lib.check(_lib.lib().hig_dpm2m_step(_lib.ptr(sample), _lib.ptr(ec), _lib.ptr(hist), _lib.ptr(t64), _lib.ptr(tab),
+                                                 self.num_timesteps, B, sample.numel() // B, int(bool(clip_denoised)),
+                                                 _lib.stream_ptr()))
+            return {"sample": sample, "pred_xstart": hist}
+        out = self.p_mean_variance(model, x, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                   model_kwargs=model_kwargs)
+        x0 = out["pred_xstart"]
+        c_x, c_0, c_1 = (_extract_into_tensor(coef[r], t, x.shape) for r in (2, 3, 4))
+        sample = c_x * x + c_0 * x0
+        if prev_xstart is not None:
+            # a select, as in the kernel: the history of a sample whose c_1 is 0 is never used (it may hold NaN)
+            sample = th.where(c_1 != 0, sample + c_1 * prev_xstart.to(sample.dtype), sample)
+        return {"sample": sample, "pred_xstart": x0}
+
+    def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                               model_kwargs=None, device=None, progress=False, order=2, known=None, known_mask=None):
+        """K model calls from pure noise, t = K-1 ... 0, the x0 estimate carried from step to step.  Deterministic without a
+        known region; with known + known_mask every step first writes the freshly noised known part over the state (the history
+        holds model predictions and stays valid)."""
+        core, cfg = _guided(model, model_kwargs)
+        if self._graph_ok(core, model_kwargs) and self._ddim_fused_ok(denoised_fn, cond_fn):
+            self.dpm_solver_coefficients(order)
+            known, known_mask = _known_args(shape, known, known_mask, None)
+            return self._spaced_loop_graph(core, shape, noise, model_kwargs, device, "dpmpp2m", 0.0, clip_denoised,
+                                           known, known_mask, cfg=cfg, order=order)
+        final = None
+        for sample in self.dpm_solver_sample_loop_progressive(
+                model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                model_kwargs=model_kwargs, device=device, progress=progress, order=order, known=known,
+                known_mask=known_mask):
+            final = sample
+        return final["sample"]
+
+    def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
+                                           cond_fn=None, model_kwargs=None, device=None, progress=False, order=2,
+                                           known=None, known_mask=None):
+        """t = K-1 ... 0, no_grad; yields every step's {"sample", "pred_xstart"}."""
+        if device is None:
+            device = next(model.parameters()).device
+        assert isinstance(shape, (tuple, list))
+        known, known_mask = _known_args(shape, known, known_mask, None)    # (the mask is expanded once)
+        cond = {} if known is None else dict(known=known.to(device), known_mask=known_mask.to(device))
+        img = noise if noise is not None else th.randn(*shape, device=device)
+        indices = list(range(self.num_timesteps))[::-1]
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        prev = None
+        for i in indices:
+            t = th.tensor([i] * shape[0], device=device)
+            with th.no_grad():
+                out = self.dpm_solver_sample(model, img, t, prev_xstart=prev, order=order, clip_denoised=clip_denoised,
+                                             denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, **cond)
+                yield out
+                img, prev = out["sample"], out["pred_xstart"]
+
     # ---- captured loops -----------------------------------------------------------------------
     def _graph_ok(self, core, model_kwargs):
         return (self.use_hip_graph and hasattr(core, "_launch_forward") and model_kwargs is not None
@@ -236,7 +402,7 @@ class SpacedDiffusion(GaussianDiffusion):
         return final["sample"]
 
     def _spaced_loop_graph(self, core, shape, noise, model_kwargs, device, method, eta, clip_denoised, known=None,
-                           known_mask=None, pre_seq=None, cfg=None):
+                           known_mask=None, pre_seq=None, cfg=None, order=2):
         """One captured step replayed num_timesteps times: denoiser forward at the ORIGINAL timestep (t_model), fresh noise
         (ancestral, or DDIM with eta > 0: at eta == 0 the graph has no noise node and the update gets z = NULL), the update in
         place, then hig_advance_timesteps (t -= 1, t_model = map[t]).  The warm-up step outside the graph builds the text
@@ -250,7 +416,11 @@ class SpacedDiffusion(GaussianDiffusion):
         cfg (a ClassifierFreeGuidedModel around `core`): the state, both step vectors and the text inputs are kept in the stacked
         layout of models/guidance.py (2 B rows, the two rows of a sample equal); the forward runs once at 2 B and
         hig_impose_known_cfg / hig_ddim_step_cfg / hig_p_sample_step_cfg take the place of the unguided kernels, the counter
-        advances 2 B entries: launch for launch the unguided step, noise for B rows, the B conditional rows returned."""
+        advances 2 B entries: launch for launch the unguided step, noise for B rows, the B conditional rows returned.
+        method "dpmpp2m": the update is hig_dpm2m_step[_cfg] with the table of `order`; no noise node (a known region still
+        draws zk); `hist`, the x0 estimate of the step before, is one buffer of B rows (not stacked under guidance) that the
+        kernel reads and rewrites in place.  Step K-1 never reads it, so what the warm-up leaves there is harmless; it is
+        cleared with the state all the same."""
         if device is None:
             device = next(core.parameters()).device
         K, B = self.num_timesteps, shape[0]
@@ -273,9 +443,13 @@ class SpacedDiffusion(GaussianDiffusion):
             tmap = self.device_map(device)
             t_dev = th.full((rows,), K - 1, dtype=th.int64, device=device)
             t_model = th.full((rows,), self.timestep_map[K - 1], dtype=th.int64, device=device)
-            ddim = method == "ddim"
-            needs_z = not ddim or eta != 0
-            tab = self.ddim_table(device) if ddim else self.device_table(device)
+            if method not in ("ddpm", "ddim", "dpmpp2m"):
+                raise ValueError("_spaced_loop_graph: unknown method %r" % (method,))
+            ddim, dpm = method == "ddim", method == "dpmpp2m"
+            needs_z = method == "ddpm" or (ddim and eta != 0)
+            tab = (self.dpm_solver_table(device, order) if dpm else self.ddim_table(device) if ddim
+                   else self.device_table(device))
+            hist = th.zeros_like(img) if dpm else None
             L = _lib.lib()
             per = img.numel() // B
             if pre_seq is not None:
@@ -303,7 +477,13 @@ class SpacedDiffusion(GaussianDiffusion):
                 eps, _ = core._launch_forward(state, t_model, length, xf_proj, xf_out, training=False)
                 if needs_z and not cond and not self._debug_zero_noise:
                     z.normal_()
-                if cfg is not None and ddim:
+                if dpm and cfg is not None:
+                    _lib.check(L.hig_dpm2m_step_cfg(_lib.ptr(state), _lib.ptr(eps), cfg.scale, _lib.ptr(hist), _lib.ptr(t_dev),
+                                                    _lib.ptr(tab), K, B, group, per, int(bool(clip_denoised)), _lib.stream_ptr()))
+                elif dpm:
+                    _lib.check(L.hig_dpm2m_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(hist), _lib.ptr(t_dev), _lib.ptr(tab), K, B,
+                                                per, int(bool(clip_denoised)), _lib.stream_ptr()))
+                elif cfg is not None and ddim:
                     _lib.check(L.hig_ddim_step_cfg(_lib.ptr(state), _lib.ptr(eps), cfg.scale, _lib.ptr(z), _lib.ptr(t_dev),
                                                    _lib.ptr(tab), K, B, group, per, eta, int(bool(clip_denoised)), None,
                                                    _lib.stream_ptr()))
@@ -327,6 +507,8 @@ class SpacedDiffusion(GaussianDiffusion):
                 step()
             th.cuda.current_stream().wait_stream(s)
             state.copy_(img0)
+            if dpm:
+                hist.zero_()
             t_dev.fill_(K - 1)
             t_model.fill_(self.timestep_map[K - 1])
             graph = th.cuda.CUDAGraph()

@@ -27,7 +27,7 @@ from .. import _lib
 from ..models.gaussian_diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType,
                                          create_named_schedule_sampler, get_named_beta_schedule)
 from ..models.guidance import ClassifierFreeGuidedModel, check_scale
-from ..models.spaced_diffusion import SpacedDiffusion, space_timesteps
+from ..models.spaced_diffusion import SpacedDiffusion, space_timesteps, space_timesteps_logsnr
 from ..parallel import (FlatGradAllReduce, OverlappedGradAllReduce, ShardedSampler, broadcast_flat, broadcast_parameters,
                         exchange_active)
 
@@ -208,18 +208,29 @@ class DDPMTrainer(object):
                 p.grad.copy_(v)
 
     # ---- sampling ----------------------------------------------------------------------------------------------
-    def set_sampler(self, steps=None, method="ddpm", eta=0.0, guidance_scale=None):
+    def set_sampler(self, steps=None, method="ddpm", eta=0.0, guidance_scale=None, spacing=None):
         """How `generate` samples.  steps=None: the full ancestral chain of `self.diffusion` (the default).  Otherwise
-        `steps` of the diffusion_steps training steps (space_timesteps), walked by the ancestral update (method="ddpm")
-        or by DDIM with the given eta (method="ddim"; eta = 0 is deterministic).  Training always uses self.diffusion.
+        `steps` of the diffusion_steps training steps, walked by the ancestral update (method="ddpm"), by DDIM with the
+        given eta (method="ddim"; eta = 0 is deterministic) or by the second-order multistep solver DPM-Solver++(2M)
+        (method="dpmpp2m": needs `steps`, eta must be 0).  Training always uses self.diffusion.
+        spacing: which steps are kept -- "uniform" in t (space_timesteps) or "logsnr", uniform in log-SNR
+        (space_timesteps_logsnr).  None: "uniform" for ddpm and ddim, "logsnr" for dpmpp2m, whose extrapolation needs it.
         guidance_scale: classifier-free guidance, eps_u + s (eps_c - eps_u) with the empty caption as the unconditional
         branch (train with opt.cond_drop_prob > 0); kept independently of `steps`, so it applies to the full chain too.
         None or 1.0: unguided, launch for launch the loop without it.  ValueError unless it is a finite number."""
-        if method not in ("ddpm", "ddim"):
-            raise ValueError("set_sampler: method must be 'ddpm' or 'ddim', got %r" % (method,))
+        if method not in ("ddpm", "ddim", "dpmpp2m"):
+            raise ValueError("set_sampler: method must be 'ddpm', 'ddim' or 'dpmpp2m', got %r" % (method,))
         eta = float(eta)
         if not 0.0 <= eta < float("inf"):
             raise ValueError("set_sampler: eta must be a finite number >= 0, got %r" % (eta,))
+        if method == "dpmpp2m" and steps is None:
+            raise ValueError("set_sampler: method 'dpmpp2m' needs steps")
+        if method == "dpmpp2m" and eta != 0.0:
+            raise ValueError("set_sampler: method 'dpmpp2m' is deterministic, eta must be 0, got %r" % (eta,))
+        if spacing is None:
+            spacing = "logsnr" if method == "dpmpp2m" else "uniform"
+        if spacing not in ("uniform", "logsnr"):
+            raise ValueError("set_sampler: spacing must be 'uniform' or 'logsnr', got %r" % (spacing,))
         scale = None if guidance_scale is None else check_scale(guidance_scale, "set_sampler")
         if scale is not None and scale != 1.0 and getattr(self, "cap_id", False):
             raise NotImplementedError("guidance on a cap_id model: it takes class embeddings, there is no empty caption")
@@ -227,7 +238,9 @@ class DDPMTrainer(object):
         if steps is None:
             self._few_step = None
             return
-        spaced = SpacedDiffusion(space_timesteps(self.diffusion_steps, steps), betas=self.diffusion.betas,
+        use = (space_timesteps(self.diffusion_steps, steps) if spacing == "uniform"
+               else space_timesteps_logsnr(self.diffusion.betas, steps))
+        spaced = SpacedDiffusion(use, betas=self.diffusion.betas,
                                  model_mean_type=self.diffusion.model_mean_type,
                                  model_var_type=self.diffusion.model_var_type, loss_type=self.diffusion.loss_type,
                                  rescale_timesteps=self.diffusion.rescale_timesteps)
@@ -245,6 +258,9 @@ class DDPMTrainer(object):
         if method == "ddim":
             return spaced.ddim_sample_loop(model, shape, clip_denoised=False, progress=True,
                                            model_kwargs=model_kwargs, eta=eta, **cond)
+        if method == "dpmpp2m":
+            return spaced.dpm_solver_sample_loop(model, shape, clip_denoised=False, progress=True,
+                                                 model_kwargs=model_kwargs, **cond)
         return spaced.p_sample_loop(model, shape, clip_denoised=False, progress=True, model_kwargs=model_kwargs,
                                     **cond)
 

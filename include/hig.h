@@ -1029,6 +1029,34 @@ int hig_dec_timesteps(int64_t* t, int32_t B, hig_stream_t s);
 int hig_ddim_step(const float* x, const float* eps, const float* z /* nullable iff eta == 0 */, const int64_t* t,
                   const float* tab, int32_t nsteps, int32_t B, int64_t per_sample, float eta, int32_t clip_denoised,
                   float* x_prev, float* pred_xstart /* nullable */, hig_stream_t s);
+/* Second-order few-step sampling.  The DPM-Solver++(2M) update (data prediction, multistep) on the eps-prediction branch, one
+ * launch, in place on x and on the history:
+ *   x0 = a x - b eps;  if clip_denoised: x0 = clamp(x0, -1, 1);  r = c_x x + c_0 x0;  if (c_1 != 0) r = r + c_1 hist;
+ *   hist = x0;  x = r
+ * with (a, b, c_x, c_0, c_1) = row t[b] of `tab`: HIG_DPM_TAB_ROWS x nsteps fp32 rows -- sqrt_recip_alphas_cumprod,
+ * sqrt_recipm1_alphas_cumprod and the three coefficients of the linear update, which the host computes per kept step in fp64
+ * (SpacedDiffusion.dpm_solver_coefficients) and rounds once.  t is per sample (0 <= t[b] < nsteps; a value outside reads the
+ * nearest row).  hist (B * per_sample floats, the x0 estimate of the step before) is read only where c_1 != 0 -- it may hold
+ * anything, NaN included, in a sample whose row has c_1 == 0, as at the first step of a loop -- and is always written: on return
+ * it holds this step's x0, after the clamp.  Neither eps nor hist may overlap x.  float4 path when x, eps and hist are 16-byte
+ * aligned (a vector that straddles a sample boundary looks its coefficients up per element), scalar otherwise: the same bits.
+ * Grid-stride loops; no allocation, no synchronisation, nothing read back: capturable.  Refused with HIG_EINVAL, nothing
+ * written: a NULL x / eps / hist / t / tab, B, per_sample or nsteps <= 0.
+ * Bound: fp32 in the order written above, nothing fused.  With u = 2^-24 and the table's fp32 entries taken as exact, hist is
+ * within e_x0 = 2 u (|a x| + |b eps|) of its fp64 value (two products and a difference; the clamp is exact and 1-Lipschitz), and
+ * x within
+ *   |c_0| e_x0 + u (|c_x x| + |c_0 x0| + |r|)   [ + u (|c_1 hist| + |r + c_1 hist|)  where c_1 != 0 ]
+ * -- the x0 error scaled, the two products, the sum, and for the history term its product and its sum.  tests/dpm_bounds.py
+ * derives it.
+ * hig_dpm2m_step_cfg is the same update on eps_g = eps_u + s (eps_c - eps_u) over the stacked layout described below (xx, eps2
+ * and t2 stacked, hist B rows, both rows of the state stored): one template over a flag with hig_dpm2m_step, so at eps_u ==
+ * eps_c it returns the unguided kernel's bits; otherwise e_x0 = 2 u (|a x| + |b eps_g|) + b e_g with the e_g stated there.  It
+ * refuses what the other guided entries refuse (B % group != 0, group <= 0, a scale that is NaN or infinite) and a NULL hist. */
+#define HIG_DPM_TAB_ROWS 5
+int hig_dpm2m_step(float* x, const float* eps, float* hist, const int64_t* t, const float* tab, int32_t nsteps, int32_t B,
+                   int64_t per_sample, int32_t clip_denoised, hig_stream_t s);
+int hig_dpm2m_step_cfg(float* xx, const float* eps2, float scale, float* hist, const int64_t* t2, const float* tab,
+                       int32_t nsteps, int32_t B, int32_t group, int64_t per_sample, int32_t clip_denoised, hig_stream_t s);
 /* t[b] -= 1, then t_model[b] = map[max(t[b], 0)] (map: nsteps int64 entries, the original timestep of each kept step), one
  * launch: the counter of the strided loops.  After the last step t = -1 and t_model = map[0], which nobody reads. */
 int hig_advance_timesteps(int64_t* t, const int64_t* map, int32_t nsteps, int32_t B, int64_t* t_model, hig_stream_t s);

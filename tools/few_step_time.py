@@ -3,6 +3,13 @@
 and DDIM (eta = 0) loops at K = 1000 / 100 / 50 / 20, with fp32 and with bf16 storage.
 
     python tools/few_step_time.py [--repeats 5] [--ks 1000,100,50,20] [--out FILE] [--known | --guided]
+                                  [--methods ddpm,ddim] [--spacing uniform]
+
+--methods: which strided loops every K gets, out of ddpm, ddim (eta = 0) and dpmpp2m (DPM-Solver++(2M), dpm_solver_sample_loop);
+the full 1000-step chain is timed only when ddpm is among them.  --spacing: uniform (space_timesteps), logsnr
+(space_timesteps_logsnr) or both; the replay time does not depend on which steps are kept, the sample does.  With dpmpp2m and
+ddim both listed, DPM lines at the end give the second-order step against DDIM at the same K and spacing, in the same run:
+the difference is the history buffer's 8 bytes per element.
 
 --known: what known-region conditioning adds to a step.  Instead of the list above, every K gets its strided ancestral and DDIM
 (eta = 0) loops twice, unconditioned (the path without hig_impose_known, launch for launch the parent commit's) and with the
@@ -110,7 +117,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--known", action="store_true")
     ap.add_argument("--guided", action="store_true")
+    ap.add_argument("--methods", default="ddpm,ddim")
+    ap.add_argument("--spacing", default="uniform", choices=("uniform", "logsnr", "both"))
     a = ap.parse_args()
+    methods = a.methods.split(",")
+    if not methods or any(m not in ("ddpm", "ddim", "dpmpp2m") for m in methods):
+        raise SystemExit("--methods: a comma-separated list out of ddpm, ddim, dpmpp2m")
+    spacings = ("uniform", "logsnr") if a.spacing == "both" else (a.spacing,)
     if a.known and a.guided:
         raise SystemExit("--known and --guided are two different comparisons: give one of them")
     if not torch.cuda.is_available():
@@ -130,14 +143,20 @@ def main():
     un = {"xf_proj": torch.randn(c["B"], 4 * c["d"], generator=g).to(dev), "xf_out": torch.randn(c["B"], c["N"], c["Lt"], generator=g).to(dev)}
     kw2 = {k: torch.cat([v, un.get(k, v)]) for k, v in kw.items()}       # the unguided loop at 2 B: the guided forward's inputs
     shape2, x02 = (2 * c["B"],) + shape[1:], torch.cat([x0, x0])
-    loops = [] if a.known or a.guided else [("GaussianDiffusion ddpm", N, lambda: hig_amd.GaussianDiffusion(**diffusion_args()), "p")]
+    loops = [] if a.known or a.guided or "ddpm" not in methods else [("GaussianDiffusion ddpm", N, lambda: hig_amd.GaussianDiffusion(**diffusion_args()), "p")]
     variants = (("", ""), (" + known", "k")) if a.known else ((" guided", "g"), ("", ""), (" at 2B", "2")) if a.guided else (("", ""),)
+    names = dict(ddpm=("ddpm", "p"), ddim=("ddim eta=0", "d"), dpmpp2m=("dpmpp2m", "m"))
+
+    def kept(k, spacing):
+        return hig_amd.space_timesteps(N, k) if spacing == "uniform" else hig_amd.space_timesteps_logsnr(diffusion_args()["betas"], k)
+
     for k in (int(v) for v in a.ks.split(",")):
-        for name, kind in (("ddpm", "p"), ("ddim eta=0", "d")):
-            for tag, suffix in variants:
-                loops.append(("SpacedDiffusion %s%s" % (name, tag), k,
-                              lambda k=k: hig_amd.SpacedDiffusion(hig_amd.space_timesteps(N, k), **diffusion_args()),
-                              kind + suffix))
+        for name, kind in (names[m] for m in methods):
+            for spacing in spacings:
+                for tag, suffix in variants:
+                    loops.append(("SpacedDiffusion %s%s%s" % (name, "" if spacing == "uniform" else " logsnr", tag), k,
+                                  lambda k=k, spacing=spacing: hig_amd.SpacedDiffusion(kept(k, spacing), **diffusion_args()),
+                                  kind + suffix))
     results = []
     for storage in ("f32", "bf16"):
         model.precision, model.storage = ("bf16", "bf16") if storage == "bf16" else ("f32", "f32")
@@ -148,6 +167,8 @@ def main():
             sh, start, mk = (shape2, x02, kw2) if kind.endswith("2") else (shape, x0, kw)
             if kind[0] == "p":
                 return lambda: gd.p_sample_loop(mdl, sh, noise=start, clip_denoised=False, model_kwargs=mk, **cond)
+            if kind[0] == "m":
+                return lambda: gd.dpm_solver_sample_loop(mdl, sh, noise=start, clip_denoised=False, model_kwargs=mk, **cond)
             return lambda: gd.ddim_sample_loop(mdl, sh, noise=start, clip_denoised=False, model_kwargs=mk, eta=0.0, **cond)
 
         calls = [(name, k, caller(make(), kind)) for name, k, make, kind in loops]
@@ -180,6 +201,18 @@ def main():
                   "guided / (2 x at B) %.3f  guided - at 2B %+6.1f us" % (
                       storage, base, k, g_us["median"], b_us["median"], b_us["min"], b_us["max"], b2_us["median"],
                       g_us["median"] / (2 * b_us["median"]), g_us["median"] - b2_us["median"]), flush=True)
+    if "dpmpp2m" in methods and "ddim" in methods:
+        by = {(r["storage"], r["loop"], r["K"]): r for r in results}
+        for (storage, loop, k), row in by.items():
+            if not loop.startswith("SpacedDiffusion dpmpp2m"):
+                continue
+            base = by[(storage, loop.replace("dpmpp2m", "ddim eta=0"), k)]
+            m_us, d_us = row["step_us"], base["step_us"]
+            print("DPM %-5s %-40s K=%-4d step %7.1f us [%7.1f .. %7.1f]  ddim %7.1f us [%7.1f .. %7.1f]  difference %+6.1f us  | "
+                  "call %7.1f ms [%7.1f .. %7.1f]  ddim %7.1f ms" % (
+                      storage, loop, k, m_us["median"], m_us["min"], m_us["max"], d_us["median"], d_us["min"], d_us["max"],
+                      m_us["median"] - d_us["median"], row["call_ms"]["median"], row["call_ms"]["min"], row["call_ms"]["max"],
+                      base["call_ms"]["median"]), flush=True)
     lines = [json.dumps(r) for r in results]
     print("\n".join(lines))
     if a.out:
