@@ -61,6 +61,55 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restric
   for (int64_t i = 4 * n4 + tid; i < total; i += stride) out[i] = eps_at<true>(eps2, cfg_cond<true>(i, gp), gp, scale);
 }
 
+// ---- the step stream: what the three fused updates (ancestral, DDIM, DPM-Solver++(2M)) share ----
+// Op supplies at(t), the coefficients of one sample's step; reads_aux(coef), whether the update reads its auxiliary input under
+// them; and elem(coef, x, eps, aux, &x0), one element: returns x_prev and hands back the x0 estimate.  aux_in (z, or the
+// history) is B rows, NULL reads as 0; aux_out (pred_xstart, or the history again) is B rows, NULL is skipped.  x_prev may alias
+// x and aux_out may BE aux_in (every element is read before its own store), so none of the four is __restrict__.
+// n4 float4 groups first, then the scalar rest [4 n4, total); the host passes n4 = 0 unless every pointer is 16-byte aligned
+// (and, guided, gp % 4 == 0, which keeps a group inside one block of the layout).  A float4 that straddles a sample boundary
+// looks its coefficients (and its auxiliary input) up per element.  Guided (see cfg_cond): x == x_prev is the stacked state,
+// read at the conditional copy and stored to both; eps and t are stacked.
+template <bool CFG, class Op>
+__device__ __forceinline__ void step_stream(const Op op, const float* x, const float* __restrict__ eps, const float* aux_in,
+                                            const int64_t* __restrict__ t, int64_t per_sample, int64_t total, int64_t n4,
+                                            float scale, int64_t gp, float* x_prev, float* aux_out) {
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = tid; i < n4; i += stride) {
+    const int64_t oc = cfg_cond<CFG>(4 * i, gp);
+    const float4 xv = *reinterpret_cast<const float4*>(x + oc), ev = eps4_at<CFG>(eps, oc, gp, scale);
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
+    float o[4], p[4];
+    const int64_t s0 = oc / per_sample, s3 = (oc + 3) / per_sample;
+    if (s0 == s3) {
+      const auto c = op.at(t[s0]);
+      const float4 av = aux_in && op.reads_aux(c) ? reinterpret_cast<const float4*>(aux_in)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float as[4] = {av.x, av.y, av.z, av.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = op.elem(c, xs[k], es[k], as[k], &p[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const auto c = op.at(t[(oc + k) / per_sample]);
+        o[k] = op.elem(c, xs[k], es[k], aux_in && op.reads_aux(c) ? aux_in[4 * i + k] : 0.f, &p[k]);
+      }
+    }
+    if (aux_out) reinterpret_cast<float4*>(aux_out)[i] = make_float4(p[0], p[1], p[2], p[3]);
+    const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(x_prev + oc) = ov;
+    if constexpr (CFG) *reinterpret_cast<float4*>(x_prev + oc + gp) = ov;
+  }
+  for (int64_t i = 4 * n4 + tid; i < total; i += stride) {
+    const int64_t oc = cfg_cond<CFG>(i, gp);
+    const auto c = op.at(t[oc / per_sample]);
+    float p;
+    const float o = op.elem(c, x[oc], eps_at<CFG>(eps, oc, gp, scale), aux_in && op.reads_aux(c) ? aux_in[i] : 0.f, &p);
+    if (aux_out) aux_out[i] = p;
+    x_prev[oc] = o;
+    if constexpr (CFG) x_prev[oc + gp] = o;
+  }
+}
+
 // The ancestral update.  Same operation order as the reference: x0 = a*x - b*eps; mean = c1*x0 + c2*x; x_prev = mean +
 // [t != 0] sd z, with the three fusions the compiler has always made here written out (x0 = fma(a, x, -(b eps)), mean =
 // fma(c1, x0, c2 x), x_prev = fma([t != 0] sd, z, mean)) so that the float4 and the scalar path of the guided instance cannot
@@ -89,51 +138,22 @@ __device__ __forceinline__ float p_elem(const p_coef& c, float xi, float e, floa
   return __builtin_fmaf(c.nzsd, z, mean);
 }
 
-// Unguided: x, eps, z, x_prev, pred_xstart are B rows and the loop is the scalar stream it has always been.  Guided: x ==
-// x_prev is the stacked state (read at the conditional copy, stored to both), eps the stacked model output, t the stacked
-// step vector; z and pred_xstart stay B rows.  n4 float4 groups first (the host passes 0 unless every pointer is 16-byte
-// aligned and gp % 4 == 0, which keeps a group inside one block of the layout), then the scalar rest.
+struct p_op {
+  const float* tab;
+  int nsteps;
+  __device__ p_coef at(int64_t t) const { return p_coef_at(tab, nsteps, (int)t); }
+  __device__ bool reads_aux(const p_coef&) const { return true; }
+  __device__ float elem(const p_coef& c, float x, float e, float z, float* x0_out) const { return p_elem(c, x, e, z, x0_out); }
+};
+
+// z and pred_xstart are B rows.  Unguided, the host passes n4 = 0: the scalar stream this kernel has always been.
 template <bool CFG>
 __global__ void p_step_kernel(const float* x, const float* __restrict__ eps,
                               const float* __restrict__ z, const int64_t* __restrict__ t,
                               const float* __restrict__ tab, int nsteps, int64_t per_sample,
                               int64_t total, int64_t n4, float scale, int64_t gp, float* x_prev,
                               float* __restrict__ pred_xstart) {
-  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-  int64_t first = tid;
-  if constexpr (CFG) {
-    for (int64_t i = tid; i < n4; i += stride) {
-      const int64_t oc = cfg_cond<true>(4 * i, gp);
-      const float4 xv = *reinterpret_cast<const float4*>(x + oc), ev = eps4_at<true>(eps, oc, gp, scale);
-      const float4 zv = reinterpret_cast<const float4*>(z)[i];
-      const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w}, zs[4] = {zv.x, zv.y, zv.z, zv.w};
-      float o[4], p[4];
-      const int64_t s0 = oc / per_sample, s3 = (oc + 3) / per_sample;
-      if (s0 == s3) {
-        const p_coef c = p_coef_at(tab, nsteps, (int)t[s0]);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = p_elem(c, xs[k], es[k], zs[k], &p[k]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          o[k] = p_elem(p_coef_at(tab, nsteps, (int)t[(oc + k) / per_sample]), xs[k], es[k], zs[k], &p[k]);
-      }
-      if (pred_xstart) reinterpret_cast<float4*>(pred_xstart)[i] = make_float4(p[0], p[1], p[2], p[3]);
-      const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
-      *reinterpret_cast<float4*>(x_prev + oc) = ov;
-      *reinterpret_cast<float4*>(x_prev + oc + gp) = ov;
-    }
-    first = 4 * n4 + tid;
-  }
-  for (int64_t i = first; i < total; i += stride) {
-    const int64_t oc = cfg_cond<CFG>(i, gp);
-    const int tt = (int)t[oc / per_sample];
-    float x0;
-    const float o = p_elem(p_coef_at(tab, nsteps, tt), x[oc], eps_at<CFG>(eps, oc, gp, scale), z[i], &x0);
-    if (pred_xstart) pred_xstart[i] = x0;
-    x_prev[oc] = o;
-    if constexpr (CFG) x_prev[oc + gp] = o;
-  }
+  step_stream<CFG>(p_op{tab, nsteps}, x, eps, z, t, per_sample, total, n4, scale, gp, x_prev, pred_xstart);
 }
 
 __global__ void dec_t_kernel(int64_t* t, int B) {
@@ -174,47 +194,26 @@ __device__ __forceinline__ float ddim_elem(const ddim_coef& c, float x, float e,
   return mean + c.nzsigma * z;
 }
 
-// x_prev may alias x (every element is read before its own store), so neither is __restrict__.  n4 float4 groups, then the
-// scalar rest [4 n4, total); the host passes n4 = 0 when a pointer is not 16-byte aligned.  A float4 that straddles a sample
-// boundary looks its coefficients up per element.  Guided (see cfg_cond): x == x_prev is the stacked state, read at the
-// conditional copy and stored to both; eps and t are stacked; z and pred_xstart are B rows.
+struct ddim_op {
+  const float* tab;
+  int nsteps;
+  float eta;
+  int clip;
+  __device__ ddim_coef at(int64_t t) const { return ddim_coef_at(tab, nsteps, t, eta); }
+  __device__ bool reads_aux(const ddim_coef&) const { return true; }
+  __device__ float elem(const ddim_coef& c, float x, float e, float z, float* x0_out) const {
+    return ddim_elem(c, x, e, z, clip, x0_out);
+  }
+};
+
+// z (NULL at eta == 0) and pred_xstart are B rows.
 template <bool CFG>
 __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const float* __restrict__ eps,
                                                         const float* __restrict__ z, const int64_t* __restrict__ t,
                                                         const float* __restrict__ tab, int nsteps, int64_t per_sample,
                                                         int64_t total, int64_t n4, float eta, int clip, float scale, int64_t gp,
                                                         float* x_prev, float* __restrict__ pred_xstart) {
-  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = tid; i < n4; i += stride) {
-    const int64_t oc = cfg_cond<CFG>(4 * i, gp);
-    const float4 xv = *reinterpret_cast<const float4*>(x + oc), ev = eps4_at<CFG>(eps, oc, gp, scale);
-    const float4 zv = z ? reinterpret_cast<const float4*>(z)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w}, zs[4] = {zv.x, zv.y, zv.z, zv.w};
-    float o[4], p[4];
-    const int64_t s0 = oc / per_sample, s3 = (oc + 3) / per_sample;
-    if (s0 == s3) {
-      const ddim_coef c = ddim_coef_at(tab, nsteps, t[s0], eta);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = ddim_elem(c, xs[k], es[k], zs[k], clip, &p[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        o[k] = ddim_elem(ddim_coef_at(tab, nsteps, t[(oc + k) / per_sample], eta), xs[k], es[k], zs[k], clip, &p[k]);
-    }
-    if (pred_xstart) reinterpret_cast<float4*>(pred_xstart)[i] = make_float4(p[0], p[1], p[2], p[3]);
-    const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
-    *reinterpret_cast<float4*>(x_prev + oc) = ov;
-    if constexpr (CFG) *reinterpret_cast<float4*>(x_prev + oc + gp) = ov;
-  }
-  for (int64_t i = 4 * n4 + tid; i < total; i += stride) {
-    const int64_t oc = cfg_cond<CFG>(i, gp);
-    float p;
-    const float o = ddim_elem(ddim_coef_at(tab, nsteps, t[oc / per_sample], eta), x[oc], eps_at<CFG>(eps, oc, gp, scale),
-                              z ? z[i] : 0.f, clip, &p);
-    if (pred_xstart) pred_xstart[i] = p;
-    x_prev[oc] = o;
-    if constexpr (CFG) x_prev[oc + gp] = o;
-  }
+  step_stream<CFG>(ddim_op{tab, nsteps, eta, clip}, x, eps, z, t, per_sample, total, n4, scale, gp, x_prev, pred_xstart);
 }
 
 // ---- second-order few-step sampling: the DPM-Solver++(2M) update, data prediction, multistep ----
@@ -253,48 +252,23 @@ __device__ __forceinline__ float dpm_elem(const dpm_coef& c, float x, float e, f
   return r;
 }
 
-// In place on x and on hist.  n4 float4 groups, then the scalar rest [4 n4, total); the host passes n4 = 0 when a pointer is not
-// 16-byte aligned.  A float4 that straddles a sample boundary looks its coefficients (and its history) up per element.  Guided
-// (see cfg_cond): x is the stacked state, read at the conditional copy and stored to both; eps and t are stacked; hist is B rows.
+struct dpm_op {
+  const float* tab;
+  int nsteps, clip;
+  __device__ dpm_coef at(int64_t t) const { return dpm_coef_at(tab, nsteps, t); }
+  __device__ bool reads_aux(const dpm_coef& c) const { return c.c1 != 0.0f; }
+  __device__ float elem(const dpm_coef& c, float x, float e, float h, float* x0_out) const {
+    return dpm_elem(c, x, e, h, clip, x0_out);
+  }
+};
+
+// In place on x and on hist (B rows): the history is the stream's auxiliary input and its auxiliary output at once.
 template <bool CFG>
 __global__ __launch_bounds__(256) void dpm2m_step_kernel(float* x, const float* __restrict__ eps, float* __restrict__ hist,
                                                          const int64_t* __restrict__ t, const float* __restrict__ tab,
                                                          int nsteps, int64_t per_sample, int64_t total, int64_t n4, int clip,
                                                          float scale, int64_t gp) {
-  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = tid; i < n4; i += stride) {
-    const int64_t oc = cfg_cond<CFG>(4 * i, gp);
-    const float4 xv = *reinterpret_cast<const float4*>(x + oc), ev = eps4_at<CFG>(eps, oc, gp, scale);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, es[4] = {ev.x, ev.y, ev.z, ev.w};
-    float o[4], p[4];
-    const int64_t s0 = oc / per_sample, s3 = (oc + 3) / per_sample;
-    if (s0 == s3) {
-      const dpm_coef c = dpm_coef_at(tab, nsteps, t[s0]);
-      const float4 hv = c.c1 != 0.0f ? reinterpret_cast<const float4*>(hist)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-      const float hs[4] = {hv.x, hv.y, hv.z, hv.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = dpm_elem(c, xs[k], es[k], hs[k], clip, &p[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const dpm_coef c = dpm_coef_at(tab, nsteps, t[(oc + k) / per_sample]);
-        o[k] = dpm_elem(c, xs[k], es[k], c.c1 != 0.0f ? hist[4 * i + k] : 0.f, clip, &p[k]);
-      }
-    }
-    reinterpret_cast<float4*>(hist)[i] = make_float4(p[0], p[1], p[2], p[3]);
-    const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
-    *reinterpret_cast<float4*>(x + oc) = ov;
-    if constexpr (CFG) *reinterpret_cast<float4*>(x + oc + gp) = ov;
-  }
-  for (int64_t i = 4 * n4 + tid; i < total; i += stride) {
-    const int64_t oc = cfg_cond<CFG>(i, gp);
-    const dpm_coef c = dpm_coef_at(tab, nsteps, t[oc / per_sample]);
-    float p;
-    const float o = dpm_elem(c, x[oc], eps_at<CFG>(eps, oc, gp, scale), c.c1 != 0.0f ? hist[i] : 0.f, clip, &p);
-    hist[i] = p;
-    x[oc] = o;
-    if constexpr (CFG) x[oc + gp] = o;
-  }
+  step_stream<CFG>(dpm_op{tab, nsteps, clip}, x, eps, hist, t, per_sample, total, n4, scale, gp, x, hist);
 }
 
 // t[b] -= 1; t_model[b] = map[t[b]] with the index held inside the map (after the last step t = -1 reads map[0]).
@@ -636,35 +610,51 @@ extern "C" int hig_q_sample(const float* x0, const float* noise, const int64_t* 
   return HIG_OK;
 }
 
-extern "C" int hig_p_sample_step(const float* x, const float* eps, const float* z, const int64_t* t,
-                                 const float* tab, int32_t nsteps, int32_t B, int64_t per_sample,
-                                 float* x_prev, float* pred_xstart, hig_stream_t s) {
-  HIG_REQUIRE(x && eps && z && t && tab && x_prev && B > 0 && per_sample > 0, "hig_p_sample_step: bad arguments");
-  const int64_t total = (int64_t)B * per_sample;
-  hipLaunchKernelGGL(p_step_kernel<false>, dim3(stream_blocks(total)), dim3(256), 0, hig_stream(s), x, eps, z, t,
-                     tab, nsteps, per_sample, total, (int64_t)0, 0.0f, (int64_t)0, x_prev, pred_xstart);
-  HIG_CHECK_LAUNCH();
-  return HIG_OK;
-}
-
-// ---- classifier-free guidance: the entries over the stacked layout (cfg_cond) ----
+// ---- the sampler entries: the three fused updates, the imposition and the combine, unguided and over the stacked layout ----
 namespace {
 bool cfg_shape_ok(float scale, int32_t nsteps, int32_t B, int32_t group, int64_t per_sample) {
   return nsteps > 0 && B > 0 && group > 0 && per_sample > 0 && B % group == 0 && fabsf(scale) <= 3.402823466e+38f;   // (NaN fails)
 }
-// float4 groups of the B-row view: all of them when every base pointer is 16-byte aligned and a group of four cannot leave
-// its block of the layout (gp % 4 == 0, which makes total a multiple of 4 as well), none otherwise.
-int64_t cfg_n4(uintptr_t bits, int64_t gp, int64_t total) { return (bits & 15) == 0 && gp % 4 == 0 ? total / 4 : 0; }
-int64_t cfg_work(int64_t n4, int64_t total) { return n4 > total - 4 * n4 ? n4 : total - 4 * n4; }
+
+template <class... P> uintptr_t ptr_bits(const P*... p) { return (reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0); }
+
+// The extent and the launch shape of one stream over B rows of per_sample elements (both > 0, checked by the caller); group > 0:
+// the stacked layout of 2 B rows in blocks of `group`, group == 0: unguided (gp = 0).  n4, the float4 groups of the B-row view:
+// all of them when every base pointer is 16-byte aligned (`bits`), the entry's own condition `vec_ok` holds and a group of four
+// cannot leave its block of the layout (gp % 4 == 0, which makes total a multiple of 4 as well), none otherwise.  Refuses an
+// extent whose last index, 2 B per_sample - 1 when stacked, does not fit an int64.
+struct stream_plan { int64_t total, gp, n4; int grid; };
+
+int plan_stream(const char* who, uintptr_t bits, bool vec_ok, int32_t B, int32_t group, int64_t per_sample, stream_plan* p) {
+  HIG_REQUIRE(per_sample <= INT64_MAX / ((int64_t)B * (group > 0 ? 2 : 1)),
+              "%s: %d%s rows of %lld elements overflow the index", who, B, group > 0 ? " x 2" : "", (long long)per_sample);
+  p->total = (int64_t)B * per_sample;
+  p->gp = (int64_t)group * per_sample;
+  p->n4 = (bits & 15) == 0 && vec_ok && p->gp % 4 == 0 ? p->total / 4 : 0;
+  const int64_t rest = p->total - 4 * p->n4;
+  p->grid = stream_blocks(p->n4 > rest ? p->n4 : rest);
+  return HIG_OK;
+}
 }  // namespace
+
+extern "C" int hig_p_sample_step(const float* x, const float* eps, const float* z, const int64_t* t,
+                                 const float* tab, int32_t nsteps, int32_t B, int64_t per_sample,
+                                 float* x_prev, float* pred_xstart, hig_stream_t s) {
+  HIG_REQUIRE(x && eps && z && t && tab && x_prev && B > 0 && per_sample > 0, "hig_p_sample_step: bad arguments");
+  stream_plan p;
+  HIG_TRY(plan_stream("hig_p_sample_step", 0, false, B, 0, per_sample, &p));   // (the scalar stream it has always been)
+  hipLaunchKernelGGL(p_step_kernel<false>, dim3(p.grid), dim3(256), 0, hig_stream(s), x, eps, z, t, tab, nsteps, per_sample,
+                     p.total, p.n4, 0.0f, p.gp, x_prev, pred_xstart);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
 
 extern "C" int hig_cfg_combine(const float* eps2, float scale, int32_t B, int32_t group, int64_t per_sample, float* eps_out,
                                hig_stream_t s) {
   HIG_REQUIRE(eps2 && eps_out && cfg_shape_ok(scale, 1, B, group, per_sample), "hig_cfg_combine: bad arguments");
-  const int64_t total = (int64_t)B * per_sample, gp = (int64_t)group * per_sample;
-  const int64_t n4 = cfg_n4(reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(eps_out), gp, total);
-  hipLaunchKernelGGL(cfg_combine_kernel, dim3(stream_blocks(cfg_work(n4, total))), dim3(256), 0, hig_stream(s), eps2, scale, gp,
-                     total, n4, eps_out);
+  stream_plan p;
+  HIG_TRY(plan_stream("hig_cfg_combine", ptr_bits(eps2, eps_out), true, B, group, per_sample, &p));
+  hipLaunchKernelGGL(cfg_combine_kernel, dim3(p.grid), dim3(256), 0, hig_stream(s), eps2, scale, p.gp, p.total, p.n4, eps_out);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -674,11 +664,10 @@ extern "C" int hig_p_sample_step_cfg(float* xx, const float* eps2, float scale, 
                                      float* pred_xstart, hig_stream_t s) {
   HIG_REQUIRE(xx && eps2 && z && t2 && tab && cfg_shape_ok(scale, nsteps, B, group, per_sample),
               "hig_p_sample_step_cfg: bad arguments");
-  const int64_t total = (int64_t)B * per_sample, gp = (int64_t)group * per_sample;
-  const int64_t n4 = cfg_n4(reinterpret_cast<uintptr_t>(xx) | reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(z) |
-                                reinterpret_cast<uintptr_t>(pred_xstart), gp, total);
-  hipLaunchKernelGGL(p_step_kernel<true>, dim3(stream_blocks(cfg_work(n4, total))), dim3(256), 0, hig_stream(s), xx, eps2, z, t2,
-                     tab, nsteps, per_sample, total, n4, scale, gp, xx, pred_xstart);
+  stream_plan p;
+  HIG_TRY(plan_stream("hig_p_sample_step_cfg", ptr_bits(xx, eps2, z, pred_xstart), true, B, group, per_sample, &p));
+  hipLaunchKernelGGL(p_step_kernel<true>, dim3(p.grid), dim3(256), 0, hig_stream(s), xx, eps2, z, t2, tab, nsteps, per_sample,
+                     p.total, p.n4, scale, p.gp, xx, pred_xstart);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -689,13 +678,11 @@ extern "C" int hig_ddim_step_cfg(float* xx, const float* eps2, float scale, cons
   HIG_REQUIRE(xx && eps2 && t2 && tab && cfg_shape_ok(scale, nsteps, B, group, per_sample), "hig_ddim_step_cfg: bad arguments");
   HIG_REQUIRE(eta >= 0.0f && eta <= 3.402823466e+38f, "hig_ddim_step_cfg: eta must be a finite number >= 0 (got %g)", (double)eta);
   HIG_REQUIRE(z || eta == 0.0f, "hig_ddim_step_cfg: z may be NULL only when eta == 0");
-  const int64_t total = (int64_t)B * per_sample, gp = (int64_t)group * per_sample;
-  const int64_t n4 = cfg_n4(reinterpret_cast<uintptr_t>(xx) | reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(z) |
-                                reinterpret_cast<uintptr_t>(pred_xstart), gp, total);
+  stream_plan p;
+  HIG_TRY(plan_stream("hig_ddim_step_cfg", ptr_bits(xx, eps2, z, pred_xstart), true, B, group, per_sample, &p));
   // eta == 0 never reads z (sigma = 0 multiplies a literal zero instead)
-  hipLaunchKernelGGL(ddim_step_kernel<true>, dim3(stream_blocks(cfg_work(n4, total))), dim3(256), 0, hig_stream(s), xx, eps2,
-                     eta == 0.0f ? nullptr : z, t2, tab, nsteps, per_sample, total, n4, eta, clip_denoised ? 1 : 0, scale, gp, xx,
-                     pred_xstart);
+  hipLaunchKernelGGL(ddim_step_kernel<true>, dim3(p.grid), dim3(256), 0, hig_stream(s), xx, eps2, eta == 0.0f ? nullptr : z, t2,
+                     tab, nsteps, per_sample, p.total, p.n4, eta, clip_denoised ? 1 : 0, scale, p.gp, xx, pred_xstart);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -705,11 +692,10 @@ extern "C" int hig_impose_known_cfg(float* xx, const float* known, const uint8_t
                                     hig_stream_t s) {
   HIG_REQUIRE(xx && known && mask && z && t2 && tab && cfg_shape_ok(0.0f, nsteps, B, group, per_sample),
               "hig_impose_known_cfg: bad arguments");
-  const int64_t total = (int64_t)B * per_sample, gp = (int64_t)group * per_sample;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(xx) | reinterpret_cast<uintptr_t>(known) | reinterpret_cast<uintptr_t>(z);
-  const int64_t n4 = (reinterpret_cast<uintptr_t>(mask) & 3) == 0 ? cfg_n4(bits, gp, total) : 0;
-  hipLaunchKernelGGL(impose_known_kernel<true>, dim3(stream_blocks(cfg_work(n4, total))), dim3(256), 0, hig_stream(s), xx, known,
-                     mask, z, t2, tab, nsteps, per_sample, total, n4, gp);
+  stream_plan p;
+  HIG_TRY(plan_stream("hig_impose_known_cfg", ptr_bits(xx, known, z), (ptr_bits(mask) & 3) == 0, B, group, per_sample, &p));
+  hipLaunchKernelGGL(impose_known_kernel<true>, dim3(p.grid), dim3(256), 0, hig_stream(s), xx, known, mask, z, t2, tab, nsteps,
+                     per_sample, p.total, p.n4, p.gp);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -727,15 +713,11 @@ extern "C" int hig_ddim_step(const float* x, const float* eps, const float* z, c
   HIG_REQUIRE(x && eps && t && tab && x_prev && B > 0 && per_sample > 0 && nsteps > 0, "hig_ddim_step: bad arguments");
   HIG_REQUIRE(eta >= 0.0f && eta <= 3.402823466e+38f, "hig_ddim_step: eta must be a finite number >= 0 (got %g)", (double)eta);
   HIG_REQUIRE(z || eta == 0.0f, "hig_ddim_step: z may be NULL only when eta == 0");
-  const int64_t total = (int64_t)B * per_sample;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(z) |
-                         reinterpret_cast<uintptr_t>(x_prev) | reinterpret_cast<uintptr_t>(pred_xstart);
-  const int64_t n4 = (bits & 15) == 0 ? total / 4 : 0;
-  const int64_t work = n4 > total - 4 * n4 ? n4 : total - 4 * n4;
+  stream_plan p;
+  HIG_TRY(plan_stream("hig_ddim_step", ptr_bits(x, eps, z, x_prev, pred_xstart), true, B, 0, per_sample, &p));
   // eta == 0 never reads z (sigma = 0 multiplies a literal zero instead)
-  hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, eps,
-                     eta == 0.0f ? nullptr : z, t, tab, nsteps, per_sample, total, n4, eta, clip_denoised ? 1 : 0, 0.0f, (int64_t)0,
-                     x_prev, pred_xstart);
+  hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(p.grid), dim3(256), 0, hig_stream(s), x, eps, eta == 0.0f ? nullptr : z, t,
+                     tab, nsteps, per_sample, p.total, p.n4, eta, clip_denoised ? 1 : 0, 0.0f, p.gp, x_prev, pred_xstart);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -743,12 +725,10 @@ extern "C" int hig_ddim_step(const float* x, const float* eps, const float* z, c
 extern "C" int hig_dpm2m_step(float* x, const float* eps, float* hist, const int64_t* t, const float* tab, int32_t nsteps,
                               int32_t B, int64_t per_sample, int32_t clip_denoised, hig_stream_t s) {
   HIG_REQUIRE(x && eps && hist && t && tab && B > 0 && per_sample > 0 && nsteps > 0, "hig_dpm2m_step: bad arguments");
-  const int64_t total = (int64_t)B * per_sample;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(hist);
-  const int64_t n4 = (bits & 15) == 0 ? total / 4 : 0;
-  const int64_t work = n4 > total - 4 * n4 ? n4 : total - 4 * n4;
-  hipLaunchKernelGGL(dpm2m_step_kernel<false>, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, eps, hist, t, tab, nsteps,
-                     per_sample, total, n4, clip_denoised ? 1 : 0, 0.0f, (int64_t)0);
+  stream_plan p;
+  HIG_TRY(plan_stream("hig_dpm2m_step", ptr_bits(x, eps, hist), true, B, 0, per_sample, &p));
+  hipLaunchKernelGGL(dpm2m_step_kernel<false>, dim3(p.grid), dim3(256), 0, hig_stream(s), x, eps, hist, t, tab, nsteps,
+                     per_sample, p.total, p.n4, clip_denoised ? 1 : 0, 0.0f, p.gp);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -758,11 +738,10 @@ extern "C" int hig_dpm2m_step_cfg(float* xx, const float* eps2, float scale, flo
                                   hig_stream_t s) {
   HIG_REQUIRE(xx && eps2 && hist && t2 && tab && cfg_shape_ok(scale, nsteps, B, group, per_sample),
               "hig_dpm2m_step_cfg: bad arguments");
-  const int64_t total = (int64_t)B * per_sample, gp = (int64_t)group * per_sample;
-  const int64_t n4 = cfg_n4(reinterpret_cast<uintptr_t>(xx) | reinterpret_cast<uintptr_t>(eps2) | reinterpret_cast<uintptr_t>(hist),
-                            gp, total);
-  hipLaunchKernelGGL(dpm2m_step_kernel<true>, dim3(stream_blocks(cfg_work(n4, total))), dim3(256), 0, hig_stream(s), xx, eps2, hist,
-                     t2, tab, nsteps, per_sample, total, n4, clip_denoised ? 1 : 0, scale, gp);
+  stream_plan p;
+  HIG_TRY(plan_stream("hig_dpm2m_step_cfg", ptr_bits(xx, eps2, hist), true, B, group, per_sample, &p));
+  hipLaunchKernelGGL(dpm2m_step_kernel<true>, dim3(p.grid), dim3(256), 0, hig_stream(s), xx, eps2, hist, t2, tab, nsteps,
+                     per_sample, p.total, p.n4, clip_denoised ? 1 : 0, scale, p.gp);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
@@ -770,12 +749,10 @@ extern "C" int hig_dpm2m_step_cfg(float* xx, const float* eps2, float scale, flo
 extern "C" int hig_impose_known(float* x, const float* known, const uint8_t* mask, const float* z, const int64_t* t,
                                 const float* tab, int32_t nsteps, int32_t B, int64_t per_sample, hig_stream_t s) {
   HIG_REQUIRE(x && known && mask && z && t && tab && B > 0 && per_sample > 0 && nsteps > 0, "hig_impose_known: bad arguments");
-  const int64_t total = (int64_t)B * per_sample;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(known) | reinterpret_cast<uintptr_t>(z);
-  const int64_t n4 = (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0 ? total / 4 : 0;
-  const int64_t work = n4 > total - 4 * n4 ? n4 : total - 4 * n4;
-  hipLaunchKernelGGL(impose_known_kernel<false>, dim3(stream_blocks(work)), dim3(256), 0, hig_stream(s), x, known, mask, z, t,
-                     tab, nsteps, per_sample, total, n4, (int64_t)0);
+  stream_plan p;
+  HIG_TRY(plan_stream("hig_impose_known", ptr_bits(x, known, z), (ptr_bits(mask) & 3) == 0, B, 0, per_sample, &p));
+  hipLaunchKernelGGL(impose_known_kernel<false>, dim3(p.grid), dim3(256), 0, hig_stream(s), x, known, mask, z, t, tab, nsteps,
+                     per_sample, p.total, p.n4, p.gp);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

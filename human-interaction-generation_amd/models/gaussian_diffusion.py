@@ -25,6 +25,7 @@ Classifier-free guidance (not in the reference): a model wrapped in models/guida
 every sampler as any callable does; the captured loop keeps it (it is not stripped like a DDP wrapper) and runs the step on the
 stacked batch with hig_impose_known_cfg / hig_p_sample_step_cfg.  cond_fn (classifier guidance) still raises.
 """
+import collections
 import enum
 import math
 from abc import ABC, abstractmethod
@@ -190,6 +191,39 @@ def _pre_seq_as_known(pre_seq, shape, device):
     return known, mask
 
 
+# A fused update as the eager steps and the captured loop launch it: the unguided entry's name (the guided one is that name plus
+# "_cfg"); table(device), its fp32 coefficient table; whether it reads noise z; whether its auxiliary buffer is instead the
+# history of x0 estimates, read and rewritten in place (such an entry has no x_prev / pred_xstart arguments); and the scalars
+# that follow per_sample in its argument list.
+_Update = collections.namedtuple("_Update", "entry table needs_z history tail")
+
+
+def _launch_update(L, upd, x, eps, aux, t, tab, K, B, per, stream, scale=None, group=None, x_prev=None, pred=None):
+    """ONE launch of the fused update `upd` through the library handle L; every tensor argument is a device pointer already.
+        unguided (group None):  (x, eps, aux, t, tab, K, B, per, *tail, [x_prev, pred,] stream)
+        guided:                 (xx, eps2, scale, aux, t2, tab, K, B, group, per, *tail, [pred,] stream), in place on xx
+    aux is z (None where the update reads none) or the history; the bracketed outputs exist where upd.history is false."""
+    guided = group is not None
+    args = (x, eps) + ((scale,) if guided else ()) + (aux, t, tab, K, B) + ((group,) if guided else ()) + (per,) + tuple(upd.tail)
+    if not upd.history:
+        args += (pred,) if guided else (x_prev, pred)
+    _lib.check(getattr(L, upd.entry + ("_cfg" if guided else ""))(*args, stream))
+
+
+def _launch_impose_known(L, x, known, mask, z, t, tab, K, B, per, stream, group=None):
+    """ONE hig_impose_known launch (group None) or hig_impose_known_cfg launch (`group` goes in before per) through L."""
+    args = (x, known, mask, z, t, tab, K, B) + (() if group is None else (group,)) + (per, stream)
+    _lib.check(getattr(L, "hig_impose_known" + ("" if group is None else "_cfg"))(*args))
+
+
+def _last_sample(steps):
+    """The sample of the last step a *_loop_progressive generator yields."""
+    final = None
+    for final in steps:
+        pass
+    return final["sample"]
+
+
 class GaussianDiffusion:
     def __init__(self, *, betas, model_mean_type, model_var_type, loss_type, rescale_timesteps=False):
         if model_var_type in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE) or loss_type.is_vb():
@@ -239,6 +273,23 @@ class GaussianDiffusion:
 
     def _fused_ok(self, *tensors):
         return all(t.is_cuda and t.dtype == th.float32 for t in tensors)
+
+    device_map = None      # (SpacedDiffusion: device -> its timestep_map as an int64 tensor; None: the model sees the step itself)
+
+    def _p_update(self):
+        return _Update("hig_p_sample_step", self.device_table, True, False, ())
+
+    def _fused_update(self, upd, x, eps, aux, t, B, scale=None, group=None, x_prev=None, pred=None):
+        """ONE launch of `upd` on contiguous fp32 ROCm tensors of B samples (x, eps and t stacked to 2 B rows when guided)."""
+        P, rows = _lib.ptr, (B if group is None else 2 * B)
+        _launch_update(_lib.lib(), upd, P(x), P(eps), P(aux), P(t), P(upd.table(x.device)), self.num_timesteps, B,
+                       x.numel() // rows, _lib.stream_ptr(), scale, group, P(x_prev), P(pred))
+
+    def _impose_known(self, x, known, mask, z, t, B, group=None):
+        """ONE imposition launch on contiguous tensors of B samples, in place on x (x and t stacked to 2 B rows when guided)."""
+        P, rows = _lib.ptr, (B if group is None else 2 * B)
+        _launch_impose_known(_lib.lib(), P(x), P(known), P(mask), P(z), P(t), P(self.device_table(x.device)), self.num_timesteps,
+                             B, x.numel() // rows, _lib.stream_ptr(), group)
 
     # ---- q(x_t | x_0) ---------------------------------------------------------------------
     def q_mean_variance(self, x_start, t):
@@ -341,10 +392,7 @@ class GaussianDiffusion:
     def _launch_impose(self, x, known, mask, z, t):
         """ONE hig_impose_known launch on x in place (through a contiguous copy when x is a strided view)."""
         xc = x if x.is_contiguous() else x.contiguous()
-        kc, zc, t64, tab = known.contiguous(), z.contiguous(), t.long().contiguous(), self.device_table(x.device)
-        B = xc.shape[0]
-        _lib.check(_lib.lib().hig_impose_known(_lib.ptr(xc), _lib.ptr(kc), _lib.ptr(mask), _lib.ptr(zc), _lib.ptr(t64),
-                                              _lib.ptr(tab), self.num_timesteps, B, xc.numel() // B, _lib.stream_ptr()))
+        self._impose_known(xc, known.contiguous(), mask, z.contiguous(), t.long().contiguous(), xc.shape[0])
         if xc is not x:
             x.copy_(xc)
 
@@ -390,13 +438,10 @@ class GaussianDiffusion:
         if self._is_trainer_branch(clip_denoised, denoised_fn, cond_fn, pre_seq, transl_req) and self._fused_ok(x):
             eps = model(x, t, **(model_kwargs or {}))
             noise = th.randn_like(x)
-            xc, ec = x.contiguous(), eps.float().contiguous()
+            xc = x.contiguous()
             sample, pred = th.empty_like(xc), th.empty_like(xc)
-            B = xc.shape[0]
-            _lib.check(_lib.lib().hig_p_sample_step(
-                _lib.ptr(xc), _lib.ptr(ec), _lib.ptr(noise.contiguous()), _lib.ptr(t.long().contiguous()),
-                _lib.ptr(self.device_table(xc.device)), self.num_timesteps, B, xc.numel() // B,
-                _lib.ptr(sample), _lib.ptr(pred), _lib.stream_ptr()))
+            self._fused_update(self._p_update(), xc, eps.float().contiguous(), noise.contiguous(), t.long().contiguous(),
+                               xc.shape[0], x_prev=sample, pred=pred)
             return {"sample": sample, "pred_xstart": pred}
         out = self.p_mean_variance(model, x, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                    model_kwargs=model_kwargs)
@@ -405,29 +450,39 @@ class GaussianDiffusion:
         sample = out["mean"] + nonzero_mask * th.exp(0.5 * out["log_variance"]) * noise
         return {"sample": sample, "pred_xstart": out["pred_xstart"]}
 
+    def _graph_ok(self, core, model_kwargs):
+        """Whether a loop over `core` with these model_kwargs can be captured: our model, its text precomputed."""
+        return (self.use_hip_graph and hasattr(core, "_launch_forward") and model_kwargs is not None
+                and model_kwargs.get("xf_proj") is not None and model_kwargs.get("xf_out") is not None)
+
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, pre_seq=None, transl_req=None, progress=False, known=None,
                       known_mask=None):
         """gaussian_diffusion.py:668-716.  pre_seq / transl_req / known + known_mask: see p_sample; the captured loop takes
         pre_seq and known (one more launch per step), a call with transl_req runs eagerly."""
         core, cfg = _guided(model, model_kwargs)
-        if (self.use_hip_graph and hasattr(core, "_launch_forward") and model_kwargs is not None
-                and model_kwargs.get("xf_proj") is not None and model_kwargs.get("xf_out") is not None
-                and self._is_trainer_branch(clip_denoised, denoised_fn, cond_fn, pre_seq, transl_req)):
+        if self._graph_ok(core, model_kwargs) and self._is_trainer_branch(clip_denoised, denoised_fn, cond_fn, pre_seq, transl_req):
             known, known_mask = _known_args(shape, known, known_mask, pre_seq)
-            return self._p_sample_loop_graph(core, shape, noise, model_kwargs, device, known, known_mask, pre_seq, cfg)
-        final = None
-        for sample in self.p_sample_loop_progressive(
-                model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                cond_fn=cond_fn, model_kwargs=model_kwargs, device=device, pre_seq=pre_seq,
-                transl_req=transl_req, progress=progress, known=known, known_mask=known_mask):
-            final = sample
-        return final["sample"]
+            return self._captured_loop(core, shape, noise, model_kwargs, device, self._p_update(), self.device_map, known, known_mask,
+                                       pre_seq, cfg)
+        return _last_sample(self.p_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+            cond_fn=cond_fn, model_kwargs=model_kwargs, device=device, pre_seq=pre_seq,
+            transl_req=transl_req, progress=progress, known=known, known_mask=known_mask))
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                   cond_fn=None, model_kwargs=None, device=None, pre_seq=None,
                                   transl_req=None, progress=False, known=None, known_mask=None):
         """gaussian_diffusion.py:718-769: t = N-1 ... 0, fresh noise every step, no_grad."""
+        return self._loop_progressive(
+            lambda img, t, last, **cond: self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                                       cond_fn=cond_fn, model_kwargs=model_kwargs, pre_seq=pre_seq,
+                                                       transl_req=transl_req, **cond),
+            model, shape, noise, device, progress, known, known_mask, pre_seq, transl_req)
+
+    def _loop_progressive(self, step, model, shape, noise, device, progress, known, known_mask, pre_seq=None, transl_req=None):
+        """The eager loop of every sampler: t = num_timesteps - 1 ... 0 under no_grad, yielding step(img, t, last, **cond), where
+        `last` is what the step before yielded (None at the first) and cond the checked known + known_mask, if any."""
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
@@ -438,35 +493,44 @@ class GaussianDiffusion:
         if progress:
             from tqdm.auto import tqdm
             indices = tqdm(indices)
+        out = None
         for i in indices:
             t = th.tensor([i] * shape[0], device=device)
             with th.no_grad():
-                out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                    cond_fn=cond_fn, model_kwargs=model_kwargs, pre_seq=pre_seq,
-                                    transl_req=transl_req, **cond)
+                out = step(img, t, out, **cond)
                 yield out
                 img = out["sample"]
 
-    def _p_sample_loop_graph(self, core, shape, noise, model_kwargs, device, known=None, known_mask=None, pre_seq=None,
-                             cfg=None):
-        """The 1000-step loop as ONE captured hipGraph replayed num_timesteps times.
+    def _captured_loop(self, core, shape, noise, model_kwargs, device, upd, device_map, known=None, known_mask=None, pre_seq=None,
+                       cfg=None):
+        """Every sampler's loop as ONE captured hipGraph step replayed num_timesteps times.  `upd` is the fused update; with a
+        device_map (SpacedDiffusion's) the model is called at t_model = map[t_dev], the original timestep, and the counter is
+        hig_advance_timesteps (t -= 1, t_model = map[t]); with None it is called at t_dev itself and the counter is
+        hig_dec_timesteps.
 
-        Captured per step: denoiser forward (text context hoisted: it is step-invariant), fresh
-        Gaussian noise (torch's graph-safe Philox), the fused x_{t-1} update in place, and the
-        device-side `t -= 1`.  Nothing crosses PCIe inside the loop (the reference does ~8 H2D
-        copies and B device syncs per step).
+        Captured per step: denoiser forward (text context hoisted: it is step-invariant), fresh Gaussian noise where the update
+        reads any (torch's graph-safe Philox; DDIM at eta == 0 and dpmpp2m have no noise node and the update gets z = NULL), the
+        fused update in place, the counter.  Nothing crosses PCIe inside the loop (the reference does ~8 H2D copies and B device
+        syncs per step).  The warm-up step outside the graph builds the text context of this call's xf_out, whose
+        buffer the captured forward reads: the graph is not kept beyond the call.
 
         With known + known_mask (or pre_seq, turned into that pair) the step opens with the imposition:
-        zz.normal_() -> hig_impose_known(img, known, mask, zk, t_dev) -> forward -> update with z -> dec, where zk and z are
-        the two halves of ONE buffer drawn by a single normal_(): a conditioned step has one launch more, not two.
+            zz.normal_() -> hig_impose_known(state, known, mask, zk, t_dev, device_table) -> forward -> update with z -> counter
+        It reads t_dev, the index into this object's own table, not t_model.  zk (and z, where the update needs one) are parts of
+        ONE buffer drawn by a single normal_(): a conditioned step has one launch more than an unconditioned one with noise, two
+        more where the update reads no noise -- such a loop now draws noise and is no longer a pure function of its start.
 
-        cfg (a ClassifierFreeGuidedModel around `core`): the state, the step vector and the text inputs are kept in the stacked
-        layout of models/guidance.py (2 B rows, the two rows of a sample equal), the forward runs once at 2 B, and
-        hig_impose_known_cfg / hig_p_sample_step_cfg take the place of the unguided kernels: the same number of launches, noise
-        for B rows, and the B conditional rows returned."""
+        cfg (a ClassifierFreeGuidedModel around `core`): the state, the step vectors and the text inputs are kept in the stacked
+        layout of models/guidance.py (2 B rows, the two rows of a sample equal), the forward runs once at 2 B, the _cfg entries
+        take the place of the unguided kernels and the counter advances 2 B entries: launch for launch the unguided step, noise
+        for B rows, and the B conditional rows returned.
+
+        upd.history (dpmpp2m): `hist`, the x0 estimate of the step before, is one buffer of B rows (not stacked under guidance)
+        that the kernel reads and rewrites in place.  The first step never reads it, so what the warm-up leaves there is
+        harmless; it is cleared with the state all the same."""
         if device is None:
             device = next(core.parameters()).device
-        B = shape[0]
+        K, B = self.num_timesteps, shape[0]
         with th.no_grad():
             img = (noise.to(device).float().clone() if noise is not None
                    else th.randn(*shape, device=device)).contiguous()
@@ -477,51 +541,43 @@ class GaussianDiffusion:
                 length = th.full((B,), shape[1], dtype=th.int64, device=device)
             else:
                 length = th.as_tensor(length).to(device).long().contiguous()
+            guide = {}
             if cfg is not None:
                 group, xf_proj, xf_out, length = _stacked_inputs(cfg, B, xf_proj, xf_out, length)
                 state = stack_rows(img, img, group).contiguous()
+                guide = dict(scale=cfg.scale, group=group)
             else:
                 state = img
             rows = state.shape[0]
-            t_dev = th.full((rows,), self.num_timesteps - 1, dtype=th.int64, device=device)
-            tab = self.device_table(device)
-            L = _lib.lib()
-            per = img.numel() // B
+            tmap = None if device_map is None else device_map(device)
+            t_dev = th.full((rows,), K - 1, dtype=th.int64, device=device)
+            t_model = t_dev if tmap is None else tmap[t_dev]
+            hist = th.zeros_like(img) if upd.history else None
             if pre_seq is not None:
                 known, known_mask = _pre_seq_as_known(pre_seq.float(), img.shape, device)
             cond = known is not None
             if cond:
                 known = known.to(device).float().contiguous()
                 known_mask = known_mask.to(device).contiguous()
-                zz = th.zeros(2, *img.shape, device=device)
-                zk, z = zz[0], zz[1]
+                zz = th.zeros(2 if upd.needs_z else 1, *img.shape, device=device)
+                zk, z = zz[0], (zz[1] if upd.needs_z else None)
             else:
-                z = th.zeros_like(img)
+                z = th.zeros_like(img) if upd.needs_z else None
 
             def step():
                 if cond:
                     if not self._debug_zero_noise:
                         zz.normal_()
-                    if cfg is not None:
-                        _lib.check(L.hig_impose_known_cfg(_lib.ptr(state), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
-                                                          _lib.ptr(t_dev), _lib.ptr(tab), self.num_timesteps, B, group, per,
-                                                          _lib.stream_ptr()))
-                    else:
-                        _lib.check(L.hig_impose_known(_lib.ptr(img), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
-                                                      _lib.ptr(t_dev), _lib.ptr(tab), self.num_timesteps, B, per,
-                                                      _lib.stream_ptr()))
-                eps, _ = core._launch_forward(state, t_dev, length, xf_proj, xf_out, training=False)
-                if not cond and not self._debug_zero_noise:
+                    self._impose_known(state, known, known_mask, zk, t_dev, B, guide.get("group"))
+                eps, _ = core._launch_forward(state, t_model, length, xf_proj, xf_out, training=False)
+                if upd.needs_z and not cond and not self._debug_zero_noise:
                     z.normal_()
-                if cfg is not None:
-                    _lib.check(L.hig_p_sample_step_cfg(_lib.ptr(state), _lib.ptr(eps), cfg.scale, _lib.ptr(z), _lib.ptr(t_dev),
-                                                       _lib.ptr(tab), self.num_timesteps, B, group, per, None,
-                                                       _lib.stream_ptr()))
+                self._fused_update(upd, state, eps, hist if upd.history else z, t_dev, B, x_prev=state, **guide)
+                if tmap is None:
+                    _lib.check(_lib.lib().hig_dec_timesteps(_lib.ptr(t_dev), rows, _lib.stream_ptr()))
                 else:
-                    _lib.check(L.hig_p_sample_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(z), _lib.ptr(t_dev),
-                                                   _lib.ptr(tab), self.num_timesteps, B, per, _lib.ptr(img),
-                                                   None, _lib.stream_ptr()))
-                _lib.check(L.hig_dec_timesteps(_lib.ptr(t_dev), rows, _lib.stream_ptr()))
+                    _lib.check(_lib.lib().hig_advance_timesteps(_lib.ptr(t_dev), _lib.ptr(tmap), K, rows, _lib.ptr(t_model),
+                                                                _lib.stream_ptr()))
 
             # warm-up on a side stream (allocations, text context), then undo its effect
             img0 = state.clone()
@@ -531,12 +587,16 @@ class GaussianDiffusion:
                 step()
             th.cuda.current_stream().wait_stream(s)
             state.copy_(img0)
-            t_dev.fill_(self.num_timesteps - 1)
+            if upd.history:
+                hist.zero_()
+            t_dev.fill_(K - 1)
+            if tmap is not None:
+                t_model.copy_(tmap[t_dev])
             graph = th.cuda.CUDAGraph()
             with th.cuda.graph(graph, capture_error_mode="thread_local"):
                 step()
-            # capture does not execute: state is still (img0, N-1)
-            for _ in range(self.num_timesteps):
+            # capture does not execute: state is still (img0, K - 1)
+            for _ in range(K):
                 graph.replay()
         return state if cfg is None else split_rows(state, group)[0].contiguous()
 

@@ -14,7 +14,7 @@ row at 2 (b // group) group + b % group and its unconditional row `group` furthe
 
 `ClassifierFreeGuidedModel` is a callable with the model's signature and works with every sampler entry of GaussianDiffusion /
 SpacedDiffusion, on any device.  The captured loops recognise it and keep the whole state stacked instead (one fused
-hig_*_step_cfg per step, no combine launch): see `_p_sample_loop_graph` / `_spaced_loop_graph`.
+hig_*_step_cfg per step, no combine launch): see `GaussianDiffusion._captured_loop`.
 """
 import math
 

@@ -7,9 +7,9 @@
     step, int64), or that step scaled to [0, 1000) as a float when `rescale_timesteps`.
   * `p_sample` / `p_sample_loop` run the ancestral chain on the short schedule (the fused hig_p_sample_step with this
     object's own K-column table); `ddim_sample` / `ddim_sample_loop` run DDIM, fused as hig_ddim_step for fp32 ROCm tensors.
-  * Both loops are captured as one hipGraph step replayed K times when the model is our MotionTransformer: forward at the
-    mapped step, noise (no noise node at all when eta == 0), the update in place, hig_advance_timesteps.  The graph lives for
-    one call: it reads the text context the warm-up step built for THIS call's xf_out.
+  * Every loop is captured as one hipGraph step replayed K times when the model is our MotionTransformer: the base class's
+    _captured_loop, given this object's device_map -- forward at the mapped step, noise (no noise node at all when eta == 0),
+    the update in place, hig_advance_timesteps.  `p_sample_loop` itself is inherited.
 
   * Every sampler takes known-region conditioning (`known` + `known_mask`; the ancestral family also the reference's `pre_seq`
     / `transl_req`): the known part, noised to the level of this object's own step t, is written over the state before each
@@ -22,7 +22,7 @@
     host (`dpm_solver_coefficients`), and for fp32 ROCm tensors it is one kernel, hig_dpm2m_step, in place on the state and the
     history.  The two belong together: on the uniform-in-t selection the last steps are huge in log-SNR and the extrapolation
     overshoots there.  order=1 is DDIM at eta = 0 in other arithmetic.  The captured loop is the same single step replayed K
-    times (method "dpmpp2m"): no noise node, one history buffer of B rows.
+    times: no noise node, one history buffer of B rows.
 
 `GaussianDiffusion`'s four DDIM names still raise; `SpacedDiffusion(space_timesteps(N, N), ...)` is
 the unstrided DDIM sampler.
@@ -33,9 +33,7 @@ import numpy as np
 import torch as th
 
 from .. import _lib
-from .gaussian_diffusion import (GaussianDiffusion, ModelMeanType, _extract_into_tensor, _guided, _known_args,
-                                 _pre_seq_as_known, _stacked_inputs)
-from .guidance import split_rows, stack_rows
+from .gaussian_diffusion import GaussianDiffusion, ModelMeanType, _Update, _extract_into_tensor, _guided, _known_args, _last_sample
 
 _DDIM_TAB_ORDER = ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "alphas_cumprod", "alphas_cumprod_prev")
 
@@ -169,6 +167,10 @@ class SpacedDiffusion(GaussianDiffusion):
         return (self.model_mean_type == ModelMeanType.EPSILON and denoised_fn is None and cond_fn is None
                 and not self.rescale_timesteps)
 
+    def _ddim_update(self, eta, clip_denoised):
+        # eta == 0 reads no z: the eager step draws none and the captured loop has no noise node
+        return _Update("hig_ddim_step", self.ddim_table, eta != 0, False, (float(eta), int(bool(clip_denoised))))
+
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0,
                     known=None, known_mask=None):
         """gaussian_diffusion.py:771-819.  For fp32 ROCm tensors on the eps-prediction branch the whole update is ONE kernel
@@ -186,14 +188,10 @@ class SpacedDiffusion(GaussianDiffusion):
         if self._ddim_fused_ok(denoised_fn, cond_fn) and self._fused_ok(x):
             eps = self._wrap(model)(x, t, **(model_kwargs or {}))
             noise = th.randn_like(x).contiguous() if eta != 0 else None
-            xc, ec = x.contiguous(), eps.float().contiguous()
+            xc = x.contiguous()
             sample, pred = th.empty_like(xc), th.empty_like(xc)
-            B = xc.shape[0]
-            t64, tab = t.long().contiguous(), self.ddim_table(xc.device)    # (alive until the launch is enqueued)
-            _lib.check(_lib.lib().hig_ddim_step(
-                _lib.ptr(xc), _lib.ptr(ec), _lib.ptr(noise), _lib.ptr(t64),
-                _lib.ptr(tab), self.num_timesteps, B, xc.numel() // B, float(eta),
-                int(bool(clip_denoised)), _lib.ptr(sample), _lib.ptr(pred), _lib.stream_ptr()))
+            self._fused_update(self._ddim_update(eta, clip_denoised), xc, eps.float().contiguous(), noise, t.long().contiguous(),
+                               xc.shape[0], x_prev=sample, pred=pred)
             return {"sample": sample, "pred_xstart": pred}
         out = self.p_mean_variance(model, x, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                    model_kwargs=model_kwargs)
@@ -226,35 +224,19 @@ class SpacedDiffusion(GaussianDiffusion):
         core, cfg = _guided(model, model_kwargs)
         if self._graph_ok(core, model_kwargs) and self._ddim_fused_ok(denoised_fn, cond_fn):
             known, known_mask = _known_args(shape, known, known_mask, None)
-            return self._spaced_loop_graph(core, shape, noise, model_kwargs, device, "ddim", float(eta), clip_denoised,
-                                           known, known_mask, cfg=cfg)
-        final = None
-        for sample in self.ddim_sample_loop_progressive(
-                model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                model_kwargs=model_kwargs, device=device, progress=progress, eta=eta, known=known, known_mask=known_mask):
-            final = sample
-        return final["sample"]
+            return self._captured_loop(core, shape, noise, model_kwargs, device, self._ddim_update(eta, clip_denoised),
+                                       self.device_map, known, known_mask, cfg=cfg)
+        return _last_sample(self.ddim_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+            model_kwargs=model_kwargs, device=device, progress=progress, eta=eta, known=known, known_mask=known_mask))
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, eta=0.0, known=None, known_mask=None):
         """gaussian_diffusion.py:893-941: t = K-1 ... 0, no_grad."""
-        if device is None:
-            device = next(model.parameters()).device
-        assert isinstance(shape, (tuple, list))
-        known, known_mask = _known_args(shape, known, known_mask, None)    # (the mask is expanded once)
-        cond = {} if known is None else dict(known=known.to(device), known_mask=known_mask.to(device))
-        img = noise if noise is not None else th.randn(*shape, device=device)
-        indices = list(range(self.num_timesteps))[::-1]
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        for i in indices:
-            t = th.tensor([i] * shape[0], device=device)
-            with th.no_grad():
-                out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                       cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta, **cond)
-                yield out
-                img = out["sample"]
+        return self._loop_progressive(
+            lambda img, t, last, **cond: self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                                          cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta, **cond),
+            model, shape, noise, device, progress, known, known_mask)
 
     # ---- DPM-Solver++(2M) -------------------------------------------------------------------
     def dpm_solver_coefficients(self, order=2):
@@ -295,6 +277,10 @@ class SpacedDiffusion(GaussianDiffusion):
             self._dev_dpm_tabs[key] = th.from_numpy(tab).to(device).contiguous()
         return self._dev_dpm_tabs[key]
 
+    def _dpm_update(self, order, clip_denoised):
+        return _Update("hig_dpm2m_step", lambda device: self.dpm_solver_table(device, order), False, True,
+                       (int(bool(clip_denoised)),))
+
     def dpm_solver_sample(self, model, x, t, prev_xstart=None, order=2, clip_denoised=True, denoised_fn=None,
                           model_kwargs=None, known=None, known_mask=None, cond_fn=None):
         """One DPM-Solver++(2M) step: {"sample", "pred_xstart"}; pred_xstart (after denoised_fn and the clamp, as
@@ -317,13 +303,10 @@ class SpacedDiffusion(GaussianDiffusion):
         if (self._ddim_fused_ok(denoised_fn, cond_fn) and self._fused_ok(x)
                 and (prev_xstart is None or self._fused_ok(prev_xstart))):
             eps = self._wrap(model)(x, t, **(model_kwargs or {}))
-            sample, ec = x.contiguous().clone(), eps.float().contiguous()
+            sample = x.contiguous().clone()
             hist = th.empty_like(sample) if prev_xstart is None else prev_xstart.contiguous().clone()
-            B = sample.shape[0]
-            t64, tab = t.long().contiguous(), self.dpm_solver_table(sample.device, order)   # (alive until the launch is enqueued)
-            _lib.check(_lib.lib().hig_dpm2m_step(_lib.ptr(sample), _lib.ptr(ec), _lib.ptr(hist), _lib.ptr(t64), _lib.ptr(tab),
-                                                 self.num_timesteps, B, sample.numel() // B, int(bool(clip_denoised)),
-                                                 _lib.stream_ptr()))
+            self._fused_update(self._dpm_update(order, clip_denoised), sample, eps.float().contiguous(), hist,
+                               t.long().contiguous(), sample.shape[0])
             return {"sample": sample, "pred_xstart": hist}
         out = self.p_mean_variance(model, x, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                    model_kwargs=model_kwargs)
@@ -344,177 +327,18 @@ class SpacedDiffusion(GaussianDiffusion):
         if self._graph_ok(core, model_kwargs) and self._ddim_fused_ok(denoised_fn, cond_fn):
             self.dpm_solver_coefficients(order)
             known, known_mask = _known_args(shape, known, known_mask, None)
-            return self._spaced_loop_graph(core, shape, noise, model_kwargs, device, "dpmpp2m", 0.0, clip_denoised,
-                                           known, known_mask, cfg=cfg, order=order)
-        final = None
-        for sample in self.dpm_solver_sample_loop_progressive(
-                model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                model_kwargs=model_kwargs, device=device, progress=progress, order=order, known=known,
-                known_mask=known_mask):
-            final = sample
-        return final["sample"]
+            return self._captured_loop(core, shape, noise, model_kwargs, device, self._dpm_update(order, clip_denoised),
+                                       self.device_map, known, known_mask, cfg=cfg)
+        return _last_sample(self.dpm_solver_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+            model_kwargs=model_kwargs, device=device, progress=progress, order=order, known=known, known_mask=known_mask))
 
     def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                            cond_fn=None, model_kwargs=None, device=None, progress=False, order=2,
                                            known=None, known_mask=None):
         """t = K-1 ... 0, no_grad; yields every step's {"sample", "pred_xstart"}."""
-        if device is None:
-            device = next(model.parameters()).device
-        assert isinstance(shape, (tuple, list))
-        known, known_mask = _known_args(shape, known, known_mask, None)    # (the mask is expanded once)
-        cond = {} if known is None else dict(known=known.to(device), known_mask=known_mask.to(device))
-        img = noise if noise is not None else th.randn(*shape, device=device)
-        indices = list(range(self.num_timesteps))[::-1]
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        prev = None
-        for i in indices:
-            t = th.tensor([i] * shape[0], device=device)
-            with th.no_grad():
-                out = self.dpm_solver_sample(model, img, t, prev_xstart=prev, order=order, clip_denoised=clip_denoised,
-                                             denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, **cond)
-                yield out
-                img, prev = out["sample"], out["pred_xstart"]
-
-    # ---- captured loops -----------------------------------------------------------------------
-    def _graph_ok(self, core, model_kwargs):
-        return (self.use_hip_graph and hasattr(core, "_launch_forward") and model_kwargs is not None
-                and model_kwargs.get("xf_proj") is not None and model_kwargs.get("xf_out") is not None)
-
-    def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                      model_kwargs=None, device=None, pre_seq=None, transl_req=None, progress=False, known=None,
-                      known_mask=None):
-        """The ancestral chain over the K kept steps; captured under the base class's conditions (pre_seq and known +
-        known_mask stay on the captured path, transl_req runs eagerly)."""
-        core, cfg = _guided(model, model_kwargs)
-        if (self._graph_ok(core, model_kwargs)
-                and self._is_trainer_branch(clip_denoised, denoised_fn, cond_fn, pre_seq, transl_req)):
-            known, known_mask = _known_args(shape, known, known_mask, pre_seq)
-            return self._spaced_loop_graph(core, shape, noise, model_kwargs, device, "ddpm", 0.0, False, known, known_mask,
-                                           pre_seq, cfg)
-        final = None
-        for sample in self.p_sample_loop_progressive(
-                model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                model_kwargs=model_kwargs, device=device, pre_seq=pre_seq, transl_req=transl_req, progress=progress,
-                known=known, known_mask=known_mask):
-            final = sample
-        return final["sample"]
-
-    def _spaced_loop_graph(self, core, shape, noise, model_kwargs, device, method, eta, clip_denoised, known=None,
-                           known_mask=None, pre_seq=None, cfg=None, order=2):
-        """One captured step replayed num_timesteps times: denoiser forward at the ORIGINAL timestep (t_model), fresh noise
-        (ancestral, or DDIM with eta > 0: at eta == 0 the graph has no noise node and the update gets z = NULL), the update in
-        place, then hig_advance_timesteps (t -= 1, t_model = map[t]).  The warm-up step outside the graph builds the text
-        context of this call's xf_out, whose buffer the captured forward reads: the graph is not kept beyond the call.
-        With known + known_mask (or pre_seq, turned into that pair) the step becomes
-            zz.normal_() -> hig_impose_known(img, known, mask, zk, t_dev, device_table) -> forward -> update with z -> advance
-        The imposition reads t_dev, the index into this object's own K-column table, not t_model.  zk (and z, where the update
-        needs one) are parts of ONE buffer drawn by a single normal_(): a conditioned step has one launch more than an
-        unconditioned one with noise, two more at DDIM eta == 0 -- which now draws noise and is no longer a pure function of
-        its start.
-        cfg (a ClassifierFreeGuidedModel around `core`): the state, both step vectors and the text inputs are kept in the stacked
-        layout of models/guidance.py (2 B rows, the two rows of a sample equal); the forward runs once at 2 B and
-        hig_impose_known_cfg / hig_ddim_step_cfg / hig_p_sample_step_cfg take the place of the unguided kernels, the counter
-        advances 2 B entries: launch for launch the unguided step, noise for B rows, the B conditional rows returned.
-        method "dpmpp2m": the update is hig_dpm2m_step[_cfg] with the table of `order`; no noise node (a known region still
-        draws zk); `hist`, the x0 estimate of the step before, is one buffer of B rows (not stacked under guidance) that the
-        kernel reads and rewrites in place.  Step K-1 never reads it, so what the warm-up leaves there is harmless; it is
-        cleared with the state all the same."""
-        if device is None:
-            device = next(core.parameters()).device
-        K, B = self.num_timesteps, shape[0]
-        with th.no_grad():
-            img = (noise.to(device).float().clone() if noise is not None
-                   else th.randn(*shape, device=device)).contiguous()
-            xf_proj = model_kwargs["xf_proj"].detach().float().contiguous()
-            xf_out = model_kwargs["xf_out"].detach().float().contiguous()
-            length = model_kwargs.get("length")
-            if length is None:
-                length = th.full((B,), shape[1], dtype=th.int64, device=device)
-            else:
-                length = th.as_tensor(length).to(device).long().contiguous()
-            if cfg is not None:
-                group, xf_proj, xf_out, length = _stacked_inputs(cfg, B, xf_proj, xf_out, length)
-                state = stack_rows(img, img, group).contiguous()
-            else:
-                state = img
-            rows = state.shape[0]
-            tmap = self.device_map(device)
-            t_dev = th.full((rows,), K - 1, dtype=th.int64, device=device)
-            t_model = th.full((rows,), self.timestep_map[K - 1], dtype=th.int64, device=device)
-            if method not in ("ddpm", "ddim", "dpmpp2m"):
-                raise ValueError("_spaced_loop_graph: unknown method %r" % (method,))
-            ddim, dpm = method == "ddim", method == "dpmpp2m"
-            needs_z = method == "ddpm" or (ddim and eta != 0)
-            tab = (self.dpm_solver_table(device, order) if dpm else self.ddim_table(device) if ddim
-                   else self.device_table(device))
-            hist = th.zeros_like(img) if dpm else None
-            L = _lib.lib()
-            per = img.numel() // B
-            if pre_seq is not None:
-                known, known_mask = _pre_seq_as_known(pre_seq.float(), img.shape, device)
-            cond = known is not None
-            if cond:
-                known = known.to(device).float().contiguous()
-                known_mask = known_mask.to(device).contiguous()
-                qtab = self.device_table(device)
-                zz = th.zeros(2 if needs_z else 1, *img.shape, device=device)
-                zk, z = zz[0], (zz[1] if needs_z else None)
-            else:
-                z = th.zeros_like(img) if needs_z else None
-
-            def step():
-                if cond:
-                    if not self._debug_zero_noise:
-                        zz.normal_()
-                    if cfg is not None:
-                        _lib.check(L.hig_impose_known_cfg(_lib.ptr(state), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
-                                                          _lib.ptr(t_dev), _lib.ptr(qtab), K, B, group, per, _lib.stream_ptr()))
-                    else:
-                        _lib.check(L.hig_impose_known(_lib.ptr(img), _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(zk),
-                                                      _lib.ptr(t_dev), _lib.ptr(qtab), K, B, per, _lib.stream_ptr()))
-                eps, _ = core._launch_forward(state, t_model, length, xf_proj, xf_out, training=False)
-                if needs_z and not cond and not self._debug_zero_noise:
-                    z.normal_()
-                if dpm and cfg is not None:
-                    _lib.check(L.hig_dpm2m_step_cfg(_lib.ptr(state), _lib.ptr(eps), cfg.scale, _lib.ptr(hist), _lib.ptr(t_dev),
-                                                    _lib.ptr(tab), K, B, group, per, int(bool(clip_denoised)), _lib.stream_ptr()))
-                elif dpm:
-                    _lib.check(L.hig_dpm2m_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(hist), _lib.ptr(t_dev), _lib.ptr(tab), K, B,
-                                                per, int(bool(clip_denoised)), _lib.stream_ptr()))
-                elif cfg is not None and ddim:
-                    _lib.check(L.hig_ddim_step_cfg(_lib.ptr(state), _lib.ptr(eps), cfg.scale, _lib.ptr(z), _lib.ptr(t_dev),
-                                                   _lib.ptr(tab), K, B, group, per, eta, int(bool(clip_denoised)), None,
-                                                   _lib.stream_ptr()))
-                elif cfg is not None:
-                    _lib.check(L.hig_p_sample_step_cfg(_lib.ptr(state), _lib.ptr(eps), cfg.scale, _lib.ptr(z), _lib.ptr(t_dev),
-                                                       _lib.ptr(tab), K, B, group, per, None, _lib.stream_ptr()))
-                elif ddim:
-                    _lib.check(L.hig_ddim_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(z), _lib.ptr(t_dev), _lib.ptr(tab), K, B,
-                                               per, eta, int(bool(clip_denoised)), _lib.ptr(img), None, _lib.stream_ptr()))
-                else:
-                    _lib.check(L.hig_p_sample_step(_lib.ptr(img), _lib.ptr(eps), _lib.ptr(z), _lib.ptr(t_dev), _lib.ptr(tab),
-                                                   K, B, per, _lib.ptr(img), None, _lib.stream_ptr()))
-                _lib.check(L.hig_advance_timesteps(_lib.ptr(t_dev), _lib.ptr(tmap), K, rows, _lib.ptr(t_model),
-                                                   _lib.stream_ptr()))
-
-            # warm-up on a side stream (allocations, text context), then undo its effect
-            img0 = state.clone()
-            s = th.cuda.Stream()
-            s.wait_stream(th.cuda.current_stream())
-            with th.cuda.stream(s):
-                step()
-            th.cuda.current_stream().wait_stream(s)
-            state.copy_(img0)
-            if dpm:
-                hist.zero_()
-            t_dev.fill_(K - 1)
-            t_model.fill_(self.timestep_map[K - 1])
-            graph = th.cuda.CUDAGraph()
-            with th.cuda.graph(graph, capture_error_mode="thread_local"):
-                step()
-            # capture does not execute: state is still (img0, K-1)
-            for _ in range(K):
-                graph.replay()
-        return state if cfg is None else split_rows(state, group)[0].contiguous()
+        return self._loop_progressive(
+            lambda img, t, last, **cond: self.dpm_solver_sample(
+                model, img, t, prev_xstart=None if last is None else last["pred_xstart"], order=order,
+                clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, **cond),
+            model, shape, noise, device, progress, known, known_mask)

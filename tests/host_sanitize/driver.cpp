@@ -286,6 +286,68 @@ int main() {
     EXPECT(hig_denoiser_plan(nullptr, 0, 0, 0, 0, 0, 256, 1, nullptr, out, NS) == HIG_EINVAL);
     EXPECT(hig_denoiser_last_schedule(out, NS) == -1 && hig_denoiser_last_schedule(nullptr, 0) == -1);       // no entry point has run here
   }
+  // ---- sampler entries (ddpm.hip): the fused updates, the impositions and the combine.  Every call below is refused, and a
+  // refusal returns before any HIP call; the pointers are made up, nothing may read through them.  The last case is an extent
+  // B * per_sample (twice that over the stacked layout) that does not fit an int64: refused, not computed.  (hig_p_sample_step
+  // does not look at nsteps, hig_cfg_combine has none.) ----
+  {
+    struct A { float* p[5]; uint8_t* mask; float scale, eta; int32_t nsteps, B, group; int64_t per; };   // p: x, eps | known, aux, t, tab
+    enum { X = 0, EPS, AUX, T, TAB, NP, MASK = NP };
+    const uintptr_t base = (uintptr_t)1 << 32;
+    A good;
+    for (int i = 0; i < NP; ++i) good.p[i] = reinterpret_cast<float*>(base * (i + 1));
+    good.mask = reinterpret_cast<uint8_t*>(base * 7);
+    good.scale = 2.5f; good.eta = 0.5f; good.nsteps = 10; good.B = 4; good.group = 2; good.per = 6;
+    struct E { const char* name; int (*call)(const A&); unsigned required; bool guided, has_scale, has_eta, checks_nsteps; };
+    const unsigned all = (1u << NP) - 1;
+    const E entries[] = {
+        {"hig_p_sample_step", [](const A& a) { return hig_p_sample_step(a.p[X], a.p[EPS], a.p[AUX], reinterpret_cast<const int64_t*>(a.p[T]), a.p[TAB], a.nsteps, a.B, a.per, a.p[X], nullptr, nullptr); }, all, false, false, false, false},
+        {"hig_p_sample_step_cfg", [](const A& a) { return hig_p_sample_step_cfg(a.p[X], a.p[EPS], a.scale, a.p[AUX], reinterpret_cast<const int64_t*>(a.p[T]), a.p[TAB], a.nsteps, a.B, a.group, a.per, nullptr, nullptr); }, all, true, true, false, true},
+        {"hig_ddim_step", [](const A& a) { return hig_ddim_step(a.p[X], a.p[EPS], a.p[AUX], reinterpret_cast<const int64_t*>(a.p[T]), a.p[TAB], a.nsteps, a.B, a.per, a.eta, 1, a.p[X], nullptr, nullptr); }, all, false, false, true, true},
+        {"hig_ddim_step_cfg", [](const A& a) { return hig_ddim_step_cfg(a.p[X], a.p[EPS], a.scale, a.p[AUX], reinterpret_cast<const int64_t*>(a.p[T]), a.p[TAB], a.nsteps, a.B, a.group, a.per, a.eta, 1, nullptr, nullptr); }, all, true, true, true, true},
+        {"hig_dpm2m_step", [](const A& a) { return hig_dpm2m_step(a.p[X], a.p[EPS], a.p[AUX], reinterpret_cast<const int64_t*>(a.p[T]), a.p[TAB], a.nsteps, a.B, a.per, 1, nullptr); }, all, false, false, false, true},
+        {"hig_dpm2m_step_cfg", [](const A& a) { return hig_dpm2m_step_cfg(a.p[X], a.p[EPS], a.scale, a.p[AUX], reinterpret_cast<const int64_t*>(a.p[T]), a.p[TAB], a.nsteps, a.B, a.group, a.per, 1, nullptr); }, all, true, true, false, true},
+        {"hig_impose_known", [](const A& a) { return hig_impose_known(a.p[X], a.p[EPS], a.mask, a.p[AUX], reinterpret_cast<const int64_t*>(a.p[T]), a.p[TAB], a.nsteps, a.B, a.per, nullptr); }, all | 1u << MASK, false, false, false, true},
+        {"hig_impose_known_cfg", [](const A& a) { return hig_impose_known_cfg(a.p[X], a.p[EPS], a.mask, a.p[AUX], reinterpret_cast<const int64_t*>(a.p[T]), a.p[TAB], a.nsteps, a.B, a.group, a.per, nullptr); }, all | 1u << MASK, true, false, false, true},
+        {"hig_cfg_combine", [](const A& a) { return hig_cfg_combine(a.p[EPS], a.scale, a.B, a.group, a.per, a.p[X], nullptr); }, 1u << X | 1u << EPS, true, true, false, false},
+    };
+    const float nan = __builtin_nanf(""), inf = __builtin_inff();
+    for (const E& e : entries) {
+      int refusals = 0;
+      auto refused = [&](const A& a) {
+        const int rc = e.call(a);
+        if (rc != HIG_EINVAL) fprintf(stderr, "driver.cpp: %s returned %d, refusal %d\n", e.name, rc, refusals);
+        EXPECT(rc == HIG_EINVAL);
+        EXPECT(hig_last_error(msg, sizeof(msg)) >= 0 && strstr(msg, e.name) != nullptr);
+        ++refusals;
+      };
+      A a;
+      for (int i = 0; i <= MASK; ++i) {
+        if (!(e.required >> i & 1)) continue;
+        if (i == AUX && e.has_eta) continue;                         // (z may be NULL at eta == 0: its own case below)
+        a = good;
+        if (i == MASK) a.mask = nullptr; else a.p[i] = nullptr;
+        refused(a);
+      }
+      for (int v : {0, -2, INT32_MIN}) {
+        a = good; a.B = v; refused(a);
+        a = good; a.per = v; refused(a);
+        if (e.checks_nsteps) { a = good; a.nsteps = v; refused(a); }
+        if (e.guided) { a = good; a.group = v; refused(a); }
+      }
+      a = good; a.per = INT64_MIN; refused(a);
+      if (e.guided) { a = good; a.group = 3; refused(a); }             // B % group != 0
+      if (e.has_scale) for (float v : {nan, inf, -inf}) { a = good; a.scale = v; refused(a); }
+      if (e.has_eta) {
+        for (float v : {-1.0f, nan, inf, -inf}) { a = good; a.eta = v; refused(a); }
+        a = good; a.p[AUX] = nullptr; refused(a);                      // z == NULL with eta != 0
+      }
+      a = good; a.per = INT64_MAX / (e.guided ? 4 : 2); refused(a);    // 4 [x 2] rows of that many elements
+      a = good; a.per = INT64_MAX; refused(a);
+      a = good; a.B = INT32_MAX; a.group = e.guided ? INT32_MAX : a.group; a.per = INT64_MAX / INT32_MAX + 1; refused(a);
+      EXPECT(refusals >= 11);
+    }
+  }
   // ---- diagnostics pointers: set and cleared ----
   EXPECT(hig_gemm_bf16_debug_stamps(nullptr) == HIG_OK && hig_gemm_ws16_debug_stamps(nullptr) == HIG_OK &&
          hig_gemm_debug_stamps(nullptr) == HIG_OK);

@@ -264,3 +264,44 @@ def test_set_sampler_validates_and_builds_the_spaced_diffusion():
     assert sd.use_timesteps == tuple(hig_amd.space_timesteps(N, 10))
     tr.set_sampler(None)
     assert tr._few_step is None
+
+
+# ---- the launch helpers: argument order against the library's declared signatures ---------------------------------------------
+class _Recording:
+    """Stands in for the library handle: every entry returns 0 and leaves (name, args) behind."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        return lambda *args: (self.calls.append((name, args)), 0)[1]
+
+
+def test_launch_helpers_put_every_argument_where_the_entry_declares_it():
+    from hig_amd import _lib
+    real = _lib.lib()
+    sd = spaced(10)
+    X, EPS, AUX, T, TAB, XP, PRED, STREAM = 101, 102, 103, 104, 105, 106, 107, 999        # made-up pointers: nothing reads them
+    KNOWN, MASK = 108, 109
+    K, B, GROUP, PER, SCALE = 10, 4, 2, 7, 2.5
+    updates = (("hig_p_sample_step", sd._p_update(), (), True), ("hig_ddim_step", sd._ddim_update(0.5, True), (0.5, 1), True),
+               ("hig_dpm2m_step", sd._dpm_update(2, True), (1,), False))
+    for name, upd, tail, has_outputs in updates:
+        assert upd.entry == name and tuple(upd.tail) == tail and upd.history == (not has_outputs)
+        rec = _Recording()
+        gdm._launch_update(rec, upd, X, EPS, AUX, T, TAB, K, B, PER, STREAM, x_prev=XP, pred=PRED)
+        gdm._launch_update(rec, upd, X, EPS, AUX, T, TAB, K, B, PER, STREAM, scale=SCALE, group=GROUP, x_prev=XP, pred=PRED)
+        (plain_name, plain), (guided_name, guided) = rec.calls
+        assert (plain_name, guided_name) == (name, name + "_cfg")
+        assert len(plain) == len(getattr(real, plain_name).argtypes) and len(guided) == len(getattr(real, guided_name).argtypes)
+        assert plain == (X, EPS, AUX, T, TAB, K, B, PER) + tail + ((XP, PRED) if has_outputs else ()) + (STREAM,)
+        assert guided == (X, EPS, SCALE, AUX, T, TAB, K, B, GROUP, PER) + tail + ((PRED,) if has_outputs else ()) + (STREAM,)
+        assert guided[2] == SCALE and guided[8:10] == (GROUP, PER) and plain[-1] == guided[-1] == STREAM
+    rec = _Recording()
+    gdm._launch_impose_known(rec, X, KNOWN, MASK, AUX, T, TAB, K, B, PER, STREAM)
+    gdm._launch_impose_known(rec, X, KNOWN, MASK, AUX, T, TAB, K, B, PER, STREAM, group=GROUP)
+    (plain_name, plain), (guided_name, guided) = rec.calls
+    assert (plain_name, guided_name) == ("hig_impose_known", "hig_impose_known_cfg")
+    assert len(plain) == len(real.hig_impose_known.argtypes) and len(guided) == len(real.hig_impose_known_cfg.argtypes)
+    assert plain == (X, KNOWN, MASK, AUX, T, TAB, K, B, PER, STREAM)
+    assert guided == (X, KNOWN, MASK, AUX, T, TAB, K, B, GROUP, PER, STREAM)

@@ -368,6 +368,8 @@ def guided_setup(gold_file=None, scale=S_GOLD, storage="f32"):
 def run_loop(sd, model, shape, x0, kw, method, eta, **cond):
     if method == "ddim":
         return sd.ddim_sample_loop(model, shape, noise=x0.clone(), clip_denoised=False, model_kwargs=kw, eta=eta, **cond)
+    if method == "dpmpp2m":
+        return sd.dpm_solver_sample_loop(model, shape, noise=x0.clone(), clip_denoised=False, model_kwargs=kw, **cond)
     return sd.p_sample_loop(model, shape, noise=x0.clone(), clip_denoised=False, model_kwargs=kw, **cond)
 
 
@@ -384,11 +386,12 @@ def test_captured_guided_ddim_loop_matches_reference_golden(gold):
     assert e < gate
 
 
-SAMPLER_KERNELS = ("hig_impose_known", "hig_p_sample_step", "hig_ddim_step", "hig_dec_timesteps", "hig_advance_timesteps",
-                   "hig_cfg_combine")
+SAMPLER_KERNELS = ("hig_impose_known", "hig_p_sample_step", "hig_ddim_step", "hig_dpm2m_step", "hig_dec_timesteps",
+                   "hig_advance_timesteps", "hig_cfg_combine")
 
 
-@pytest.mark.parametrize("method,eta,with_known", (("ddim", 0.0, False), ("ddim", 1.0, True), ("ddpm", 0.0, True), ("ddpm", 0.0, False)))
+@pytest.mark.parametrize("method,eta,with_known", (("ddim", 0.0, False), ("ddim", 1.0, True), ("ddpm", 0.0, True), ("ddpm", 0.0, False),
+                                                    ("dpmpp2m", 0.0, False), ("dpmpp2m", 0.0, True)))
 def test_guided_step_launches_one_cfg_kernel_for_each_unguided_one(method, eta, with_known):
     gm, m, kw, un, shape, x0 = guided_setup()
     cond = dict(zip(("known", "known_mask"), known_for(shape))) if with_known else {}
@@ -399,7 +402,7 @@ def test_guided_step_launches_one_cfg_kernel_for_each_unguided_one(method, eta, 
     print("LAUNCHES %s eta%g known%d: %s" % (method, eta, with_known, ours(guided)))
     assert "hig_cfg_combine" not in guided
     assert [n.replace("_cfg", "") for n in guided] == plain         # launch for launch the unguided step (warm-up + capture) ...
-    step = "hig_ddim_step" if method == "ddim" else "hig_p_sample_step"
+    step = {"ddim": "hig_ddim_step", "dpmpp2m": "hig_dpm2m_step", "ddpm": "hig_p_sample_step"}[method]
     want = (["hig_impose_known_cfg"] if with_known else []) + [step + "_cfg"]
     want += ["hig_advance_timesteps"]
     assert ours(guided) == want * 2                                 # ... with one _cfg kernel in the place of each unguided one

@@ -238,15 +238,15 @@ def loop_case(kind):
     if kind == "bf16":
         m, kw, shape, x0 = setup16()
         return m, kw, shape, x0, {}
-    if kind == "guided":
+    if kind in ("guided", "guided_known"):
         gm, m, kw, un, shape, x0 = guided_setup()
-        return gm, kw, shape, x0, {}
+        return gm, kw, shape, x0, (dict(zip(("known", "known_mask"), known_for(shape))) if kind == "guided_known" else {})
     m, kw, shape, x0 = loop_setup()
     cond = dict(zip(("known", "known_mask"), known_for(shape))) if kind == "known" else {}
     return m, kw, shape, x0, cond
 
 
-@pytest.mark.parametrize("kind", ("plain", "known", "guided", "bf16"))
+@pytest.mark.parametrize("kind", ("plain", "known", "guided", "guided_known", "bf16"))
 def test_captured_loop_equals_eager_loop(kind):
     model, kw, shape, x0, cond = loop_case(kind)
     outs = []
@@ -262,8 +262,9 @@ def test_captured_loop_equals_eager_loop(kind):
         assert n == (K if use_graph else 0)
         ours = [x for x in launches if x.startswith(SAMPLER_KERNELS)]
         if use_graph:       # the warm-up step and the captured one: the imposition where asked for, ONE update kernel, the counter
-            cfg = "_cfg" if kind == "guided" else ""
-            assert ours == ((["hig_impose_known" + cfg] if kind == "known" else []) + ["hig_dpm2m_step" + cfg, "hig_advance_timesteps"]) * 2
+            cfg = "_cfg" if kind.startswith("guided") else ""
+            impose = ["hig_impose_known" + cfg] if kind.endswith("known") else []
+            assert ours == (impose + ["hig_dpm2m_step" + cfg, "hig_advance_timesteps"]) * 2
         else:
             assert ours.count("hig_dpm2m_step") == K and "hig_ddim_step" not in ours
         outs.append(out)
