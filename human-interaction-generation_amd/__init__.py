@@ -12,7 +12,8 @@ from .models import (ClassifierFreeGuidedModel, GaussianDiffusion, MotionConsist
                      MotionInteractionTransformer, MotionTransformer, SpacedDiffusion, space_timesteps,
                      space_timesteps_logsnr)
 from .trainers import DDPMMulTrainer, DDPMTrainer, EvalModelTrainer  # noqa: F401
+from .evaluation import evaluation  # noqa: F401  (the function; its module stays importable as hig_amd.evaluation in sys.modules)
 
 __all__ = ["MotionTransformer", "MotionInteractionTransformer", "MotionEncoder", "MotionConsistencyEvalModel",
            "GaussianDiffusion", "SpacedDiffusion", "space_timesteps", "space_timesteps_logsnr", "DDPMTrainer", "DDPMMulTrainer",
-           "EvalModelTrainer", "ClassifierFreeGuidedModel"]
+           "EvalModelTrainer", "ClassifierFreeGuidedModel", "evaluation"]

@@ -96,6 +96,8 @@ SYMBOLS = (
     # training the evaluation classifiers
     "hig_fullattn_bwd_kpad", "hig_softmax_xent", "hig_eval_encoder_train_workspace_bytes", "hig_eval_encoder_bwd_workspace_bytes",
     "hig_eval_encoder_fwd_train", "hig_eval_encoder_bwd",
+    # the evaluation protocol
+    "hig_eval_pairs_build",
 )
 
 
@@ -294,6 +296,7 @@ def lib():
         L.hig_transpose_batch.argtypes = [i32, vp, vp, vp, vp, vp]
         L.hig_recover_joints.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
         L.hig_gather_frames.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+        L.hig_eval_pairs_build.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]
         L.hig_text_context_bf16_train.argtypes = [C.POINTER(Dims), vp, vp, vp, vp, vp]
         L.hig_denoiser_fwd_bf16_train.argtypes = [C.POINTER(Dims)] + [vp] * 10
         L.hig_denoiser_bwd_bf16.argtypes = [C.POINTER(Dims)] + [vp] * 15

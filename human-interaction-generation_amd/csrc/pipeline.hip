@@ -32,6 +32,38 @@ __global__ __launch_bounds__(256) void gather_frames_kernel(const float* __restr
   }
 }
 
+// ---- evaluation inputs from generated motions --------------------------------------------
+// Reference: EvaluationDataset.__getitem__ / MMGeneratedDataset.__getitem__, codes/datasets/evaluator.py:143-166,
+// 346-387, restated on the un-rotated motion (row 0 = init pose, rows 1 .. n = frames, n = m_len - 1), W = T_out - 1:
+//   out row 0 = src row 0;   n < W: out row j = src row min(j, n);   n >= W: out row j = src row shift + j.
+// One wave per output row, EVAL_ROWS rows per workgroup; a row is F_out contiguous floats out of a source row of F_in.
+// 16-byte accesses only on a row whose source AND destination address are both 16-byte aligned (F_in = 263 and
+// F_out = 259 / 263 rows are not, three times out of four); plain dword accesses otherwise.  A pure copy either way.
+constexpr int EVAL_ROWS = 4;
+
+__global__ __launch_bounds__(64 * EVAL_ROWS) void eval_pairs_build_kernel(
+    const float* __restrict__ src, const int64_t* __restrict__ src_off, const int32_t* __restrict__ m_len,
+    const int32_t* __restrict__ shift, int N, int F_in, int F_out, int T_out, float* __restrict__ out) {
+  const int r = blockIdx.y;                               // person-sample: person 1 of all pairs, then person 2
+  const int j = blockIdx.x * EVAL_ROWS + threadIdx.y;     // output row
+  if (j >= T_out) return;
+  const int pair = r < N ? r : r - N;
+  const int n = m_len[pair] - 1, W = T_out - 1;
+  const int s = j == 0 ? 0 : (n < W ? (j < n ? j : n) : shift[pair] + j);
+  const float* srow = src + src_off[r] + (int64_t)s * F_in;
+  float* drow = out + ((int64_t)r * T_out + j) * F_out;
+  const int lane = threadIdx.x;
+  int done = 0;
+  if ((((uintptr_t)srow | (uintptr_t)drow) & 15) == 0) {
+    const int nv = F_out >> 2;
+    const float4* s4 = reinterpret_cast<const float4*>(srow);
+    float4* d4 = reinterpret_cast<float4*>(drow);
+    for (int v = lane; v < nv; v += 64) d4[v] = s4[v];
+    done = nv << 2;
+  }
+  for (int f = done + lane; f < F_out; f += 64) drow[f] = srow[f];
+}
+
 // ---- post-sampling joint recovery ------------------------------------------------------
 // Reference: recover_root_rot_pos / recover_from_ric2 (codes/utils/motion_process.py:362-382, 418-462),
 // qinv / qrot (codes/utils/quaternion.py:16-20, 54-73) and the de-normalisation in
@@ -136,6 +168,36 @@ extern "C" int hig_recover_joints(const float* motion, const float* stats, int32
   if (rows == 0) return HIG_OK;
   hipLaunchKernelGGL(recover_joints_kernel, dim3(rows), dim3(256), (size_t)4 * T * sizeof(float), hig_stream(stream),
                      motion, stats, T, F, joints, init_first, pos);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_eval_pairs_build(const float* src, const int64_t* src_off, const int32_t* m_len, const int32_t* shift,
+                                    const int64_t* src_off_host, const int32_t* m_len_host, const int32_t* shift_host,
+                                    int64_t src_floats, int32_t N, int32_t F_in, int32_t F_out, int32_t T_out, float* out,
+                                    hig_stream_t stream) {
+  HIG_REQUIRE(N >= 0 && 2 * (int64_t)N <= 65535, "hig_eval_pairs_build: 0 <= 2 N <= 65535 required");
+  if (N == 0) return HIG_OK;
+  HIG_REQUIRE(src && src_off && m_len && shift && src_off_host && m_len_host && shift_host && out,
+              "hig_eval_pairs_build: null argument");
+  HIG_REQUIRE(T_out >= 2 && T_out <= (1 << 20) && F_out >= 1 && F_out <= F_in && F_in <= (1 << 20) && src_floats >= 0,
+              "hig_eval_pairs_build: 2 <= T_out <= 2^20, 1 <= F_out <= F_in <= 2^20, src_floats >= 0 required");
+  const int W = T_out - 1;
+  for (int i = 0; i < N; ++i) {
+    const int64_t len = m_len_host[i], sh = shift_host[i], n = len - 1;
+    HIG_REQUIRE(len >= 2, "hig_eval_pairs_build: m_len[%d] = %d, need an init-pose row and one frame", i, (int)len);
+    HIG_REQUIRE(sh >= 0, "hig_eval_pairs_build: shift[%d] = %d is negative", i, (int)sh);
+    HIG_REQUIRE(n < W || sh + W <= n, "hig_eval_pairs_build: shift[%d] = %d puts the window of %d frames past frame %d", i,
+                (int)sh, W, (int)n);
+    for (int p = 0; p < 2; ++p) {
+      const int64_t off = src_off_host[(int64_t)p * N + i];
+      HIG_REQUIRE(off >= 0 && off <= src_floats && len * F_in <= src_floats - off,
+                  "hig_eval_pairs_build: person %d of pair %d lies outside src[0, src_floats)", p + 1, i);
+    }
+  }
+  const dim3 grid((T_out + EVAL_ROWS - 1) / EVAL_ROWS, 2 * N);
+  hipLaunchKernelGGL(eval_pairs_build_kernel, grid, dim3(64, EVAL_ROWS), 0, hig_stream(stream), src, src_off, m_len, shift, N,
+                     F_in, F_out, T_out, out);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

@@ -3,17 +3,26 @@ evaluation drives (`EvaluatorModelWrapper`, codes/datasets/evaluator.py:431-493)
 scoring passes built on it (`evaluate_matching_score` / `evaluate_fid`,
 codes/tools/evaluation.py:56-135), with both classifiers running through `hig_eval_encoder_fwd`.
 
-Not built (out of the tier's scope): the generated-motion dataset classes of evaluator.py:24-428
-(they only call `trainer.generate` in a loop), confusion-matrix plots, log files.  The wrapper's
+The generated-motion side of the evaluation (evaluator.py:24-409) is here too: `GeneratedMotionSet` mirrors
+`EvaluationDataset` + `MMGeneratedDataset` with the generated motions kept on the device, their classifier inputs built by
+one `hig_eval_pairs_build` launch per batch; `eval_frame_plan` / `eval_frame_rows` state the row rule those classes apply
+(pinned bit for bit, draw count included, by tests/golden/g20_evaluation.npz); `Text2MotionDatasetV2` is the ground-truth
+set.  The run itself is `hig_amd.evaluation`.
+
+Not built: confusion-matrix plots, the pickled `generated=` / `mm_generated=` constructor path.  The wrapper's
 `get_co_embeddings` is dead code in the reference (it reads attributes the class never sets,
 evaluator.py:466-482) and has no counterpart here.
 """
+import copy
+import random
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
+from .. import _lib
 from ..models import MotionConsistencyEvalModel, MotionEncoder
+from .mul_dataset import NUM_FRAMES, Text2MotionMulDataset, frame_indices
 from ..utils.metrics import calculate_activation_statistics, calculate_frechet_distance
 
 EVAL_MODEL_PATH = 'checkpoints/ntu_mul/eval_model/model/best_eval_model.pth'
@@ -103,3 +112,288 @@ def evaluate_fid(activation_dict, reference_name='ground truth'):
         mu, cov = calculate_activation_statistics(act)
         out[name] = calculate_frechet_distance(gt_mu, gt_cov, mu, cov)
     return out
+
+
+# ---- the generated-motion sets (evaluator.py:24-409) --------------------------------------------------------------
+# A motion of m_len rows: row 0 is the init-pose row, rows 1 .. n the frames, n = m_len - 1 (the sampler's token order).
+# The reference rotates the init-pose row to the end and indexes with `frame_ix`; stated on the un-rotated motion, with
+# W = frames wanted:  out row 0 = row 0;  n < W: out row j = row min(j, n);  n >= W: out row j = row shift + j  (1 <= j <= W).
+
+def eval_frame_plan(m_lens, frames=NUM_FRAMES, rng=random):
+    """The int32 `shift` of every item, drawn as `EvaluationDataset.__getitem__` / `MMGeneratedDataset.__getitem__` draw
+    it when called on the items in this order (evaluator.py:150-164, 359-373): one `rng.randint(0, max(0, n - frames - 1))`
+    per item with n >= frames -- also when that range is [0, 0] -- and no draw for a shorter one (shift 0, never read)."""
+    shift = np.zeros(len(m_lens), dtype=np.int32)
+    for i, m_len in enumerate(m_lens):
+        n = int(m_len) - 1
+        if n >= frames:
+            shift[i] = rng.randint(0, max(0, n - frames - 1))
+    return shift
+
+
+def eval_frame_rows(m_len, shift=0, frames=NUM_FRAMES):
+    """(frames + 1,) row indices into a motion of m_len rows: the rule above in numpy, what `hig_eval_pairs_build` applies
+    in-kernel.  Every index is below m_len."""
+    n = int(m_len) - 1
+    if n < 1:
+        raise ValueError("a motion needs its init-pose row and one frame, got m_len = %d" % m_len)
+    j = np.arange(1, frames + 1, dtype=np.int64)
+    if n < frames:
+        rows = np.minimum(j, n)
+    else:
+        if not 0 <= int(shift) <= n - frames:
+            raise ValueError("shift %d puts a window of %d frames outside the %d frames of the motion" % (shift, frames, n))
+        rows = int(shift) + j
+    return np.concatenate((np.zeros(1, dtype=np.int64), rows))
+
+
+def mark_multimodality(class_ids, mm_num_repeats):
+    """Positions of the multimodality items (evaluator.py:50-53): item i is one when fewer than mm_num_repeats + 1 items of
+    its class were marked before it -- so every class gets its first mm_num_repeats + 1 items."""
+    count, marked = {}, []
+    for i, c in enumerate(class_ids):
+        if count.get(c, 0) <= mm_num_repeats:
+            marked.append(i)
+            count[c] = count.get(c, 0) + 1
+    return marked
+
+
+def mm_length_order(m_lens):
+    """The order `MMGeneratedDataset` returns a class's motions in (evaluator.py:380): by length, descending."""
+    return np.argsort(np.asarray(m_lens, dtype=int))[::-1].copy()
+
+
+def _host_ptr(a):
+    return a.ctypes.data_as(_lib.C.c_void_p)
+
+
+class GeneratedMotionSet(object):
+    """Mirror of `EvaluationDataset` (evaluator.py:24-166) with `MMGeneratedDataset` (:336-387) folded in.
+
+    One pass over `dataset` -- items `(class_id, caption1, caption2, motion1, motion2, m_length)`, what `Text2MotionDatasetV2`
+    returns -- in `order` (default: `torch.randperm(len(dataset), generator=generator)`, standing in for the reference's
+    shuffled batch-1 loader), marking the multimodality items with `mark_multimodality`; then ONE
+    `trainer.generate(all_caption1, all_caption2, all_m_lens, opt.dim_pose)`, so whatever `set_sampler` chose applies and
+    the reference's slicing of the second caption list in non-final chunks is what it is there.  The generated tensors stay
+    on the device as `generate` returned them (views of its chunks): nothing is copied to the host and nothing is cut per
+    sample; rows at and beyond an item's m_len are simply never read.
+
+    It does NOT load a checkpoint (the reference's constructor calls `trainer.load(opt.model_dir/opt.which_epoch.tar)`):
+    the caller loads the trainer it wants measured.
+
+    `batches` / `mm_sets` build the classifiers' inputs on the device with one `hig_eval_pairs_build` launch per batch /
+    class, at F_out = F: the wrapper cuts the four flags as it always did (`get_motion_embeddings(..., keep_dim=False)`).
+    `host_batches` / `host_mm_sets` are the reference's route -- CPU copies indexed with `eval_frame_rows` -- kept as the
+    yardstick for tests and timing; nothing falls back to them."""
+
+    def __init__(self, opt, trainer, dataset, mm_num_repeats, frames=NUM_FRAMES, order=None, generator=None):
+        self.opt, self.frames = opt, int(frames)
+        self.device = torch.device(opt.device)
+        if self.device.type != "cuda":
+            raise RuntimeError("GeneratedMotionSet: ROCm device required (no CPU fallback)")
+        if order is None:
+            order = torch.randperm(len(dataset), generator=generator).tolist()
+        cap_id = bool(getattr(opt, "cap_id", False))
+        class_ids, lens, all_caption1, all_caption2 = [], [], [], []
+        self.caption1, self.caption2, self._gt = [], [], []
+        for item in order:
+            class_id, caption1, caption2, motion1, motion2, m_len = dataset[int(item)]
+            class_ids.append(int(class_id))
+            lens.append(int(m_len))
+            self.caption1.append(caption1)
+            self.caption2.append(caption2)
+            self._gt.append((np.asarray(motion1), np.asarray(motion2)))
+            if cap_id:      # [key] per item (evaluator.py:62-64)
+                all_caption1.extend(caption1)
+                all_caption2.extend(caption2)
+            else:
+                all_caption1.append(caption1)
+                all_caption2.append(caption2)
+        self.class_ids = np.asarray(class_ids, dtype=np.int64)
+        self.lengths = np.asarray(lens, dtype=np.int32)
+        if len(lens) and self.lengths.min() < 2:
+            raise ValueError("GeneratedMotionSet: every item needs m_length >= 2 (init-pose row + one frame)")
+        self.mm_indices = mark_multimodality(class_ids, mm_num_repeats)
+        trainer.eval_mode()
+        trainer.to(opt.device)
+        with torch.no_grad():
+            pred = trainer.generate(all_caption1, all_caption2, torch.tensor(lens, dtype=torch.int64), opt.dim_pose)
+        assert len(pred) == len(lens)
+        self.F = F = int(opt.dim_pose)
+        self.motions = []
+        for i, (m1, m2) in enumerate(pred):
+            if m1.shape[0] < lens[i]:     # the reference asserts the same after cutting (evaluator.py:97)
+                raise ValueError("GeneratedMotionSet: item %d asks for %d rows, the model generates %d" % (i, lens[i], m1.shape[0]))
+            pair = []
+            for m in (m1, m2):
+                assert m.is_cuda and m.dtype == torch.float32 and m.shape[1] == F
+                pair.append(m if m.stride() == (F, 1) else m.contiguous())
+            self.motions.append(pair)
+        # element offsets of every person-sample from the lowest address among them (float storage: multiples of 4 bytes)
+        ptrs = np.array([[m.data_ptr() for m in pair] for pair in self.motions], dtype=np.int64).reshape(-1, 2)
+        self._base = int(ptrs.min()) if len(lens) else 0
+        assert ((ptrs - self._base) % 4 == 0).all()
+        self._off = (ptrs - self._base) // 4                                    # (items, 2)
+        rows = np.array([pair[0].shape[0] for pair in self.motions], dtype=np.int64)
+        self._src_floats = int((self._off.max(axis=1) + rows * F).max()) if len(lens) else 0
+        self._class_d = torch.from_numpy(self.class_ids).to(self.device)
+        self._len_d = torch.from_numpy(self.lengths.astype(np.int64)).to(self.device)
+        self._host = None
+
+    def __len__(self):
+        return len(self.lengths)
+
+    # ---- device route ----------------------------------------------------------------------------------------
+    def _tables(self, groups, shifts):
+        """Host and device copies of [person-1 offsets | person-2 offsets], m_len and shift for every group of item
+        indices, concatenated: ONE upload for a whole pass; -> per group (start in the offset table, start in the others)."""
+        off = np.concatenate([np.concatenate([self._off[g, 0], self._off[g, 1]]) for g in groups]).astype(np.int64)
+        mlen = np.concatenate([self.lengths[g] for g in groups]).astype(np.int32)
+        shift = np.concatenate(shifts).astype(np.int32)
+        host = (np.ascontiguousarray(off), np.ascontiguousarray(mlen), np.ascontiguousarray(shift))
+        dev = tuple(torch.from_numpy(a).to(self.device, non_blocking=True) for a in host)
+        return host, dev
+
+    def _build(self, host, dev, start, n):
+        """One launch: items [start, start + n) of the tables -> (2 n, frames + 1, F)."""
+        out = torch.empty(2 * n, self.frames + 1, self.F, device=self.device, dtype=torch.float32)
+        (off_h, len_h, shift_h), (off_d, len_d, shift_d) = host, dev
+        _lib.check(_lib.lib().hig_eval_pairs_build(
+            _lib.C.c_void_p(self._base), _lib.ptr(off_d[2 * start:]), _lib.ptr(len_d[start:]), _lib.ptr(shift_d[start:]),
+            _host_ptr(off_h[2 * start:]), _host_ptr(len_h[start:]), _host_ptr(shift_h[start:]), self._src_floats, n, self.F,
+            self.F, self.frames + 1, _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def _groups(self, batch_size, drop_last):
+        n = len(self)
+        stop = n - n % batch_size if drop_last else n
+        return [np.arange(lo, min(lo + batch_size, stop)) for lo in range(0, stop, batch_size)]
+
+    def batches(self, batch_size=32, drop_last=True, rng=random):
+        """Yields `(class_id, caption1, caption2, motions1, motions2, m_lens)` like the reference's generated loader
+        (DataLoader(dataset, batch_size, drop_last=True), evaluator.py:403), every tensor on the device: motions* are
+        (B, frames + 1, F) views of one kernel-built (2B, frames + 1, F) buffer, class_id and m_lens int64.  The shifts of
+        the whole pass are drawn from `rng` when the first batch is asked for, in item order (the items a dropped last
+        batch holds draw nothing, as their `__getitem__` is never called), and uploaded once."""
+        groups = self._groups(batch_size, drop_last)
+        if not groups:
+            return
+        shifts = [eval_frame_plan(self.lengths[g], self.frames, rng) for g in groups]
+        host, dev = self._tables(groups, shifts)
+        start = 0
+        for g in groups:
+            n = len(g)
+            out = self._build(host, dev, start, n)
+            start += n
+            lo, hi = int(g[0]), int(g[-1]) + 1
+            yield (self._class_d[lo:hi], self.caption1[lo:hi], self.caption2[lo:hi], out[:n], out[n:], self._len_d[lo:hi])
+
+    def _mm_groups(self):
+        """Per class that has marked items, in class order: their positions in the order they were met."""
+        per = {}
+        for i in self.mm_indices:
+            per.setdefault(int(self.class_ids[i]), []).append(i)
+        return [np.asarray(per[c], dtype=np.int64) for c in sorted(per)]
+
+    def mm_sets(self, rng=random):
+        """Per class with multimodality items: `(motions1, motions2, m_lens)` as `MMGeneratedDataset.__getitem__` returns
+        them -- windows drawn in the order the items were met, then sorted by length, descending (`mm_length_order`) -- on
+        the device; the kernel writes them in the sorted order."""
+        groups = self._mm_groups()
+        if not groups:
+            return
+        shifts = [eval_frame_plan(self.lengths[g], self.frames, rng) for g in groups]
+        orders = [mm_length_order(self.lengths[g]) for g in groups]
+        groups = [g[o] for g, o in zip(groups, orders)]
+        shifts = [s[o] for s, o in zip(shifts, orders)]
+        host, dev = self._tables(groups, shifts)
+        lens_d = dev[1].to(torch.int64)
+        start = 0
+        for g in groups:
+            n = len(g)
+            out = self._build(host, dev, start, n)
+            yield out[:n], out[n:], lens_d[start:start + n]
+            start += n
+
+    # ---- the reference's route: host copies + eval_frame_rows ----------------------------------------------------------
+    def _host_motions(self):
+        if self._host is None:
+            self._host = [tuple(m[:int(n)].cpu().numpy() for m in pair) for pair, n in zip(self.motions, self.lengths)]
+        return self._host
+
+    def _host_rows(self, motions, lens, shifts):
+        m1 = np.stack([m[0][eval_frame_rows(n, s, self.frames)] for m, n, s in zip(motions, lens, shifts)])
+        m2 = np.stack([m[1][eval_frame_rows(n, s, self.frames)] for m, n, s in zip(motions, lens, shifts)])
+        return torch.from_numpy(m1), torch.from_numpy(m2)
+
+    def host_batches(self, batch_size=32, drop_last=True, rng=random):
+        """`batches` through CPU copies of the generated motions and `eval_frame_rows`; every tensor on the host."""
+        host = self._host_motions()
+        for g in self._groups(batch_size, drop_last):
+            shift = eval_frame_plan(self.lengths[g], self.frames, rng)
+            m1, m2 = self._host_rows([host[i] for i in g], self.lengths[g], shift)
+            lo, hi = int(g[0]), int(g[-1]) + 1
+            yield (torch.from_numpy(self.class_ids[lo:hi]), self.caption1[lo:hi], self.caption2[lo:hi], m1, m2,
+                   torch.from_numpy(self.lengths[lo:hi].astype(np.int64)))
+
+    def _host_sets(self, motions, lens, rng):
+        shift = eval_frame_plan(lens, self.frames, rng)
+        m1, m2 = self._host_rows(motions, lens, shift)
+        o = mm_length_order(lens)
+        return m1[o], m2[o], torch.from_numpy(np.asarray(lens, dtype=np.int64)[o])
+
+    def host_mm_sets(self, rng=random):
+        """`mm_sets` through the CPU copies."""
+        host = self._host_motions()
+        for g in self._mm_groups():
+            yield self._host_sets([host[i] for i in g], self.lengths[g], rng)
+
+    def gt_mm_sets(self, rng=random):
+        """The ground-truth motions at the multimodality positions, through the same rule (evaluator.py:112-116, 401): the
+        dataset's motion cut to its first m_len rows (it has frames + 1 of them, so lengths above that become frames + 1
+        and draw a shift from [0, 0]).  Host tensors: the ground truth comes from the host."""
+        for g in self._mm_groups():
+            motions = [tuple(m[:int(self.lengths[i])] for m in self._gt[i]) for i in g]
+            yield self._host_sets(motions, [m[0].shape[0] for m in motions], rng)
+
+
+class Text2MotionDatasetV2(Text2MotionMulDataset):
+    """The evaluation's ground-truth set (evaluator.py:175-312) on the loading code of `Text2MotionMulDataset`: the same
+    files, filters and statistics (never adjusted or saved here: is_train is not consulted, nor is limit_data_num; clips
+    shorter than 20 rows are dropped whatever the dataset's name), but `__getitem__` returns
+    `(class_id, caption1, caption2, motion1, motion2, m_length)` and draws in the reference's order for this class: the
+    caption first, then the window."""
+
+    def __init__(self, opt, mean, std, split_file, w_vectorizer=None, caption_table=None):
+        load = copy.copy(opt)
+        load.is_train, load.limit_data_num, load.dataset_name = False, -1, "ntu_mul"     # (the name only picks min length 20)
+        super().__init__(load, mean, std, split_file, times=1, w_vectorizer=w_vectorizer, eval_mode=True,
+                         caption_table=caption_table)
+        self.opt = opt
+        self.max_motion_length = getattr(opt, "max_motion_length", 196)
+        self.reset_max_len(20)
+
+    def reset_max_len(self, length):
+        assert length <= self.max_motion_length
+        self.pointer = int(np.searchsorted(self.length_arr, length))
+        self.max_length = length
+
+    def __len__(self):
+        return len(self.data_dict) - self.pointer
+
+    def __getitem__(self, item):
+        d = self.data_dict[self.name_list[self.pointer + item]]
+        caption1, caption2 = random.choice(d['text'])['captions']
+        class_id = self.cap2classid[caption1]
+        if self.cap_id:
+            caption1, caption2 = [self.cap2key[caption1]], [self.cap2key[caption2]]
+        elif self.cap_same:
+            caption2 = caption1
+        motion = d['motion']
+        frame_ix = frame_indices(motion.shape[1] - 1)
+        motion1, motion2 = motion[0][frame_ix], motion[1][frame_ix]
+        motion1[1:] = (motion1[1:] - self.mean) / self.std
+        motion2[1:] = (motion2[1:] - self.mean) / self.std
+        motion1[0, :4] = (motion1[0, :4] - self.init_mean) / self.init_std
+        motion2[0, :4] = (motion2[0, :4] - self.init_mean) / self.init_std
+        return class_id, caption1, caption2, motion1, motion2, d['length']

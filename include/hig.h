@@ -501,6 +501,33 @@ int hig_gather_frames(const float* bank, const int64_t* seq_off, const int32_t* 
                       float* out, hig_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluation inputs: generated motions that are still on the device -> both persons' classifier inputs, one
+ * launch.  Reference: EvaluationDataset.__getitem__ / MMGeneratedDataset.__getitem__, datasets/evaluator.py:143-166, 346-387,
+ * restated on the un-rotated motion: row 0 of a motion is its init-pose row, rows 1 .. n its frames, n = m_len - 1.  With
+ * W = T_out - 1 frames wanted,
+ *   out[r][0] = motion_r[0];    n <  W: out[r][j] = motion_r[min(j, n)]     (short clips repeat their last frame)
+ *                               n >= W: out[r][j] = motion_r[shift + j]     (1 <= j <= W)
+ * and of every row the leading F_out of its F_in features (F_out = F_in - 4 is EvaluatorModelWrapper's cut of the flags).
+ *   src        any float pointer; motion_r starts at src + src_off[r], its rows F_in floats apart
+ *   src_off    device, 2 N element offsets: person 1 of all pairs, then person 2 (the chunks of generate() have different
+ *              T, so every person-sample carries its own offset)
+ *   m_len, shift   device, N each, shared by the two persons of a pair; shift is read only where n >= W
+ *   *_host     the same three arrays on the host: what is checked before the launch (nothing is copied back from the device)
+ *   src_floats the extent of src the offsets may address
+ *   out        (2 N, T_out, F_out), out[:N] person 1, out[N:] person 2
+ * A pure copy: every output element has the bits of its source element; rows of a motion at or beyond m_len are never read.
+ * 16-byte accesses only on rows whose source and destination are both 16-byte aligned, dword accesses otherwise; no
+ * alignment is asked of the caller beyond that of a float.  Refused with HIG_EINVAL before any launch: N < 0 or 2 N > 65535,
+ * a NULL pointer, T_out outside [2, 2^20], F_out outside [1, F_in], F_in > 2^20, m_len < 2, shift < 0, shift + W > n where
+ * n >= W, a motion whose m_len rows do not lie inside src[0, src_floats).  N == 0: HIG_OK, nothing launched.  No allocation,
+ * no synchronisation: capturable.
+ * ---------------------------------------------------------------------------------------- */
+int hig_eval_pairs_build(const float* src, const int64_t* src_off, const int32_t* m_len, const int32_t* shift,
+                         const int64_t* src_off_host, const int32_t* m_len_host, const int32_t* shift_host,
+                         int64_t src_floats, int32_t N, int32_t F_in, int32_t F_out, int32_t T_out, float* out,
+                         hig_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Post-sampling joint recovery: de-normalise a generated motion and integrate it to
  * world-space joint positions.  Reference: tools/visualization.py:146-152 (x * std + mean, init row on
  * 4 features), utils/motion_process.py:362-382 recover_root_rot_pos, :418-462 recover_from_ric2
