@@ -98,6 +98,8 @@ SYMBOLS = (
     "hig_eval_encoder_fwd_train", "hig_eval_encoder_bwd",
     # the evaluation protocol
     "hig_eval_pairs_build",
+    # EMA weights
+    "hig_clip_adam_ema", "hig_ema_update", "hig_swap_f32",
 )
 
 
@@ -314,6 +316,9 @@ def lib():
         L.hig_gemm_bf16_split_scratch_floats.restype = i64
         L.hig_gemm_bf16_split_scratch_floats.argtypes = [C.POINTER(Gemm16Desc), i32]
         L.hig_clip_adam_shadow.argtypes = [vp, vp, vp, vp, i64, f32, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp, i64, vp]
+        L.hig_clip_adam_ema.argtypes = [vp, vp, vp, vp, i64, f32, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp, i64, vp, f32, i32, i32, vp]
+        L.hig_ema_update.argtypes = [vp, vp, i64, f32, i32, vp, i32, i32, vp]
+        L.hig_swap_f32.argtypes = [vp, vp, i64, vp]
         L.hig_debug_marker.argtypes = [i32, vp]
         L.hig_denoiser_fwd_x.argtypes = [C.POINTER(Dims), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]
         L.hig_wgrad_bf16.argtypes = [vp, i64, vp, i64, i64, i32, i32, vp, vp, i32, vp, i64, vp]

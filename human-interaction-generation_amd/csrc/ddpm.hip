@@ -429,6 +429,24 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
   if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// ---- EMA of the weights (include/hig.h, "EMA weights") ---------------------------------------------------
+// w = fp32(1 - d_n) of EMA update number n (clamped to >= 1), in double from the fp32 decay, rounded once.
+__device__ __forceinline__ float ema_weight(int64_t n, float decay, int warmup) {
+  const double nn = (double)(n < 1 ? 1 : n);
+  double d = (double)decay;
+  if (warmup) {
+    const double dw = (1.0 + nn) / (10.0 + nn);
+    d = dw < d ? dw : d;
+  }
+  return (float)(1.0 - d);
+}
+// e' = e + w (p' - e): the ONE statement of the blend (clip_adam_kernel<true>, ema_update_kernel); an explicit fma, so
+// both callers round the same way whatever the compiler contracts around it.
+__device__ __forceinline__ float ema_blend(float e, float p, float w) { return fmaf(w, p - e, e); }
+
+// EMA = false: the update pass as it always was (hig_clip_adam / _lrdev / _shadow).  EMA = true: the new parameter, still
+// in a register, is blended into `ema` before it is stored (hig_clip_adam_ema): 8 B per element more, no launch more.
+template <bool EMA>
 __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v,
                                                         int64_t n, float lr, float b1, float b2,
@@ -437,9 +455,11 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, c
                                                         float* __restrict__ gnorm_out,
                                                         const int32_t* __restrict__ step_dev,
                                                         const float* __restrict__ lr_dev,
-                                                        __bf16* __restrict__ shadow, int64_t shadow_n) {
+                                                        __bf16* __restrict__ shadow, int64_t shadow_n,
+                                                        float* __restrict__ ema, float decay, int warmup,
+                                                        int ema_origin) {
   __shared__ float red[256];
-  __shared__ float s_coef, s_step_size, s_inv_sqrt_bc2;
+  __shared__ float s_coef, s_step_size, s_inv_sqrt_bc2, s_ema_w;
   {
     float s = 0.f;
     for (int i = threadIdx.x; i < HIG_NORM_BLOCKS; i += 256) s += partial[i];
@@ -459,12 +479,14 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, c
       const double bc1 = 1.0 - pow((double)b1, t), bc2 = 1.0 - pow((double)b2, t);
       s_step_size = (float)((double)(lr_dev ? lr_dev[0] : lr) / bc1);
       s_inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+      if (EMA) s_ema_w = ema_weight((int64_t)*step_dev + 1 - ema_origin, decay, warmup);
       if (blockIdx.x == 0 && gnorm_out) gnorm_out[0] = gnorm;
     }
     __syncthreads();
   }
   const float coef = s_coef, step_size = s_step_size, isb2 = s_inv_sqrt_bc2;
   const float ob1 = 1.0f - b1, ob2 = 1.0f - b2;
+  const float ema_w = EMA ? s_ema_w : 0.f;
   const int64_t n4 = n / 4;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4;
        i += (int64_t)gridDim.x * blockDim.x) {
@@ -479,6 +501,11 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, c
       mm[e] = b1 * mm[e] + ob1 * gg[e];
       v2[e] = b2 * v2[e] + ob2 * gg[e] * gg[e];
       pp[e] -= step_size * (mm[e] / (sqrtf(v2[e]) * isb2 + eps));
+    }
+    if (EMA) {   // the new parameters are still in registers: p is not read again
+      const float4 ev = reinterpret_cast<const float4*>(ema)[i];
+      reinterpret_cast<float4*>(ema)[i] = make_float4(ema_blend(ev.x, pp[0], ema_w), ema_blend(ev.y, pp[1], ema_w),
+                                                      ema_blend(ev.z, pp[2], ema_w), ema_blend(ev.w, pp[3], ema_w));
     }
     reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
     if (shadow && 4 * i + 3 < shadow_n) {   // bf16 shadow of the new parameters (bf16-storage training: no separate cast pass)
@@ -497,9 +524,62 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, c
     const float pn = p[i] - step_size * (mm / (sqrtf(v2) * isb2 + eps));
     p[i] = pn;
     if (shadow && i < shadow_n) shadow[i] = (__bf16)pn;
+    if (EMA) ema[i] = ema_blend(ema[i], pn, ema_w);
   }
 }
 __global__ void inc_step_kernel(int32_t* s) { s[0] += 1; }
+
+// The blend as a pass of its own (hig_ema_update) and the in-place exchange (hig_swap_f32).  VEC: both pointers are 16-byte
+// aligned -> float4 body + scalar tail; otherwise dword accesses throughout (the rule of eval_pairs_build_kernel).
+template <bool VEC>
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n,
+                                                         float decay, int warmup, const int32_t* __restrict__ step_dev,
+                                                         int ema_origin, int n_host) {
+  __shared__ float s_w;
+  if (threadIdx.x == 0) s_w = ema_weight(step_dev ? (int64_t)step_dev[0] - ema_origin : (int64_t)n_host, decay, warmup);
+  __syncthreads();
+  const float w = s_w;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (VEC) {
+    const int64_t n4 = n / 4;
+    for (int64_t i = tid; i < n4; i += stride) {
+      const float4 ev = reinterpret_cast<const float4*>(ema)[i], pv = reinterpret_cast<const float4*>(p)[i];
+      reinterpret_cast<float4*>(ema)[i] = make_float4(ema_blend(ev.x, pv.x, w), ema_blend(ev.y, pv.y, w),
+                                                      ema_blend(ev.z, pv.z, w), ema_blend(ev.w, pv.w, w));
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+      const int64_t i = n4 * 4 + threadIdx.x;
+      ema[i] = ema_blend(ema[i], p[i], w);
+    }
+  } else {
+    for (int64_t i = tid; i < n; i += stride) ema[i] = ema_blend(ema[i], p[i], w);
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (VEC) {
+    const int64_t n4 = n / 4;
+    for (int64_t i = tid; i < n4; i += stride) {
+      const float4 av = reinterpret_cast<const float4*>(a)[i], bv = reinterpret_cast<const float4*>(b)[i];
+      reinterpret_cast<float4*>(a)[i] = bv;
+      reinterpret_cast<float4*>(b)[i] = av;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+      const int64_t i = n4 * 4 + threadIdx.x;
+      const float av = a[i], bv = b[i];
+      a[i] = bv;
+      b[i] = av;
+    }
+  } else {
+    for (int64_t i = tid; i < n; i += stride) {
+      const float av = a[i], bv = b[i];
+      a[i] = bv;
+      b[i] = av;
+    }
+  }
+}
 
 int stream_blocks(int64_t total) {
   const int64_t b = (total + 255) / 256;
@@ -831,10 +911,68 @@ extern "C" int hig_clip_adam_shadow(float* p, const float* g, float* m, float* v
                 reinterpret_cast<uintptr_t>(v)) & 15) == 0 && (reinterpret_cast<uintptr_t>(shadow16) & 7) == 0,
               "hig_clip_adam: buffers must be 16-byte aligned (the bf16 shadow 8-byte)");
   HIG_REQUIRE(!shadow16 || (shadow_n >= 0 && shadow_n <= n && shadow_n % 4 == 0), "hig_clip_adam: shadow_n must be a multiple of 4, <= n");
-  hipLaunchKernelGGL(clip_adam_kernel, dim3(stream_blocks(n / 4 + 1)), dim3(256), 0, hig_stream(s), p, g, m, v,
-                     n, lr, b1, b2, eps, max_norm, inv_world, scratch, gnorm_out, step_dev, lr_dev, static_cast<__bf16*>(shadow16), shadow_n);
+  hipLaunchKernelGGL(clip_adam_kernel<false>, dim3(stream_blocks(n / 4 + 1)), dim3(256), 0, hig_stream(s), p, g, m, v,
+                     n, lr, b1, b2, eps, max_norm, inv_world, scratch, gnorm_out, step_dev, lr_dev, static_cast<__bf16*>(shadow16), shadow_n,
+                     static_cast<float*>(nullptr), 0.f, 0, 0);
   HIG_CHECK_LAUNCH();
   hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, hig_stream(s), step_dev);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_clip_adam_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr,
+                                 const float* lr_dev, float b1, float b2, float eps, float max_norm,
+                                 float inv_world, const float* scratch, float* gnorm_out, int32_t* step_dev,
+                                 void* shadow16, int64_t shadow_n, float* ema, float decay, int32_t warmup,
+                                 int32_t ema_origin, hig_stream_t s) {
+  HIG_REQUIRE(p && g && m && v && scratch && step_dev && n > 0, "hig_clip_adam_ema: bad arguments");
+  HIG_REQUIRE(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                reinterpret_cast<uintptr_t>(v)) & 15) == 0 && (reinterpret_cast<uintptr_t>(shadow16) & 7) == 0,
+              "hig_clip_adam_ema: buffers must be 16-byte aligned (the bf16 shadow 8-byte)");
+  HIG_REQUIRE(!shadow16 || (shadow_n >= 0 && shadow_n <= n && shadow_n % 4 == 0), "hig_clip_adam_ema: shadow_n must be a multiple of 4, <= n");
+  HIG_REQUIRE(ema && (reinterpret_cast<uintptr_t>(ema) & 15) == 0, "hig_clip_adam_ema: ema must be non-null and 16-byte aligned");
+  HIG_REQUIRE(decay > 0.f && decay < 1.f, "hig_clip_adam_ema: 0 < decay < 1 required, got %g", (double)decay);
+  HIG_REQUIRE(warmup == 0 || warmup == 1, "hig_clip_adam_ema: warmup must be 0 or 1, got %d", (int)warmup);
+  HIG_REQUIRE(ema_origin >= 0, "hig_clip_adam_ema: ema_origin must be >= 0, got %d", (int)ema_origin);
+  hipLaunchKernelGGL(clip_adam_kernel<true>, dim3(stream_blocks(n / 4 + 1)), dim3(256), 0, hig_stream(s), p, g, m, v,
+                     n, lr, b1, b2, eps, max_norm, inv_world, scratch, gnorm_out, step_dev, lr_dev, static_cast<__bf16*>(shadow16), shadow_n,
+                     ema, decay, (int)warmup, (int)ema_origin);
+  HIG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(inc_step_kernel, dim3(1), dim3(1), 0, hig_stream(s), step_dev);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_ema_update(float* ema, const float* p, int64_t n, float decay, int32_t warmup, const int32_t* step_dev,
+                              int32_t ema_origin, int32_t n_host, hig_stream_t s) {
+  HIG_REQUIRE(ema && p && n > 0, "hig_ema_update: ema, p non-null and n > 0 required");
+  HIG_REQUIRE(((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(p)) & 3) == 0, "hig_ema_update: pointers must be 4-byte aligned");
+  HIG_REQUIRE(decay > 0.f && decay < 1.f, "hig_ema_update: 0 < decay < 1 required, got %g", (double)decay);
+  HIG_REQUIRE(warmup == 0 || warmup == 1, "hig_ema_update: warmup must be 0 or 1, got %d", (int)warmup);
+  HIG_REQUIRE(ema_origin >= 0, "hig_ema_update: ema_origin must be >= 0, got %d", (int)ema_origin);
+  const bool vec = ((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(ema_update_kernel<true>, dim3(stream_blocks(n / 4 + 1)), dim3(256), 0, hig_stream(s), ema, p, n, decay,
+                       (int)warmup, step_dev, (int)ema_origin, (int)n_host);
+  else
+    hipLaunchKernelGGL(ema_update_kernel<false>, dim3(stream_blocks(n)), dim3(256), 0, hig_stream(s), ema, p, n, decay,
+                       (int)warmup, step_dev, (int)ema_origin, (int)n_host);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_swap_f32(float* a, float* b, int64_t n, hig_stream_t s) {
+  HIG_REQUIRE(a && b && n > 0, "hig_swap_f32: a, b non-null and n > 0 required");
+  HIG_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3) == 0, "hig_swap_f32: pointers must be 4-byte aligned");
+  {
+    const uintptr_t ua = reinterpret_cast<uintptr_t>(a), ub = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * 4;
+    HIG_REQUIRE(ua + bytes <= ub || ub + bytes <= ua, "hig_swap_f32: the operands overlap");
+  }
+  const bool vec = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(swap_f32_kernel<true>, dim3(stream_blocks(n / 4 + 1)), dim3(256), 0, hig_stream(s), a, b, n);
+  else
+    hipLaunchKernelGGL(swap_f32_kernel<false>, dim3(stream_blocks(n)), dim3(256), 0, hig_stream(s), a, b, n);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

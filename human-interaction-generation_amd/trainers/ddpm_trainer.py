@@ -14,6 +14,7 @@ names and the checkpoint keys); the bodies are this project's own and are organi
 written to / restored from checkpoints in torch-Adam's own `state_dict` layout, so a checkpoint resumes under either
 step (and under the reference's trainer).
 """
+import contextlib
 import time
 from collections import OrderedDict
 from os.path import join as pjoin
@@ -42,6 +43,20 @@ def _core(encoder):
 
 def _dist_world():
     return dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
+
+
+def ema_options(opt):
+    """(decay, warmup) of the EMA of the weights that `opt` asks for, or None: opt.ema_decay None or 0 (the default) is off,
+    otherwise a number in (0, 1) -- anything else is a ValueError; opt.ema_warmup (default True) ramps the decay up as
+    min(decay, (1 + n) / (10 + n)) (include/hig.h, 'EMA weights')."""
+    d = getattr(opt, "ema_decay", None)
+    if d is None or (not isinstance(d, bool) and isinstance(d, (int, float)) and d == 0):
+        return None
+    if isinstance(d, bool) or not isinstance(d, (int, float)) or not 0.0 < float(d) < 1.0:
+        raise ValueError("opt.ema_decay must be None, 0 (no EMA) or a number in (0, 1), got %r" % (d,))
+    if float(torch.tensor(float(d), dtype=torch.float32)) >= 1.0:
+        raise ValueError("opt.ema_decay = %r rounds to 1 in fp32: the average would never move" % (d,))
+    return float(d), bool(getattr(opt, "ema_warmup", True))
 
 
 class _RunningMean:
@@ -83,6 +98,10 @@ class DDPMTrainer(object):
         self._fused = None
         self._few_step = None          # set_sampler: (SpacedDiffusion, method, eta), or None = the full chain
         self._guidance_scale = None    # set_sampler: the classifier-free guidance scale, or None = unguided
+        ema_options(args)              # (a bad opt.ema_decay is refused here, not at the first step)
+        self._ema = None               # ema_state(): the EMA of the weights, lazy
+        self._ema_scope = False        # inside `with trainer.ema_weights()`
+        self._sample_weights = "model"   # set_sampler: which weights `generate` samples from
         self.to(self.device)
 
     # ---- small helpers the reference exposes as static methods ----------------------------------------------
@@ -159,12 +178,16 @@ class DDPMTrainer(object):
 
     def update(self):
         """zero_grad -> loss -> backward -> clip_grad_norm_(0.5) -> Adam (ddpm_trainer.py:180-187)."""
+        self._ema_refuse_in_scope("update")
         self.zero_grad([self.opt_encoder])
         logs = self.backward_G()
         self.loss_mot_rec.backward()
         self._exchange_param_grads()
         self.clip_norm([self.encoder])
+        ema = self.ema_state()         # (before the step: a new EMA starts from the weights this step updates)
         self.step([self.opt_encoder])
+        if ema is not None:
+            self._ema_update_after_torch_step(ema)
         _core(self.encoder).params_changed()
         return logs
 
@@ -207,8 +230,151 @@ class DDPMTrainer(object):
             else:
                 p.grad.copy_(v)
 
+    # ---- EMA of the weights (include/hig.h, 'EMA weights') -------------------------------------------------------
+    def _ema_outside_params(self):
+        """[(state-dict name, parameter)] of what trains outside the flat buffer: a torch text head, a trainable CLIP tower
+        (no_clip=True), cap_id embeddings."""
+        core = _core(self.encoder)
+        fp = core.flat_params()
+        in_flat = {id(p) for p in fp.params + fp.text_params}
+        return [(k, p) for k, p in core.named_parameters() if p.requires_grad and id(p) not in in_flat]
+
+    def _ema_new(self, decay, warmup, origin, num_updates):
+        """An EMA that equals the current weights: an fp32 twin of the flat buffer and one twin per outside tensor."""
+        fp = _core(self.encoder).flat_params()
+        outside = OrderedDict()
+        for k, p in self._ema_outside_params():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise NotImplementedError("EMA: trainable parameter %s is %s%s -- the EMA kernels take contiguous fp32"
+                                          % (k, p.dtype, "" if p.is_contiguous() else ", not contiguous"))
+            outside[k] = p.detach().clone()
+        flat = torch.zeros_like(fp.flat)
+        flat.copy_(fp.flat)
+        self._ema = {"flat": flat, "outside": outside, "decay": float(decay), "warmup": bool(warmup), "origin": int(origin),
+                     "num_updates": int(num_updates), "ptr": fp.flat.data_ptr()}
+        return self._ema
+
+    def ema_state(self, create=True):
+        """The EMA of the weights, or None when there is none: {'flat': fp32 twin of the flat parameter buffer, 'outside':
+        {name: twin} for trainable tensors outside it, 'decay', 'warmup', 'origin' (the Adam step count at which it was
+        switched on), 'num_updates' (host count), 'ptr'}.  Created on first use when opt.ema_decay is set (a copy of the
+        current weights); an EMA that a checkpoint brought along is kept up whether or not the option is set.  Tied to the flat
+        buffer's pointer as `fused_state()` is: when `.to()` re-homes the parameters the EMA moves along, and the captured
+        graphs (keyed on its pointer) are dropped."""
+        st = self._ema
+        if st is None and (not create or ema_options(self.opt) is None):
+            return None                # (EMA off: nothing is touched, not even the flat buffer)
+        fp = _core(self.encoder).flat_params()
+        if st is not None and st["ptr"] != fp.flat.data_ptr():
+            if st["flat"].numel() == fp.flat.numel():
+                st["flat"] = st["flat"].to(fp.flat.device)
+                now = dict(self._ema_outside_params())
+                st["outside"] = OrderedDict((k, t.to(now[k].device)) for k, t in st["outside"].items() if k in now)
+                st["ptr"] = fp.flat.data_ptr()
+                if self._fused is not None:
+                    self._fused["graphs"] = {}
+            else:
+                st = self._ema = None
+        if st is None and create:
+            cfg = ema_options(self.opt)
+            if cfg is not None:
+                origin = int(self._fused["step"].item()) if self._fused is not None else 0
+                st = self._ema_new(cfg[0], cfg[1], origin, 0)
+        return st
+
+    def _ema_refuse_in_scope(self, what):
+        if self._ema_scope:
+            raise RuntimeError("%s inside `with trainer.ema_weights()`: the model holds the averaged weights there, leave the "
+                               "scope first" % what)
+
+    def _ema_update_after_torch_step(self, st):
+        """Route 3: torch.optim.Adam has stepped; one hig_ema_update over the flat buffer, one per outside tensor."""
+        L = _lib.lib()
+        fp = _core(self.encoder).flat_params()
+        n_host = st["num_updates"] + 1
+        args = (st["decay"], int(st["warmup"]), None, st["origin"], n_host, _lib.stream_ptr())
+        _lib.check(L.hig_ema_update(_lib.ptr(st["flat"]), _lib.ptr(fp.flat), fp.numel, *args))
+        now = dict(self._ema_outside_params())
+        for k, e in st["outside"].items():
+            _lib.check(L.hig_ema_update(_lib.ptr(e), _lib.ptr(now[k].data), e.numel(), *args))
+        st["num_updates"] = n_host
+
+    def _ema_exchange(self, st):
+        """Weights <-> EMA in place (hig_swap_f32): no pointer moves, so parameter tables, derived-operand caches and captured
+        training graphs stay valid; what is DERIVED from the weights (bf16 shadow, text context) follows params_changed()."""
+        L = _lib.lib()
+        core = _core(self.encoder)
+        fp = core.flat_params()
+        _lib.check(L.hig_swap_f32(_lib.ptr(fp.flat), _lib.ptr(st["flat"]), fp.numel, _lib.stream_ptr()))
+        now = dict(self._ema_outside_params())
+        for k, e in st["outside"].items():
+            _lib.check(L.hig_swap_f32(_lib.ptr(now[k].data), _lib.ptr(e), e.numel(), _lib.stream_ptr()))
+        core.params_changed()
+        if getattr(core, "storage", "f32") == "bf16" and getattr(fp, "_shadow", None) is not None:
+            fp.shadow16(core._param_version())      # eagerly: a captured training graph reads the shadow without re-deriving it
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with trainer.ema_weights():` -- the model computes with the averaged weights inside, and has its own back, bit for
+        bit, afterwards (a pure exchange on entry and on exit).  Inside, `update`, `train_step_fused`,
+        `train_step_captured` and `save` raise RuntimeError, and so does a nested entry."""
+        if self._ema_scope:
+            raise RuntimeError("ema_weights() is already entered: the scope does not nest")
+        st = self.ema_state()
+        if st is None:
+            raise RuntimeError("there is no EMA of the weights: set opt.ema_decay (e.g. 0.9999) before training, or load a "
+                               "checkpoint that was written with it (key 'encoder_ema')")
+        self._ema_exchange(st)
+        self._ema_scope = True
+        try:
+            yield self
+        finally:
+            self._ema_exchange(st)
+            self._ema_scope = False
+
+    def _sampling_weights(self):
+        """The scope `generate` runs in: nothing for weights="model", `ema_weights()` for "ema" (set_sampler)."""
+        return self.ema_weights() if getattr(self, "_sample_weights", "model") == "ema" else contextlib.nullcontext()
+
+    def _ema_state_dict(self, st):
+        """state-dict name -> averaged tensor, trainable parameters only (a frozen CLIP tower is not duplicated)."""
+        fp = _core(self.encoder).flat_params()
+        off = {id(p): o for p, o in zip(fp.params + fp.text_params, fp.offsets + fp.text_offsets)}
+        out = OrderedDict()
+        for k, p in _core(self.encoder).named_parameters():
+            if id(p) in off:
+                out[k] = st["flat"][off[id(p)]:off[id(p)] + p.numel()].view(p.shape).clone()
+            elif k in st["outside"]:
+                out[k] = st["outside"][k].clone()
+        return out
+
+    def _ema_load(self, ck):
+        """The EMA side of `load`: the checkpoint's EMA when it has one (opt.ema_decay / ema_warmup, where set, override its
+        decay and warm-up); otherwise, under opt.ema_decay, a copy of the loaded weights whose origin is the loaded Adam
+        step."""
+        self._ema = None
+        cfg = ema_options(self.opt)
+        if 'encoder_ema' in ck and 'ema' in ck:
+            info = ck['ema']
+            decay, warmup = cfg if cfg is not None else (info['decay'], info['warmup'])
+            st = self._ema_new(decay, warmup, info['origin'], info['num_updates'])
+            fp = _core(self.encoder).flat_params()
+            off = {id(p): o for p, o in zip(fp.params + fp.text_params, fp.offsets + fp.text_offsets)}
+            with torch.no_grad():
+                for k, p in _core(self.encoder).named_parameters():
+                    if k not in ck['encoder_ema']:
+                        continue
+                    t = ck['encoder_ema'][k].to(p.device, torch.float32)
+                    if id(p) in off:
+                        st["flat"][off[id(p)]:off[id(p)] + p.numel()].copy_(t.reshape(-1))
+                    elif k in st["outside"]:
+                        st["outside"][k].copy_(t)
+        elif cfg is not None:
+            steps = [int(float(e['step'])) for e in ck.get('opt_encoder', {}).get('state', {}).values() if 'step' in e]
+            self._ema_new(cfg[0], cfg[1], max(steps) if steps else 0, 0)
+
     # ---- sampling ----------------------------------------------------------------------------------------------
-    def set_sampler(self, steps=None, method="ddpm", eta=0.0, guidance_scale=None, spacing=None):
+    def set_sampler(self, steps=None, method="ddpm", eta=0.0, guidance_scale=None, spacing=None, weights="model"):
         """How `generate` samples.  steps=None: the full ancestral chain of `self.diffusion` (the default).  Otherwise
         `steps` of the diffusion_steps training steps, walked by the ancestral update (method="ddpm"), by DDIM with the
         given eta (method="ddim"; eta = 0 is deterministic) or by the second-order multistep solver DPM-Solver++(2M)
@@ -217,7 +383,11 @@ class DDPMTrainer(object):
         (space_timesteps_logsnr).  None: "uniform" for ddpm and ddim, "logsnr" for dpmpp2m, whose extrapolation needs it.
         guidance_scale: classifier-free guidance, eps_u + s (eps_c - eps_u) with the empty caption as the unconditional
         branch (train with opt.cond_drop_prob > 0); kept independently of `steps`, so it applies to the full chain too.
-        None or 1.0: unguided, launch for launch the loop without it.  ValueError unless it is a finite number."""
+        None or 1.0: unguided, launch for launch the loop without it.  ValueError unless it is a finite number.
+        weights: "model" (the default: the weights as they are) or "ema": `generate` runs inside `ema_weights()`, once
+        around all its chunks; without an EMA (opt.ema_decay, or a checkpoint that has one) that call is a RuntimeError."""
+        if weights not in ("model", "ema"):
+            raise ValueError("set_sampler: weights must be 'model' or 'ema', got %r" % (weights,))
         if method not in ("ddpm", "ddim", "dpmpp2m"):
             raise ValueError("set_sampler: method must be 'ddpm', 'ddim' or 'dpmpp2m', got %r" % (method,))
         eta = float(eta)
@@ -235,6 +405,7 @@ class DDPMTrainer(object):
         if scale is not None and scale != 1.0 and getattr(self, "cap_id", False):
             raise NotImplementedError("guidance on a cap_id model: it takes class embeddings, there is no empty caption")
         self._guidance_scale = None if scale == 1.0 else scale
+        self._sample_weights = weights
         if steps is None:
             self._few_step = None
             return
@@ -308,11 +479,12 @@ class DDPMTrainer(object):
             known = torch.as_tensor(known)
             known_mask = torch.broadcast_to(torch.as_tensor(known_mask), known.shape)
         samples = []
-        for lo in range(0, len(caption), batch_size):
-            hi = min(len(caption), lo + batch_size)
-            k = known if known is None else known[lo:hi]
-            km = known_mask if known_mask is None or known is None else known_mask[lo:hi]
-            samples.extend(self.generate_batch(caption[lo:hi], m_lens[lo:hi], dim_pose, known=k, known_mask=km).unbind(0))
+        with self._sampling_weights():
+            for lo in range(0, len(caption), batch_size):
+                hi = min(len(caption), lo + batch_size)
+                k = known if known is None else known[lo:hi]
+                km = known_mask if known_mask is None or known is None else known_mask[lo:hi]
+                samples.extend(self.generate_batch(caption[lo:hi], m_lens[lo:hi], dim_pose, known=k, known_mask=km).unbind(0))
         return samples
 
     # ---- checkpoints (keys: opt_encoder / ep / total_it / encoder, ddpm_trainer.py:200-218) ---------------------
@@ -363,10 +535,20 @@ class DDPMTrainer(object):
         st["covered"] = max(st["covered"], covered)
 
     def save(self, file_name, ep, total_it):
-        torch.save({'opt_encoder': self._optimizer_state_dict(), 'ep': ep, 'total_it': total_it,
-                    'encoder': _core(self.encoder).state_dict()}, file_name)
+        """The reference's four keys; with an EMA of the weights two more, which the reference's `load` ignores:
+        'encoder_ema' (state-dict names -> averaged tensors, trainable parameters only: loads into a reference-layout model
+        with strict=False) and 'ema' ({'decay', 'warmup', 'origin', 'num_updates'})."""
+        self._ema_refuse_in_scope("save")
+        ck = {'opt_encoder': self._optimizer_state_dict(), 'ep': ep, 'total_it': total_it,
+              'encoder': _core(self.encoder).state_dict()}
+        ema = self.ema_state()
+        if ema is not None:
+            ck['encoder_ema'] = self._ema_state_dict(ema)
+            ck['ema'] = {k: ema[k] for k in ('decay', 'warmup', 'origin', 'num_updates')}
+        torch.save(ck, file_name)
 
     def load(self, model_dir):
+        self._ema_refuse_in_scope("load")
         ck = torch.load(model_dir, map_location=self.device)
         core = _core(self.encoder)
         core.load_state_dict(ck['encoder'], strict=True)
@@ -375,6 +557,7 @@ class DDPMTrainer(object):
             self._torch_optimizer().load_state_dict(ck['opt_encoder'])
             if getattr(self.opt, "fused_step", False) or self._fused is not None:
                 self._adopt_optimizer_state(ck['opt_encoder'])
+        self._ema_load(ck)       # (also with is_train False: an inference-only trainer can sample from the average)
         return ck['ep'], ck.get('total_it', 0)
 
     # ---- the epoch loop (ddpm_trainer.py:220-266: logging and checkpoint cadence) ----------------------------------
@@ -402,6 +585,14 @@ class DDPMTrainer(object):
             stp = self._fused["step"].to(torch.int64)
             dist.broadcast(stp, src=0)
             self._fused["step"].copy_(stp.to(torch.int32))
+        ema = self.ema_state()
+        if ema is not None:     # (a deterministic function of the parameters, but a resumed rank 0 must win)
+            broadcast_flat(ema["flat"])
+            for e in ema["outside"].values():
+                dist.broadcast(e, src=0)
+            cnt = torch.tensor([ema["origin"], ema["num_updates"]], dtype=torch.int64, device=fp.flat.device)
+            dist.broadcast(cnt, src=0)
+            ema["origin"], ema["num_updates"] = int(cnt[0]), int(cnt[1])
         core.params_changed()
 
     def _one_step(self, batch_data, fused):
@@ -576,11 +767,20 @@ class DDPMTrainer(object):
         # bf16 storage: the update kernel also writes bf16(new parameters) into the weight shadow the next forward reads
         # (fp32 master weights, no separate cast pass over the 81 M parameters)
         shadow = fp.shadow16_buffer() if bf16 else None
-        _lib.check(L.hig_clip_adam_shadow(_lib.ptr(fp.flat), _lib.ptr(fp.grad), _lib.ptr(st["m"]), _lib.ptr(st["v"]),
-                                          n, st["lr_host"], _lib.ptr(st["lr"]), ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS,
-                                          GRAD_CLIP, 1.0 / world, _lib.ptr(st["scratch"]), _lib.ptr(st["gnorm"]),
-                                          _lib.ptr(st["step"]), _lib.ptr(shadow), fp.core_numel if bf16 else 0,
-                                          _lib.stream_ptr()))
+        ema = self.ema_state()
+        if ema is None:
+            _lib.check(L.hig_clip_adam_shadow(_lib.ptr(fp.flat), _lib.ptr(fp.grad), _lib.ptr(st["m"]), _lib.ptr(st["v"]),
+                                              n, st["lr_host"], _lib.ptr(st["lr"]), ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS,
+                                              GRAD_CLIP, 1.0 / world, _lib.ptr(st["scratch"]), _lib.ptr(st["gnorm"]),
+                                              _lib.ptr(st["step"]), _lib.ptr(shadow), fp.core_numel if bf16 else 0,
+                                              _lib.stream_ptr()))
+        else:   # the same pass also blends the new parameters into the EMA; its update number comes from the device counter
+            _lib.check(L.hig_clip_adam_ema(_lib.ptr(fp.flat), _lib.ptr(fp.grad), _lib.ptr(st["m"]), _lib.ptr(st["v"]),
+                                           n, st["lr_host"], _lib.ptr(st["lr"]), ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS,
+                                           GRAD_CLIP, 1.0 / world, _lib.ptr(st["scratch"]), _lib.ptr(st["gnorm"]),
+                                           _lib.ptr(st["step"]), _lib.ptr(shadow), fp.core_numel if bf16 else 0,
+                                           _lib.ptr(ema["flat"]), ema["decay"], int(ema["warmup"]), ema["origin"],
+                                           _lib.stream_ptr()))
         st["covered"] = max(st["covered"], n)
         core.params_changed()
         if bf16:
@@ -596,7 +796,9 @@ class DDPMTrainer(object):
         inside the step and EVERY trainable parameter is updated -- the reference's full update.
         With more than one rank the replicas must start identical: call `sync_replicas()` once (train() does).
         No host synchronisation: the loss stays on the device (`fused_state()['loss']`)."""
+        self._ema_refuse_in_scope("train_step_fused")
         st = self.fused_state()
+        ema = self.ema_state()            # (created here, from the weights before the step, when opt.ema_decay asks for one)
         with_text = clip_out is not None
         n = self._fused_numel(with_text)
         self._set_lr(lr)
@@ -608,6 +810,8 @@ class DDPMTrainer(object):
             self._fused_fwd_bwd(x_start, t, length, xf_proj, xf_out, noise, clip_out=clip_out, eot=eot)
             world = st["allreduce"](fp.grad[:n])                                  # one all-reduce after the backward
         self._fused_clip_adam(world, with_text)
+        if ema is not None:
+            ema["num_updates"] += 1
         return st["loss"]
 
     def train_fused_batch(self, batch_data, captured=False, noise=None):
@@ -641,8 +845,11 @@ class DDPMTrainer(object):
         sampler through the same staging copy (the reference draws it with numpy, gaussian_diffusion.py:47-62), the
         learning rate through a device scalar (`_set_lr`).  A graph is keyed on the shapes AND on the flat parameter /
         gradient buffers it was captured against.  Text inputs as in `train_step_fused`: embeddings, or CLIP
-        features."""
+        features.  The EMA of the weights rides in the same update kernel (its update number comes from the device step
+        counter, its origin is a constant of the graph); the graph key carries its configuration."""
+        self._ema_refuse_in_scope("train_step_captured")
         st = self.fused_state()
+        ema = self.ema_state()            # (created eagerly, never inside a capture)
         world = _dist_world()
         split = exchange_active()         # there is an exchange to run (more than one rank, or HIG_FORCE_EXCHANGE)
         # (gloo stages through the host: its collectives cannot be captured -- that backend always takes the split form)
@@ -653,7 +860,8 @@ class DDPMTrainer(object):
         n = self._fused_numel(with_text)
         self._set_lr(lr)
         key = (tuple(x_start.shape), tuple(text_in[0].shape), tuple(text_in[1].shape), with_text, noise is None,
-               world, split, in_graph, st["ptrs"])
+               world, split, in_graph, st["ptrs"],
+               None if ema is None else (ema["decay"], ema["warmup"], ema["origin"], ema["flat"].data_ptr()))
         cap = st["graphs"].get(key)
         if cap is None:
             static = {"x0": x_start.clone(), "t": t.clone(), "length": length.clone(),
@@ -674,7 +882,8 @@ class DDPMTrainer(object):
             # it runs a real step, so restore parameters / moments / step counter afterwards
             core = _core(self.encoder)
             fp = core.flat_params()
-            keep = (fp.flat.clone(), st["m"].clone(), st["v"].clone(), st["step"].clone(), st["covered"])
+            keep = (fp.flat.clone(), st["m"].clone(), st["v"].clone(), st["step"].clone(), st["covered"],
+                    None if ema is None else (ema["flat"].clone(), ema["num_updates"]))
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
@@ -691,6 +900,9 @@ class DDPMTrainer(object):
                     st["m"].copy_(keep[1])
                     st["v"].copy_(keep[2])
                     st["step"].copy_(keep[3])
+                    if ema is not None:     # the warm-up's update also moved the EMA
+                        ema["flat"].copy_(keep[5][0])
+                        ema["num_updates"] = keep[5][1]
                 st["covered"] = keep[4]
                 core.params_changed()
                 if getattr(core, "storage", "f32") == "bf16":   # the warm-up's update also wrote the bf16 shadow: re-derive it
@@ -748,6 +960,8 @@ class DDPMTrainer(object):
         if gb is not None:
             st["allreduce"](_core(self.encoder).flat_params().grad[:n])
             gb.replay()
+        if ema is not None:
+            ema["num_updates"] += 1
         st["covered"] = max(st["covered"], n)
         core = _core(self.encoder)
         core.params_changed()

@@ -186,21 +186,22 @@ class DDPMMulTrainer(DDPMTrainer):
         cur_idx = 0
         self.encoder.eval()
         all_output = []
-        while cur_idx < N:
-            end = N if cur_idx + batch_size >= N else cur_idx + batch_size
-            batch_caption1 = caption1[cur_idx:end]
-            # the reference slices caption1 again for the second person of a non-final chunk (:212);
-            # kept, so chunked generation gives the same conditioning as upstream
-            batch_caption2 = caption2[cur_idx:] if end == N else caption1[cur_idx:end]
-            batch_m_lens = m_lens[cur_idx:end]
-            k = known if known is None else known[:, cur_idx:end]
-            km = known_mask if known_mask is None or known is None else known_mask[:, cur_idx:end]
-            output = self.generate_batch(batch_caption1, batch_caption2, batch_m_lens, dim_pose, known=k, known_mask=km)
-            B = len(batch_caption1)
-            motion1, motion2 = output[:B], output[B:]
-            for i in range(B):
-                all_output.append([motion1[i], motion2[i]])
-            cur_idx += batch_size
+        with self._sampling_weights():      # set_sampler(weights="ema"): one exchange around all the chunks
+            while cur_idx < N:
+                end = N if cur_idx + batch_size >= N else cur_idx + batch_size
+                batch_caption1 = caption1[cur_idx:end]
+                # the reference slices caption1 again for the second person of a non-final chunk (:212);
+                # kept, so chunked generation gives the same conditioning as upstream
+                batch_caption2 = caption2[cur_idx:] if end == N else caption1[cur_idx:end]
+                batch_m_lens = m_lens[cur_idx:end]
+                k = known if known is None else known[:, cur_idx:end]
+                km = known_mask if known_mask is None or known is None else known_mask[:, cur_idx:end]
+                output = self.generate_batch(batch_caption1, batch_caption2, batch_m_lens, dim_pose, known=k, known_mask=km)
+                B = len(batch_caption1)
+                motion1, motion2 = output[:B], output[B:]
+                for i in range(B):
+                    all_output.append([motion1[i], motion2[i]])
+                cur_idx += batch_size
         return all_output
 
     # ---- pseudo-labelling of the caption order (:313-440) --------------------------------------

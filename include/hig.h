@@ -1172,6 +1172,38 @@ int hig_clip_adam_lrdev(float* p, const float* g, float* m, float* v, int64_t n,
 int hig_clip_adam_shadow(float* p, const float* g, float* m, float* v, int64_t n, float lr, const float* lr_dev,
                          float b1, float b2, float eps, float max_norm, float inv_world, const float* scratch,
                          float* gnorm_out, int32_t* step_dev, void* shadow16, int64_t shadow_n, hig_stream_t s);
+/* ------------------------------------------------------------------------------------------
+ * EMA weights: an exponential moving average of the parameters, kept in an fp32 buffer `ema` of its own.
+ * For EMA update number n, counted from n = 1 at the first update after the EMA was switched on:
+ *     d_n = decay                                  warmup == 0
+ *     d_n = min(decay, (1 + n) / (10 + n))         warmup == 1
+ *     w   = fp32(1 - d_n)                          computed in fp64 from fp64(fp32 decay), rounded once
+ *     e'  = e + w * (p' - e)                       fp32, per element; p' = the parameter AFTER this step's Adam update
+ * The lerp form, not d e + w p': its rounding scales with |p' - e| instead of |e| (6 to 25 times closer to the fp64
+ * recurrence on Adam-sized trajectories, tests/ema_bounds.py).  No compensation term; n below 1 counts as 1.
+ *
+ * hig_clip_adam_ema: hig_clip_adam_shadow that also blends the new parameter, while it is still in a register, into ema[i]
+ *   for every i < n -- p, m, v, the shadow and gnorm_out get exactly the bits hig_clip_adam_shadow gives them.
+ *   n = step_dev[0] + 1 - ema_origin, read BEFORE this call's increment of the counter; ema_origin = the Adam step count at
+ *   which the EMA was switched on, a host scalar that is constant for a trainer's life (it can be baked into a captured
+ *   graph, the counter it is subtracted from lives on the device).  HIG_EINVAL before any launch: ema NULL or not 16-byte
+ *   aligned, decay outside (0, 1), warmup outside {0, 1}, ema_origin < 0, and whatever hig_clip_adam_shadow refuses.
+ * hig_ema_update: the same blend (one __device__ function: bit-equal for the same p', e and w) as a streaming pass of its
+ *   own, for a step whose parameters something else has updated (torch.optim.Adam).  step_dev == NULL: the update number is
+ *   n_host.  Otherwise it is step_dev[0] - ema_origin: the counter HAS ALREADY BEEN incremented by the step this update
+ *   follows.  Any 4-byte aligned pointers: 16-byte accesses where both allow them, dword accesses otherwise.
+ * hig_swap_f32: exchanges a[0, n) and b[0, n) in place, one pass, a pure copy; alignment rule as hig_ema_update;
+ *   overlapping operands are HIG_EINVAL.
+ * All three: n <= 0 or a NULL buffer is HIG_EINVAL; elements at index >= n are neither read nor written; no allocation, no
+ * synchronisation: capturable.
+ * ---------------------------------------------------------------------------------------- */
+int hig_clip_adam_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, const float* lr_dev,
+                      float b1, float b2, float eps, float max_norm, float inv_world, const float* scratch,
+                      float* gnorm_out, int32_t* step_dev, void* shadow16, int64_t shadow_n, float* ema, float decay,
+                      int32_t warmup, int32_t ema_origin, hig_stream_t s);
+int hig_ema_update(float* ema, const float* p, int64_t n, float decay, int32_t warmup, const int32_t* step_dev,
+                   int32_t ema_origin, int32_t n_host, hig_stream_t s);
+int hig_swap_f32(float* a, float* b, int64_t n, hig_stream_t s);
 /* Diagnostic: launches a one-thread kernel named hig_marker_kernel with a grid of `id` blocks -- a named, numbered mark in a
  * rocprofv3 kernel trace (bench.py brackets its roofline microbenchmark with markers 1 and 2; tools/summarize_profiles.py
  * averages the launches between them).  Does nothing else. */
