@@ -691,7 +691,7 @@ __global__ __launch_bounds__(256) void ctx16_mfma_kernel(const __bf16* __restric
 
 // Out = silu( LN( softmax_hd(Q) . A ) * (1 + scale) + shift ), bf16 matrix products (see the kernel).  Q, Out bf16 (B * rows,
 // H * hd); At16 bf16 (B, H, hd, hd) [l][c] = the TRANSPOSED context matrices (hig_linattn_ctx_bf16); gamma, beta, ss fp32; scale = ss[b][0 .. d), shift = ss[b][shift_off .. + d).
-// Head dim 64 with 4 or 8 heads (other shapes: hig_linattn_apply_sty_bf16 / the unfused pair).
+// Head dim 64 or 128 with 4 or 8 heads (other shapes: hig_linattn_apply_sty_bf16 / the unfused pair).
 unsigned long long* g_ap_stamps = nullptr;
 // Diagnostic: thread 0 of every workgroup of apply_sty16_kernel writes s_memtime stamps to buf[workgroup * 8 + k] (k: 0 start,
 // 1 Q tile landed, 2 softmax done, 3 context matrices landed, 4 products + row sums done, 5 output tile in LDS, 6 end).
@@ -814,7 +814,8 @@ extern "C" int hig_rows_out16(const void* Y, int64_t ldy, const float* gamma, co
 
 // A (fp32, [c][l]) + kstat (column max, column sum) + At16 (nullable: transposed bf16 copy) of the linear-attention context,
 // K / V bf16, on the bf16 matrix cores (ctx16_mfma_kernel): softmax_r(K) and V are rounded to bf16 for the product, fp32
-// accumulate and statistics.  Head dim 64; one workgroup per (sample, head).
+// accumulate and statistics.  Head dim 64 or 128; one workgroup per (sample, head).  K and V rows at and beyond length[b] are
+// never used and may hold anything.
 extern "C" int hig_linattn_ctx_mm16(const void* K, const void* V, int64_t ld, int32_t B, int32_t rows, int32_t H, int32_t hd,
                                     const int64_t* length, float* A, float* kstat, void* At16, hig_stream_t stream) {
   HIG_REQUIRE(K && V && A && kstat && B > 0 && rows > 0 && H > 0, "hig_linattn_ctx_mm16: bad arguments");

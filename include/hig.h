@@ -854,7 +854,10 @@ int hig_linattn_apply_bf16(const void* Q, int64_t ldq, const float* A, void* Y, 
                            int32_t H, int32_t hd, hig_stream_t stream);
 /* hig_linattn_ctx_bf16 with the k^T v product on the bf16 matrix cores (csrc/linattn16.hip: softmax_r(K) and V rounded to
  * bf16 for the product, fp32 accumulate / statistics; K and V chunks by LDS-DMA, ds_read_b64_tr_b16 transpose reads).
- * Head dim 64, one workgroup per (sample, head).  Default of the bf16-storage forward (HIG_CTX16=1). */
+ * Head dim 64 or 128, one workgroup per (sample, head).  Default of the bf16-storage forward (HIG_CTX16=1).
+ * Padded rows: K and V rows at and beyond length[b] are never used and may hold anything (NaN included): the loads are
+ * clamped to row length[b] - 1 and the weights of those rows are masked.  The denominator of the column softmax (kstat) is
+ * summed from the unrounded fp32 weights; tests/linattn16_bounds.py states every rounding point. */
 int hig_linattn_ctx_mm16(const void* K, const void* V, int64_t ld, int32_t B, int32_t rows, int32_t H, int32_t hd,
                          const int64_t* length, float* A, float* kstat, void* At16, hig_stream_t stream);
 /* hig_linattn_apply_bf16 followed by the stylization front hig_ln_bf16(ss != NULL) over all H heads, as one kernel:
