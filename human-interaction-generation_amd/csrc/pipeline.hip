@@ -158,6 +158,20 @@ __global__ __launch_bounds__(256) void recover_joints_kernel(const float* __rest
   }
 }
 
+// Bytes of LDS one workgroup of the current device may ask for (hipDeviceAttributeMaxSharedMemoryPerBlock), read once per
+// device; 0 when the device cannot be asked.
+int lds_bytes_per_workgroup() {
+  static int cache[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  int v = __atomic_load_n(&cache[dev], __ATOMIC_RELAXED);
+  if (v == 0) {
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v < 0) v = 0;
+    __atomic_store_n(&cache[dev], v, __ATOMIC_RELAXED);
+  }
+  return v;
+}
+
 }  // namespace
 
 extern "C" int hig_recover_joints(const float* motion, const float* stats, int32_t rows, int32_t T, int32_t F,
@@ -166,7 +180,14 @@ extern "C" int hig_recover_joints(const float* motion, const float* stats, int32
   HIG_REQUIRE(rows >= 0 && T > 0 && T <= 8192 && joints >= 1 && F >= 4 + 3 * (joints - 1),
               "hig_recover_joints: need 0 < T <= 8192 and F >= 4 + 3 * (joints - 1)");
   if (rows == 0) return HIG_OK;
-  hipLaunchKernelGGL(recover_joints_kernel, dim3(rows), dim3(256), (size_t)4 * T * sizeof(float), hig_stream(stream),
+  // The four per-frame arrays live in dynamic LDS.  The HIP headers ask for no opt-in above a default size on AMD devices
+  // (hipFuncAttributeMaxDynamicSharedMemorySize is documented as ignored there), so the device's per-workgroup limit is the
+  // whole condition, and it is checked here rather than found out by a launch.
+  const size_t lds = (size_t)4 * T * sizeof(float);
+  const int lds_max = lds_bytes_per_workgroup();
+  HIG_REQUIRE(lds <= (size_t)lds_max, "hig_recover_joints: T = %d needs %zu bytes of LDS, a workgroup of this device has %d", T,
+              lds, lds_max);
+  hipLaunchKernelGGL(recover_joints_kernel, dim3(rows), dim3(256), lds, hig_stream(stream),
                      motion, stats, T, F, joints, init_first, pos);
   HIG_CHECK_LAUNCH();
   return HIG_OK;

@@ -536,6 +536,9 @@ int hig_eval_pairs_build(const float* src, const int64_t* src_off, const int32_t
  * (init_first = 1, the sampler's token order) or last (0, recover_from_ric2's order).
  * stats = [mean F | std F | init_mean 4 | init_std 4] floats, or NULL if already de-normalised.
  * pos (rows, T, joints, 3).
+ * T <= 8192, and the 16 T bytes of LDS a workgroup keeps its per-frame arrays in must not exceed the device's
+ * per-workgroup limit (hipDeviceAttributeMaxSharedMemoryPerBlock, read on the host): a larger T is refused with
+ * HIG_EINVAL before any launch, as is any T when the device cannot be asked.
  * ---------------------------------------------------------------------------------------- */
 int hig_recover_joints(const float* motion, const float* stats, int32_t rows, int32_t T, int32_t F,
                        int32_t joints, int32_t init_first, float* pos, hig_stream_t stream);
@@ -1157,7 +1160,11 @@ int hig_masked_mse(const float* pred, const float* target, const int64_t* length
 /* Two-person losses of DDPMMulTrainer.backward_G (mul_ddpm_trainer.py:223-247): per-token MSE with the
  * init-pose token (t == 0) scored on its first 4 features, masked by length[r].  pit == 0: the labelled loss
  * sum / sum(mask).  pit == 1: rows are [m1|c1, m1|c2, m2|c2, m2|c1] (R = 4 x pairs); per pair the cheaper of the
- * two caption assignments, / (sum(mask) / 2).  dpred (optional) = d loss / d pred.  scratch: 2 R floats. */
+ * two caption assignments (a tie takes the first), / (sum(mask) / 2).  mask[r][t] = t < clamp(length[r], 0, T); length may
+ * be NULL (every row has T tokens).  dpred (may be NULL: the loss alone) = d loss / d pred, exactly 0 off the mask, on features
+ * >= 4 of the init-pose token and on the rows of the unchosen assignment; off the mask and on those features pred and target
+ * are never read.
+ * scratch: 2 R floats (the row losses, then d loss / d rowloss). */
 int hig_pair_mse(const float* pred, const float* target, const int64_t* length, int32_t R, int32_t T,
                  int32_t F, int32_t pit, float* loss, float* dpred, float* scratch, hig_stream_t s);
 int hig_sumsq_partial(const float* g, int64_t n, float inv_world, float* scratch, hig_stream_t s);

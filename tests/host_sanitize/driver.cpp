@@ -143,6 +143,14 @@ int main() {
     EXPECT(hig_linattn_ctx_mm16(b16, b16, 1536, 1, 4, 8, 32, nullptr, f32v, f32v, nullptr, nullptr) == HIG_EUNSUPPORTED);                         // head dim 32
     EXPECT(hig_linattn_apply_sty_mm16(b16, 1536, b16, f32v, f32v, f32v, 1024, 512, b16, 512, 1, 4, 3, 64, nullptr) == HIG_EUNSUPPORTED);         // 3 heads
     EXPECT(hig_timestep_embedding_bf16(nullptr, 1, 64, nullptr, nullptr) != HIG_OK);
+    // hig_recover_joints: a null pointer and T > 8192 are refused before any HIP call.  (Its third refusal, 16 T bytes above the
+    // device's per-workgroup LDS limit, asks the device first, so it is not exercised here: tests/test_gpu_boundary_contract.py.)
+    EXPECT(hig_recover_joints(nullptr, nullptr, 1, 2, 4, 1, 0, nullptr, nullptr) == HIG_EINVAL);
+    EXPECT(hig_recover_joints(f32v, nullptr, 1, 8193, 4, 1, 0, f32v, nullptr) == HIG_EINVAL);
+    EXPECT(hig_recover_joints(f32v, nullptr, 1, 0, 4, 1, 0, f32v, nullptr) == HIG_EINVAL);
+    EXPECT(hig_pair_mse(f32v, f32v, nullptr, 6, 2, 4, 1, f32v, nullptr, f32v, nullptr) == HIG_EINVAL);                  // PIT with R % 4 != 0
+    EXPECT(hig_pair_mse(f32v, f32v, nullptr, 4, 2, 3, 1, f32v, nullptr, f32v, nullptr) == HIG_EINVAL);                  // F < 4
+    EXPECT(hig_gather_frames(f32v, nullptr, nullptr, f32v, 0, 1, 1, 4, f32v, nullptr) == HIG_EINVAL);
     h.R = 32; h.ldx = 33;
     EXPECT(hig_gemm_bf16(&h, nullptr) == HIG_EINVAL);                  // leading dimension not a multiple of 8
     h.ldx = 48; h.epi = HIG_EPI_BIAS_RES; h.bias = reinterpret_cast<const float*>(dummy);
