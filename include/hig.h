@@ -21,6 +21,31 @@
  *     joined back into it with events.  No host synchronisation, device allocation, blocking copy or
  *     host read-back happens inside, so any call sequence can be captured into a hipGraph.
  *   - Matrices are row-major fp32 unless stated; nn.Linear weights are (out, in).
+ *
+ * This header is also the ONLY place an entry point, a struct or a code is written down: the Python binding is derived from it
+ * (human-interaction-generation_amd/_abi.py reads this file, _lib.py builds constants, Structures, argtypes and restype from the
+ * reading; tests/test_cpu_abi.py holds the result to the compiler's view).  To add something, declare it here in one of the
+ * forms below; anything else makes the binding's import fail with the declaration's name.
+ *   constants    `#define HIG_NAME <integer>` (optionally parenthesised / negative), or a member of an unnamed `enum { ... }`
+ *                with integer or implicit values; exported as NAME.  Any other `#define HIG_*` (function-like, non-integer)
+ *                must be listed in IGNORED_DEFINES of _abi.py.
+ *   structs      `typedef struct hig_<name> { type field[, field...]; ... } hig_<name>;` -- no arrays, bit-fields or nested
+ *                structs -- plus its Python class name in STRUCT_NAMES of _lib.py
+ *   callbacks    `typedef ret (*hig_<name>)(params);`
+ *   functions    `ret hig_<name>(params);` over any number of lines, comments allowed between parameters
+ *   types        C type                                      ctypes class
+ *                int, int32_t by value                       c_int32
+ *                int64_t by value                            c_int64
+ *                float by value                              c_float
+ *                void (return type only)                     None
+ *                hig_stream_t                                c_void_p
+ *                a callback typedef                          its CFUNCTYPE
+ *                char*                                       c_char_p
+ *                [const] hig_<name>* of a struct declared here POINTER(its Structure)
+ *                every other pointer (const void* const*,    c_void_p  (the binding cannot tell a host out-parameter from a
+ *                int32_t*, const uint8_t*, ...)                         device pointer; callers pass byref / arrays / addresses)
+ *                a struct by value, any other scalar         refused
+ *                (double, size_t, ...), variadic arguments
  */
 #ifndef HIG_H
 #define HIG_H

@@ -17,7 +17,6 @@ d.X, d.ldx, d.Y, d.ldy, d.C, d.ldc = X.data_ptr(), R, W.data_ptr(), R, out.data_
 d.I, d.J, d.R, d.epi, d.bias, d.prec = I, J, R, epi, b.data_ptr(), int(os.environ.get("PREC", 0))
 if epi == _lib.EPI_BIAS_RES: d.res, d.ldr = res.data_ptr(), J
 lib = _lib.lib()
-lib.hig_gemm_debug_stamps.argtypes = [C.c_void_p]
 tail = torch.zeros(lib.hig_gemm_tail_ws_bytes(), dtype=torch.uint8, device=dev)
 stamps = torch.zeros(4096 * 8, dtype=torch.int64, device=dev)
 lib.hig_gemm_debug_stamps(C.c_void_p(stamps.data_ptr()))
