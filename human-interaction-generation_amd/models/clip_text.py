@@ -1,0 +1,268 @@
+"""The text tower of OpenAI CLIP (clip/model.py: `Transformer` of `ResidualAttentionBlock`s under `CLIP.encode_text`) as a
+stand-alone module, and its native route.
+
+`MotionTransformer._clip_features` runs the frozen tower in front of the text head (transformer.py:381-388).  The `clip`
+package brings the tower as stock torch ops; this module has
+
+  * `ClipTextTransformer` / `ClipTextModel`: the same structure and state-dict names on stock torch ops, so OpenAI's weights
+    load without the package.  This forward is the YARDSTICK of the native route, never its fallback;
+  * `load_text_tower`: a state dict, a checkpoint of this project (`clip.` keys) or a file -> `ClipTextModel`;
+  * `tower_refusal` / `TowerTable` / `tower_forward`: the rule that says whether hig_clip_text_fwd (csrc/cliptext.hip) can run
+    a given tower, its pointer table, and the call.
+
+The BPE vocabulary is data this repository does not carry: without the `clip` package the caller supplies the tokenizer
+(`MotionTransformer(clip_model=..., clip_tokenize=...)`).
+"""
+import ctypes as C
+import math
+import os
+import re
+from collections import OrderedDict
+
+import torch
+from torch import nn
+
+HEAD_DIM = 64          # what hig_causal_attn_fwd is built for
+MAX_TOKENS = 128
+
+
+class QuickGELU(nn.Module):
+    def forward(self, x):
+        return x * torch.sigmoid(1.702 * x)
+
+
+def causal_mask(context_length):
+    """CLIP.build_attention_mask: additive, -inf above the diagonal."""
+    return torch.full((context_length, context_length), float("-inf")).triu_(1)
+
+
+class ResidualAttentionBlock(nn.Module):
+    def __init__(self, d_model, n_head, attn_mask=None):
+        super().__init__()
+        self.attn = nn.MultiheadAttention(d_model, n_head)
+        self.ln_1 = nn.LayerNorm(d_model)
+        self.mlp = nn.Sequential(OrderedDict([("c_fc", nn.Linear(d_model, d_model * 4)), ("gelu", QuickGELU()),
+                                              ("c_proj", nn.Linear(d_model * 4, d_model))]))
+        self.ln_2 = nn.LayerNorm(d_model)
+        self.attn_mask = attn_mask        # a plain attribute, as in OpenAI's class: not part of the state dict
+
+    def attention(self, x):
+        mask = self.attn_mask
+        if mask is not None:
+            self.attn_mask = mask = mask.to(dtype=x.dtype, device=x.device)
+        return self.attn(x, x, x, need_weights=False, attn_mask=mask)[0]
+
+    def forward(self, x):
+        x = x + self.attention(self.ln_1(x))
+        return x + self.mlp(self.ln_2(x))
+
+
+class ClipTextTransformer(nn.Module):
+    """Sequence-first (N, B, W) -> (N, B, W) on stock torch ops; every block carries the causal mask."""
+
+    def __init__(self, width=512, layers=12, heads=8, context_length=77):
+        super().__init__()
+        self.width, self.layers, self.heads, self.context_length = width, layers, heads, context_length
+        self.resblocks = nn.Sequential(*[ResidualAttentionBlock(width, heads, causal_mask(context_length)) for _ in range(layers)])
+
+    def forward(self, x):
+        return self.resblocks(x)
+
+
+class ClipTextModel(nn.Module):
+    """The attributes `_clip_features` and the stub touch: token_embedding, positional_embedding, transformer, ln_final,
+    text_projection, logit_scale, dtype, initialize_parameters."""
+
+    def __init__(self, width=512, layers=12, heads=8, context_length=77, vocab_size=49408, embed_dim=512):
+        super().__init__()
+        self.context_length, self.vocab_size = context_length, vocab_size
+        self.transformer = ClipTextTransformer(width, layers, heads, context_length)
+        self.token_embedding = nn.Embedding(vocab_size, width)
+        self.positional_embedding = nn.Parameter(torch.empty(context_length, width))
+        self.ln_final = nn.LayerNorm(width)
+        self.text_projection = nn.Parameter(torch.empty(width, embed_dim))
+        self.logit_scale = nn.Parameter(torch.ones([]) * math.log(1 / 0.07))
+        self.initialize_parameters()
+
+    @property
+    def dtype(self):
+        return self.token_embedding.weight.dtype
+
+    def initialize_parameters(self, generator=None):
+        """CLIP.initialize_parameters' standard deviations (the text side)."""
+        t = self.transformer
+        n = lambda p, std: nn.init.normal_(p, std=std, generator=generator)   # noqa: E731
+        n(self.token_embedding.weight, 0.02)
+        n(self.positional_embedding, 0.01)
+        proj_std = (t.width ** -0.5) * ((2 * t.layers) ** -0.5)
+        attn_std = t.width ** -0.5
+        fc_std = (2 * t.width) ** -0.5
+        for block in t.resblocks:
+            n(block.attn.in_proj_weight, attn_std)
+            n(block.attn.out_proj.weight, proj_std)
+            n(block.mlp.c_fc.weight, fc_std)
+            n(block.mlp.c_proj.weight, proj_std)
+        n(self.text_projection, t.width ** -0.5)
+
+    def features(self, tokens):
+        """tokens (B, N) -> ln_final's output, sequence-first (N, B, W): the lines of `_clip_features` on torch ops."""
+        x = self.token_embedding(tokens).type(self.dtype) + self.positional_embedding.type(self.dtype)
+        return self.ln_final(self.transformer(x.permute(1, 0, 2))).type(self.dtype)
+
+
+_NOT_WEIGHTS = ("input_resolution", "context_length", "vocab_size")   # scalars OpenAI's TorchScript archive keeps as buffers
+
+
+def load_text_tower(source):
+    """A `ClipTextModel` (fp32, on the CPU) from
+      * a state dict of CLIP (OpenAI's names; `visual.*` is dropped),
+      * a state dict or checkpoint of this project, whose tower keys start with `clip.` (everything else is dropped),
+      * a path that torch.jit.load (OpenAI's ViT-B-32.pt is a TorchScript archive) or torch.load opens.
+    Width, layers and heads = width / 64 are read off the shapes."""
+    if isinstance(source, (str, os.PathLike)):
+        try:
+            source = torch.jit.load(source, map_location="cpu").state_dict()
+        except RuntimeError:
+            source = torch.load(source, map_location="cpu", weights_only=False)
+    if isinstance(source, nn.Module):
+        source = source.state_dict()
+    for wrap in ("state_dict", "encoder"):
+        if isinstance(source, dict) and wrap in source and isinstance(source[wrap], dict):
+            source = source[wrap]
+    sd = {k: v for k, v in source.items() if torch.is_tensor(v)}
+    if any(k.startswith("clip.") for k in sd):
+        sd = {k[len("clip."):]: v for k, v in sd.items() if k.startswith("clip.")}
+    sd = {k: v for k, v in sd.items() if not k.startswith("visual.") and k not in _NOT_WEIGHTS}
+    if "ln_final.weight" not in sd or "positional_embedding" not in sd or "token_embedding.weight" not in sd:
+        raise ValueError("load_text_tower: no CLIP text tower in these %d keys" % len(sd))
+    width = sd["ln_final.weight"].shape[0]
+    blocks = {int(m.group(1)) for m in (re.match(r"transformer\.resblocks\.(\d+)\.", k) for k in sd) if m}
+    if not blocks or blocks != set(range(len(blocks))) or width % HEAD_DIM:
+        raise ValueError("load_text_tower: blocks %s of width %d are not a CLIP text tower" % (sorted(blocks), width))
+    embed_dim = sd["text_projection"].shape[1] if "text_projection" in sd else width
+    model = ClipTextModel(width, len(blocks), width // HEAD_DIM, sd["positional_embedding"].shape[0],
+                          sd["token_embedding.weight"].shape[0], embed_dim)
+    missing, unexpected = model.load_state_dict({k: v.float() for k, v in sd.items()}, strict=False)
+    if unexpected or set(missing) - {"text_projection", "logit_scale"}:
+        raise ValueError("load_text_tower: missing %s, unexpected %s" % (missing, unexpected))
+    return model
+
+
+# ---- the native route ----------------------------------------------------------------------------------------------------------
+def _tower_tensors(clip_model):
+    """The tower's parameters in the order of include/hig.h: HIG_CT_*, then HIG_CTL_* per layer."""
+    out = [clip_model.token_embedding.weight, clip_model.positional_embedding, clip_model.ln_final.weight, clip_model.ln_final.bias]
+    for b in clip_model.transformer.resblocks:
+        out += [b.ln_1.weight, b.ln_1.bias, b.attn.in_proj_weight, b.attn.in_proj_bias, b.attn.out_proj.weight, b.attn.out_proj.bias,
+                b.ln_2.weight, b.ln_2.bias, b.mlp.c_fc.weight, b.mlp.c_fc.bias, b.mlp.c_proj.weight, b.mlp.c_proj.bias]
+    return out
+
+
+def tower_refusal(clip_model, device=None):
+    """None when hig_clip_text_fwd computes what `clip_model`'s torch ops compute, else the reason it does not: the tower has
+    `resblocks` of OpenAI's structure, every tower parameter is a frozen contiguous fp32 tensor (on `device`, when given),
+    the head dim is 64, there are at most 128 tokens and every block's `attn_mask` is the causal one (compared on the host)."""
+    blocks = getattr(getattr(clip_model, "transformer", None), "resblocks", None)
+    if blocks is None or len(blocks) == 0:
+        return "the tower has no resblocks"
+    try:
+        tensors = _tower_tensors(clip_model)
+    except AttributeError as e:
+        return "a block is not a ResidualAttentionBlock (%s)" % e
+    if any(t is None for t in tensors):
+        return "a block lacks in_proj_weight or a bias"
+    for t in tensors:
+        if t.dtype != torch.float32:
+            return "a tower parameter is %s, not fp32" % t.dtype
+        if t.requires_grad:
+            return "a tower parameter requires grad (the backward is not built)"
+        if not t.is_contiguous():
+            return "a tower parameter is not contiguous"
+        if device is not None and (not t.is_cuda or t.device != torch.device(device)):
+            return "a tower parameter lives on %s, not on %s" % (t.device, device)
+    N, W = clip_model.positional_embedding.shape
+    if clip_model.token_embedding.weight.shape[1] != W or clip_model.ln_final.weight.shape[0] != W:
+        return "widths disagree"
+    if N > MAX_TOKENS:
+        return "%d tokens (the causal attention covers %d)" % (N, MAX_TOKENS)
+    want = None
+    for b in blocks:
+        a = b.attn
+        if a.embed_dim != W or a.embed_dim // a.num_heads != HEAD_DIM:
+            return "head dim %d, not %d" % (a.embed_dim // a.num_heads, HEAD_DIM)
+        if getattr(a, "batch_first", False) or a.bias_k is not None or a.add_zero_attn or a.dropout != 0:
+            return "an attention option the kernels do not cover"
+        if b.mlp.c_fc.weight.shape != (4 * W, W) or b.mlp.c_proj.weight.shape != (W, 4 * W):
+            return "an FFN that is not 4 W wide"
+        if b.ln_1.eps != 1e-5 or b.ln_2.eps != 1e-5:
+            return "a LayerNorm eps other than 1e-5"
+        mask = getattr(b, "attn_mask", None)
+        if mask is None or tuple(mask.shape) != (N, N):
+            return "a block without an (N, N) attn_mask"
+        if want is None:
+            want = causal_mask(N)
+        if mask.dtype == torch.bool or not torch.equal(mask.detach().float().cpu(), want):
+            return "an attn_mask that is not the causal one"
+    if clip_model.ln_final.eps != 1e-5:
+        return "a LayerNorm eps other than 1e-5"
+    return None
+
+
+def clip_dims(B, N, W, H, L, vocab, prec=0):
+    """The HIG_CD_* slots of hig_clip_text_fwd / hig_clip_text_workspace_bytes as a ctypes array."""
+    from .. import _lib
+    d = (C.c_int32 * _lib.CD_NSLOTS)()
+    for slot, v in (("B", B), ("N", N), ("W", W), ("H", H), ("L", L), ("VOCAB", vocab), ("PREC", prec)):
+        d[getattr(_lib, "CD_" + slot)] = v
+    return d
+
+
+class TowerRefused(ValueError):
+    """tower_refusal's reason, raised by TowerTable."""
+
+
+class TowerTable:
+    """The pointer table of a qualifying tower, built once: the tensors (kept alive), their addresses in hig.h's order and
+    the shape.  `stale()` says whether a parameter has been moved or un-frozen since."""
+
+    def __init__(self, clip_model, device):
+        why = tower_refusal(clip_model, device)
+        if why is not None:
+            raise TowerRefused("CLIP text tower: " + why)
+        from .. import _lib
+        self.tensors = _tower_tensors(clip_model)
+        blocks = clip_model.transformer.resblocks
+        assert len(self.tensors) == _lib.CT_NGLOBAL + _lib.CTL_NLAYER * len(blocks)
+        self.ptrs = tuple(t.data_ptr() for t in self.tensors)
+        self.table = (C.c_void_p * len(self.ptrs))(*self.ptrs)
+        self.N, self.W = clip_model.positional_embedding.shape
+        self.H, self.L = blocks[0].attn.num_heads, len(blocks)
+        self.vocab = clip_model.token_embedding.weight.shape[0]
+        self.device = torch.device(device)
+
+    def stale(self):
+        return any(t.data_ptr() != p or t.requires_grad for t, p in zip(self.tensors, self.ptrs))
+
+
+_PREC = {"f32": 0, "bf16x3": 1, "bf16": 2}
+
+
+def tower_forward(table, tokens, pool=None, precision="f32"):
+    """tokens (B, N) int64 on the table's device -> ln_final's output (B, N, W), batch-first, through hig_clip_text_fwd on the
+    current stream.  There is no fallback: a refusal of the library raises."""
+    from .. import _lib
+    if tokens.dim() != 2 or tokens.shape[1] != table.N or tokens.dtype != torch.int64 or tokens.device != table.device:
+        raise RuntimeError("CLIP text tower: tokens must be (B, %d) int64 on %s" % (table.N, table.device))
+    tokens = tokens.contiguous()
+    B = tokens.shape[0]
+    dims = clip_dims(B, table.N, table.W, table.H, table.L, table.vocab, _PREC[precision])
+    L = _lib.lib()
+    nbytes = L.hig_clip_text_workspace_bytes(dims)
+    if nbytes < 0:
+        raise RuntimeError("libhig: %s (clip_tower='torch' selects stock PyTorch ops)" % _lib.last_error())
+    ws = pool.take("clip", nbytes, table.device) if pool is not None else torch.empty(nbytes, dtype=torch.uint8, device=table.device)
+    out = torch.empty(B, table.N, table.W, device=table.device, dtype=torch.float32)
+    _lib.check(L.hig_clip_text_fwd(dims, table.table, _lib.ptr(tokens), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()))
+    if pool is not None:
+        pool.give("clip", ws, table.device)
+    return out

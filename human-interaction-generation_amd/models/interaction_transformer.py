@@ -82,7 +82,7 @@ class MotionInteractionTransformer(MotionTransformer):
             self.cap_embedding = nn.Parameter(torch.randn(43, text_latent_dim))
             self.text_proj = nn.Sequential(nn.Linear(text_latent_dim, self.time_embed_dim))
         else:
-            self.clip, _ = clip.load('ViT-B/32', "cpu")
+            self.clip = kargs["clip_model"] if kargs.get("clip_model") is not None else clip.load('ViT-B/32', "cpu")[0]
             self.no_clip = no_clip
             if no_clip:
                 self.clip.d_type = self.clip.token_embedding.weight.dtype
@@ -124,6 +124,7 @@ class MotionInteractionTransformer(MotionTransformer):
         self.precision = kargs.get("precision", os.environ.get("HIG_PREC", "f32"))
         self.text_head = kargs.get("text_head", os.environ.get("HIG_TEXT_HEAD", "hip"))
         self.storage = kargs.get("storage", os.environ.get("HIG_STORAGE", "f32"))   # "bf16": inference with bf16 activations
+        self._init_clip_route(kargs)
         self._flat = None
         self._pool = _WorkspacePool()
         self._textctx_cache = None
@@ -158,7 +159,7 @@ class MotionInteractionTransformer(MotionTransformer):
         """:532-556; with `no_clip` the CLIP text tower is trained too (no no_grad)."""
         if not self.no_clip:
             return MotionTransformer.encode_text(self, text, device)
-        text = clip.tokenize(text, truncate=True).to(device)
+        text = self._tokenize(text).to(device)      # (a trainable tower stays on torch ops: its backward is not built)
         x = self.clip.token_embedding(text).type(self.clip.d_type)
         x = x + self.clip.positional_embedding.type(self.clip.d_type)
         x = x.permute(1, 0, 2)

@@ -11,6 +11,7 @@ There is no CPU execution path: calling the module on host tensors, or without l
 """
 import ctypes as C
 import math
+import os
 
 import torch
 from torch import nn
@@ -21,6 +22,7 @@ try:  # the real OpenAI CLIP when installed (transformer.py:10), else the determ
     import clip  # type: ignore
 except Exception:  # pragma: no cover - depends on the environment
     from . import stub_clip as clip
+from . import clip_text
 
 
 def timestep_embedding(timesteps, dim, max_period=10000):
@@ -416,7 +418,8 @@ class MotionTransformer(nn.Module):
         self.sequence_embedding = nn.Parameter(torch.randn(num_frames, latent_dim))
 
         # Text side: CLIP + the parameter containers of the text head (transformer.py:318-340)
-        self.clip, _ = clip.load('ViT-B/32', "cpu")
+        # (`clip_model=`: a module used in place of clip.load's, e.g. models.clip_text.load_text_tower(...))
+        self.clip = kargs["clip_model"] if kargs.get("clip_model") is not None else clip.load('ViT-B/32', "cpu")[0]
         if no_clip:
             self.clip.initialize_parameters()
         else:
@@ -432,6 +435,7 @@ class MotionTransformer(nn.Module):
                                                       enable_nested_tensor=False)
         self.text_ln = nn.LayerNorm(text_latent_dim)
         self.text_proj = nn.Sequential(nn.Linear(text_latent_dim, self.time_embed_dim))
+        self._init_clip_route(kargs)
 
         # Denoiser core (parameters only; the math is in libhig.so)
         self.joint_embed = nn.Linear(self.input_feats, self.latent_dim)
@@ -463,10 +467,21 @@ class MotionTransformer(nn.Module):
         self.cache_text_context = True
 
     # ---- nn.Module plumbing -------------------------------------------------------------
+    def _init_clip_route(self, kargs):
+        # `clip_tokenize=`: a callable used in place of the module-level clip.tokenize (the BPE vocabulary is data the stub
+        # does not have).  `clip_tower`: "hip" runs a qualifying frozen tower through hig_clip_text_fwd (clip_text.tower_refusal
+        # is the rule; the stub and a trainable tower never qualify), "torch" keeps the tower on stock PyTorch ops.
+        self._clip_tokenize = kargs.get("clip_tokenize")
+        self.clip_tower = kargs.get("clip_tower", os.environ.get("HIG_CLIP_TOWER", "hip"))
+        if self.clip_tower not in ("hip", "torch"):
+            raise ValueError("clip_tower must be 'hip' or 'torch' (got %r)" % (self.clip_tower,))
+        self._clip_table = None
+
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
         self._flat = None            # .to()/.cuda()/.float() re-home parameters: re-flatten lazily
         self._textctx_cache = None
+        self._clip_table = None
         return r
 
     def params_changed(self):
@@ -477,6 +492,7 @@ class MotionTransformer(nn.Module):
 
     def _load_from_state_dict(self, *a, **k):
         self._textctx_cache = None
+        self._clip_table = None
         return super()._load_from_state_dict(*a, **k)
 
     def _textctx_param_version(self):
@@ -515,13 +531,38 @@ class MotionTransformer(nn.Module):
     def _clip_features(self, text, device):
         """Frozen CLIP text tower up to ln_final (transformer.py:381-388): tokens + (L, B, 512)."""
         with torch.no_grad():
-            text = clip.tokenize(text, truncate=True).to(device)
+            text = self._tokenize(text).to(device)
+            table = self._clip_native_table(text)
+            if table is not None:   # the frozen tower in HIP (csrc/cliptext.hip); always exact-fp32 products
+                return text, clip_text.tower_forward(table, text, self._pool).permute(1, 0, 2)
             x = self.clip.token_embedding(text).type(self.clip.dtype)
             x = x + self.clip.positional_embedding.type(self.clip.dtype)
             x = x.permute(1, 0, 2)
             x = self.clip.transformer(x)
             x = self.clip.ln_final(x).type(self.clip.dtype)
         return text, x
+
+    def _tokenize(self, text):
+        return (self._clip_tokenize or clip.tokenize)(text, truncate=True)
+
+    def _clip_native_table(self, tokens):
+        """The pointer table of the tower when `_clip_features` takes the native route for these tokens, else None: the flag
+        is "hip", the tokens are on a ROCm device and clip_text.tower_refusal finds nothing (checked once, when the table is
+        built; a tower that did not qualify is asked again only after `_apply` or a load)."""
+        if self.clip_tower != "hip" or not tokens.is_cuda or getattr(self, "no_clip", False):
+            return None
+        if not hasattr(getattr(self.clip, "transformer", None), "resblocks"):
+            return None
+        t = self._clip_table
+        if isinstance(t, clip_text.TowerTable) and (t.device != tokens.device or t.stale()):
+            t = None
+        if t is None:
+            try:
+                t = clip_text.TowerTable(self.clip, tokens.device)
+            except clip_text.TowerRefused:
+                t = False
+            self._clip_table = t
+        return t or None
 
     def _text_head_torch(self, text, x):
         """transformer.py:389-397 on stock torch ops (`text_head="torch"`)."""

@@ -449,6 +449,53 @@ int hig_text_head_bwd(const hig_text_dims* dims, const void* const* params, cons
                       hig_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Frozen CLIP text tower (csrc/cliptext.hip): what MotionTransformer._clip_features runs in front of the text head
+ * (transformer.py:381-388 over OpenAI CLIP's model.py: Transformer of ResidualAttentionBlocks, pre-norm, causal), inference only:
+ *     x = token_embedding[tokens] + positional_embedding
+ *     per layer:  x = x + out_proj(attn(ln_1(x)));   x = x + c_proj(quick_gelu(c_fc(ln_2(x))))
+ *     out = ln_final(x)
+ * attn = nn.MultiheadAttention (in_proj_weight (3W, W), 1/sqrt(64) scaling) under CLIP's causal mask (row n sees keys m <= n);
+ * quick_gelu(z) = z * sigmoid(1.702 z); the FFN is 4W wide; LayerNorm eps 1e-5.  Batch-first (B, N, .) rows.
+ * The dims travel as HIG_CD_NSLOTS int32 slots (the form hig_denoiser_plan takes its switches in), not as a sixth struct:
+ *     B samples, N tokens (77; <= 128), W width (512), H heads (8: the head dim W / H must be 64), L layers (12),
+ *     vocab rows of token_embedding, prec HIG_PREC_* of the GEMM products.
+ * Parameter table: HIG_CT_* then HIG_CTL_* per layer.
+ * ---------------------------------------------------------------------------------------- */
+enum { HIG_CD_B = 0, HIG_CD_N, HIG_CD_W, HIG_CD_H, HIG_CD_L, HIG_CD_VOCAB, HIG_CD_PREC, HIG_CD_NSLOTS };
+enum {
+  HIG_CT_TOK_EMB = 0,          /* token_embedding.weight (vocab, W) */
+  HIG_CT_POS_EMB,              /* positional_embedding (N, W) */
+  HIG_CT_LNF_W, HIG_CT_LNF_B,  /* ln_final */
+  HIG_CT_NGLOBAL
+};
+enum {
+  HIG_CTL_LN1_W = 0, HIG_CTL_LN1_B,   /* ln_1 */
+  HIG_CTL_IN_W, HIG_CTL_IN_B,         /* attn.in_proj_weight (3W, W) / in_proj_bias */
+  HIG_CTL_OUT_W, HIG_CTL_OUT_B,       /* attn.out_proj */
+  HIG_CTL_LN2_W, HIG_CTL_LN2_B,       /* ln_2 */
+  HIG_CTL_FC_W, HIG_CTL_FC_B,         /* mlp.c_fc (4W, W) */
+  HIG_CTL_PROJ_W, HIG_CTL_PROJ_B,     /* mlp.c_proj (W, 4W) */
+  HIG_CTL_NLAYER
+};
+/* -1 (and a message) for dims the tower refuses.  The workspace ping-pongs between two layer blocks. */
+int64_t hig_clip_text_workspace_bytes(const int32_t* dims);
+/* tokens (B, N) int64; out (B, N, W) = ln_final's output, batch-first.  No allocation, no synchronisation, every launch on
+ * `stream`.  HIG_EUNSUPPORTED: head dim != 64, N > 128. */
+int hig_clip_text_fwd(const int32_t* dims, const void* const* params, const int64_t* tokens, float* out,
+                      void* workspace, hig_stream_t stream);
+/* out[b*N + n][:W] = tok_emb[tokens[b][n]][:W] + pos_emb[n][:W].  An id outside [0, vocab) reads no embedding row: that
+ * output row is the positional row alone. */
+int hig_clip_embed(const float* tok_emb, const float* pos_emb, const int64_t* tokens, int32_t B, int32_t N, int32_t W,
+                   int32_t vocab, float* out, int64_t ldo, hig_stream_t stream);
+/* x[i] = x[i] * sigmoid(1.702 x[i]), i < n, in place (v_exp_f32 / v_rcp_f32). */
+int hig_quick_gelu(float* x, int64_t n, hig_stream_t stream);
+/* Causal softmax attention, head dim 64, N <= 128 (else HIG_EUNSUPPORTED): Y[b*N + n][h*64 ..] = softmax_{m <= n}(q_n . k_m / 8) V.
+ * Exact fp32 products, the row maximum subtracted.  Keys m > n are skipped, not masked: their K and V rows are never read
+ * into a score or a sum, whatever they hold.  Takes no HIG_ATTN_PATH_* number and no plan: one kernel serves every call. */
+int hig_causal_attn_fwd(const float* Q, int64_t ldq, const float* K, const float* V, int64_t ldk, int32_t B, int32_t N,
+                        int32_t H, float* Y, int64_t ldy, hig_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Evaluator feature extraction: the two classifiers that score generated pairs,
  * `MotionEncoder` (interaction_transformer.py:641-741: class logits + the pooled feature FID /
  * diversity are computed on) and `MotionConsistencyEvalModel` (:743-829: real/fake logits from a
