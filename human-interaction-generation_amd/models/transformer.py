@@ -476,12 +476,35 @@ class MotionTransformer(nn.Module):
         if self.clip_tower not in ("hip", "torch"):
             raise ValueError("clip_tower must be 'hip' or 'torch' (got %r)" % (self.clip_tower,))
         self._clip_table = None
+        # `caption_bank=capacity`: keep the frozen tower's output per caption string on the device (models/caption_bank.py) and
+        # fetch it by slot instead of running the tower; None / 0 (the default): no bank, nothing launches differently.
+        # `text_dedup` (with a bank): run the text head once per DISTINCT caption where no autograd graph is asked for.
+        self._caption_bank = None
+        self.text_dedup = bool(kargs.get("text_dedup", True))
+        if kargs.get("caption_bank"):
+            self.enable_caption_bank(kargs["caption_bank"])
+
+    @property
+    def caption_bank(self):
+        return getattr(self, "_caption_bank", None)
+
+    def enable_caption_bank(self, capacity, spill=None):
+        """Turn the caption bank on with `capacity` persistent slots (157 696 bytes each at N = 77, W = 512); ValueError for a
+        trainable tower or a cap_id model.  None / 0 turns it off."""
+        if not capacity:
+            self._caption_bank = None
+            return None
+        from .caption_bank import DEFAULT_SPILL, CaptionBank
+        self._caption_bank = CaptionBank(self, capacity, DEFAULT_SPILL if spill is None else spill)
+        return self._caption_bank
 
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
         self._flat = None            # .to()/.cuda()/.float() re-home parameters: re-flatten lazily
         self._textctx_cache = None
         self._clip_table = None
+        if self.caption_bank is not None:
+            self._caption_bank.clear()
         return r
 
     def params_changed(self):
@@ -493,6 +516,8 @@ class MotionTransformer(nn.Module):
     def _load_from_state_dict(self, *a, **k):
         self._textctx_cache = None
         self._clip_table = None
+        if self.caption_bank is not None:
+            self._caption_bank.clear()
         return super()._load_from_state_dict(*a, **k)
 
     def _textctx_param_version(self):
@@ -564,31 +589,48 @@ class MotionTransformer(nn.Module):
             self._clip_table = t
         return t or None
 
-    def _text_head_torch(self, text, x):
-        """transformer.py:389-397 on stock torch ops (`text_head="torch"`)."""
+    def _text_head_torch(self, text, x, eot=None):
+        """transformer.py:389-397 on stock torch ops (`text_head="torch"`); eot: the EOT positions when there are no tokens."""
         x = self.text_pre_proj(x)
         xf_out = self.textTransEncoder(x)
         xf_out = self.text_ln(xf_out)
-        xf_proj = self.text_proj(xf_out[text.argmax(dim=-1), torch.arange(xf_out.shape[1])])
+        xf_proj = self.text_proj(xf_out[text.argmax(dim=-1) if eot is None else eot, torch.arange(xf_out.shape[1])])
         xf_out = xf_out.permute(1, 0, 2)
         return xf_proj, xf_out
 
     def encode_text(self, text, device):
         """transformer.py:380-397.  CLIP stays on its own (frozen / stubbed) ops; the trainable head
         after it -- text_pre_proj, the post-norm encoder, text_ln, EOT gather, text_proj -- runs in
-        the HIP kernels."""
+        the HIP kernels.  With a caption bank the CLIP features come from hig_caption_gather instead of the
+        tower, and where no autograd graph is asked for (and `text_dedup`) the head runs on the distinct captions only."""
+        if self.caption_bank is not None:
+            return self._encode_text_banked(text, device)
         text, x = self._clip_features(text, device)
         return self._text_head(text, x)
 
-    def _text_head(self, text, x):
-        """tokens (B, N) + CLIP features (N, B, W) -> xf_proj (B, E), xf_out (B, N, Lt)."""
+    def _encode_text_banked(self, text, device):
+        from .caption_bank import expand_rows
+        bank = self._caption_bank
+        cb = bank.batch([text] if isinstance(text, str) else list(text), device)
+        wants_graph = torch.is_grad_enabled() and any(p.requires_grad for p in self._text_params())
+        if wants_graph or not self.text_dedup:
+            clip_out, eot = bank.gather(cb.slot, cb.rows)
+            return self._text_head(None, clip_out.permute(1, 0, 2), eot=eot)
+        clip_out, eot = bank.gather(cb.uniq_slot, cb.U_pad)
+        xf_proj, xf_out = self._text_head(None, clip_out.permute(1, 0, 2), eot=eot)
+        return (expand_rows(xf_proj.detach().contiguous(), cb.inv, cb.rows),
+                expand_rows(xf_out.detach().contiguous(), cb.inv, cb.rows))
+
+    def _text_head(self, text, x, eot=None):
+        """tokens (B, N) + CLIP features (N, B, W) -> xf_proj (B, E), xf_out (B, N, Lt); eot (B,): the EOT positions, for
+        features that come without their tokens (the caption bank)."""
         if self.text_head == "torch":
-            return self._text_head_torch(text, x)
+            return self._text_head_torch(text, x, eot)
         if not x.is_cuda:
             raise RuntimeError("encode_text: ROCm device required (no CPU fallback); pass text_head='torch' "
                                "to run the text head on stock PyTorch ops")
         clip_out = x.permute(1, 0, 2).float().contiguous()
-        eot = text.argmax(dim=-1).contiguous()
+        eot = (text.argmax(dim=-1) if eot is None else eot).contiguous()
         tp = self._text_params()
         if torch.is_grad_enabled() and (clip_out.requires_grad or any(p.requires_grad for p in tp)):
             return _TextHeadFn.apply(self, clip_out, eot, *tp)

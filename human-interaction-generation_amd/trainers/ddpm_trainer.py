@@ -25,6 +25,7 @@ import torch.optim as optim
 from torch.nn.utils import clip_grad_norm_
 
 from .. import _lib
+from ..models.caption_bank import expand_rows, segment_sum_rows
 from ..models.gaussian_diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType,
                                          create_named_schedule_sampler, get_named_beta_schedule)
 from ..models.guidance import ClassifierFreeGuidedModel, check_scale
@@ -102,6 +103,11 @@ class DDPMTrainer(object):
         self._ema = None               # ema_state(): the EMA of the weights, lazy
         self._ema_scope = False        # inside `with trainer.ema_weights()`
         self._sample_weights = "model"   # set_sampler: which weights `generate` samples from
+        # opt.caption_bank = capacity: the model keeps the frozen tower's output per caption (models/caption_bank.py);
+        # opt.text_dedup (default True with a bank): the text head runs once per distinct caption of a step
+        if getattr(args, "caption_bank", None):
+            _core(encoder).enable_caption_bank(args.caption_bank)
+            _core(encoder).text_dedup = bool(getattr(args, "text_dedup", True))
         self.to(self.device)
 
     # ---- small helpers the reference exposes as static methods ----------------------------------------------
@@ -686,14 +692,40 @@ class DDPMTrainer(object):
         return xf_proj, xf_out, (clip_out, eot, xf_out, tsaved)
 
     def _text_backward(self, tstate, dxf_proj, dxf_out):
-        clip_out, eot, xf_out, tsaved = tstate
+        clip_out, eot, xf_out, tsaved = tstate[:4]
+        if len(tstate) == 5:     # the head ran on the distinct captions: their rows' gradients, added in row order
+            cb = tstate[4]
+            dxf_proj = segment_sum_rows(dxf_proj.contiguous(), cb.order, cb.seg, cb.U_pad)
+            dxf_out = segment_sum_rows(dxf_out.contiguous(), cb.order, cb.seg, cb.U_pad)
         _core(self.encoder)._launch_text_head_backward(clip_out, eot, xf_out, tsaved, dxf_out, dxf_proj,
                                                        want_dclip=False, into_flat=True)
 
-    def _fused_fwd_bwd(self, x_start, t, length, xf_proj, xf_out, noise, clip_out=None, eot=None, exchange=None):
+    def _caption_batch_check(self, caption_batch, clip_out, eot):
+        """`caption_batch=` of the fused steps sits beside `clip_out=` / `eot=` and is exclusive with them."""
+        if caption_batch is None:
+            return
+        if clip_out is not None or eot is not None:
+            raise ValueError("caption_batch= and clip_out= / eot= are exclusive: the bank supplies the CLIP features")
+        if getattr(_core(self.encoder), "caption_bank", None) is None:
+            raise RuntimeError("caption_batch= needs the model's caption bank (opt.caption_bank / enable_caption_bank)")
+
+    def _text_forward_banked(self, cb):
+        """Text side of the fused step out of the caption bank: hig_caption_gather stands where the tower stood.  With
+        `text_dedup` the head runs on the U_pad distinct captions and two hig_rows_gather_f32 expand its outputs to the model
+        batch (`_text_backward` sums the upstream gradients back); without it the gather fetches every row."""
+        core = _core(self.encoder)
+        bank = core.caption_bank
+        if not core.text_dedup:
+            return self._text_forward(*bank.gather(cb.slot, cb.rows))
+        xp_u, xo_u, tstate = self._text_forward(*bank.gather(cb.uniq_slot, cb.U_pad))
+        return expand_rows(xp_u, cb.inv, cb.rows), expand_rows(xo_u, cb.inv, cb.rows), tstate + (cb,)
+
+    def _fused_fwd_bwd(self, x_start, t, length, xf_proj, xf_out, noise, clip_out=None, eot=None, exchange=None,
+                       caption_batch=None):
         """q_sample -> [text head] -> denoiser forward -> masked MSE -> denoiser backward [-> text head backward]
-        into the flat gradient.  With `clip_out` / `eot` the text embeddings are computed here and the text
-        head is trained too (the reference's full update); otherwise xf_proj / xf_out are inputs.
+        into the flat gradient.  With `clip_out` / `eot`, or with a `caption_batch` of the model's caption bank, the text
+        embeddings are computed here and the text head is trained too (the reference's full update); otherwise xf_proj /
+        xf_out are inputs.
         `exchange` (an OverlappedGradAllReduce that has been begun): the gradient all-reduce of each decoder layer is
         started from inside the backward."""
         core = _core(self.encoder)
@@ -701,7 +733,9 @@ class DDPMTrainer(object):
         st = self.fused_state()
         B, T, F = x_start.shape
         tstate = None
-        if clip_out is not None:
+        if caption_batch is not None:
+            xf_proj, xf_out, tstate = self._text_forward_banked(caption_batch)
+        elif clip_out is not None:
             xf_proj, xf_out, tstate = self._text_forward(clip_out, eot)
         if noise is None:
             noise = torch.randn_like(x_start)
@@ -719,13 +753,13 @@ class DDPMTrainer(object):
         if tstate is not None:
             self._text_backward(tstate, dxp, dxo)
 
-    def _fwd_bwd_overlapped_exchange(self, x_start, t, length, xf_proj, xf_out, noise, clip_out, eot):
+    def _fwd_bwd_overlapped_exchange(self, x_start, t, length, xf_proj, xf_out, noise, clip_out, eot, caption_batch=None):
         """_fused_fwd_bwd with the gradient exchange of layer l issued while layers l-1 ... 0 are still in backward
         (RCCL on a side stream); returns the world size.  Capturable: see OverlappedGradAllReduce."""
         st = self.fused_state()
         core = _core(self.encoder)
         fp = core.flat_params()
-        n = self._fused_numel(clip_out is not None)
+        n = self._fused_numel(clip_out is not None or caption_batch is not None)
         ex = st["overlap"]
         want = getattr(self.opt, "grad_wire", "f32")
         if want != ex.wire:      # (the option is read when the fused state is built; changing it later used to be ignored silently)
@@ -735,7 +769,8 @@ class DDPMTrainer(object):
         per_layer, tail = fp.layer_buckets(core.num_layers, nsty, core.latent_dim, core.time_embed_dim)
         assert per_layer[-1][1][1] - per_layer[0][1][0] == core.num_layers * nsty * 2 * core.latent_dim * core.time_embed_dim
         ex.begin(fp.grad, per_layer, tail)
-        self._fused_fwd_bwd(x_start, t, length, xf_proj, xf_out, noise, clip_out=clip_out, eot=eot, exchange=ex)
+        self._fused_fwd_bwd(x_start, t, length, xf_proj, xf_out, noise, clip_out=clip_out, eot=eot, exchange=ex,
+                            **({} if caption_batch is None else dict(caption_batch=caption_batch)))
         return ex.finish([(fp.core_numel, n)] if n > fp.core_numel else ())
 
     def _fused_numel(self, with_text):
@@ -787,27 +822,31 @@ class DDPMTrainer(object):
             fp.shadow16_mark_current(core._param_version())
 
     def train_step_fused(self, x_start, t, length, xf_proj=None, xf_out=None, noise=None, lr=None, clip_out=None,
-                         eot=None):
+                         eot=None, caption_batch=None):
         """One DDPM training step on device tensors, reference semantics (ddpm_trainer.py:97-119,172-187):
           x_t = q_sample(x0, t, noise); pred = denoiser(x_t, t); loss = masked MSE(pred, noise);
           backward; grads = all_reduce(grads) / world; clip_grad_norm_(0.5); Adam.
         With text embeddings (`xf_proj`, `xf_out`) the denoiser-core parameters are updated; with CLIP features
         (`clip_out` (B, N, W) batch-first, `eot` (B,), see MotionTransformer._clip_features) the text head runs
-        inside the step and EVERY trainable parameter is updated -- the reference's full update.
+        inside the step and EVERY trainable parameter is updated -- the reference's full update.  `caption_batch` (a
+        CaptionBatch of the model's caption bank, exclusive with clip_out / eot) is that same update with the CLIP features
+        fetched from the bank by hig_caption_gather.
         With more than one rank the replicas must start identical: call `sync_replicas()` once (train() does).
         No host synchronisation: the loss stays on the device (`fused_state()['loss']`)."""
         self._ema_refuse_in_scope("train_step_fused")
+        self._caption_batch_check(caption_batch, clip_out, eot)
         st = self.fused_state()
         ema = self.ema_state()            # (created here, from the weights before the step, when opt.ema_decay asks for one)
-        with_text = clip_out is not None
+        with_text = clip_out is not None or caption_batch is not None
         n = self._fused_numel(with_text)
         self._set_lr(lr)
         core = _core(self.encoder)
         fp = core.flat_params()
+        banked = {} if caption_batch is None else dict(caption_batch=caption_batch)
         if OverlappedGradAllReduce.active() and getattr(self.opt, "overlap_allreduce", True):
-            world = self._fwd_bwd_overlapped_exchange(x_start, t, length, xf_proj, xf_out, noise, clip_out, eot)
+            world = self._fwd_bwd_overlapped_exchange(x_start, t, length, xf_proj, xf_out, noise, clip_out, eot, **banked)
         else:
-            self._fused_fwd_bwd(x_start, t, length, xf_proj, xf_out, noise, clip_out=clip_out, eot=eot)
+            self._fused_fwd_bwd(x_start, t, length, xf_proj, xf_out, noise, clip_out=clip_out, eot=eot, **banked)
             world = st["allreduce"](fp.grad[:n])                                  # one all-reduce after the backward
         self._fused_clip_adam(world, with_text)
         if ema is not None:
@@ -822,19 +861,32 @@ class DDPMTrainer(object):
         caption, x_start, cur_len = self._stage_batch(batch_data)
         caption = self._drop_captions(caption)
         t, _ = self.sampler.sample(x_start.shape[0], x_start.device)
-        clip_out, eot = self.clip_inputs(caption)
         step = self.train_step_captured if captured else self.train_step_fused
-        return step(x_start.contiguous(), t, cur_len, noise=noise, clip_out=clip_out, eot=eot)
+        return step(x_start.contiguous(), t, cur_len, noise=noise, **self._text_inputs(caption))
+
+    def _text_inputs(self, caption):
+        """The text arguments of a fused step for these captions: a CaptionBatch when the model has a caption bank (the tower
+        runs for captions the bank has not met, and only for them), else the tower's output for every row."""
+        bank = getattr(_core(self.encoder), "caption_bank", None)
+        if bank is not None:
+            return dict(caption_batch=bank.batch(caption, self.device))
+        clip_out, eot = self.clip_inputs(caption)
+        return dict(clip_out=clip_out, eot=eot)
 
     def clip_inputs(self, caption):
         """Captions -> (clip_out (B, N, W) batch-first fp32, eot (B,)) for `train_step_fused(clip_out=...)`: the
         frozen CLIP tower on its own ops, outside the fused / captured region."""
         core = _core(self.encoder)
         tokens, feat = core._clip_features(caption, self.device)
-        return feat.permute(1, 0, 2).float().contiguous(), tokens.argmax(dim=-1).contiguous()
+        clip_out = feat.permute(1, 0, 2)      # (the native tower's output is batch-first already: this view IS that buffer)
+        if clip_out.dtype != torch.float32:
+            clip_out = clip_out.float()
+        if not clip_out.is_contiguous():
+            clip_out = clip_out.contiguous()
+        return clip_out, tokens.argmax(dim=-1).contiguous()
 
     def train_step_captured(self, x_start, t, length, xf_proj=None, xf_out=None, noise=None, lr=None, clip_out=None,
-                            eot=None):
+                            eot=None, caption_batch=None):
         """The same step as hipGraphs.  Captured once per batch shape.  One rank: ONE graph (q_sample [+ text head] +
         forward + loss + backward + clip + Adam).  With a gradient exchange (more than one rank, or HIG_FORCE_EXCHANGE)
         still ONE graph: the per-layer RCCL all-reduces of `OverlappedGradAllReduce` are captured with the backward they
@@ -846,8 +898,11 @@ class DDPMTrainer(object):
         learning rate through a device scalar (`_set_lr`).  A graph is keyed on the shapes AND on the flat parameter /
         gradient buffers it was captured against.  Text inputs as in `train_step_fused`: embeddings, or CLIP
         features.  The EMA of the weights rides in the same update kernel (its update number comes from the device step
-        counter, its origin is a constant of the graph); the graph key carries its configuration."""
+        counter, its origin is a constant of the graph); the graph key carries its configuration.
+        With `caption_batch` the packed int32 index buffer is the static text input, copied like `t`; the graph is keyed on
+        its layout (rows, U_pad), on `text_dedup` and on the bank's buffers, which are allocated once and never move."""
         self._ema_refuse_in_scope("train_step_captured")
+        self._caption_batch_check(caption_batch, clip_out, eot)
         st = self.fused_state()
         ema = self.ema_state()            # (created eagerly, never inside a capture)
         world = _dist_world()
@@ -855,27 +910,36 @@ class DDPMTrainer(object):
         # (gloo stages through the host: its collectives cannot be captured -- that backend always takes the split form)
         in_graph = (split and getattr(self.opt, "capture_exchange", True) and getattr(self.opt, "overlap_allreduce", True)
                     and dist.get_backend() == "nccl")
-        with_text = clip_out is not None
-        text_in = (clip_out, eot) if with_text else (xf_proj, xf_out)
+        banked = caption_batch is not None
+        with_text = clip_out is not None or banked
+        # (banked: the one packed index buffer stands in both text slots; it is copied once per replay)
+        text_in = (caption_batch.dev, caption_batch.dev) if banked else (clip_out, eot) if with_text else (xf_proj, xf_out)
         n = self._fused_numel(with_text)
         self._set_lr(lr)
+        bank = getattr(_core(self.encoder), "caption_bank", None)
         key = (tuple(x_start.shape), tuple(text_in[0].shape), tuple(text_in[1].shape), with_text, noise is None,
                world, split, in_graph, st["ptrs"],
                None if ema is None else (ema["decay"], ema["warmup"], ema["origin"], ema["flat"].data_ptr()))
+        if banked:
+            key += ((caption_batch.rows, caption_batch.U_pad, bool(_core(self.encoder).text_dedup), bank.feat.data_ptr(),
+                     bank.eot.data_ptr()),)
         cap = st["graphs"].get(key)
         if cap is None:
             static = {"x0": x_start.clone(), "t": t.clone(), "length": length.clone(),
-                      "ta": text_in[0].clone(), "tb": text_in[1].clone(),
+                      "ta": text_in[0].clone(), "tb": None if banked else text_in[1].clone(),
                       "noise": None if noise is None else noise.clone()}
-            sargs = ((static["x0"], static["t"], static["length"], None, None, static["noise"], static["ta"], static["tb"])
+            sargs = ((static["x0"], static["t"], static["length"], None, None, static["noise"], None, None)
+                     if banked else
+                     (static["x0"], static["t"], static["length"], None, None, static["noise"], static["ta"], static["tb"])
                      if with_text else
                      (static["x0"], static["t"], static["length"], static["ta"], static["tb"], static["noise"], None, None))
+            skw = dict(caption_batch=caption_batch.on_buffer(static["ta"])) if banked else {}
 
             def part_a():
-                self._fused_fwd_bwd(*sargs[:6], clip_out=sargs[6], eot=sargs[7])
+                self._fused_fwd_bwd(*sargs[:6], clip_out=sargs[6], eot=sargs[7], **skw)
 
             def whole_step_with_exchange():
-                w = self._fwd_bwd_overlapped_exchange(*sargs)
+                w = self._fwd_bwd_overlapped_exchange(*sargs, **skw)
                 self._fused_clip_adam(w, with_text)
 
             # warm-up (allocations, workspace pools, RCCL's communicator) on a side stream, as torch.cuda.graph requires;
@@ -953,7 +1017,8 @@ class DDPMTrainer(object):
             static["t"].copy_(t)
             static["length"].copy_(length)
             static["ta"].copy_(text_in[0])
-            static["tb"].copy_(text_in[1])
+            if static["tb"] is not None:
+                static["tb"].copy_(text_in[1])
             if noise is not None:
                 static["noise"].copy_(noise)
         ga.replay()

@@ -94,20 +94,24 @@ class DDPMMulTrainer(DDPMTrainer):
         return OrderedDict({'loss_mot_rec': self.loss_mot_rec.item()})
 
     # ---- MI355X fused step (inherits train_step_fused / train_step_captured) ---------------------
-    def _fused_fwd_bwd(self, x_start, t, length, xf_proj, xf_out, noise, clip_out=None, eot=None, exchange=None):
+    def _fused_fwd_bwd(self, x_start, t, length, xf_proj, xf_out, noise, clip_out=None, eot=None, exchange=None,
+                       caption_batch=None):
         """Two-person version of the fused forward/backward: x_start = cat([motion1, motion2]) (2B, T, F),
         t (B,) or (2B,), length (B,) per pair.  PIT mode (no label file): the noised motions run twice,
         rows [m1|c1, m1|c2, m2|c2, m2|c1] -- xf_proj / xf_out must hold the 4B text embeddings in that
         order (2B rows [c1 | c2] with a label file) -- and `hig_pair_mse` picks the cheaper caption
-        assignment per pair (mul_ddpm_trainer.py:96-131, 223-247)."""
+        assignment per pair (mul_ddpm_trainer.py:96-131, 223-247).  `caption_batch`: the captions of those rows as a
+        CaptionBatch of the model's caption bank (half of the 4B PIT rows are duplicates by construction)."""
         if not self.multi:
             return super()._fused_fwd_bwd(x_start, t, length, xf_proj, xf_out, noise, clip_out=clip_out, eot=eot,
-                                          exchange=exchange)
+                                          exchange=exchange, caption_batch=caption_batch)
         core = _core(self.encoder)
         L = _lib.lib()
         st = self.fused_state()
         tstate = None
-        if clip_out is not None:     # CLIP features of the model batch's captions (4B rows in PIT mode)
+        if caption_batch is not None:
+            xf_proj, xf_out, tstate = self._text_forward_banked(caption_batch)
+        elif clip_out is not None:     # CLIP features of the model batch's captions (4B rows in PIT mode)
             xf_proj, xf_out, tstate = self._text_forward(clip_out, eot)
         B2, T, F = x_start.shape
         B = B2 // 2
@@ -147,9 +151,8 @@ class DDPMMulTrainer(DDPMTrainer):
         t, _ = self.sampler.sample(B, x_start.device)
         if self.cap_id:
             raise NotImplementedError("cap_id models take class embeddings, not the text head: use forward()/update()")
-        clip_out, eot = self.clip_inputs(caption)
         step = self.train_step_captured if captured else self.train_step_fused
-        return step(x_start.contiguous(), t, cur_len, noise=noise, clip_out=clip_out, eot=eot)
+        return step(x_start.contiguous(), t, cur_len, noise=noise, **self._text_inputs(caption))
 
     # ---- sampling ---------------------------------------------------------------------------
     def generate_batch(self, caption1, caption2, m_lens, dim_pose, known=None, known_mask=None):

@@ -1286,6 +1286,30 @@ int hig_clip_adam_ema(float* p, const float* g, float* m, float* v, int64_t n, f
 int hig_ema_update(float* ema, const float* p, int64_t n, float decay, int32_t warmup, const int32_t* step_dev,
                    int32_t ema_origin, int32_t n_host, hig_stream_t s);
 int hig_swap_f32(float* a, float* b, int64_t n, hig_stream_t s);
+/* ------------------------------------------------------------------------------------------
+ * Whole-row movement for the caption bank (csrc/textrows.hip; models/caption_bank.py): the text side of a step runs once per
+ * distinct caption.  Rows are `row_floats` contiguous fp32; index arrays are int32 on the device.
+ * hig_rows_gather_f32: dst[r][:] = src[idx[r]][:] for r < n_out, a pure copy.  An index outside [0, n_src) reads nothing and
+ *   makes row r quiet NaN: the host validates indices before it stages them, the NaN makes a plumbing bug visible instead
+ *   of letting it fault.
+ * hig_caption_gather: the same gather out of the bank's feature buffer (n_slots rows) plus eot[r] = eot_src[slot[r]] (int64;
+ *   0 for a slot out of range), in one launch: the node that stands where the CLIP tower stood in the step.
+ * hig_rows_segment_sum_f32: dst[u][:] = src[order[seg[u]]][:] + src[order[seg[u] + 1]][:] + ... + src[order[seg[u + 1] - 1]][:]
+ *   for u < n_seg (`seg` holds n_seg + 1 ascending offsets into `order`: the CSR form of "which rows belong to u").  fp32,
+ *   added strictly in list order starting from the first member, so the result is the same bits on every run; an empty
+ *   segment gives +0.0; rows that `order` does not name are never read; an entry of `order` outside [0, n_src) reads nothing
+ *   and contributes NaN.  No atomics.
+ * All three: 16-byte accesses when row_floats % 4 == 0 and both row bases are 16-byte aligned, single floats otherwise (the
+ *   same bits); an index is read once per row and workgroup, not per element; the grid follows the chip's compute units.
+ *   HIG_EINVAL before any HIP call: a NULL pointer, a negative size, a pointer not aligned to its element.  A size of zero is
+ *   HIG_OK and launches nothing.  dst must not overlap src.  No allocation, no synchronisation: capturable.
+ * ---------------------------------------------------------------------------------------- */
+int hig_rows_gather_f32(const float* src, int32_t n_src, const int32_t* idx, int32_t n_out, int64_t row_floats, float* dst,
+                        hig_stream_t stream);
+int hig_caption_gather(const float* feat, const int64_t* eot_src, int32_t n_slots, const int32_t* slot, int32_t rows,
+                       int64_t row_floats, float* clip_out, int64_t* eot, hig_stream_t stream);
+int hig_rows_segment_sum_f32(const float* src, int32_t n_src, const int32_t* order, const int32_t* seg, int32_t n_seg,
+                             int64_t row_floats, float* dst, hig_stream_t stream);
 /* Diagnostic: launches a one-thread kernel named hig_marker_kernel with a grid of `id` blocks -- a named, numbered mark in a
  * rocprofv3 kernel trace (bench.py brackets its roofline microbenchmark with markers 1 and 2; tools/summarize_profiles.py
  * averages the launches between them).  Does nothing else. */
