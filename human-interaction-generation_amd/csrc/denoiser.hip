@@ -1832,6 +1832,42 @@ int64_t fwd16t_total(const Dims& D) { return fwd16t_layout(D).total; }
 int64_t text16t_total(const Dims& D) { return text16t_layout(D).total; }
 int64_t bwd16_total(const Dims& D) { return bwd16_layout(D).total; }
 
+// The debug tap of the bf16 backward (hig_denoiser_bwd_bf16_debug_tap, include/hig.h): off[slot] is an absolute byte offset for the
+// slots written once and an offset from the layer's base for the per-layer ones; -1 where the model has no such buffer.
+struct Tap16Layout {
+  int64_t off[HIG_TAP16_NSLOTS], bytes[HIG_TAP16_NSLOTS];
+};
+Tap16Layout tap16_layout(const Dims& D) {
+  Tap16Layout t;
+  const int64_t row = D.M * D.d * 2, ctx = (int64_t)D.B * D.H * D.hd * D.hd * 4, be = (int64_t)D.B * D.E * 4;
+  const bool inter = D.two == 1;
+  for (int s = 0; s < HIG_TAP16_NSLOTS; ++s) t.bytes[s] = row;      // (most slots are one (M, d) bf16 matrix)
+  t.bytes[HIG_TAP16_DTMP_EMB] = t.bytes[HIG_TAP16_DEMB] = t.bytes[HIG_TAP16_DTMP_TE] = t.bytes[HIG_TAP16_DTE_H] = be;
+  t.bytes[HIG_TAP16_DSS] = (int64_t)D.B * D.nsty * D.L * 2 * D.d * 4;
+  t.bytes[HIG_TAP16_TOK0] = D.two ? (int64_t)D.B * D.d * 4 : -1;
+  t.bytes[HIG_TAP16_POSTMP] = D.two ? (int64_t)D.T * D.d * 4 : -1;
+  t.bytes[HIG_TAP16_FFN_DZ] = D.M * D.ff * 2;
+  for (int s = HIG_TAP16_INT_T1; s <= HIG_TAP16_INT_DH; ++s)
+    if (!inter) t.bytes[s] = -1;
+  t.bytes[HIG_TAP16_SA_DQKV] = 3 * row;
+  if (inter) { t.bytes[HIG_TAP16_INT_DQKV] = 3 * row; t.bytes[HIG_TAP16_INT_DA] = ctx; }
+  t.bytes[HIG_TAP16_CA_DA] = t.bytes[HIG_TAP16_SA_DA] = ctx;
+  t.bytes[HIG_TAP16_CA_DKV] = D.Mt * 2 * D.d * 2;
+  t.bytes[HIG_TAP16_CA_DXFN] = D.Mt * D.Lt * 2;
+  t.bytes[HIG_TAP16_CA_DXF_OUT] = D.Mt * D.Lt * 4;
+  int64_t o = 0;
+  auto take = [&](int s) { t.off[s] = t.bytes[s] < 0 ? -1 : o; if (t.bytes[s] > 0) o += alb(t.bytes[s]); };
+  for (int s = 0; s < HIG_TAP16_LAYER0; ++s) take(s);
+  t.off[HIG_TAP16_LAYER0] = o;
+  o = 0;
+  for (int s = HIG_TAP16_LSTRIDE + 1; s < HIG_TAP16_TOTAL; ++s) take(s);
+  t.off[HIG_TAP16_LSTRIDE] = o;
+  t.off[HIG_TAP16_TOTAL] = t.off[HIG_TAP16_LAYER0] + o * D.L;
+  return t;
+}
+char* g_bwd16_tap = nullptr;          // diagnostic only (hig_denoiser_bwd_bf16_debug_tap): NULL in every real run
+int64_t g_bwd16_tap_bytes = 0;
+
 int require_bf16_train(const Dims& D, const char* who) {
   if (!D.bf16) return hig_set_error(HIG_EINVAL, "%s: dims->storage must be HIG_STORE_BF16", who);
   if (bf16_train_unsupported(D, 1)) return HIG_EUNSUPPORTED;
@@ -1839,6 +1875,61 @@ int require_bf16_train(const Dims& D, const char* who) {
 }
 
 }  // namespace
+
+// ---- test hooks (include/hig.h): the three layouts above and the tap's, by named slot; the tap buffer ----
+extern "C" int hig_bf16_train_layout(const hig_dims* dims, int32_t which, int64_t* out, int32_t n_out) {
+  Dims D;
+  HIG_TRY(check_dims(dims, D));
+  HIG_TRY(require_bf16_train(D, "hig_bf16_train_layout"));
+  int64_t v[HIG_TAP16_NSLOTS > HIG_FW16_NSLOTS ? HIG_TAP16_NSLOTS : HIG_FW16_NSLOTS];
+  int n = 0;
+  if (which == HIG_LAYOUT16_FWD) {
+    const Fwd16TLayout w = fwd16t_layout(D);
+    const bool inter = D.two == 1;
+    n = HIG_FW16_NSLOTS;
+    v[HIG_FW16_TE] = w.te; v[HIG_FW16_TE_H] = w.te_h; v[HIG_FW16_EMB] = w.emb; v[HIG_FW16_SS] = w.ss; v[HIG_FW16_H0] = w.h0;
+    v[HIG_FW16_TOK0] = D.two ? w.tok0 : -1; v[HIG_FW16_LENP] = D.two ? w.lenp : -1;
+    v[HIG_FW16_LAYER0] = w.layer0; v[HIG_FW16_LSTRIDE] = w.lstride;
+    v[HIG_FW16_XN1] = w.xn1; v[HIG_FW16_QKV] = w.qkv; v[HIG_FW16_A1] = w.A1; v[HIG_FW16_AT1] = w.At1; v[HIG_FW16_KST1] = w.kst1;
+    v[HIG_FW16_Y1] = w.y1; v[HIG_FW16_A1S] = w.a1; v[HIG_FW16_H1] = w.h1; v[HIG_FW16_XN2] = w.xn2; v[HIG_FW16_QC] = w.qc;
+    v[HIG_FW16_Y2] = w.y2; v[HIG_FW16_A2S] = w.a2; v[HIG_FW16_H2] = w.h2; v[HIG_FW16_Z1] = w.z1; v[HIG_FW16_F1] = w.f1;
+    v[HIG_FW16_Y3] = w.y3; v[HIG_FW16_A3S] = w.a3; v[HIG_FW16_H3] = w.h3;
+    v[HIG_FW16_XN3] = inter ? w.xn3 : -1; v[HIG_FW16_IQKV] = inter ? w.iqkv : -1; v[HIG_FW16_AI] = inter ? w.Ai : -1;
+    v[HIG_FW16_ATI] = inter ? w.Ati : -1; v[HIG_FW16_KSTI] = inter ? w.ksti : -1; v[HIG_FW16_Y4] = inter ? w.y4 : -1;
+    v[HIG_FW16_A4S] = inter ? w.a4 : -1; v[HIG_FW16_H2B] = inter ? w.h2b : -1;
+    v[HIG_FW16_TOTAL] = w.total;
+  } else if (which == HIG_LAYOUT16_TEXT) {
+    const Text16TLayout t = text16t_layout(D);
+    n = HIG_TX16_NSLOTS;
+    v[HIG_TX16_LAYER0] = t.layer0; v[HIG_TX16_LSTRIDE] = t.lstride; v[HIG_TX16_XFN] = t.xfn; v[HIG_TX16_KV] = t.kv; v[HIG_TX16_AC] = t.Ac;
+    v[HIG_TX16_ATC] = t.Atc; v[HIG_TX16_KSTC] = t.kstc; v[HIG_TX16_TOTAL] = t.total;
+  } else if (which == HIG_LAYOUT16_BWD) {
+    const Bwd16Layout w = bwd16_layout(D);
+    n = HIG_BW16_NSLOTS;
+    v[HIG_BW16_DSS] = w.dss; v[HIG_BW16_DEMB] = w.demb; v[HIG_BW16_DTE_H] = w.dte_h; v[HIG_BW16_MP] = w.Mp; v[HIG_BW16_MTP] = w.Mtp;
+    v[HIG_BW16_TOTAL] = w.total;
+  } else if (which == HIG_LAYOUT16_TAP) {
+    const Tap16Layout t = tap16_layout(D);
+    n = HIG_TAP16_NSLOTS;
+    for (int s = 0; s < HIG_TAP16_NSLOTS; ++s) v[s] = t.off[s];
+  } else {
+    return hig_set_error(HIG_EINVAL, "hig_bf16_train_layout: no layout table %d", which);
+  }
+  for (int s = 0; out && s < n && s < n_out; ++s) out[s] = v[s];
+  return n;
+}
+extern "C" int hig_denoiser_bwd_bf16_debug_tap(void* buf, int64_t bytes) {
+  if (buf && bytes <= 0) return hig_set_error(HIG_EINVAL, "hig_denoiser_bwd_bf16_debug_tap: a tap buffer of %lld bytes", (long long)bytes);
+  g_bwd16_tap = static_cast<char*>(buf);
+  g_bwd16_tap_bytes = buf ? bytes : 0;
+  return HIG_OK;
+}
+extern "C" int64_t hig_denoiser_bwd_bf16_tap_bytes(const hig_dims* dims) {
+  Dims D;
+  HIG_TRY(check_dims(dims, D));
+  HIG_TRY(require_bf16_train(D, "hig_denoiser_bwd_bf16_tap_bytes"));
+  return tap16_layout(D).off[HIG_TAP16_TOTAL];
+}
 
 extern "C" int hig_text_context_bf16_train(const hig_dims* dims, const void* const* params, const void* const* params16,
                                            const float* xf_out, void* textctx, hig_stream_t stream) {
@@ -2053,7 +2144,27 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
   const char* ws = static_cast<const char*>(workspace);
   const char* tc = static_cast<const char*>(textctx);
   char* b = static_cast<char*>(bwd_workspace);
+  // the debug tap (include/hig.h): NULL in every real run
+  char* const tapb = g_bwd16_tap;
+  Tap16Layout tp{};
+  if (tapb) {
+    tp = tap16_layout(D);
+    if (g_bwd16_tap_bytes < tp.off[HIG_TAP16_TOTAL])
+      return hig_set_error(HIG_EINVAL, "hig_denoiser_bwd_bf16: the tap buffer has %lld bytes, these dims need %lld", (long long)g_bwd16_tap_bytes,
+                           (long long)tp.off[HIG_TAP16_TOTAL]);
+  }
   hipStream_t st = hig_stream(stream);
+  if (tapb && is_capturing(st)) return hig_set_error(HIG_EINVAL, "hig_denoiser_bwd_bf16: a debug tap is set and the stream is capturing");
+  // copies `src` into the tap's slot (of layer l, or l < 0: a slot written once) behind the launch that wrote it
+  auto tap = [&](int slot, int l, const void* src) -> int {
+    char* dst = tapb + tp.off[slot] + (l < 0 ? 0 : tp.off[HIG_TAP16_LAYER0] + tp.off[HIG_TAP16_LSTRIDE] * l);
+    const int64_t n = tp.bytes[slot] / 4;
+    hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(src),
+                       reinterpret_cast<float*>(dst), n);
+    HIG_CHECK_LAUNCH();
+    return HIG_OK;
+  };
+#define HIG_TAP(slot, l, src) do { if (tapb) HIG_TRY(tap(slot, l, src)); } while (0)
   const int d = D.d, E = D.E, ff = D.ff, F = D.F, Lt = D.Lt;
   const int64_t M = D.M, Mt = D.Mt;
   const int64_t ss_ld = (int64_t)D.nsty * D.L * 2 * d;
@@ -2160,11 +2271,14 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
     return hig_gemm16_launch(g.g, st);
   };
   auto sty_bwd = [&](int l, int s, const void* dh, const void* y, const void* a_saved, int norm_w, int norm_b, int out_w, int out_b,
-                     int64_t wt_off, void* dy_out) -> int {
+                     int64_t wt_off, void* dy_out, int tap_t1, int tap_dy) -> int {
     HIG_TRY(wgrad_act(dh, d, a_saved, d, GL(grads, l, out_w), M, bw.Mp, GL(grads, l, out_b)));
     HIG_TRY(dgrad(dh, d, wt_off, b + bw.t1, d, M, HIG_EPI_NONE, nullptr, 0));
-    return ln_bwd16(b + bw.t1, d, y, 0, d, PL(params, l, norm_w), PL(params, l, norm_b), ssf + (int64_t)s * 2 * d, ss_ld, d, 1, nullptr, 0,
-                           dy_out, 0, d, M, d, D.T, GL(grads, l, norm_w), GL(grads, l, norm_b), dss + (int64_t)s * 2 * d, ss_ld);
+    HIG_TAP(tap_t1, l, b + bw.t1);
+    HIG_TRY(ln_bwd16(b + bw.t1, d, y, 0, d, PL(params, l, norm_w), PL(params, l, norm_b), ssf + (int64_t)s * 2 * d, ss_ld, d, 1, nullptr, 0,
+                           dy_out, 0, d, M, d, D.T, GL(grads, l, norm_w), GL(grads, l, norm_b), dss + (int64_t)s * 2 * d, ss_ld));
+    HIG_TAP(tap_dy, l, dy_out);
+    return HIG_OK;
   };
 
   // ---- output projection ---------------------------------------------------------------------------------------------------
@@ -2251,6 +2365,7 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
     HIG_TRY(hig_cast_bf16(dh32, dh, M * d, stream));
     if (D.two) HIG_TRY(out2_rows(dh));
   }
+  HIG_TAP(HIG_TAP16_DHL, -1, dh);
 
   for (int l = D.L - 1; l >= 0; --l) {
     const char* lb = ws + w.layer0 + w.lstride * l;
@@ -2280,21 +2395,24 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
       HIG_TRY(hig_transpose_bf16_batch(n, srcs, lds_, dsts, ldd, rws, cls, stream));
     }
     const char* hffn = D.two == 1 ? lb + w.h2b : lb + w.h2;
+    HIG_TAP(HIG_TAP16_DH_IN, l, dh);
     // ---- FFN --------------------------------------------------------------------------
     HIG_TRY(sty_bwd(l, D.nsty * l + D.nsty - 1, dh, lb + w.y3, lb + w.a3, HIG_L_FFN_STY_NORM_W, HIG_L_FFN_STY_NORM_B, HIG_L_FFN_STY_OUT_W,
-                    HIG_L_FFN_STY_OUT_B, o_sty3, b + bw.t2));
+                    HIG_L_FFN_STY_OUT_B, o_sty3, b + bw.t2, HIG_TAP16_FFN_T1, HIG_TAP16_FFN_DY));
     const char* dy3 = b + bw.t2;
     HIG_TRY(wgrad_act(dy3, d, lb + w.f1, ff, GL(grads, l, HIG_L_FFN_W2), M, bw.Mp, GL(grads, l, HIG_L_FFN_B2)));
     HIG_TRY(dgrad(dy3, d, o_w2t, b + bw.tff, ff, M, HIG_EPI_DGELU, lb + w.z1, ff));     // dz = (dy3 . W2) gelu'(z)
     const char* dz1 = b + bw.tff;
+    HIG_TAP(HIG_TAP16_FFN_DZ, l, dz1);
     HIG_TRY(wgrad_act(dz1, ff, hffn, d, GL(grads, l, HIG_L_FFN_W1), M, bw.Mp, GL(grads, l, HIG_L_FFN_B1)));
     HIG_TRY(wg_launch());     // FFN group: d(h3) (dh), dy3 (t2) and dz (tff) all exist and none has been overwritten yet
     HIG_TRY(dgrad(dz1, ff, o_w1t, dh_alt, d, M, HIG_EPI_RES, dh, d));                  // d(h2) = d(h3) + dz . W1
     { char* tmp = dh; dh = dh_alt; dh_alt = tmp; }  // dh = d(h2), or d(h2b) in the interaction model
+    HIG_TAP(HIG_TAP16_FFN_DH, l, dh);
     if (D.two == 1) {
       // ---- person <-> person cross attention (adjoint of interaction_transformer.py:181-205) ------------------------------------
       HIG_TRY(sty_bwd(l, D.nsty * l + 2, dh, lb + w.y4, lb + w.a4, HIG_L_INT_STY_NORM_W, HIG_L_INT_STY_NORM_B, HIG_L_INT_STY_OUT_W,
-                      HIG_L_INT_STY_OUT_B, o_isty, b + bw.t2));
+                      HIG_L_INT_STY_OUT_B, o_isty, b + bw.t2, HIG_TAP16_INT_T1, HIG_TAP16_INT_DY));
       const int64_t* len_partner = reinterpret_cast<const int64_t*>(ws + w.lenp);
       const int64_t halfA = (int64_t)Bp * D.H * D.hd * D.hd, halfM = (int64_t)Bp * D.T;
       char* dqkv = b + bw.dqkv;
@@ -2304,50 +2422,65 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
       HIG_TRY(hig_linattn_apply_bwd_bf16(b + bw.t2, d, iqkv, 3 * d, Ai + halfA, dqkv, 3 * d, dA + halfA, Bp, D.T, D.H, D.hd, attn, stream));
       HIG_TRY(hig_linattn_apply_bwd_bf16(b + bw.t2 + halfM * d * 2, d, iqkv + halfM * 3 * d * 2, 3 * d, Ai, dqkv + halfM * 3 * d * 2, 3 * d, dA, Bp,
                                          D.T, D.H, D.hd, attn, stream));
+      HIG_TAP(HIG_TAP16_INT_DA, l, dA);
       HIG_TRY(hig_linattn_ctx_bwd_bf16(dA, Ai, iqkv + (int64_t)d * 2, iqkv + (int64_t)2 * d * 2, 3 * d, reinterpret_cast<const float*>(lb + w.ksti),
                                        len_partner, dqkv + (int64_t)d * 2, dqkv + (int64_t)2 * d * 2, 3 * d, D.B, D.T, D.H, D.hd, stream));
+      HIG_TAP(HIG_TAP16_INT_DQKV, l, dqkv);
       HIG_TRY(wgrad_act(dqkv, 3 * d, lb + w.xn3, d, GL(grads, l, HIG_L_INT_QKV_W), M, bw.Mp, GL(grads, l, HIG_L_INT_QKV_B)));
       HIG_TRY(wg_launch());   // person <-> person group: d(h2b) (dh) and dqkv
       HIG_TRY(dgrad(dqkv, 3 * d, o_iqkv, b + bw.t2, d, M, HIG_EPI_NONE, nullptr, 0));
+      HIG_TAP(HIG_TAP16_INT_T2, l, b + bw.t2);
       HIG_TRY(ln_bwd16(b + bw.t2, d, lb + w.h2, 0, d, PL(params, l, HIG_L_INT_NORM_W), PL(params, l, HIG_L_INT_NORM_B), nullptr, 0, 0, 0, dh, d,
                               dh_alt, 0, d, M, d, D.T, GL(grads, l, HIG_L_INT_NORM_W), GL(grads, l, HIG_L_INT_NORM_B), nullptr, 0));
       { char* tmp = dh; dh = dh_alt; dh_alt = tmp; }  // dh = d(h2)
+      HIG_TAP(HIG_TAP16_INT_DH, l, dh);
     }
     // ---- cross attention ---------------------------------------------------------------
     HIG_TRY(sty_bwd(l, D.nsty * l + 1, dh, lb + w.y2, lb + w.a2, HIG_L_CA_STY_NORM_W, HIG_L_CA_STY_NORM_B, HIG_L_CA_STY_OUT_W,
-                    HIG_L_CA_STY_OUT_B, o_sty2, b + bw.t2));
+                    HIG_L_CA_STY_OUT_B, o_sty2, b + bw.t2, HIG_TAP16_CA_T1, HIG_TAP16_CA_DY));
     const float* Ac = reinterpret_cast<const float*>(tlb + tl.Ac);
     HIG_TRY(hig_linattn_apply_bwd_bf16(b + bw.t2, d, lb + w.qc, d, Ac, b + bw.t1, d, dA, D.B, D.T, D.H, D.hd, attn, stream));
     const char* dqc = b + bw.t1;
+    HIG_TAP(HIG_TAP16_CA_DQ, l, dqc);
+    HIG_TAP(HIG_TAP16_CA_DA, l, dA);
     HIG_TRY(wgrad_act(dqc, d, lb + w.xn2, d, GL(grads, l, HIG_L_CA_Q_W), M, bw.Mp, GL(grads, l, HIG_L_CA_Q_B)));
     HIG_TRY(dgrad(dqc, d, o_caq, b + bw.t2, d, M, HIG_EPI_NONE, nullptr, 0));
+    HIG_TAP(HIG_TAP16_CA_T2, l, b + bw.t2);
     HIG_TRY(ln_bwd16(b + bw.t2, d, lb + w.h1, 0, d, PL(params, l, HIG_L_CA_NORM_W), PL(params, l, HIG_L_CA_NORM_B), nullptr, 0, 0, 0, dh, d,
                             dh_alt, 0, d, M, d, D.T, GL(grads, l, HIG_L_CA_NORM_W), GL(grads, l, HIG_L_CA_NORM_B), nullptr, 0));
     { char* tmp = dh; dh = dh_alt; dh_alt = tmp; }  // dh = d(h1)
+    HIG_TAP(HIG_TAP16_CA_DH, l, dh);
     // text side of this layer: d(A_c) -> d(key, value) -> text_norm -> d(xf_out)
     HIG_TRY(hig_linattn_ctx_bwd_bf16(dA, Ac, tlb + tl.kv, tlb + tl.kv + (int64_t)d * 2, 2 * d, reinterpret_cast<const float*>(tlb + tl.kstc), nullptr,
                                      b + bw.dkv, b + bw.dkv + (int64_t)d * 2, 2 * d, D.B, D.N, D.H, D.hd, stream));
+    HIG_TAP(HIG_TAP16_CA_DKV, l, b + bw.dkv);
     HIG_TRY(wgrad_act(b + bw.dkv, 2 * d, tlb + tl.xfn, Lt, GL(grads, l, HIG_L_CA_KV_W), Mt, bw.Mtp, GL(grads, l, HIG_L_CA_KV_B)));
     HIG_TRY(wg_launch());     // cross-attention group: d(h2) (the buffer dh pointed to when it was queued), dqc (t1), dkv
     HIG_TRY(dgrad(b + bw.dkv, 2 * d, o_kv, b + bw.dxfn, Lt, Mt, HIG_EPI_NONE, nullptr, 0));
+    HIG_TAP(HIG_TAP16_CA_DXFN, l, b + bw.dxfn);
     HIG_TRY(ln_bwd16(b + bw.dxfn, Lt, xf_out, 1, Lt, PL(params, l, HIG_L_CA_TNORM_W), PL(params, l, HIG_L_CA_TNORM_B), nullptr, 0, 0, 0,
                             l == D.L - 1 ? nullptr : dxf_out, Lt, dxf_out, 1, Lt, Mt, Lt, D.N, GL(grads, l, HIG_L_CA_TNORM_W),
                             GL(grads, l, HIG_L_CA_TNORM_B), nullptr, 0));
+    HIG_TAP(HIG_TAP16_CA_DXF_OUT, l, dxf_out);
     // ---- self attention ----------------------------------------------------------------
     HIG_TRY(sty_bwd(l, D.nsty * l, dh, lb + w.y1, lb + w.a1, HIG_L_SA_STY_NORM_W, HIG_L_SA_STY_NORM_B, HIG_L_SA_STY_OUT_W,
-                    HIG_L_SA_STY_OUT_B, o_sty1, b + bw.t2));
+                    HIG_L_SA_STY_OUT_B, o_sty1, b + bw.t2, HIG_TAP16_SA_T1, HIG_TAP16_SA_DY));
     char* dqkv = b + bw.dqkv;
     const float* A1 = reinterpret_cast<const float*>(lb + w.A1);
     HIG_TRY(hig_linattn_apply_bwd_bf16(b + bw.t2, d, lb + w.qkv, 3 * d, A1, dqkv, 3 * d, dA, D.B, D.T, D.H, D.hd, attn, stream));
+    HIG_TAP(HIG_TAP16_SA_DA, l, dA);
     HIG_TRY(hig_linattn_ctx_bwd_bf16(dA, A1, lb + w.qkv + (int64_t)d * 2, lb + w.qkv + (int64_t)2 * d * 2, 3 * d,
                                      reinterpret_cast<const float*>(lb + w.kst1), length, dqkv + (int64_t)d * 2, dqkv + (int64_t)2 * d * 2, 3 * d,
                                      D.B, D.T, D.H, D.hd, stream));
+    HIG_TAP(HIG_TAP16_SA_DQKV, l, dqkv);
     HIG_TRY(wgrad_act(dqkv, 3 * d, lb + w.xn1, d, GL(grads, l, HIG_L_SA_QKV_W), M, bw.Mp, GL(grads, l, HIG_L_SA_QKV_B)));
     HIG_TRY(wg_launch());     // self-attention group: d(h1) (dh) and dqkv
     HIG_TRY(dgrad(dqkv, 3 * d, o_qkv, b + bw.t2, d, M, HIG_EPI_NONE, nullptr, 0));
+    HIG_TAP(HIG_TAP16_SA_T2, l, b + bw.t2);
     HIG_TRY(ln_bwd16(b + bw.t2, d, hin, 0, d, PL(params, l, HIG_L_SA_NORM_W), PL(params, l, HIG_L_SA_NORM_B), nullptr, 0, 0, 0, dh, d, dh_alt,
                             0, d, M, d, D.T, GL(grads, l, HIG_L_SA_NORM_W), GL(grads, l, HIG_L_SA_NORM_B), nullptr, 0));
     { char* tmp = dh; dh = dh_alt; dh_alt = tmp; }  // dh = d(h_in of this layer)
+    HIG_TAP(HIG_TAP16_SA_DH, l, dh);
     HIG_TRY(wg_flush());      // the layer's weight gradients are final from here on
     HIG_TRY(ln_flush());
     if (hook) {
@@ -2376,6 +2509,7 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
     // joint_embed / sequence_embedding adjoints below see only the motion rows                 (interaction_transformer.py:596)
     hipLaunchKernelGGL(tok0_bf16_kernel, dim3((D.B * d + 255) / 256), dim3(256), 0, st, reinterpret_cast<__bf16*>(dh), (int64_t)D.T * d, D.B, d, tok0, 1);
     HIG_CHECK_LAUNCH();
+    HIG_TAP(HIG_TAP16_TOK0, -1, tok0);
     HIG_TRY(hig_colsum(tok0, d, D.B, d, GP(grads, HIG_P_JOINT2_B), colp, stream));
     HIG_TRY(wgrad32(G(tok0, d, 1, x, (int64_t)D.T * F, 1, GP(grads, HIG_P_JOINT2_W), 4, d, 4, D.B)));
   }
@@ -2392,6 +2526,7 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
     HIG_TRY(wgrad32(G(f32b, d, 1, x, F, 1, GP(grads, HIG_P_JOINT_W), F, d, F, M)));
     HIG_TRY(hig_colsum(f32b, (int64_t)D.T * d, D.B, D.T * d, dpos, colp, stream));
   }
+  if (D.two) HIG_TAP(HIG_TAP16_POSTMP, -1, dpos);
   if (D.two) {   // (frame t used row t - 1 of the table: shift by one row; a kernel for the same reason as the init-pose rows above)
     const int64_t nsh = (int64_t)Tpos * d;
     hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)((nsh + 255) / 256)), dim3(256), 0, st, dpos + d, GP(grads, HIG_P_SEQ_EMB), nsh);
@@ -2428,19 +2563,25 @@ static int denoiser_bwd_bf16_impl(const hig_dims* dims, const void* const* param
     if (s > 16) s = 16;
     HIG_TRY(hig_gemm_launch(gd.g, s < 1 ? 1 : s, slabs, st));
   }
+  HIG_TAP(HIG_TAP16_DSS, -1, dss);
+  HIG_TAP(HIG_TAP16_DTMP_EMB, -1, dtmp);
   const int64_t nBE = (int64_t)D.B * E;
   const int eb = (int)((nBE + 255) / 256);
   hipLaunchKernelGGL(mul_dsilu_kernel, dim3(eb), dim3(256), 0, st, dtmp, emb, nBE, demb);
   HIG_CHECK_LAUNCH();
+  HIG_TAP(HIG_TAP16_DEMB, -1, demb);
   hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)((nBE + 255) / 256)), dim3(256), 0, st, demb, dxf_proj, nBE);
   HIG_CHECK_LAUNCH();
   HIG_TRY(hig_colsum(demb, E, D.B, E, GP(grads, HIG_P_TE2_B), colp, stream));
   HIG_TRY(hig_gemm_launch(G(demb, E, 1, te_h, E, 1, GP(grads, HIG_P_TE2_W), E, E, E, D.B).silu(1).g, 1, nullptr, st));
   HIG_TRY(hig_gemm_launch(G(demb, E, 0, P(params, HIG_P_TE2_W), E, 1, dtmp, E, D.B, E, E).g, 1, nullptr, st));
+  HIG_TAP(HIG_TAP16_DTMP_TE, -1, dtmp);
   hipLaunchKernelGGL(mul_dsilu_kernel, dim3(eb), dim3(256), 0, st, dtmp, te_h, nBE, dte_h);
   HIG_CHECK_LAUNCH();
+  HIG_TAP(HIG_TAP16_DTE_H, -1, dte_h);
   HIG_TRY(hig_colsum(dte_h, E, D.B, E, GP(grads, HIG_P_TE0_B), colp, stream));
   HIG_TRY(hig_gemm_launch(G(dte_h, E, 1, te, d, 1, GP(grads, HIG_P_TE0_W), d, E, d, D.B).g, 1, nullptr, st));
+#undef HIG_TAP
   return HIG_OK;
 }
 

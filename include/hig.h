@@ -14,6 +14,7 @@
  *   - No global mutable state except (a) what hig_shutdown() releases (the per-thread weight-gradient stream below),
  *     (b) the diagnostic stamp pointers of hig_gemm_debug_stamps / hig_gemm_bf16_debug_stamps /
  *     hig_gemm_ws16_debug_stamps / hig_linattn16_debug_stamps (NULL unless a profiling tool sets them; never set during a timed or captured run),
+ *     and the tap buffer of hig_denoiser_bwd_bf16_debug_tap (NULL unless a test sets it; a captured backward refuses it),
  *     and (c) tuning knobs read ONCE from the environment (HIG_*: DESIGN.md section 5 lists them) into function-local
  *     constants on first use -- after that first call they never change, so calls stay re-entrant.
  *   - Every launch is ordered through the `stream` argument (a hipStream_t passed as void*): on it,
@@ -897,6 +898,48 @@ int32_t hig_denoiser_last_schedule(int32_t* out, int32_t n_out);
 int hig_wgrad16_debug_stamps(void* buf);      /* wgrad16.hip (see there): 8192 x 8 bytes */
 /* the same for hig_linattn_apply_sty_mm16: 8 stamps per workgroup (see linattn16.hip) */
 int hig_linattn16_debug_stamps(void* buf);
+/* Test hooks of the bf16-storage training step (hig_text_context_bf16_train / hig_denoiser_fwd_bf16_train / hig_denoiser_bwd_bf16).
+ * hig_bf16_train_layout: the byte offsets those entries compute for `dims`, out[slot] for the first n_out slots of table `which`;
+ *   returns the number of slots of that table, HIG_EINVAL for an unknown table, dims the step does not train or a NULL dims.  No
+ *   HIP call.  Per-layer members are offsets from the layer's base LAYER0 + l * LSTRIDE; a member the model does not have (the
+ *   person <-> person block outside the two-person model) is -1.  HIG_LAYOUT16_FWD: `workspace`; _TEXT: `textctx`; _BWD: `bwd_workspace`
+ *   (what is left there when the call returns, and the padded reduce extents MP, MTP); _TAP: the tap buffer below.
+ * hig_denoiser_bwd_bf16_debug_tap(buf, bytes): while buf != NULL every hig_denoiser_bwd_bf16[_hooked] call of the process copies each
+ *   buffer that one of its later launches reads into buf -- one slot per (layer, stage), copied on the caller's stream directly
+ *   behind the launch that wrote the buffer; no buffer moves, no launch changes order.  NULL switches it off (the cost is then a
+ *   null check on the host per stage).  buf != NULL with bytes <= 0 is HIG_EINVAL.  A backward whose tap buffer is shorter than
+ *   hig_denoiser_bwd_bf16_tap_bytes(dims) is refused with HIG_EINVAL before any HIP call, one on a capturing stream with a tap set
+ *   before any launch.  Never set during a timed or captured run.
+ * Tap slots, in the order they are written.  Once: DHL d(h_L) behind the output projection, then the layers L-1 .. 0, then DTMP_EMB
+ * (d(silu(emb)) before the SiLU derivative), DEMB, DTMP_TE, DTE_H, DSS; two-person also TOK0 (fp32 init-pose rows of d(h_0)) and
+ * POSTMP (d(sequence_embedding) before its shift).  Per layer: DH_IN; per stylization block T1 (data gradient of its output
+ * projection) and DY (behind its LayerNorm backward); FFN_DZ, FFN_DH (d(h2), two-person d(h2b)); INT_ / SA_ DQKV, DA, T2, DH;
+ * CA_DQ, CA_DA, CA_T2, CA_DH (d(h1)), CA_DKV, CA_DXFN, CA_DXF_OUT (fp32, the sum over the layers so far). */
+#define HIG_LAYOUT16_FWD 0
+#define HIG_LAYOUT16_TEXT 1
+#define HIG_LAYOUT16_BWD 2
+#define HIG_LAYOUT16_TAP 3
+enum {
+  HIG_FW16_TE = 0, HIG_FW16_TE_H, HIG_FW16_EMB, HIG_FW16_SS, HIG_FW16_H0, HIG_FW16_TOK0, HIG_FW16_LENP, HIG_FW16_LAYER0, HIG_FW16_LSTRIDE,
+  HIG_FW16_XN1, HIG_FW16_QKV, HIG_FW16_A1, HIG_FW16_AT1, HIG_FW16_KST1, HIG_FW16_Y1, HIG_FW16_A1S, HIG_FW16_H1, HIG_FW16_XN2, HIG_FW16_QC,
+  HIG_FW16_Y2, HIG_FW16_A2S, HIG_FW16_H2, HIG_FW16_Z1, HIG_FW16_F1, HIG_FW16_Y3, HIG_FW16_A3S, HIG_FW16_H3, HIG_FW16_XN3, HIG_FW16_IQKV,
+  HIG_FW16_AI, HIG_FW16_ATI, HIG_FW16_KSTI, HIG_FW16_Y4, HIG_FW16_A4S, HIG_FW16_H2B, HIG_FW16_TOTAL, HIG_FW16_NSLOTS
+};
+enum { HIG_TX16_LAYER0 = 0, HIG_TX16_LSTRIDE, HIG_TX16_XFN, HIG_TX16_KV, HIG_TX16_AC, HIG_TX16_ATC, HIG_TX16_KSTC, HIG_TX16_TOTAL, HIG_TX16_NSLOTS };
+enum { HIG_BW16_DSS = 0, HIG_BW16_DEMB, HIG_BW16_DTE_H, HIG_BW16_MP, HIG_BW16_MTP, HIG_BW16_TOTAL, HIG_BW16_NSLOTS };
+enum {
+  HIG_TAP16_DHL = 0, HIG_TAP16_DTMP_EMB, HIG_TAP16_DEMB, HIG_TAP16_DTMP_TE, HIG_TAP16_DTE_H, HIG_TAP16_DSS, HIG_TAP16_TOK0, HIG_TAP16_POSTMP,
+  HIG_TAP16_LAYER0, HIG_TAP16_LSTRIDE,
+  HIG_TAP16_DH_IN, HIG_TAP16_FFN_T1, HIG_TAP16_FFN_DY, HIG_TAP16_FFN_DZ, HIG_TAP16_FFN_DH,
+  HIG_TAP16_INT_T1, HIG_TAP16_INT_DY, HIG_TAP16_INT_DQKV, HIG_TAP16_INT_DA, HIG_TAP16_INT_T2, HIG_TAP16_INT_DH,
+  HIG_TAP16_CA_T1, HIG_TAP16_CA_DY, HIG_TAP16_CA_DQ, HIG_TAP16_CA_DA, HIG_TAP16_CA_T2, HIG_TAP16_CA_DH, HIG_TAP16_CA_DKV, HIG_TAP16_CA_DXFN,
+  HIG_TAP16_CA_DXF_OUT,
+  HIG_TAP16_SA_T1, HIG_TAP16_SA_DY, HIG_TAP16_SA_DQKV, HIG_TAP16_SA_DA, HIG_TAP16_SA_T2, HIG_TAP16_SA_DH,
+  HIG_TAP16_TOTAL, HIG_TAP16_NSLOTS
+};
+int hig_bf16_train_layout(const hig_dims* dims, int32_t which, int64_t* out, int32_t n_out);
+int hig_denoiser_bwd_bf16_debug_tap(void* buf, int64_t bytes);
+int64_t hig_denoiser_bwd_bf16_tap_bytes(const hig_dims* dims);
 /* dst[i] = bf16(src[i]) (round to nearest even): builds the bf16 shadow of the flat fp32 parameter buffer. */
 /* joint_embed + sequence_embedding of the bf16-storage forward (transformer.py:418-419) as its own kernel pair:
  * out[m][:] = bf16( x[m][:F] . W^T + bias + pos[(m % T) - pos_shift] ), x fp32 with F (e.g. 150, 263) features per

@@ -359,6 +359,48 @@ int main() {
   // ---- diagnostics pointers: set and cleared ----
   EXPECT(hig_gemm_bf16_debug_stamps(nullptr) == HIG_OK && hig_gemm_ws16_debug_stamps(nullptr) == HIG_OK &&
          hig_gemm_debug_stamps(nullptr) == HIG_OK);
+  // ---- the layouts of the bf16 training step by named slot, and the tap of its backward: refusals before any HIP call ----
+  {
+    hig_dims T16 = dims(4, 21, 12, 128, 2, 96, 2, 1, 1, 0, 0);       // two-person, bf16 storage, linear attention
+    hig_dims F32 = dims(4, 21, 12, 128, 2, 96, 2, 1, 0, 0, 0);
+    int64_t v[64];
+    const int tables[][2] = {{HIG_LAYOUT16_FWD, HIG_FW16_NSLOTS}, {HIG_LAYOUT16_TEXT, HIG_TX16_NSLOTS}, {HIG_LAYOUT16_BWD, HIG_BW16_NSLOTS},
+                             {HIG_LAYOUT16_TAP, HIG_TAP16_NSLOTS}};
+    for (const auto& t : tables) {
+      for (int64_t& x : v) x = -7;
+      EXPECT(hig_bf16_train_layout(&T16, t[0], v, 64) == t[1]);
+      for (int s = 0; s < 64; ++s) EXPECT(s < t[1] ? v[s] >= 0 : v[s] == -7);         // (the two-person model has every member)
+      for (int64_t& x : v) x = -7;
+      EXPECT(hig_bf16_train_layout(&T16, t[0], v, 3) == t[1] && v[2] >= 0 && v[3] == -7);   // n_out is respected
+      EXPECT(hig_bf16_train_layout(&T16, t[0], nullptr, 64) == t[1]);
+    }
+    EXPECT(hig_bf16_train_layout(&T16, HIG_LAYOUT16_FWD, v, 64) == HIG_FW16_NSLOTS && v[HIG_FW16_TOTAL] == hig_workspace_bytes(&T16, 1));
+    EXPECT(hig_bf16_train_layout(&T16, HIG_LAYOUT16_TEXT, v, 64) == HIG_TX16_NSLOTS && v[HIG_TX16_TOTAL] == hig_textctx_bytes(&T16, 1));
+    EXPECT(hig_bf16_train_layout(&T16, HIG_LAYOUT16_BWD, v, 64) == HIG_BW16_NSLOTS && v[HIG_BW16_TOTAL] == hig_bwd_workspace_bytes(&T16) &&
+           v[HIG_BW16_MP] == 128);
+    EXPECT(hig_bf16_train_layout(&T16, HIG_LAYOUT16_TAP, v, 64) == HIG_TAP16_NSLOTS && v[HIG_TAP16_TOTAL] == hig_denoiser_bwd_bf16_tap_bytes(&T16));
+    hig_dims one = T16; one.two_person = 0;
+    EXPECT(hig_bf16_train_layout(&one, HIG_LAYOUT16_TAP, v, 64) == HIG_TAP16_NSLOTS && v[HIG_TAP16_INT_DA] == -1 && v[HIG_TAP16_TOK0] == -1 &&
+           v[HIG_TAP16_SA_DH] > 0);
+    EXPECT(hig_bf16_train_layout(&one, HIG_LAYOUT16_FWD, v, 64) == HIG_FW16_NSLOTS && v[HIG_FW16_H2B] == -1 && v[HIG_FW16_LENP] == -1);
+    EXPECT(hig_bf16_train_layout(&T16, 4, v, 64) == HIG_EINVAL && hig_bf16_train_layout(&T16, -1, v, 64) == HIG_EINVAL);
+    EXPECT(hig_bf16_train_layout(nullptr, HIG_LAYOUT16_FWD, v, 64) < 0 && hig_bf16_train_layout(&F32, HIG_LAYOUT16_FWD, v, 64) == HIG_EINVAL);
+    EXPECT(hig_denoiser_bwd_bf16_tap_bytes(nullptr) < 0 && hig_denoiser_bwd_bf16_tap_bytes(&F32) == HIG_EINVAL);
+    const int64_t need = hig_denoiser_bwd_bf16_tap_bytes(&T16);
+    EXPECT(need > 0 && need % 256 == 0);
+    void* fake = reinterpret_cast<void*>((uintptr_t)1 << 32);
+    EXPECT(hig_denoiser_bwd_bf16_debug_tap(fake, 0) == HIG_EINVAL && hig_denoiser_bwd_bf16_debug_tap(fake, -1) == HIG_EINVAL);
+    // a tap buffer one byte short: the backward is refused before it touches the device or any of its arguments
+    EXPECT(hig_denoiser_bwd_bf16_debug_tap(fake, need - 1) == HIG_OK);
+    const void* tab[1] = {nullptr};
+    void* gtab[1] = {nullptr};
+    const float* ff = static_cast<const float*>(fake);
+    const int64_t* fi = static_cast<const int64_t*>(fake);
+    EXPECT(hig_denoiser_bwd_bf16(&T16, tab, tab, ff, fi, fi, ff, fake, fake, ff, gtab, nullptr, static_cast<float*>(fake), static_cast<float*>(fake), fake,
+                                 nullptr) == HIG_EINVAL);
+    EXPECT(hig_last_error(msg, sizeof(msg)) >= 0 && strstr(msg, "tap buffer") != nullptr);
+    EXPECT(hig_denoiser_bwd_bf16_debug_tap(nullptr, 0) == HIG_OK);
+  }
   if (failures) {
     fprintf(stderr, "%d expectation(s) failed\n", failures);
     return 1;

@@ -216,23 +216,29 @@ def check(out, ref, bnd, what=""):
     return worst
 
 
-def check_gemm(out, X, W, epi=NONE, bias=None, res=None, aux=None, what=""):
-    """Element-wise bound of one call (the linear bound, composed with the activation bounds)."""
-    bf16_out = out.dtype == torch.bfloat16
+def gemm_bound(X, W, epi=NONE, bias=None, res=None, bf16_out=False, bf16_aux=False):
+    """(ref, bound, pre-activation, its bound as `aux` is held) of one call: the linear bound, composed with the activation
+    bounds.  The last two are None for HIG_EPI_DGELU, which has no pre-activation output."""
     if epi == DGELU:
         acc, bnd = linear_ref(X, W, NONE, None, None)
         z = res.double()
         d = dgelu64(z)
         ref = acc * d
-        bnd = LIP * bnd + acc.abs() * act_bound(DGELU, z, d, False) + (ulp16(ref) if bf16_out else 2.0 ** -23 * ref.abs())
-        return check(out, ref, bnd, what)
+        return ref, LIP * bnd + acc.abs() * act_bound(DGELU, z, d, False) + (ulp16(ref) if bf16_out else 2.0 ** -23 * ref.abs()), None, None
     pre, bnd = linear_ref(X, W, epi, bias, res)
-    if aux is not None:   # the pre-activation output: the same linear bound, rounded like C
-        check(aux, pre, bnd + (2.0 ** -8 * pre.abs() if aux.dtype == torch.bfloat16 else 0), what + " aux")
+    aux_bnd = bnd + (2.0 ** -8 * pre.abs() if bf16_aux else 0)        # the pre-activation output: the same linear bound, rounded like C
     if epi in (GELU, SILU, RES_SILU):
         ref = gelu64(pre) if epi == GELU else silu64(pre)
-        return check(out, ref, LIP * bnd + act_bound(epi, pre, ref, bf16_out), what)
-    return check(out, pre, bnd + (2.0 ** -8 * pre.abs() if bf16_out else 0), what)
+        return ref, LIP * bnd + act_bound(epi, pre, ref, bf16_out), pre, aux_bnd
+    return pre, bnd + (2.0 ** -8 * pre.abs() if bf16_out else 0), pre, aux_bnd
+
+
+def check_gemm(out, X, W, epi=NONE, bias=None, res=None, aux=None, what=""):
+    """Element-wise bound of one call (gemm_bound)."""
+    ref, bnd, pre, aux_bnd = gemm_bound(X, W, epi, bias, res, out.dtype == torch.bfloat16, aux is not None and aux.dtype == torch.bfloat16)
+    if aux is not None:
+        check(aux, pre, aux_bnd, what + " aux")
+    return check(out, ref, bnd, what)
 
 
 def operands(entry, I, J, K, epi, seed, res_f32=False):
