@@ -430,6 +430,45 @@ extern "C" int64_t hig_eval_encoder_bwd_workspace_bytes(const hig_eval_dims* dim
   if (check_edims(dims, D) != HIG_OK) return -1;
   return ebwd_layout(D).total * 4;
 }
+// ---- test hooks (include/hig.h): the training layouts above and the tap's, by named slot ----
+extern "C" int64_t hig_eval_encoder_bwd_tap_bytes(const hig_eval_dims* dims) {
+  EDims D;
+  if (check_edims(dims, D) != HIG_OK) return HIG_EINVAL;
+  return hig_enc_tap_layout(false, D.B, D.S, D.d, D.ff, D.H, D.L).off[HIG_ETAP_TOTAL] * 4;
+}
+extern "C" int hig_eval_encoder_layout(const hig_eval_dims* dims, int32_t which, int64_t* out, int32_t n_out) {
+  EDims D;
+  if (check_edims(dims, D) != HIG_OK) return HIG_EINVAL;   // (the message is check_edims's)
+  int64_t v[HIG_EBW_NSLOTS];
+  static_assert(HIG_EFW_NSLOTS <= HIG_EBW_NSLOTS && HIG_ETAP_NSLOTS <= HIG_EBW_NSLOTS, "v holds the longest table");
+  int n = 0;
+  if (which == HIG_ENC_LAYOUT_FWD) {
+    const ETrain w = etrain_layout(D);
+    n = HIG_EFW_NSLOTS;
+    v[HIG_EFW_EMB] = w.emb; v[HIG_EFW_H] = w.h; v[HIG_EFW_KPAD] = w.kpad; v[HIG_EFW_O] = D.cls ? -1 : w.o; v[HIG_EFW_FEAT] = D.cls ? -1 : w.feat;
+    v[HIG_EFW_LAYER0] = w.layer0; v[HIG_EFW_LSTRIDE] = w.lstride;
+    v[HIG_EFW_QKV] = w.qkv; v[HIG_EFW_LSE] = w.lse; v[HIG_EFW_ATT] = w.att; v[HIG_EFW_R1] = w.r1; v[HIG_EFW_ST1] = w.st1; v[HIG_EFW_X1] = w.x1;
+    v[HIG_EFW_Z] = w.z; v[HIG_EFW_F] = w.f; v[HIG_EFW_R2] = w.r2; v[HIG_EFW_ST2] = w.st2; v[HIG_EFW_X2] = w.x2; v[HIG_EFW_TOTAL] = w.total;
+  } else if (which == HIG_ENC_LAYOUT_BWD) {
+    const EBwd w = ebwd_layout(D);
+    n = HIG_EBW_NSLOTS;
+    v[HIG_EBW_DA] = w.dA; v[HIG_EBW_DB] = w.dB; v[HIG_EBW_DC] = w.dC; v[HIG_EBW_DFF] = w.dff; v[HIG_EBW_DQKV] = w.dqkv; v[HIG_EBW_DELTA] = w.delta;
+    v[HIG_EBW_WT] = w.wT; v[HIG_EBW_SLABS] = w.slabs; v[HIG_EBW_SLAB_FLOATS] = w.slab_floats; v[HIG_EBW_COLPART] = w.colpart;
+    v[HIG_EBW_LNPART] = w.lnpart;
+    const int64_t head[][2] = {{HIG_EBW_DFT, w.dft}, {HIG_EBW_G, w.g}, {HIG_EBW_GN, w.gn}, {HIG_EBW_G2, w.g2}, {HIG_EBW_POOL1, w.pool1},
+                               {HIG_EBW_POOL2, w.pool2}, {HIG_EBW_U1, w.u1}, {HIG_EBW_U2, w.u2}};
+    for (auto& h : head) v[h[0]] = D.cls ? -1 : h[1];      // (the MotionEncoder head)
+    v[HIG_EBW_XCAT] = w.xcat; v[HIG_EBW_DMOVE] = w.dmove; v[HIG_EBW_DINIT] = w.dinit; v[HIG_EBW_POSTMP] = w.postmp; v[HIG_EBW_TOTAL] = w.total;
+  } else if (which == HIG_ENC_LAYOUT_TAP) {
+    const EncTap t = hig_enc_tap_layout(false, D.B, D.S, D.d, D.ff, D.H, D.L);
+    n = HIG_ETAP_NSLOTS;
+    for (int s = 0; s < HIG_ETAP_NSLOTS; ++s) v[s] = t.off[s];
+  } else {
+    return hig_set_error(HIG_EINVAL, "hig_eval_encoder_layout: no layout table %d", which);
+  }
+  for (int s = 0; out && s < n && s < n_out; ++s) out[s] = v[s];
+  return n;
+}
 
 extern "C" int hig_eval_encoder_fwd_train(const hig_eval_dims* dims, const void* const* params, const float* x1,
                                           const float* x2, const int64_t* length, float* logits, float* feature,
@@ -475,6 +514,7 @@ extern "C" int hig_eval_encoder_bwd(const hig_eval_dims* dims, const void* const
   e.colp = b + bw.colpart; e.lnp = b + bw.lnpart; e.wT = b + bw.wT; e.tA = nullptr; e.tB = nullptr;   // (tA / tB: bf16 product modes only)
   e.dff = b + bw.dff; e.dqkv = b + bw.dqkv; e.delta = b + bw.delta;
   e.stream = stream;
+  HIG_TRY(e.tap_begin(false, D.L, "hig_eval_encoder_bwd"));
 
   float* dA = b + bw.dA;
   float* dB = b + bw.dB;
@@ -507,15 +547,17 @@ extern "C" int hig_eval_encoder_bwd(const hig_eval_dims* dims, const void* const
     hipLaunchKernelGGL(unpool_kernel, dim3((unsigned)M), dim3(128), 0, st, b + bw.u1, b + bw.u2, length, dB, T, d);
     HIG_CHECK_LAUNCH();
   }
+  HIG_TRY(e.tap_copy(HIG_ETAP_DH_L, -1, dB));
   // ---- layers ------------------------------------------------------------------------------------------------------------
   float* dh = dB;
   for (int l = D.L - 1; l >= 0; --l) {
     const float* lb = ws + w.layer0 + w.lstride * l;
     const float* xin = l == 0 ? ws + w.h : ws + w.layer0 + w.lstride * (l - 1) + w.x2;
     const EncLayerAct a = {lb + w.qkv, lb + w.lse, lb + w.att, lb + w.r1, lb + w.st1, lb + w.x1, lb + w.z, lb + w.f, lb + w.r2, lb + w.st2};
-    HIG_TRY(hig_enc_layer_bwd(e, params + HIG_EV_NGLOBAL + l * HIG_TL_NLAYER, grads + HIG_EV_NGLOBAL + l * HIG_TL_NLAYER, a, xin, kpad, dh, dA,
+    HIG_TRY(hig_enc_layer_bwd(e, l, params + HIG_EV_NGLOBAL + l * HIG_TL_NLAYER, grads + HIG_EV_NGLOBAL + l * HIG_TL_NLAYER, a, xin, kpad, dh, dA,
                               dC));
   }
+  HIG_TRY(e.tap_copy(HIG_ETAP_DH_0, -1, dh));
   // ---- embedding -----------------------------------------------------------------------------------------------------------
   if (D.cls) HIG_TRY(e.colsum(dh, (int64_t)S * d, D.B, d, EG(grads, HIG_EV_CLS_IN)));   // the [cls] rows, summed over the batch
   float* dmove = b + bw.dmove;

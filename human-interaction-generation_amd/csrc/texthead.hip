@@ -113,7 +113,52 @@ inline float* TGL(void* const* t, int l, int idx) {
   return static_cast<float*>(t[HIG_T_NGLOBAL + l * HIG_TL_NLAYER + idx]);
 }
 
+float* g_enc_tap = nullptr;           // diagnostic only (hig_enc_bwd_debug_tap): NULL in every real run
+int64_t g_enc_tap_bytes = 0;
+
 }  // namespace
+
+// ---- test hooks (include/hig.h): the two layouts above and the tap's, by named slot; the tap buffer of both backwards ----
+void hig_enc_tap_buffer(float** buf, int64_t* bytes) { *buf = g_enc_tap; *bytes = g_enc_tap_bytes; }
+extern "C" int hig_enc_bwd_debug_tap(void* buf, int64_t bytes) {
+  if (buf && bytes <= 0) return hig_set_error(HIG_EINVAL, "hig_enc_bwd_debug_tap: a tap buffer of %lld bytes", (long long)bytes);
+  g_enc_tap = static_cast<float*>(buf);
+  g_enc_tap_bytes = buf ? bytes : 0;
+  return HIG_OK;
+}
+extern "C" int64_t hig_text_head_bwd_tap_bytes(const hig_text_dims* dims) {
+  TDims D;
+  if (check_tdims(dims, nullptr, D) != HIG_OK) return HIG_EINVAL;
+  return hig_enc_tap_layout(true, D.B, D.N, D.Lt, D.ff, D.H, D.L).off[HIG_ETAP_TOTAL] * 4;
+}
+extern "C" int hig_text_head_layout(const hig_text_dims* dims, int32_t which, int64_t* out, int32_t n_out) {
+  TDims D;
+  if (check_tdims(dims, nullptr, D) != HIG_OK) return HIG_EINVAL;   // (the message is check_tdims's)
+  int64_t v[HIG_TFW_NSLOTS > HIG_TBW_NSLOTS ? HIG_TFW_NSLOTS : HIG_TBW_NSLOTS];
+  static_assert(HIG_ETAP_NSLOTS <= HIG_TFW_NSLOTS, "v holds the longest table");
+  int n = 0;
+  if (which == HIG_ENC_LAYOUT_FWD) {
+    const TFwd w = tfwd_layout(D, 1);
+    n = HIG_TFW_NSLOTS;
+    v[HIG_TFW_X0] = w.x0; v[HIG_TFW_GATH] = w.gath; v[HIG_TFW_STF] = w.stf; v[HIG_TFW_LAYER0] = w.layer0; v[HIG_TFW_LSTRIDE] = w.lstride;
+    v[HIG_TFW_QKV] = w.qkv; v[HIG_TFW_LSE] = w.lse; v[HIG_TFW_ATT] = w.att; v[HIG_TFW_R1] = w.r1; v[HIG_TFW_ST1] = w.st1; v[HIG_TFW_X1] = w.x1;
+    v[HIG_TFW_Z] = w.z; v[HIG_TFW_F] = w.f; v[HIG_TFW_R2] = w.r2; v[HIG_TFW_ST2] = w.st2; v[HIG_TFW_X2] = w.x2; v[HIG_TFW_TOTAL] = w.total;
+  } else if (which == HIG_ENC_LAYOUT_BWD) {
+    const TBwd w = tbwd_layout(D);
+    n = HIG_TBW_NSLOTS;
+    v[HIG_TBW_DA] = w.dA; v[HIG_TBW_DB] = w.dB; v[HIG_TBW_DC] = w.dC; v[HIG_TBW_DFF] = w.dff; v[HIG_TBW_DQKV] = w.dqkv; v[HIG_TBW_DELTA] = w.delta;
+    v[HIG_TBW_DGATH] = w.dgath; v[HIG_TBW_WT] = w.wT; v[HIG_TBW_TA] = w.tA; v[HIG_TBW_TB] = w.tB; v[HIG_TBW_SLABS] = w.slabs;
+    v[HIG_TBW_SLAB_FLOATS] = w.slab_floats; v[HIG_TBW_COLPART] = w.colpart; v[HIG_TBW_LNPART] = w.lnpart; v[HIG_TBW_TOTAL] = w.total;
+  } else if (which == HIG_ENC_LAYOUT_TAP) {
+    const EncTap t = hig_enc_tap_layout(true, D.B, D.N, D.Lt, D.ff, D.H, D.L);
+    n = HIG_ETAP_NSLOTS;
+    for (int s = 0; s < HIG_ETAP_NSLOTS; ++s) v[s] = t.off[s];
+  } else {
+    return hig_set_error(HIG_EINVAL, "hig_text_head_layout: no layout table %d", which);
+  }
+  for (int s = 0; out && s < n && s < n_out; ++s) out[s] = v[s];
+  return n;
+}
 
 extern "C" int64_t hig_text_head_workspace_bytes(const hig_text_dims* dims, int training) {
   TDims D;
@@ -195,6 +240,7 @@ extern "C" int hig_text_head_bwd(const hig_text_dims* dims, const void* const* p
   e.colp = b + bw.colpart; e.lnp = b + bw.lnpart; e.wT = b + bw.wT; e.tA = b + bw.tA; e.tB = b + bw.tB;
   e.dff = b + bw.dff; e.dqkv = b + bw.dqkv; e.delta = b + bw.delta;
   e.stream = stream;
+  HIG_TRY(e.tap_begin(true, D.L, "hig_text_head_bwd"));
   float* lnp = e.lnp;
 
   float* dA = b + bw.dA;
@@ -210,11 +256,13 @@ extern "C" int hig_text_head_bwd(const hig_text_dims* dims, const void* const* p
     HIG_TRY(e.colsum(dxf_proj, E, D.B, E, TG(grads, HIG_T_PROJ_B)));
     HIG_TRY(hig_gemm_launch(G(dxf_proj, E, 1, ws + w.gath, Lt, 1, TG(grads, HIG_T_PROJ_W), Lt, E, Lt, D.B).g, 1, nullptr, st));
     HIG_TRY(hig_gemm_launch(G(dxf_proj, E, 0, TP(params, HIG_T_PROJ_W), Lt, 1, b + bw.dgath, Lt, D.B, Lt, E).g, 1, nullptr, st));
+    HIG_TRY(e.tap_copy(HIG_ETAP_DGATH, -1, b + bw.dgath));
     HIG_TRY(hig_scatter_add_rows(b + bw.dgath, Lt, D.B, D.N, eot, Lt, dA, Lt, stream));
   } else {
     HIG_TRY(hig_zero_async(TG(grads, HIG_T_PROJ_B), (size_t)E * 4, st));
     HIG_TRY(hig_zero_async(TG(grads, HIG_T_PROJ_W), (size_t)E * Lt * 4, st));
   }
+  HIG_TRY(e.tap_copy(HIG_ETAP_DXF_TOTAL, -1, dA));
   // ---- text_ln ---------------------------------------------------------------------------
   const float* xL = ws + w.layer0 + w.lstride * (D.L - 1) + w.x2;
   HIG_TRY(hig_ln_bwd(dA, Lt, xL, Lt, ws + w.stf, TP(params, HIG_T_LN_W), TP(params, HIG_T_LN_B), nullptr, 0, 0, 0,
@@ -226,7 +274,7 @@ extern "C" int hig_text_head_bwd(const hig_text_dims* dims, const void* const* p
     const float* lb = ws + w.layer0 + w.lstride * l;
     const float* xin = l == 0 ? (D.pre ? ws + w.x0 : clip_out) : ws + w.layer0 + w.lstride * (l - 1) + w.x2;
     const EncLayerAct a = {lb + w.qkv, lb + w.lse, lb + w.att, lb + w.r1, lb + w.st1, lb + w.x1, lb + w.z, lb + w.f, lb + w.r2, lb + w.st2};
-    HIG_TRY(hig_enc_layer_bwd(e, params + HIG_T_NGLOBAL + l * HIG_TL_NLAYER, grads + HIG_T_NGLOBAL + l * HIG_TL_NLAYER, a, xin, nullptr, d, t1,
+    HIG_TRY(hig_enc_layer_bwd(e, l, params + HIG_T_NGLOBAL + l * HIG_TL_NLAYER, grads + HIG_T_NGLOBAL + l * HIG_TL_NLAYER, a, xin, nullptr, d, t1,
                               t2));
   }
   // ---- text_pre_proj -----------------------------------------------------------------------

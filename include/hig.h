@@ -14,7 +14,8 @@
  *   - No global mutable state except (a) what hig_shutdown() releases (the per-thread weight-gradient stream below),
  *     (b) the diagnostic stamp pointers of hig_gemm_debug_stamps / hig_gemm_bf16_debug_stamps /
  *     hig_gemm_ws16_debug_stamps / hig_linattn16_debug_stamps (NULL unless a profiling tool sets them; never set during a timed or captured run),
- *     and the tap buffer of hig_denoiser_bwd_bf16_debug_tap (NULL unless a test sets it; a captured backward refuses it),
+ *     and the tap buffers of hig_denoiser_bwd_bf16_debug_tap and hig_enc_bwd_debug_tap (NULL unless a test sets them; a captured
+ *     backward refuses them),
  *     and (c) tuning knobs read ONCE from the environment (HIG_*: DESIGN.md section 5 lists them) into function-local
  *     constants on first use -- after that first call they never change, so calls stay re-entrant.
  *   - Every launch is ordered through the `stream` argument (a hipStream_t passed as void*): on it,
@@ -560,6 +561,58 @@ int hig_eval_encoder_bwd(const hig_eval_dims* dims, const void* const* params, c
  * of bounds: that row adds lse_b alone to the loss and has no one-hot term. */
 int hig_softmax_xent(const float* logits, const int64_t* labels, int32_t B, int32_t C, float* loss /* device scalar */,
                      float* dlogits, int64_t* pred, hig_stream_t stream);
+/* Test hooks of the two fp32 encoder chains (hig_text_head_fwd with training = 1 / hig_text_head_bwd, hig_eval_encoder_fwd_train /
+ * hig_eval_encoder_bwd), in the manner of hig_bf16_train_layout and hig_denoiser_bwd_bf16_debug_tap.
+ * hig_text_head_layout / hig_eval_encoder_layout: the offsets, in FLOATS, those entries compute for `dims`, out[slot] for the first
+ *   n_out slots of table `which`; return the number of slots of that table, HIG_EINVAL for an unknown table, a NULL dims or dims the
+ *   entry refuses.  No HIP call.  Per-layer members are offsets from the layer's base LAYER0 + l * LSTRIDE; a member the model does
+ *   not have (the MotionEncoder head in the consistency model, the other chain's once-only tap slots) is -1.  HIG_ENC_LAYOUT_FWD:
+ *   the training forward's `workspace` (KPAD: the key-padding BYTES start at that float); _BWD: `bwd_workspace` (SLAB_FLOATS is an
+ *   extent, not an offset); _TAP: the tap buffer below.
+ * hig_enc_bwd_debug_tap(buf, bytes): while buf != NULL every hig_text_head_bwd / hig_eval_encoder_bwd call of the process copies each
+ *   buffer that a later launch of the same call overwrites into buf -- one slot per (layer, stage), copied on the caller's stream
+ *   directly behind the launch that wrote the buffer; no buffer moves, no launch changes order.  NULL switches it off (the cost is
+ *   then a null check on the host per stage).  buf != NULL with bytes <= 0 is HIG_EINVAL.  A backward whose tap buffer is shorter
+ *   than hig_text_head_bwd_tap_bytes(dims) / hig_eval_encoder_bwd_tap_bytes(dims) is refused with HIG_EINVAL before any HIP call, one
+ *   on a capturing stream with a tap set before any launch.  Never set during a timed or captured run.
+ * Tap slots, in the order they are written.  Text head, once: DXF_TOTAL (d(xf_out) total: the upstream gradient with d(text_proj
+ * input) scattered onto the EOT rows) and DGATH (d(text_proj input), (B, Lt)).  Evaluator, once: DH_L (d(h) of the last layer:
+ * behind unpool_kernel or the [cls] data-gradient GEMM) and, behind the layers, DH_0 (the d(h) unassemble_kernel reads).  Per layer
+ * (hig_enc_layer_bwd, both chains), rows (M, n) unless stated: DH_IN (incoming d(x2)), DR2 (behind the norm2 backward), DZ
+ * ((M, ff): d(linear1 output)), DX1 (d(x1) behind the FF1 data gradient), DR1 (behind the norm1 backward), DATT (d(attention
+ * output)), DQKV ((M, 3 n)), DELTA ((B, H, S): the attention backward's row sums). */
+#define HIG_ENC_LAYOUT_FWD 0
+#define HIG_ENC_LAYOUT_BWD 1
+#define HIG_ENC_LAYOUT_TAP 2
+enum {
+  HIG_TFW_X0 = 0, HIG_TFW_GATH, HIG_TFW_STF, HIG_TFW_LAYER0, HIG_TFW_LSTRIDE,
+  HIG_TFW_QKV, HIG_TFW_LSE, HIG_TFW_ATT, HIG_TFW_R1, HIG_TFW_ST1, HIG_TFW_X1, HIG_TFW_Z, HIG_TFW_F, HIG_TFW_R2, HIG_TFW_ST2, HIG_TFW_X2,
+  HIG_TFW_TOTAL, HIG_TFW_NSLOTS
+};
+enum {
+  HIG_TBW_DA = 0, HIG_TBW_DB, HIG_TBW_DC, HIG_TBW_DFF, HIG_TBW_DQKV, HIG_TBW_DELTA, HIG_TBW_DGATH, HIG_TBW_WT, HIG_TBW_TA, HIG_TBW_TB,
+  HIG_TBW_SLABS, HIG_TBW_SLAB_FLOATS, HIG_TBW_COLPART, HIG_TBW_LNPART, HIG_TBW_TOTAL, HIG_TBW_NSLOTS
+};
+enum {
+  HIG_EFW_EMB = 0, HIG_EFW_H, HIG_EFW_KPAD, HIG_EFW_O, HIG_EFW_FEAT, HIG_EFW_LAYER0, HIG_EFW_LSTRIDE,
+  HIG_EFW_QKV, HIG_EFW_LSE, HIG_EFW_ATT, HIG_EFW_R1, HIG_EFW_ST1, HIG_EFW_X1, HIG_EFW_Z, HIG_EFW_F, HIG_EFW_R2, HIG_EFW_ST2, HIG_EFW_X2,
+  HIG_EFW_TOTAL, HIG_EFW_NSLOTS
+};
+enum {
+  HIG_EBW_DA = 0, HIG_EBW_DB, HIG_EBW_DC, HIG_EBW_DFF, HIG_EBW_DQKV, HIG_EBW_DELTA, HIG_EBW_WT, HIG_EBW_SLABS, HIG_EBW_SLAB_FLOATS,
+  HIG_EBW_COLPART, HIG_EBW_LNPART, HIG_EBW_DFT, HIG_EBW_G, HIG_EBW_GN, HIG_EBW_G2, HIG_EBW_POOL1, HIG_EBW_POOL2, HIG_EBW_U1, HIG_EBW_U2,
+  HIG_EBW_XCAT, HIG_EBW_DMOVE, HIG_EBW_DINIT, HIG_EBW_POSTMP, HIG_EBW_TOTAL, HIG_EBW_NSLOTS
+};
+enum {
+  HIG_ETAP_DXF_TOTAL = 0, HIG_ETAP_DGATH, HIG_ETAP_DH_L, HIG_ETAP_DH_0, HIG_ETAP_LAYER0, HIG_ETAP_LSTRIDE,
+  HIG_ETAP_DH_IN, HIG_ETAP_DR2, HIG_ETAP_DZ, HIG_ETAP_DX1, HIG_ETAP_DR1, HIG_ETAP_DATT, HIG_ETAP_DQKV, HIG_ETAP_DELTA,
+  HIG_ETAP_TOTAL, HIG_ETAP_NSLOTS
+};
+int hig_text_head_layout(const hig_text_dims* dims, int32_t which, int64_t* out, int32_t n_out);
+int hig_eval_encoder_layout(const hig_eval_dims* dims, int32_t which, int64_t* out, int32_t n_out);
+int hig_enc_bwd_debug_tap(void* buf, int64_t bytes);
+int64_t hig_text_head_bwd_tap_bytes(const hig_text_dims* dims);
+int64_t hig_eval_encoder_bwd_tap_bytes(const hig_eval_dims* dims);
 
 /* ------------------------------------------------------------------------------------------
  * Input pipeline: batch assembly from a device-resident bank of motions.

@@ -481,7 +481,7 @@ def full_reference(q, kv, dy, B, Tq, Tk, H, hd, qlen, kpad, lse_in=None, y_in=No
     isq = 1.0 / math.sqrt(hd)
     S = torch.einsum("bnhd,bmhd->bhnm", qd, kd) * isq
     MS = torch.einsum("bnhd,bmhd->bhnm", qd.abs(), kd.abs()) * isq
-    valid = torch.ones(B, Tq, dtype=torch.bool, device=DEV) if qlen is None else torch.arange(Tq, device=DEV)[None] < qlen[:, None]
+    valid = torch.ones(B, Tq, dtype=torch.bool, device=q.device) if qlen is None else torch.arange(Tq, device=q.device)[None] < qlen[:, None]
     S0 = S
     S = torch.where(valid[:, None, :, None], S, (S.float() + (-100000.0)).double())
     if kpad is not None:
