@@ -74,10 +74,12 @@ __device__ __forceinline__ float key_score(const float* kS, int m, float q) {
   return (a0 + a1) + (a2 + a3);
 }
 
-template <bool VEC>
+// LSE (the training forward): also lse[b][h][n] = mx + log(sum) of row n's n + 1 live keys, one store of lane 0 behind the
+// row's sum; nothing else of the kernel depends on the flag, so Y has the same bits in both instances.
+template <bool VEC, bool LSE>
 __global__ __launch_bounds__(CA_NT) void causal_attn_kernel(const float* __restrict__ Q, int64_t ldq, const float* __restrict__ K,
                                                              const float* __restrict__ V, int64_t ldk, int N, int H,
-                                                             float* __restrict__ Y, int64_t ldy) {
+                                                             float* __restrict__ Y, int64_t ldy, float* __restrict__ lse) {
   extern __shared__ __attribute__((aligned(16))) float ca_lds[];
   float* kS = ca_lds;                 // N x 64
   float* vS = ca_lds + N * CA_HD;     // N x 64
@@ -127,7 +129,11 @@ __global__ __launch_bounds__(CA_NT) void causal_attn_kernel(const float* __restr
     const float s0 = live0 ? a0 * 0.125f : -INFINITY, s1 = live1 ? a1 * 0.125f : -INFINITY;   // 1 / sqrt(64), exact
     const float mx = wave_max(fmaxf(s0, s1));               // key 0 is live in every row: mx is finite
     const float p0 = live0 ? __expf(s0 - mx) : 0.f, p1 = live1 ? __expf(s1 - mx) : 0.f;
-    const float inv = 1.0f / wave_sum(p0 + p1);
+    const float sum = wave_sum(p0 + p1);
+    const float inv = 1.0f / sum;
+    if constexpr (LSE) {
+      if (lane == 0) lse[(int64_t)blockIdx.x * N + n] = mx + __logf(sum);
+    }
     float y = lane_value(p0, 0) * vS[lane];
     // keys lo .. hi, whose weights sit in lanes lo - off .. of `p`: eight V rows in flight per step
     auto add_keys = [&](float p, int lo, int hi, int off) {
@@ -229,8 +235,10 @@ extern "C" int hig_quick_gelu(float* x, int64_t n, hig_stream_t stream) {
   return HIG_OK;
 }
 
-extern "C" int hig_causal_attn_fwd(const float* Q, int64_t ldq, const float* K, const float* V, int64_t ldk, int32_t B, int32_t N,
-                                   int32_t H, float* Y, int64_t ldy, hig_stream_t stream) {
+namespace {
+// the one launch site of causal_attn_kernel: lse == NULL is hig_causal_attn_fwd, else hig_causal_attn_fwd_train
+int causal_fwd_launch(const float* Q, int64_t ldq, const float* K, const float* V, int64_t ldk, int32_t B, int32_t N, int32_t H, float* Y,
+                      int64_t ldy, float* lse, hig_stream_t stream) {
   HIG_REQUIRE(Q && K && V && Y, "hig_causal_attn_fwd: null argument");
   HIG_REQUIRE(B >= 0 && N > 0 && H > 0, "hig_causal_attn_fwd: bad extent (B=%d N=%d H=%d)", B, N, H);
   if (N > CA_NMAX)
@@ -242,10 +250,25 @@ extern "C" int hig_causal_attn_fwd(const float* Q, int64_t ldq, const float* K, 
   const dim3 grid((unsigned)(B * H), (unsigned)((N + CA_QB - 1) / CA_QB));
   const size_t lds = (size_t)2 * N * CA_HD * sizeof(float);   // <= 64 KB
   const bool vec = ((reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V)) & 15) == 0 && ldk % 4 == 0;
-  if (vec) hipLaunchKernelGGL(causal_attn_kernel<true>, grid, dim3(CA_NT), lds, hig_stream(stream), Q, ldq, K, V, ldk, N, H, Y, ldy);
-  else hipLaunchKernelGGL(causal_attn_kernel<false>, grid, dim3(CA_NT), lds, hig_stream(stream), Q, ldq, K, V, ldk, N, H, Y, ldy);
+#define CA_FWD(VECV, LSEV)                                                                                                        \
+  hipLaunchKernelGGL((causal_attn_kernel<VECV, LSEV>), grid, dim3(CA_NT), lds, hig_stream(stream), Q, ldq, K, V, ldk, N, H, Y, ldy, lse)
+  if (lse) { if (vec) CA_FWD(true, true); else CA_FWD(false, true); }
+  else { if (vec) CA_FWD(true, false); else CA_FWD(false, false); }
+#undef CA_FWD
   HIG_CHECK_LAUNCH();
   return HIG_OK;
+}
+}  // namespace
+
+extern "C" int hig_causal_attn_fwd(const float* Q, int64_t ldq, const float* K, const float* V, int64_t ldk, int32_t B, int32_t N,
+                                   int32_t H, float* Y, int64_t ldy, hig_stream_t stream) {
+  return causal_fwd_launch(Q, ldq, K, V, ldk, B, N, H, Y, ldy, nullptr, stream);
+}
+
+extern "C" int hig_causal_attn_fwd_train(const float* Q, int64_t ldq, const float* K, const float* V, int64_t ldk, int32_t B, int32_t N,
+                                         int32_t H, float* Y, int64_t ldy, float* lse, hig_stream_t stream) {
+  HIG_REQUIRE(lse, "hig_causal_attn_fwd_train: null lse");
+  return causal_fwd_launch(Q, ldq, K, V, ldk, B, N, H, Y, ldy, lse, stream);
 }
 
 extern "C" int64_t hig_clip_text_workspace_bytes(const int32_t* dims) {
@@ -285,4 +308,195 @@ extern "C" int hig_clip_text_fwd(const int32_t* dims, const void* const* params,
     xin = lb + w.x2;
   }
   return hig_layernorm(xin, W, M, W, CP(params, HIG_CT_LNF_W), CP(params, HIG_CT_LNF_B), out, W, ws + w.stf, stream);
+}
+
+// ---- training: the forward that keeps what the adjoint needs, and the adjoint ---------------------------------------------------
+namespace {
+
+// What hig_clip_text_fwd_train keeps (floats): the embedded rows and ln_final's statistics, then per layer the two LayerNorms'
+// statistics, qkv, lse, the attention output, x1, the FFN's pre-activation z and x2 (the next layer's input).  The LayerNorm
+// outputs and quick_gelu(z) are not kept: the adjoint rebuilds them (hig_layernorm, hig_quick_gelu_to), bit for bit.  Behind the
+// layers: the two buffers the forward itself rebuilds per layer (h, f).
+struct CTrain {
+  int64_t x0, stf, layer0, lstride;
+  int64_t st1, qkv, lse, att, x1, st2, z, x2;
+  int64_t h, f, total;
+};
+CTrain ctrain_layout(const CDims& D) {
+  CTrain w;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { int64_t r = o; o += al(n); return r; };
+  w.x0 = take(D.M * D.W);
+  w.stf = take(D.M * 2);
+  w.layer0 = o;
+  o = 0;
+  w.st1 = take(D.M * 2);
+  w.qkv = take(D.M * 3 * D.W);
+  w.lse = take((int64_t)D.B * D.H * D.N);
+  w.att = take(D.M * D.W);
+  w.x1 = take(D.M * D.W);
+  w.st2 = take(D.M * 2);
+  w.z = take(D.M * 4 * D.W);
+  w.x2 = take(D.M * D.W);
+  w.lstride = o;
+  o = w.layer0 + w.lstride * D.L;
+  w.h = take(D.M * D.W);
+  w.f = take(D.M * 4 * D.W);
+  w.total = o;
+  return w;
+}
+
+struct CBwd {
+  int64_t d, t1, t2, h, hst, f, dff, dqkv, delta, wT, slabs, slab_floats, colpart, lnpart, emb, total;
+};
+CBwd cbwd_layout(const CDims& D) {
+  CBwd w;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { int64_t r = o; o += al(n); return r; };
+  const int64_t ff = 4 * (int64_t)D.W;
+  w.d = take(D.M * D.W);
+  w.t1 = take(D.M * D.W);
+  w.t2 = take(D.M * D.W);
+  w.h = take(D.M * D.W);
+  w.hst = take(D.M * 2);
+  w.f = take(D.M * ff);
+  w.dff = take(D.M * ff);
+  w.dqkv = take(D.M * 3 * D.W);
+  w.delta = take((int64_t)D.B * D.H * D.N);
+  const int64_t big = ff * D.W;   // the largest weight: c_fc / c_proj
+  w.wT = take(big);
+  w.slab_floats = big * 16 > (int64_t)1536 * 128 * 128 ? big * 16 : (int64_t)1536 * 128 * 128;
+  w.slabs = take(w.slab_floats);
+  w.colpart = take((int64_t)hig_colsum_chunks(D.M) * ff);
+  w.lnpart = take(hig_ln_bwd_partial_floats(D.M, D.W, D.N));
+  w.emb = take(2 * D.M * D.W);   // chunk partials and per-id sums: at most B N rows each
+  w.total = o;
+  return w;
+}
+
+int check_train(const int32_t* dims, CDims& D, const char* who) {
+  HIG_TRY(check_cdims(dims, D));
+  if (D.prec != HIG_PREC_F32) return hig_set_error(HIG_EUNSUPPORTED, "%s: prec=%d, the tower trains with exact fp32 products only", who, D.prec);
+  return HIG_OK;
+}
+
+inline float* CG(void* const* t, int idx) { return static_cast<float*>(t[idx]); }
+inline float* CGL(void* const* t, int l, int idx) { return static_cast<float*>(t[HIG_CT_NGLOBAL + l * HIG_CTL_NLAYER + idx]); }
+
+}  // namespace
+
+extern "C" int64_t hig_clip_text_train_bytes(const int32_t* dims) {
+  CDims D;
+  if (check_train(dims, D, "hig_clip_text_train_bytes") != HIG_OK) return -1;
+  return ctrain_layout(D).total * 4;
+}
+
+extern "C" int64_t hig_clip_text_bwd_workspace_bytes(const int32_t* dims) {
+  CDims D;
+  if (check_train(dims, D, "hig_clip_text_bwd_workspace_bytes") != HIG_OK) return -1;
+  return cbwd_layout(D).total * 4;
+}
+
+extern "C" int hig_clip_text_fwd_train(const int32_t* dims, const void* const* params, const int64_t* tokens, float* out, void* saved,
+                                       hig_stream_t stream) {
+  CDims D;
+  HIG_REQUIRE(params, "hig_clip_text_fwd_train: null params");
+  HIG_TRY(check_train(dims, D, "hig_clip_text_fwd_train"));
+  HIG_REQUIRE(tokens && out && saved, "hig_clip_text_fwd_train: null argument");
+  for (int i = 0; i < HIG_CT_NGLOBAL + D.L * HIG_CTL_NLAYER; ++i) HIG_REQUIRE(params[i], "hig_clip_text_fwd_train: null parameter %d", i);
+  const CTrain w = ctrain_layout(D);
+  float* ws = static_cast<float*>(saved);
+  hipStream_t st = hig_stream(stream);
+  const int W = D.W, ff = 4 * D.W;
+  const int64_t M = D.M;
+  float* h = ws + w.h;
+  float* f = ws + w.f;
+  // the launches of hig_clip_text_fwd on the same operand values: the attention also writes lse, and QuickGELU goes from z to
+  // f instead of overwriting z
+  HIG_TRY(hig_clip_embed(CP(params, HIG_CT_TOK_EMB), CP(params, HIG_CT_POS_EMB), tokens, D.B, D.N, W, D.vocab, ws + w.x0, W, stream));
+  const float* xin = ws + w.x0;
+  for (int l = 0; l < D.L; ++l) {
+    float* lb = ws + w.layer0 + l * w.lstride;
+    HIG_TRY(hig_layernorm(xin, W, M, W, CPL(params, l, HIG_CTL_LN1_W), CPL(params, l, HIG_CTL_LN1_B), h, W, lb + w.st1, stream));
+    HIG_TRY(hig_gemm_launch(G(h, W, 0, CPL(params, l, HIG_CTL_IN_W), W, 0, lb + w.qkv, 3 * W, M, 3 * W, W)
+                                .epi(HIG_EPI_BIAS, CPL(params, l, HIG_CTL_IN_B)).g, 1, nullptr, st));
+    HIG_TRY(hig_causal_attn_fwd_train(lb + w.qkv, 3 * W, lb + w.qkv + W, lb + w.qkv + 2 * W, 3 * W, D.B, D.N, D.H, lb + w.att, W,
+                                      lb + w.lse, stream));
+    HIG_TRY(hig_gemm_launch(G(lb + w.att, W, 0, CPL(params, l, HIG_CTL_OUT_W), W, 0, lb + w.x1, W, M, W, W)
+                                .epi(HIG_EPI_BIAS_RES, CPL(params, l, HIG_CTL_OUT_B)).res(xin, W).g, 1, nullptr, st));
+    HIG_TRY(hig_layernorm(lb + w.x1, W, M, W, CPL(params, l, HIG_CTL_LN2_W), CPL(params, l, HIG_CTL_LN2_B), h, W, lb + w.st2, stream));
+    HIG_TRY(hig_gemm_launch(G(h, W, 0, CPL(params, l, HIG_CTL_FC_W), W, 0, lb + w.z, ff, M, ff, W)
+                                .epi(HIG_EPI_BIAS, CPL(params, l, HIG_CTL_FC_B)).g, 1, nullptr, st));
+    HIG_TRY(hig_quick_gelu_to(lb + w.z, f, M * ff, stream));
+    HIG_TRY(hig_gemm_launch(G(f, ff, 0, CPL(params, l, HIG_CTL_PROJ_W), ff, 0, lb + w.x2, W, M, W, ff)
+                                .epi(HIG_EPI_BIAS_RES, CPL(params, l, HIG_CTL_PROJ_B)).res(lb + w.x1, W).g, 1, nullptr, st));
+    xin = lb + w.x2;
+  }
+  return hig_layernorm(xin, W, M, W, CP(params, HIG_CT_LNF_W), CP(params, HIG_CT_LNF_B), out, W, ws + w.stf, stream);
+}
+
+extern "C" int hig_clip_text_bwd(const int32_t* dims, const void* const* params, const int32_t* index, int32_t n_live, int32_t n_chunks,
+                                 int32_t n_ids, const float* dout, const void* saved, void* const* grads, void* bwd_workspace,
+                                 hig_stream_t stream) {
+  CDims D;
+  HIG_REQUIRE(params && grads, "hig_clip_text_bwd: null table");
+  HIG_TRY(check_train(dims, D, "hig_clip_text_bwd"));
+  HIG_REQUIRE(index && dout && saved && bwd_workspace, "hig_clip_text_bwd: null argument");
+  HIG_REQUIRE(n_live >= 0 && n_live <= D.M && n_chunks >= 0 && n_chunks <= n_live && n_ids >= 0 && n_ids <= n_chunks && (n_live == 0) == (n_ids == 0),
+              "hig_clip_text_bwd: index counts (live %d, chunks %d, ids %d) that no %lld rows give", n_live, n_chunks, n_ids, (long long)D.M);
+  for (int i = 0; i < HIG_CT_NGLOBAL + D.L * HIG_CTL_NLAYER; ++i)
+    HIG_REQUIRE(params[i] && grads[i], "hig_clip_text_bwd: null parameter or gradient %d", i);
+  const CTrain w = ctrain_layout(D);
+  const CBwd bw = cbwd_layout(D);
+  const float* ws = static_cast<const float*>(saved);
+  float* b = static_cast<float*>(bwd_workspace);
+  const int W = D.W, ff = 4 * D.W;
+  const int64_t M = D.M;
+  EncBwd e;
+  e.B = D.B; e.S = D.N; e.n = W; e.ff = ff; e.H = D.H; e.hd = CA_HD; e.prec = HIG_PREC_F32; e.M = M;
+  e.slabs = b + bw.slabs; e.slab_floats = bw.slab_floats;
+  e.colp = b + bw.colpart; e.lnp = b + bw.lnpart; e.wT = b + bw.wT; e.tA = nullptr; e.tB = nullptr;   // (tA / tB: bf16 product modes only)
+  e.dff = b + bw.dff; e.dqkv = b + bw.dqkv; e.delta = b + bw.delta;
+  e.stream = stream;
+  float* d = b + bw.d;      // d(x2 of layer l), then d(its input)
+  float* t1 = b + bw.t1;
+  float* t2 = b + bw.t2;
+  float* h = b + bw.h;
+  float* hst = b + bw.hst;
+  float* f = b + bw.f;
+  // ---- ln_final --------------------------------------------------------------------------------------------------------------
+  const float* xL = ws + w.layer0 + w.lstride * (D.L - 1) + w.x2;
+  HIG_TRY(hig_ln_bwd(dout, W, xL, W, ws + w.stf, CP(params, HIG_CT_LNF_W), CP(params, HIG_CT_LNF_B), nullptr, 0, 0, 0, nullptr, 0, d, W, M,
+                     W, D.N, CG(grads, HIG_CT_LNF_W), CG(grads, HIG_CT_LNF_B), nullptr, 0, e.lnp, stream));
+  for (int l = D.L - 1; l >= 0; --l) {
+    const float* lb = ws + w.layer0 + w.lstride * l;
+    const float* xin = l == 0 ? ws + w.x0 : ws + w.layer0 + w.lstride * (l - 1) + w.x2;
+    auto p = [&](int i) { return CPL(params, l, i); };
+    auto g = [&](int i) { return CGL(grads, l, i); };
+    // x2 = x1 + c_proj(f), f = quick_gelu(z)
+    HIG_TRY(hig_quick_gelu_to(lb + w.z, f, M * ff, stream));
+    HIG_TRY(e.wgrad_act(d, W, f, ff, g(HIG_CTL_PROJ_W), M, g(HIG_CTL_PROJ_B)));
+    HIG_TRY(e.dgrad(d, p(HIG_CTL_PROJ_W), W, ff, M, e.dff, HIG_EPI_NONE, nullptr, nullptr));
+    HIG_TRY(hig_quick_gelu_bwd(lb + w.z, e.dff, e.dff, M * ff, stream));                      // dff = d(z)
+    // z = c_fc(ln_2(x1))
+    HIG_TRY(hig_layernorm(lb + w.x1, W, M, W, p(HIG_CTL_LN2_W), p(HIG_CTL_LN2_B), h, W, hst, stream));
+    HIG_TRY(e.wgrad_act(e.dff, ff, h, W, g(HIG_CTL_FC_W), M, g(HIG_CTL_FC_B)));
+    HIG_TRY(e.dgrad(e.dff, p(HIG_CTL_FC_W), ff, W, M, t1, HIG_EPI_NONE, nullptr, nullptr));  // t1 = d(ln_2's output)
+    HIG_TRY(hig_ln_bwd(t1, W, lb + w.x1, W, lb + w.st2, p(HIG_CTL_LN2_W), p(HIG_CTL_LN2_B), nullptr, 0, 0, 0, d, W, t2, W, M, W, D.N,
+                       g(HIG_CTL_LN2_W), g(HIG_CTL_LN2_B), nullptr, 0, e.lnp, stream));    // t2 = d(x1) = d(x2) + the norm's
+    // x1 = xin + out_proj(att)
+    HIG_TRY(e.wgrad_act(t2, W, lb + w.att, W, g(HIG_CTL_OUT_W), M, g(HIG_CTL_OUT_B)));
+    HIG_TRY(e.dgrad(t2, p(HIG_CTL_OUT_W), W, W, M, t1, HIG_EPI_NONE, nullptr, nullptr));     // t1 = d(att)
+    const float* qkv = lb + w.qkv;
+    HIG_TRY(hig_causal_attn_bwd(t1, W, lb + w.att, W, qkv, 3 * W, qkv + W, qkv + 2 * W, 3 * W, D.B, D.N, D.H, CA_HD, lb + w.lse, e.delta,
+                                e.dqkv, 3 * W, e.dqkv + W, e.dqkv + 2 * W, 3 * W, stream));
+    // qkv = in_proj(ln_1(xin))
+    HIG_TRY(hig_layernorm(xin, W, M, W, p(HIG_CTL_LN1_W), p(HIG_CTL_LN1_B), h, W, hst, stream));
+    HIG_TRY(e.wgrad_act(e.dqkv, 3 * W, h, W, g(HIG_CTL_IN_W), M, g(HIG_CTL_IN_B)));
+    HIG_TRY(e.dgrad(e.dqkv, p(HIG_CTL_IN_W), 3 * W, W, M, t1, HIG_EPI_NONE, nullptr, nullptr));   // t1 = d(ln_1's output)
+    HIG_TRY(hig_ln_bwd(t1, W, xin, W, lb + w.st1, p(HIG_CTL_LN1_W), p(HIG_CTL_LN1_B), nullptr, 0, 0, 0, t2, W, d, W, M, W, D.N,
+                       g(HIG_CTL_LN1_W), g(HIG_CTL_LN1_B), nullptr, 0, e.lnp, stream));    // d = d(xin) = d(x1) + the norm's
+  }
+  return hig_clip_embed_bwd(d, D.B, D.N, W, D.vocab, index, n_live, n_chunks, n_ids, b + bw.emb, CG(grads, HIG_CT_TOK_EMB),
+                            CG(grads, HIG_CT_POS_EMB), stream);
 }

@@ -8,7 +8,10 @@ package brings the tower as stock torch ops; this module has
     load without the package.  This forward is the YARDSTICK of the native route, never its fallback;
   * `load_text_tower`: a state dict, a checkpoint of this project (`clip.` keys) or a file -> `ClipTextModel`;
   * `tower_refusal` / `TowerTable` / `tower_forward`: the rule that says whether hig_clip_text_fwd (csrc/cliptext.hip) can run
-    a given tower, its pointer table, and the call.
+    a given tower, its pointer table, and the call;
+  * `TrainTowerTable` / `EmbedIndex` / `tower_forward_train` / `tower_backward` / `_ClipTowerFn`: the same for a TRAINABLE tower
+    (`MotionInteractionTransformer(no_clip=True, clip_tower_train="hip")`) through hig_clip_text_fwd_train / hig_clip_text_bwd,
+    with the embedding gradient's inverted index built on the host from the tokenizer's CPU tokens.
 
 The BPE vocabulary is data this repository does not carry: without the `clip` package the caller supplies the tokenizer
 (`MotionTransformer(clip_model=..., clip_tokenize=...)`).
@@ -158,10 +161,11 @@ def _tower_tensors(clip_model):
     return out
 
 
-def tower_refusal(clip_model, device=None):
+def tower_refusal(clip_model, device=None, trainable=False):
     """None when hig_clip_text_fwd computes what `clip_model`'s torch ops compute, else the reason it does not: the tower has
     `resblocks` of OpenAI's structure, every tower parameter is a frozen contiguous fp32 tensor (on `device`, when given),
-    the head dim is 64, there are at most 128 tokens and every block's `attn_mask` is the causal one (compared on the host)."""
+    the head dim is 64, there are at most 128 tokens and every block's `attn_mask` is the causal one (compared on the host).
+    trainable=True: the same rule for hig_clip_text_fwd_train / hig_clip_text_bwd, where parameters may require grad."""
     blocks = getattr(getattr(clip_model, "transformer", None), "resblocks", None)
     if blocks is None or len(blocks) == 0:
         return "the tower has no resblocks"
@@ -174,7 +178,7 @@ def tower_refusal(clip_model, device=None):
     for t in tensors:
         if t.dtype != torch.float32:
             return "a tower parameter is %s, not fp32" % t.dtype
-        if t.requires_grad:
+        if t.requires_grad and not trainable:
             return "a tower parameter requires grad (the backward is not built)"
         if not t.is_contiguous():
             return "a tower parameter is not contiguous"
@@ -224,9 +228,10 @@ class TowerRefused(ValueError):
 class TowerTable:
     """The pointer table of a qualifying tower, built once: the tensors (kept alive), their addresses in hig.h's order and
     the shape.  `stale()` says whether a parameter has been moved or un-frozen since."""
+    TRAINABLE = False
 
     def __init__(self, clip_model, device):
-        why = tower_refusal(clip_model, device)
+        why = tower_refusal(clip_model, device, trainable=self.TRAINABLE)
         if why is not None:
             raise TowerRefused("CLIP text tower: " + why)
         from .. import _lib
@@ -241,7 +246,7 @@ class TowerTable:
         self.device = torch.device(device)
 
     def stale(self):
-        return any(t.data_ptr() != p or t.requires_grad for t, p in zip(self.tensors, self.ptrs))
+        return any(t.data_ptr() != p or (t.requires_grad and not self.TRAINABLE) for t, p in zip(self.tensors, self.ptrs))
 
 
 _PREC = {"f32": 0, "bf16x3": 1, "bf16": 2}
@@ -266,3 +271,160 @@ def tower_forward(table, tokens, pool=None, precision="f32"):
     if pool is not None:
         pool.give("clip", ws, table.device)
     return out
+
+
+# ---- the native training route -------------------------------------------------------------------------------------------------
+class TrainTowerTable(TowerTable):
+    """TowerTable under tower_refusal(trainable=True): parameters may require grad; stale when one has moved."""
+    TRAINABLE = True
+
+
+def embed_chunk():
+    from .. import _lib
+    return _lib.CLIP_EMBED_CHUNK
+
+
+class EmbedIndex:
+    """The inverted index hig_clip_embed_bwd takes (include/hig.h), built on the host from the tokenizer's CPU tokens (B, N):
+    per distinct id in [0, vocab) the rows b N + n that hold it in ascending order, cut into chunks of `chunk` rows; all of it
+    int32 in ONE packed buffer (`host`; `to(device)` uploads it from pinned memory).  Fields: order, chunk_seg, chunk_order,
+    id_seg, ids, pos_order, pos_seg (numpy views of `host`), n_live, n_chunks, n_ids."""
+
+    FIELDS = ("order", "chunk_seg", "chunk_order", "id_seg", "ids", "pos_order", "pos_seg")
+
+    def __init__(self, tokens, vocab, chunk=None):
+        import numpy as np
+        chunk = embed_chunk() if chunk is None else int(chunk)
+        tok = np.asarray(tokens.detach().cpu().numpy() if torch.is_tensor(tokens) else tokens, dtype=np.int64)
+        assert tok.ndim == 2 and chunk > 0
+        B, N = tok.shape
+        flat = tok.reshape(-1)
+        rows = np.nonzero((flat >= 0) & (flat < vocab))[0]
+        rows = rows[np.argsort(flat[rows], kind="stable")]                 # grouped by id, ascending row inside an id
+        ids, counts = np.unique(flat[rows], return_counts=True)
+        per_id = (counts + chunk - 1) // chunk                              # chunks of every id
+        starts = np.concatenate([[0], np.cumsum(counts)])[:-1]
+        chunk_seg = [np.arange(s, s + c, chunk) for s, c in zip(starts, counts)]
+        chunk_seg = np.concatenate(chunk_seg + [np.array([len(rows)])]) if len(ids) else np.zeros(1, np.int64)
+        self.B, self.N, self.vocab, self.chunk = B, N, int(vocab), chunk
+        self.n_live, self.n_chunks, self.n_ids = len(rows), len(chunk_seg) - 1, len(ids)
+        parts = [rows, chunk_seg, np.arange(self.n_chunks), np.concatenate([[0], np.cumsum(per_id)]), ids,
+                 (np.arange(B)[None, :] * N + np.arange(N)[:, None]).reshape(-1), np.arange(N + 1) * B]
+        packed = np.concatenate([np.asarray(p, dtype=np.int64) for p in parts])
+        assert B * N < 2 ** 31 and packed.size == self.numel()
+        self.host = torch.from_numpy(packed.astype(np.int32))
+        view, o = self.host.numpy(), 0
+        for name, p in zip(self.FIELDS, parts):
+            setattr(self, name, view[o:o + len(p)])
+            o += len(p)
+        self.dev = None
+
+    def numel(self):
+        return (self.n_live + (self.n_chunks + 1) + self.n_chunks + (self.n_ids + 1) + self.n_ids + self.B * self.N + (self.N + 1))
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type == "cuda" and not self.host.is_pinned():
+            self.host = self.host.pin_memory()
+        self.dev = self.host.to(device, non_blocking=True)
+        return self
+
+
+def embed_grad_restated(dx0, index, W):
+    """The fp32 sum hig_clip_embed_bwd is defined as, in numpy: each chunk added in list order from its first row, then an id's
+    chunk sums in chunk order from the first; dpos[n] over b ascending.  dx0 (B N, W) -> (dtok (vocab, W), dpos (N, W))."""
+    import numpy as np
+    dx0 = np.asarray(dx0, dtype=np.float32).reshape(index.B * index.N, W)
+    dtok = np.zeros((index.vocab, W), dtype=np.float32)
+    for u in range(index.n_ids):
+        total = None
+        for c in range(index.id_seg[u], index.id_seg[u + 1]):
+            members = index.order[index.chunk_seg[c]:index.chunk_seg[c + 1]]
+            part = dx0[members[0]].copy()
+            for r in members[1:]:
+                part = (part + dx0[r]).astype(np.float32)
+            total = part if total is None else (total + part).astype(np.float32)
+        dtok[index.ids[u]] = total
+    dpos = np.zeros((index.N, W), dtype=np.float32)
+    for n in range(index.N):
+        acc = dx0[n].copy()
+        for b in range(1, index.B):
+            acc = (acc + dx0[b * index.N + n]).astype(np.float32)
+        dpos[n] = acc
+    return dtok, dpos
+
+
+def _train_dims(table, B):
+    return clip_dims(B, table.N, table.W, table.H, table.L, table.vocab, 0)
+
+
+def _check_tokens(table, tokens):
+    if tokens.dim() != 2 or tokens.shape[1] != table.N or tokens.dtype != torch.int64 or tokens.device != table.device:
+        raise RuntimeError("CLIP text tower: tokens must be (B, %d) int64 on %s" % (table.N, table.device))
+
+
+def tower_forward_train(table, tokens, pool=None):
+    """hig_clip_text_fwd_train on the current stream: (out (B, N, W), saved).  `saved` goes to tower_backward, which returns its
+    buffer to the pool."""
+    from .. import _lib
+    _check_tokens(table, tokens)
+    tokens = tokens.contiguous()
+    B = tokens.shape[0]
+    dims = _train_dims(table, B)
+    L = _lib.lib()
+    nbytes = L.hig_clip_text_train_bytes(dims)
+    if nbytes < 0:
+        raise RuntimeError("libhig: %s (clip_tower_train='torch' selects stock PyTorch ops)" % _lib.last_error())
+    ws = pool.take("clip_t", nbytes, table.device) if pool is not None else torch.empty(nbytes, dtype=torch.uint8, device=table.device)
+    out = torch.empty(B, table.N, table.W, device=table.device, dtype=torch.float32)
+    _lib.check(L.hig_clip_text_fwd_train(dims, table.table, _lib.ptr(tokens), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()))
+    return out, (dims, ws, B)
+
+
+def tower_backward(table, index, dout, saved, pool=None):
+    """hig_clip_text_bwd: upstream dout (B, N, W) -> the gradients of table.tensors, in that order, as views of one fresh buffer."""
+    from .. import _lib
+    dims, ws, B = saved
+    dev = table.device
+    if index.dev is None or index.dev.device != dev or (index.B, index.N, index.vocab) != (B, table.N, table.vocab):
+        raise RuntimeError("CLIP text tower: the embedding index does not belong to these tokens")
+    dout = dout.contiguous()
+    assert dout.shape == (B, table.N, table.W) and dout.dtype == torch.float32
+    offs, o = [], 0
+    for p in table.tensors:
+        offs.append(o)
+        o += (p.numel() + 63) // 64 * 64
+    gflat = torch.empty(o, device=dev, dtype=torch.float32)
+    grads = [gflat[off:off + p.numel()].view(p.shape) for p, off in zip(table.tensors, offs)]
+    gtable = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+    L = _lib.lib()
+    nb = L.hig_clip_text_bwd_workspace_bytes(dims)
+    if nb < 0:
+        raise RuntimeError("libhig: %s" % _lib.last_error())
+    bws = pool.take("clip_bwd", nb, dev) if pool is not None else torch.empty(nb, dtype=torch.uint8, device=dev)
+    _lib.check(L.hig_clip_text_bwd(dims, table.table, _lib.ptr(index.dev), index.n_live, index.n_chunks, index.n_ids, _lib.ptr(dout),
+                                   _lib.ptr(ws), gtable, _lib.ptr(bws), _lib.stream_ptr()))
+    if pool is not None:
+        pool.give("clip_bwd", bws, dev)
+        pool.give("clip_t", ws, dev)
+    return grads
+
+
+class _ClipTowerFn(torch.autograd.Function):
+    """Autograd boundary of the trainable tower (hig_clip_text_fwd_train / hig_clip_text_bwd): tokens in, ln_final's output
+    (B, N, W) out; the tower's parameters are passed so that autograd routes their gradients, which come back as ordinary
+    tensors (views of one buffer per backward)."""
+
+    @staticmethod
+    def forward(ctx, owner, table, tokens, index, *params):
+        out, saved = tower_forward_train(table, tokens, owner._pool)
+        ctx.owner, ctx.table, ctx.index, ctx.saved = owner, table, index, saved
+        owner.clip_train_stats["native_forwards"] += 1
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        grads = tower_backward(ctx.table, ctx.index, dout, ctx.saved, ctx.owner._pool)
+        ctx.saved = None
+        ctx.owner.clip_train_stats["native_backwards"] += 1
+        return (None, None, None, None) + tuple(g if p.requires_grad else None for g, p in zip(grads, ctx.table.tensors))

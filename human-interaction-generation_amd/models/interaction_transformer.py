@@ -17,6 +17,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from . import clip_text
 from .transformer import (FFN, MotionTransformer, StylizationBlock, _CrossAttention, _SelfAttention,
                           _WorkspacePool, clip, set_requires_grad, timestep_embedding, zero_module)
 
@@ -125,11 +126,45 @@ class MotionInteractionTransformer(MotionTransformer):
         self.text_head = kargs.get("text_head", os.environ.get("HIG_TEXT_HEAD", "hip"))
         self.storage = kargs.get("storage", os.environ.get("HIG_STORAGE", "f32"))   # "bf16": inference with bf16 activations
         self._init_clip_route(kargs)
+        # `clip_tower_train` (with `no_clip`): "hip" runs a qualifying TRAINABLE tower through hig_clip_text_fwd_train /
+        # hig_clip_text_bwd (clip_text.tower_refusal(trainable=True) is the rule), "torch" (the default) keeps it on torch ops.
+        self.clip_tower_train = kargs.get("clip_tower_train", os.environ.get("HIG_CLIP_TOWER_TRAIN", "torch"))
+        if self.clip_tower_train not in ("hip", "torch"):
+            raise ValueError("clip_tower_train must be 'hip' or 'torch' (got %r)" % (self.clip_tower_train,))
+        self._clip_train_table = None
+        self.clip_train_stats = {"native_forwards": 0, "native_backwards": 0, "native_inference": 0}
         self._flat = None
         self._pool = _WorkspacePool()
         self._textctx_cache = None
         self._param_epoch = 0
         self.cache_text_context = True
+
+    def _apply(self, fn, *a, **k):
+        self._clip_train_table = None
+        return super()._apply(fn, *a, **k)
+
+    def _load_from_state_dict(self, *a, **k):
+        self._clip_train_table = None
+        return super()._load_from_state_dict(*a, **k)
+
+    def _clip_train_native_table(self, tokens):
+        """The pointer table of the trainable tower when `encode_text` takes the native route for these tokens, else None: the
+        model is `no_clip`, the option is "hip", the tokens are on a ROCm device and clip_text.tower_refusal(trainable=True)
+        finds nothing (asked once; a tower that did not qualify is asked again only after `_apply` or a load)."""
+        if self.clip_tower_train != "hip" or not tokens.is_cuda or not getattr(self, "no_clip", False):
+            return None
+        if not hasattr(getattr(self.clip, "transformer", None), "resblocks"):
+            return None
+        t = self._clip_train_table
+        if isinstance(t, clip_text.TrainTowerTable) and (t.device != tokens.device or t.stale()):
+            t = None
+        if t is None:
+            try:
+                t = clip_text.TrainTowerTable(self.clip, tokens.device)
+            except clip_text.TowerRefused:
+                t = False
+            self._clip_train_table = t
+        return t or None
 
     # ---- reference API ------------------------------------------------------------------
     def load_my_state_dict(self, state_dict, opt):
@@ -159,7 +194,19 @@ class MotionInteractionTransformer(MotionTransformer):
         """:532-556; with `no_clip` the CLIP text tower is trained too (no no_grad)."""
         if not self.no_clip:
             return MotionTransformer.encode_text(self, text, device)
-        text = self._tokenize(text).to(device)      # (a trainable tower stays on torch ops: its backward is not built)
+        tokens_host = self._tokenize(text)
+        text = tokens_host.to(device)
+        table = self._clip_train_native_table(text)
+        if table is not None:   # the trainable tower in HIP (csrc/cliptext.hip); exact-fp32 products
+            ids = text.long()   # (the `clip` package's tokenizer hands out int32 in some versions; the entries take int64)
+            if torch.is_grad_enabled() and any(p.requires_grad for p in table.tensors):
+                index = clip_text.EmbedIndex(tokens_host, table.vocab).to(text.device)
+                x = clip_text._ClipTowerFn.apply(self, table, ids, index, *table.tensors)
+            else:
+                x = clip_text.tower_forward(table, ids, self._pool)
+                self.clip_train_stats["native_inference"] += 1
+            return self._text_head(text, x.permute(1, 0, 2))
+        # clip_tower_train="torch", or a tower the rule refuses: stock torch ops
         x = self.clip.token_embedding(text).type(self.clip.d_type)
         x = x + self.clip.positional_embedding.type(self.clip.d_type)
         x = x.permute(1, 0, 2)

@@ -498,6 +498,64 @@ int hig_causal_attn_fwd(const float* Q, int64_t ldq, const float* K, const float
                         int32_t H, float* Y, int64_t ldy, hig_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training the CLIP text tower (`no_clip`: interaction_transformer.py:533-541 runs the tower without no_grad): the forward that
+ * keeps what the adjoint needs, and the adjoint (csrc/cliptext.hip, kernels in csrc/cliptext_bwd.hip).  Exact fp32 products only
+ * (prec != HIG_PREC_F32: HIG_EUNSUPPORTED); every launch on `stream`, no allocation, no synchronisation, no float atomics, every
+ * sum in a fixed order: two runs give the same bits.  Arguments are checked before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+/* hig_causal_attn_fwd that also writes lse (B, H, N) = log sum_{m <= n} exp(q_n . k_m / 8).  The same kernel under a template
+ * flag: Y has the bits hig_causal_attn_fwd gives. */
+int hig_causal_attn_fwd_train(const float* Q, int64_t ldq, const float* K, const float* V, int64_t ldk, int32_t B, int32_t N,
+                              int32_t H, float* Y, int64_t ldy, float* lse, hig_stream_t stream);
+/* Adjoint of the causal attention for upstream dY, head dim 64 and N <= 128 (else HIG_EUNSUPPORTED, nothing launched).  Operands in
+ * the forward's strided layout; delta (B, H, N) is scratch.  With sums over m <= n only:
+ *     w_nm = exp(q_n . k_m / 8 - lse_n)     delta_n = sum_l dY_nl Y_nl     dS_nm = w_nm (dY_n . v_m - delta_n)
+ *     dQ_n = sum_{m <= n} dS_nm k_m / 8     dK_m = sum_{n >= m} dS_nm q_n / 8     dV_m = sum_{n >= m} w_nm dY_n
+ * Two kernels on a grid of (B H, blocks of 32 rows): the query side (delta, dQ) stages keys 0 .. the block's last row, the key side
+ * (dK, dV) queries from the block's first key on; both rebuild w from lse.  Keys m > n are skipped, not masked: no K or V row
+ * beyond n enters row n's terms and no Q, dY, Y, lse row below m enters key m's sums.  Every sum runs in ascending order. */
+int hig_causal_attn_bwd(const float* dY, int64_t lddy, const float* Y, int64_t ldy, const float* Q, int64_t ldq, const float* K,
+                        const float* V, int64_t ldk, int32_t B, int32_t N, int32_t H, int32_t hd, const float* lse, float* delta,
+                        float* dQ, int64_t lddq, float* dK, float* dV, int64_t lddk, hig_stream_t stream);
+/* y[i] = z[i] sigmoid(1.702 z[i]): hig_quick_gelu out of place (the same bits), so that the training forward keeps z. */
+int hig_quick_gelu_to(const float* z, float* y, int64_t n, hig_stream_t stream);
+/* dz[i] = dy[i] s (1 + x (1 - s)), x = 1.702 z[i], s = sigmoid(x), on v_exp_f32 / v_rcp_f32; 1 - s is formed as exp(-x) s for
+ * z >= 0 (no cancellation) and as 1 - s below.  float4 body and scalar tail; dz may be dy. */
+int hig_quick_gelu_bwd(const float* z, const float* dy, float* dz, int64_t n, hig_stream_t stream);
+/* Gradient of token_embedding.weight (dtok: dense (vocab, W), zero-filled here) and positional_embedding (dpos (N, W)) from
+ * dx0 (B N, W), contiguous rows.  The host builds the inverted index from the CPU tokens (no device read-back) and uploads it as one
+ * packed int32 buffer; with n_live rows whose id lies in [0, vocab), n_ids distinct such ids and n_chunks chunks:
+ *     order[n_live]        the rows b N + n, grouped by id (ids ascending), ascending inside an id
+ *     chunk_seg[n_chunks + 1]   offsets into `order`: an id's list is cut into chunks of HIG_CLIP_EMBED_CHUNK rows (the last shorter)
+ *     chunk_order[n_chunks]     0 .. n_chunks - 1
+ *     id_seg[n_ids + 1]    offsets into the chunks: an id's chunks are consecutive, in list order
+ *     ids[n_ids]           the ids, ascending
+ *     pos_order[B N]       n-major: b N + n for b ascending, for n ascending;   pos_seg[N + 1] = 0, B, 2 B, ...
+ * (hig_clip_embed_index_ints gives the total; -1 for a negative count).  The result is DEFINED as this fp32 sum: each chunk added
+ * in list order from its first row, then an id's chunk sums added in chunk order from the first; dpos[n] = sum over b ascending.
+ * Token 0 pads every caption (~ 2 200 rows at 32 captions, > 30 000 at 480): the chunks keep one id's list from being one walker's.
+ * An id outside [0, vocab) read no row in the forward and gets none here; rows of unused ids are +0.0.
+ * Three hig_rows_segment_sum_f32 passes and one row scatter.  scratch: (n_chunks + n_ids) W floats. */
+#define HIG_CLIP_EMBED_CHUNK 64
+int64_t hig_clip_embed_index_ints(int32_t B, int32_t N, int32_t n_live, int32_t n_chunks, int32_t n_ids);
+int hig_clip_embed_bwd(const float* dx0, int32_t B, int32_t N, int32_t W, int32_t vocab, const int32_t* index, int32_t n_live,
+                       int32_t n_chunks, int32_t n_ids, float* scratch, float* dtok, float* dpos, hig_stream_t stream);
+/* The tower: dims and tables as for hig_clip_text_fwd.  hig_clip_text_fwd_train computes what hig_clip_text_fwd computes, bit for
+ * bit, and keeps in `saved` (hig_clip_text_train_bytes) the embedded rows, per layer both LayerNorms' statistics, qkv, lse, the
+ * attention output, x1, the FFN's pre-activation and x2; LayerNorm outputs and quick_gelu(z) are rebuilt by the adjoint.  That is
+ * N (W + 2) + L N (10 W + 4 + H) floats per caption: 19 126 184 bytes at N 77, W 512, H 8, L 12 (plus 788 480 of per-call scratch).
+ * hig_clip_text_bwd: upstream dout (B, N, W) -> every gradient of the table (written, not accumulated): ln_final, then per layer in
+ * reverse c_proj, QuickGELU, c_fc, ln_2 (+ the residual gradient), out_proj, the causal attention, the in-projection, ln_1
+ * (+ the residual gradient), then hig_clip_embed_bwd with the packed index above. */
+int64_t hig_clip_text_train_bytes(const int32_t* dims);
+int64_t hig_clip_text_bwd_workspace_bytes(const int32_t* dims);
+int hig_clip_text_fwd_train(const int32_t* dims, const void* const* params, const int64_t* tokens, float* out, void* saved,
+                            hig_stream_t stream);
+int hig_clip_text_bwd(const int32_t* dims, const void* const* params, const int32_t* index, int32_t n_live, int32_t n_chunks,
+                      int32_t n_ids, const float* dout, const void* saved, void* const* grads, void* bwd_workspace,
+                      hig_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Evaluator feature extraction: the two classifiers that score generated pairs,
  * `MotionEncoder` (interaction_transformer.py:641-741: class logits + the pooled feature FID /
  * diversity are computed on) and `MotionConsistencyEvalModel` (:743-829: real/fake logits from a
