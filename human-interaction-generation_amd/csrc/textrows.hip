@@ -86,6 +86,60 @@ __global__ __launch_bounds__(TR_NT) void rows_segment_sum_kernel(const float* __
   }
 }
 
+// dst[k][:] = the rows r of src with key[r] == k, added in ascending r starting from the first member: the sum by class id of
+// the class head (classhead.hip), whose step copies the ids to the device and builds no index on the host.  One wave per
+// workgroup and one (key, `width` columns) item at a time.  The wave reads the keys once, a chunk of HIG_ROWS_KEY_CHUNK rows
+// at a time, 64 keys per load; a ballot keeps the members' order, and the chunk's member rows go to LDS as an ascending list,
+// which the wave then walks four rows at a time (the loads are independent, the adds stay in row order).  No atomics; a row
+// whose key no item owns -- any key outside [0, n_keys) -- is never read; a key without rows stores +0.0.
+constexpr int BK_NT = 64;
+
+template <bool VEC>
+__global__ __launch_bounds__(BK_NT) void rows_sum_by_key_kernel(const float* __restrict__ src, const int32_t* __restrict__ key, int rows,
+                                                                int64_t nvec, int n_keys, int parts, int width, float* __restrict__ dst) {
+  using E = typename RowElem<VEC>::type;
+  __shared__ int32_t members[HIG_ROWS_KEY_CHUNK];
+  const int lane = threadIdx.x;
+  const int64_t items = (int64_t)n_keys * parts;
+  const E* in = reinterpret_cast<const E*>(src);
+  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int k = (int)(item / parts), part = (int)(item % parts);
+    const int64_t c = (int64_t)part * width + lane;
+    const bool active = lane < width && c < nvec;
+    E acc = tr_zero(E{});
+    bool any = false;
+    for (int64_t r0 = 0; r0 < rows; r0 += HIG_ROWS_KEY_CHUNK) {
+      const int nr = rows - r0 < HIG_ROWS_KEY_CHUNK ? (int)(rows - r0) : HIG_ROWS_KEY_CHUNK;
+      int count = 0;
+      for (int b = 0; b < nr; b += BK_NT) {
+        const int j = b + lane;
+        const bool m = j < nr && key[r0 + j] == k;
+        const unsigned long long mask = __ballot(m);
+        if (m) members[count + __popcll(mask & ((1ull << lane) - 1ull))] = (int32_t)(r0 + j);
+        count += __popcll(mask);
+      }
+      __syncthreads();
+      if (active) {
+        int i = 0;
+        for (; i + 4 <= count; i += 4) {
+          const E v0 = in[(int64_t)members[i] * nvec + c], v1 = in[(int64_t)members[i + 1] * nvec + c];
+          const E v2 = in[(int64_t)members[i + 2] * nvec + c], v3 = in[(int64_t)members[i + 3] * nvec + c];
+          acc = any ? tr_add(acc, v0) : v0;
+          acc = tr_add(tr_add(tr_add(acc, v1), v2), v3);
+          any = true;
+        }
+        for (; i < count; ++i) {
+          const E v = in[(int64_t)members[i] * nvec + c];
+          acc = any ? tr_add(acc, v) : v;
+          any = true;
+        }
+      }
+      __syncthreads();   // the next chunk, or the next item, rewrites the list
+    }
+    if (active) reinterpret_cast<E*>(dst)[(int64_t)k * nvec + c] = acc;
+  }
+}
+
 struct RowSplit { bool vec; int64_t nvec; int parts, grid; };
 
 // parts: as many column ranges per row as it takes to put eight workgroups on every compute unit, at most one range per TR_NT
@@ -157,6 +211,36 @@ extern "C" int hig_rows_segment_sum_f32(const float* src, int32_t n_src, const i
   else
     hipLaunchKernelGGL(rows_segment_sum_kernel<false>, dim3(s.grid), dim3(TR_NT), 0, hig_stream(stream), src, (int)n_src, order, seg,
                        (int)n_seg, s.nvec, s.parts, dst);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+// The only parallelism is keys x columns (a key's rows are added in order by one lane per column), so the column range of an
+// item narrows from a full wave (64 elements) down to 16 (256 contiguous bytes per row as float4) until there are four
+// one-wave items per compute unit or the ranges cannot narrow further: 43 keys of 2 048 floats give 1 376 items, 43 keys of
+// 256 floats 172.  The grid is the items, capped at 32 per compute unit (the kernel strides over the rest).
+extern "C" int hig_rows_sum_by_key_f32(const float* src, const int32_t* key, int32_t rows, int64_t row_floats, int32_t n_keys, float* dst,
+                                       hig_stream_t stream) {
+  HIG_REQUIRE(src && key && dst, "hig_rows_sum_by_key_f32: src, key and dst must be non-null");
+  HIG_REQUIRE(rows > 0 && row_floats > 0 && n_keys > 0, "hig_rows_sum_by_key_f32: sizes must be positive (rows %d, row_floats %lld, n_keys %d)",
+              (int)rows, (long long)row_floats, (int)n_keys);
+  HIG_REQUIRE(((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(key)) & 3) == 0,
+              "hig_rows_sum_by_key_f32: pointers must be 4-byte aligned");
+  HIG_REQUIRE(row_floats < ((int64_t)1 << 32), "hig_rows_sum_by_key_f32: row_floats %lld is out of range", (long long)row_floats);
+  const bool vec = row_floats % 4 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  const int64_t nvec = vec ? row_floats / 4 : row_floats;
+  const int64_t cus = hig_chip_cus();
+  int width = BK_NT;
+  while (width > 16 && (int64_t)n_keys * ((nvec + width - 1) / width) < 4 * cus) width /= 2;
+  const int64_t parts = (nvec + width - 1) / width;
+  const int64_t items = (int64_t)n_keys * parts;
+  const int grid = (int)(items < 32 * cus ? items : 32 * cus);
+  if (vec)
+    hipLaunchKernelGGL(rows_sum_by_key_kernel<true>, dim3(grid), dim3(BK_NT), 0, hig_stream(stream), src, key, (int)rows, nvec, (int)n_keys,
+                       (int)parts, width, dst);
+  else
+    hipLaunchKernelGGL(rows_sum_by_key_kernel<false>, dim3(grid), dim3(BK_NT), 0, hig_stream(stream), src, key, (int)rows, nvec, (int)n_keys,
+                       (int)parts, width, dst);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

@@ -11,6 +11,7 @@ attention (`int_ca_block`, :167-207) between the text cross-attention and the FF
 Only the linear-attention variant is built (`no_eff=True` raises: the reference's `no_eff` layer for
 this model, :369-394, drops the interaction attention altogether and no reference tool selects it).
 """
+import ctypes as C
 import os
 
 import torch
@@ -133,6 +134,12 @@ class MotionInteractionTransformer(MotionTransformer):
             raise ValueError("clip_tower_train must be 'hip' or 'torch' (got %r)" % (self.clip_tower_train,))
         self._clip_train_table = None
         self.clip_train_stats = {"native_forwards": 0, "native_backwards": 0, "native_inference": 0}
+        # `class_head` (with `cap_id`): "hip" puts cap_embedding and text_proj into the flat buffer behind the core and lets the
+        # fused / captured training step run them through hig_class_head_fwd / _bwd (`class_ids=` of the trainer's steps);
+        # "torch" (the default) keeps them outside it, on torch ops and torch.optim.Adam.  Without `cap_id` it has no effect.
+        self.class_head = kargs.get("class_head", os.environ.get("HIG_CLASS_HEAD", "torch"))
+        if self.class_head not in ("hip", "torch"):
+            raise ValueError("class_head must be 'hip' or 'torch' (got %r)" % (self.class_head,))
         self._flat = None
         self._pool = _WorkspacePool()
         self._textctx_cache = None
@@ -221,6 +228,56 @@ class MotionInteractionTransformer(MotionTransformer):
         xf_out = xf_proj.unsqueeze(1)
         xf_proj = self.text_proj(xf_proj)
         return xf_proj, xf_out
+
+    # ---- class head in HIP (hig_class_head_*; class_head="hip") ---------------------------------------------
+    def _has_hip_class_head(self):
+        return bool(self.cap_id) and self.class_head == "hip"
+
+    def _class_params(self):
+        """The class head's parameters in the order they take in the flat buffer behind the core."""
+        return [self.cap_embedding, self.text_proj[0].weight, self.text_proj[0].bias]
+
+    def _class_head_args(self, ids):
+        if not self._has_hip_class_head():
+            raise RuntimeError("class_ids= needs a cap_id model built with class_head='hip' (or HIG_CLASS_HEAD=hip): this model's "
+                               "class head is on torch ops, outside the flat buffer")
+        if not (ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous()):
+            raise ValueError("class_ids must be a contiguous 1-d int32 ROCm tensor, one id per model-batch row")
+        tp = self._class_params()
+        if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in tp):
+            raise RuntimeError("class head: parameters must be contiguous fp32 ROCm tensors")
+        classes, Lt = self.cap_embedding.shape
+        return tp, int(classes), int(Lt), int(self.time_embed_dim), int(ids.numel())
+
+    def _launch_class_head(self, ids):
+        """ids (rows,) int32 -> xf_proj (rows, E), xf_out (rows, 1, Lt): text_proj once per class, rows fetched by id."""
+        tp, classes, Lt, E, rows = self._class_head_args(ids)
+        L = _lib.lib()
+        dev = ids.device
+        ws = self._pool.take("cls_f", L.hig_class_head_workspace_bytes(classes, Lt, E, 0), dev)
+        xf_out = torch.empty(rows, 1, Lt, device=dev, dtype=torch.float32)
+        xf_proj = torch.empty(rows, E, device=dev, dtype=torch.float32)
+        _lib.check(L.hig_class_head_fwd(classes, Lt, E, rows, _lib.ptr(tp[0]), _lib.ptr(tp[1]), _lib.ptr(tp[2]), _lib.ptr(ids),
+                                        _lib.ptr(xf_out), _lib.ptr(xf_proj), _lib.ptr(ws), _lib.stream_ptr()))
+        self._pool.give("cls_f", ws, dev)
+        return xf_proj, xf_out
+
+    def _launch_class_head_backward(self, ids, dxf_out, dxf_proj):
+        """Writes the gradients of cap_embedding, text_proj.0.weight and text_proj.0.bias into the flat gradient buffer."""
+        tp, classes, Lt, E, rows = self._class_head_args(ids)
+        L = _lib.lib()
+        dev = ids.device
+        fp = self.flat_params()
+        fp.ensure_grad()
+        assert len(fp.text_params) == 3 and all(a is b for a, b in zip(fp.text_params, tp)), \
+            "the class head is not part of the flat parameter buffer"
+        g_emb, g_w, g_b = (C.c_void_p(fp.grad.data_ptr() + 4 * o) for o in fp.text_offsets)
+        ws = self._pool.take("cls_b", L.hig_class_head_workspace_bytes(classes, Lt, E, 1), dev)
+        _lib.check(L.hig_class_head_bwd(classes, Lt, E, rows, _lib.ptr(tp[0]), _lib.ptr(tp[1]), _lib.ptr(ids),
+                                        _lib.ptr(None if dxf_out is None else dxf_out.contiguous()),
+                                        _lib.ptr(None if dxf_proj is None else dxf_proj.contiguous()),
+                                        g_emb, g_w, g_b, _lib.ptr(ws), _lib.stream_ptr()))
+        self._pool.give("cls_b", ws, dev)
 
     def dims(self, B, T, N):
         d = MotionTransformer.dims(self, B, T, N)

@@ -200,6 +200,9 @@ class _FlatParams:
         self.offsets = offs
         # text head (HIG_T_* / HIG_TL_* order), one aligned group per tensor
         self.text_params = list(model._text_params()) if model._has_hip_text_head() else []
+        if not self.text_params and model._has_hip_class_head():
+            # a cap_id model with class_head="hip": the class head's three tensors stand where the text head goes
+            self.text_params = list(model._class_params())
         if not all(p.device == dev and p.dtype == torch.float32 for p in self.text_params):
             self.text_params = []
         self.text_offsets, o = [], self.core_numel
@@ -968,6 +971,11 @@ class MotionTransformer(nn.Module):
             return False
         l0 = self.textTransEncoder.layers[0]
         return self.text_latent_dim // l0.self_attn.num_heads in (8, 16, 32, 64, 128)
+
+    def _has_hip_class_head(self):
+        """True for a cap_id model whose class head runs through hig_class_head_fwd / _bwd (MotionInteractionTransformer,
+        class_head="hip"); this model has no class head."""
+        return False
 
     def _text_params(self):
         """Text-head parameters in hig.h table order (HIG_T_*, then HIG_TL_* per layer)."""

@@ -239,7 +239,7 @@ class DDPMTrainer(object):
     # ---- EMA of the weights (include/hig.h, 'EMA weights') -------------------------------------------------------
     def _ema_outside_params(self):
         """[(state-dict name, parameter)] of what trains outside the flat buffer: a torch text head, a trainable CLIP tower
-        (no_clip=True), cap_id embeddings."""
+        (no_clip=True), the class head of a cap_id model built with class_head="torch" (with "hip" it is in the buffer)."""
         core = _core(self.encoder)
         fp = core.flat_params()
         in_flat = {id(p) for p in fp.params + fp.text_params}
@@ -709,6 +709,15 @@ class DDPMTrainer(object):
         if getattr(_core(self.encoder), "caption_bank", None) is None:
             raise RuntimeError("caption_batch= needs the model's caption bank (opt.caption_bank / enable_caption_bank)")
 
+    def _class_ids_check(self, class_ids, xf_proj, xf_out, clip_out, eot, caption_batch):
+        """`class_ids=` of the fused steps (a cap_id model with class_head="hip") is exclusive with every other text argument."""
+        if class_ids is None:
+            return
+        if any(a is not None for a in (xf_proj, xf_out, clip_out, eot, caption_batch)):
+            raise ValueError("class_ids= is exclusive with xf_proj= / xf_out=, clip_out= / eot= and caption_batch=: the class head "
+                             "supplies the text embeddings")
+        _core(self.encoder)._class_head_args(class_ids)      # (refuses a model without the HIP class head, and bad ids)
+
     def _text_forward_banked(self, cb):
         """Text side of the fused step out of the caption bank: hig_caption_gather stands where the tower stood.  With
         `text_dedup` the head runs on the U_pad distinct captions and two hig_rows_gather_f32 expand its outputs to the model
@@ -721,11 +730,12 @@ class DDPMTrainer(object):
         return expand_rows(xp_u, cb.inv, cb.rows), expand_rows(xo_u, cb.inv, cb.rows), tstate + (cb,)
 
     def _fused_fwd_bwd(self, x_start, t, length, xf_proj, xf_out, noise, clip_out=None, eot=None, exchange=None,
-                       caption_batch=None):
+                       caption_batch=None, class_ids=None):
         """q_sample -> [text head] -> denoiser forward -> masked MSE -> denoiser backward [-> text head backward]
         into the flat gradient.  With `clip_out` / `eot`, or with a `caption_batch` of the model's caption bank, the text
         embeddings are computed here and the text head is trained too (the reference's full update); otherwise xf_proj /
-        xf_out are inputs.
+        xf_out are inputs.  With `class_ids` the class head stands where the text head stands (hig_class_head_fwd before the
+        denoiser, hig_class_head_bwd behind its backward).
         `exchange` (an OverlappedGradAllReduce that has been begun): the gradient all-reduce of each decoder layer is
         started from inside the backward."""
         core = _core(self.encoder)
@@ -737,6 +747,8 @@ class DDPMTrainer(object):
             xf_proj, xf_out, tstate = self._text_forward_banked(caption_batch)
         elif clip_out is not None:
             xf_proj, xf_out, tstate = self._text_forward(clip_out, eot)
+        elif class_ids is not None:
+            xf_proj, xf_out = core._launch_class_head(class_ids)
         if noise is None:
             noise = torch.randn_like(x_start)
         x_t = self.diffusion.q_sample(x_start, t, noise=noise)
@@ -752,14 +764,17 @@ class DDPMTrainer(object):
                                                 layer_hook=exchange.layer_done, comm_stream=exchange.stream)
         if tstate is not None:
             self._text_backward(tstate, dxp, dxo)
+        elif class_ids is not None:
+            core._launch_class_head_backward(class_ids, dxo, dxp)
 
-    def _fwd_bwd_overlapped_exchange(self, x_start, t, length, xf_proj, xf_out, noise, clip_out, eot, caption_batch=None):
+    def _fwd_bwd_overlapped_exchange(self, x_start, t, length, xf_proj, xf_out, noise, clip_out, eot, caption_batch=None,
+                                     class_ids=None):
         """_fused_fwd_bwd with the gradient exchange of layer l issued while layers l-1 ... 0 are still in backward
         (RCCL on a side stream); returns the world size.  Capturable: see OverlappedGradAllReduce."""
         st = self.fused_state()
         core = _core(self.encoder)
         fp = core.flat_params()
-        n = self._fused_numel(clip_out is not None or caption_batch is not None)
+        n = self._fused_numel(clip_out is not None or caption_batch is not None or class_ids is not None)
         ex = st["overlap"]
         want = getattr(self.opt, "grad_wire", "f32")
         if want != ex.wire:      # (the option is read when the fused state is built; changing it later used to be ignored silently)
@@ -770,7 +785,8 @@ class DDPMTrainer(object):
         assert per_layer[-1][1][1] - per_layer[0][1][0] == core.num_layers * nsty * 2 * core.latent_dim * core.time_embed_dim
         ex.begin(fp.grad, per_layer, tail)
         self._fused_fwd_bwd(x_start, t, length, xf_proj, xf_out, noise, clip_out=clip_out, eot=eot, exchange=ex,
-                            **({} if caption_batch is None else dict(caption_batch=caption_batch)))
+                            **({} if caption_batch is None else dict(caption_batch=caption_batch)),
+                            **({} if class_ids is None else dict(class_ids=class_ids)))
         return ex.finish([(fp.core_numel, n)] if n > fp.core_numel else ())
 
     def _fused_numel(self, with_text):
@@ -779,8 +795,8 @@ class DDPMTrainer(object):
         fp = core.flat_params()
         if with_text:
             if not fp.text_params:
-                raise RuntimeError("this model's text head is not on the HIP path (text_head='torch', cap_id or an "
-                                   "unsupported head dim): the fused step cannot train it")
+                raise RuntimeError("this model's text head is not on the HIP path (text_head='torch', cap_id without "
+                                   "class_head='hip', or an unsupported head dim): the fused step cannot train it")
             clip_net = getattr(core, "clip", None)
             if clip_net is not None and any(p.requires_grad for p in clip_net.parameters()):
                 # MotionInteractionTransformer(no_clip=True) trains the CLIP tower through forward()/update()
@@ -822,7 +838,7 @@ class DDPMTrainer(object):
             fp.shadow16_mark_current(core._param_version())
 
     def train_step_fused(self, x_start, t, length, xf_proj=None, xf_out=None, noise=None, lr=None, clip_out=None,
-                         eot=None, caption_batch=None):
+                         eot=None, caption_batch=None, class_ids=None):
         """One DDPM training step on device tensors, reference semantics (ddpm_trainer.py:97-119,172-187):
           x_t = q_sample(x0, t, noise); pred = denoiser(x_t, t); loss = masked MSE(pred, noise);
           backward; grads = all_reduce(grads) / world; clip_grad_norm_(0.5); Adam.
@@ -830,19 +846,24 @@ class DDPMTrainer(object):
         (`clip_out` (B, N, W) batch-first, `eot` (B,), see MotionTransformer._clip_features) the text head runs
         inside the step and EVERY trainable parameter is updated -- the reference's full update.  `caption_batch` (a
         CaptionBatch of the model's caption bank, exclusive with clip_out / eot) is that same update with the CLIP features
-        fetched from the bank by hig_caption_gather.
+        fetched from the bank by hig_caption_gather.  `class_ids` (int32 on the device, one class id per model-batch row --
+        4 B rows in the order c1, c2, c2, c1 in PIT mode; exclusive with every other text argument) is the full update of a
+        cap_id model built with class_head="hip": the class head runs inside the step.
         With more than one rank the replicas must start identical: call `sync_replicas()` once (train() does).
         No host synchronisation: the loss stays on the device (`fused_state()['loss']`)."""
         self._ema_refuse_in_scope("train_step_fused")
         self._caption_batch_check(caption_batch, clip_out, eot)
+        self._class_ids_check(class_ids, xf_proj, xf_out, clip_out, eot, caption_batch)
         st = self.fused_state()
         ema = self.ema_state()            # (created here, from the weights before the step, when opt.ema_decay asks for one)
-        with_text = clip_out is not None or caption_batch is not None
+        with_text = clip_out is not None or caption_batch is not None or class_ids is not None
         n = self._fused_numel(with_text)
         self._set_lr(lr)
         core = _core(self.encoder)
         fp = core.flat_params()
         banked = {} if caption_batch is None else dict(caption_batch=caption_batch)
+        if class_ids is not None:
+            banked = dict(class_ids=class_ids)
         if OverlappedGradAllReduce.active() and getattr(self.opt, "overlap_allreduce", True):
             world = self._fwd_bwd_overlapped_exchange(x_start, t, length, xf_proj, xf_out, noise, clip_out, eot, **banked)
         else:
@@ -886,7 +907,7 @@ class DDPMTrainer(object):
         return clip_out, tokens.argmax(dim=-1).contiguous()
 
     def train_step_captured(self, x_start, t, length, xf_proj=None, xf_out=None, noise=None, lr=None, clip_out=None,
-                            eot=None, caption_batch=None):
+                            eot=None, caption_batch=None, class_ids=None):
         """The same step as hipGraphs.  Captured once per batch shape.  One rank: ONE graph (q_sample [+ text head] +
         forward + loss + backward + clip + Adam).  With a gradient exchange (more than one rank, or HIG_FORCE_EXCHANGE)
         still ONE graph: the per-layer RCCL all-reduces of `OverlappedGradAllReduce` are captured with the backward they
@@ -900,9 +921,12 @@ class DDPMTrainer(object):
         features.  The EMA of the weights rides in the same update kernel (its update number comes from the device step
         counter, its origin is a constant of the graph); the graph key carries its configuration.
         With `caption_batch` the packed int32 index buffer is the static text input, copied like `t`; the graph is keyed on
-        its layout (rows, U_pad), on `text_dedup` and on the bank's buffers, which are allocated once and never move."""
+        its layout (rows, U_pad), on `text_dedup` and on the bank's buffers, which are allocated once and never move.
+        With `class_ids` the ids are the static text input, copied like `t`; the graph key carries their shape and that the
+        class head is inside."""
         self._ema_refuse_in_scope("train_step_captured")
         self._caption_batch_check(caption_batch, clip_out, eot)
+        self._class_ids_check(class_ids, xf_proj, xf_out, clip_out, eot, caption_batch)
         st = self.fused_state()
         ema = self.ema_state()            # (created eagerly, never inside a capture)
         world = _dist_world()
@@ -911,9 +935,11 @@ class DDPMTrainer(object):
         in_graph = (split and getattr(self.opt, "capture_exchange", True) and getattr(self.opt, "overlap_allreduce", True)
                     and dist.get_backend() == "nccl")
         banked = caption_batch is not None
-        with_text = clip_out is not None or banked
-        # (banked: the one packed index buffer stands in both text slots; it is copied once per replay)
-        text_in = (caption_batch.dev, caption_batch.dev) if banked else (clip_out, eot) if with_text else (xf_proj, xf_out)
+        classed = class_ids is not None
+        with_text = clip_out is not None or banked or classed
+        # (banked: the one packed index buffer stands in both text slots; it is copied once per replay.  classed: so do the ids)
+        text_in = ((caption_batch.dev, caption_batch.dev) if banked else (class_ids, class_ids) if classed else
+                   (clip_out, eot) if with_text else (xf_proj, xf_out))
         n = self._fused_numel(with_text)
         self._set_lr(lr)
         bank = getattr(_core(self.encoder), "caption_bank", None)
@@ -923,17 +949,20 @@ class DDPMTrainer(object):
         if banked:
             key += ((caption_batch.rows, caption_batch.U_pad, bool(_core(self.encoder).text_dedup), bank.feat.data_ptr(),
                      bank.eot.data_ptr()),)
+        if classed:
+            key += (("class_head", tuple(class_ids.shape)),)
         cap = st["graphs"].get(key)
         if cap is None:
             static = {"x0": x_start.clone(), "t": t.clone(), "length": length.clone(),
-                      "ta": text_in[0].clone(), "tb": None if banked else text_in[1].clone(),
+                      "ta": text_in[0].clone(), "tb": None if banked or classed else text_in[1].clone(),
                       "noise": None if noise is None else noise.clone()}
             sargs = ((static["x0"], static["t"], static["length"], None, None, static["noise"], None, None)
-                     if banked else
+                     if banked or classed else
                      (static["x0"], static["t"], static["length"], None, None, static["noise"], static["ta"], static["tb"])
                      if with_text else
                      (static["x0"], static["t"], static["length"], static["ta"], static["tb"], static["noise"], None, None))
-            skw = dict(caption_batch=caption_batch.on_buffer(static["ta"])) if banked else {}
+            skw = (dict(caption_batch=caption_batch.on_buffer(static["ta"])) if banked else
+                   dict(class_ids=static["ta"]) if classed else {})
 
             def part_a():
                 self._fused_fwd_bwd(*sargs[:6], clip_out=sargs[6], eot=sargs[7], **skw)

@@ -1464,6 +1464,39 @@ int hig_caption_gather(const float* feat, const int64_t* eot_src, int32_t n_slot
                        int64_t row_floats, float* clip_out, int64_t* eot, hig_stream_t stream);
 int hig_rows_segment_sum_f32(const float* src, int32_t n_src, const int32_t* order, const int32_t* seg, int32_t n_seg,
                              int64_t row_floats, float* dst, hig_stream_t stream);
+/* ------------------------------------------------------------------------------------------
+ * Sum of rows by key (csrc/textrows.hip): dst[k][:] = the fp32 sum of the rows r < rows of src (rows, row_floats) with
+ * key[r] == k, for k < n_keys; dst is (n_keys, row_floats).  The rows are added strictly in ascending r starting from the first
+ * member, so the result is the same bits on every run; dst[k] is +0.0 when no row has key k; a row whose key lies outside
+ * [0, n_keys) is never read.  No atomics and no index built on the host: the keys (int32, on the device) are all the call
+ * needs, so a captured step copies them like any other input.  One wave owns one (key, column range) item and reads the keys
+ * once, HIG_ROWS_KEY_CHUNK rows at a time; the chunk's member rows are staged in LDS as an ascending list.  16-byte accesses
+ * when row_floats % 4 == 0 and both row bases are 16-byte aligned, single floats otherwise (the same bits).
+ * HIG_EINVAL before any HIP call: a NULL pointer, a size that is not positive, a pointer not 4-byte aligned.  dst must not
+ * overlap src.  No allocation, no synchronisation: capturable.
+ * ---------------------------------------------------------------------------------------- */
+#define HIG_ROWS_KEY_CHUNK 1024
+int hig_rows_sum_by_key_f32(const float* src, const int32_t* key, int32_t rows, int64_t row_floats, int32_t n_keys, float* dst,
+                            hig_stream_t stream);
+/* ------------------------------------------------------------------------------------------
+ * Class head of a cap_id model (csrc/classhead.hip; reference: get_class_embedding, codes/models/interaction_transformer.py:
+ * 558-563): a table of C class embeddings (C, Lt) conditions the denoiser in place of the text head,
+ *     xf_out[r] = emb[id[r]],   xf_proj[r] = text_proj(emb[id[r]]) = P[id[r]]   with P = emb W^T + b  (C, E),
+ * computed per CLASS, not per row: one exact-fp32 GEMM over the C rows of the table, then two hig_rows_gather_f32 (an id
+ * outside [0, C) yields quiet NaN rows, as that entry does).  ids: int32 on the device, one per model-batch row.
+ * hig_class_head_bwd: dP = hig_rows_sum_by_key_f32 of dxf_proj (rows, E), dO = the same of dxf_out (rows, Lt) (a NULL upstream
+ *   gradient counts as zero), then g_b = column sums of dP, g_W = dP^T emb (E, Lt), g_emb = dO + dP W (C, Lt).  All three are
+ *   written, not accumulated; the rows of g_emb of classes no id names come out exactly +0.0.
+ * workspace: hig_class_head_workspace_bytes(C, Lt, E, backward) bytes, 256-byte aligned; the backward's is its own (nothing
+ *   of the forward's is kept).  HIG_EINVAL before any HIP call: a NULL pointer (dxf_out / dxf_proj excepted), an extent that is
+ *   not positive, Lt or E not a multiple of 4 (the size query returns -1).  No allocation, no synchronisation: capturable.
+ * ---------------------------------------------------------------------------------------- */
+int64_t hig_class_head_workspace_bytes(int32_t C, int32_t Lt, int32_t E, int32_t backward);
+int hig_class_head_fwd(int32_t C, int32_t Lt, int32_t E, int32_t rows, const float* emb, const float* W, const float* b,
+                       const int32_t* ids, float* xf_out, float* xf_proj, void* workspace, hig_stream_t stream);
+int hig_class_head_bwd(int32_t C, int32_t Lt, int32_t E, int32_t rows, const float* emb, const float* W, const int32_t* ids,
+                       const float* dxf_out, const float* dxf_proj, float* g_emb, float* g_W, float* g_b, void* workspace,
+                       hig_stream_t stream);
 /* Diagnostic: launches a one-thread kernel named hig_marker_kernel with a grid of `id` blocks -- a named, numbered mark in a
  * rocprofv3 kernel trace (bench.py brackets its roofline microbenchmark with markers 1 and 2; tools/summarize_profiles.py
  * averages the launches between them).  Does nothing else. */
