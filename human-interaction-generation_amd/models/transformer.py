@@ -848,57 +848,43 @@ class MotionTransformer(nn.Module):
         if nbytes < 0:
             raise RuntimeError("libhig: " + _lib.last_error())
         out = torch.empty(B, T, self.input_feats, device=x.device, dtype=torch.float32)
-        if not training and not self._bf16() and not self.cache_text_context:
-            # the reference's per-call forward (text side recomputed every call, transformer.py:144-150) as ONE library call:
-            # the text side runs on a side stream next to the first layers (hig_denoiser_fwd_text)
+        bf16 = self._bf16()
+        # per call: the reference's forward (text side recomputed every call, transformer.py:144-150) as ONE library call, which
+        # is handed xf_out and builds the text side itself, on a side stream next to the first layers (hig_denoiser_fwd_text;
+        # bf16 storage: embedding chain and text side next to the frame-row launches)
+        per_call = not training and not self.cache_text_context
+        if per_call:
             tbytes = L.hig_textctx_bytes(C.byref(dims), 0)
             if tbytes < 0:
                 raise RuntimeError("libhig: " + _lib.last_error())
             textctx = self._pool.take("textctx_i", tbytes, x.device)
-            ws = self._pool.take("fwd_i", nbytes, x.device)
-            _lib.check(L.hig_denoiser_fwd_x(C.byref(dims), fp.param_table(), self._derived32(fp), _lib.ptr(x), _lib.ptr(t),
-                                            _lib.ptr(length), _lib.ptr(xf_proj), _lib.ptr(xf_out), _lib.ptr(textctx), _lib.ptr(out),
-                                            _lib.ptr(ws), 0, _lib.stream_ptr()))
-            self._pool.give("fwd_i", ws, x.device)
-            self._pool.give("textctx_i", textctx, x.device)
-            return out, None
-        if not training and self._bf16() and not self.cache_text_context:
-            # same for bf16 storage (hig_denoiser_fwd_bf16_x): embedding chain and text side next to the frame-row launches
-            tbytes = L.hig_textctx_bytes(C.byref(dims), 0)
-            if tbytes < 0:
-                raise RuntimeError("libhig: " + _lib.last_error())
-            textctx = self._pool.take("textctx_i", tbytes, x.device)
-            ws = self._pool.take("fwd_i", nbytes, x.device)
+        else:
+            textctx = self._text_context(dims, xf_out, training)
+        ws = self._pool.take("fwd_t" if training else "fwd_i", nbytes, x.device)
+        if training:
+            if bf16:
+                _lib.check(L.hig_denoiser_fwd_bf16_train(C.byref(dims), fp.param_table(), fp.shadow16(self._param_version()),
+                                                         _lib.ptr(x), _lib.ptr(t), _lib.ptr(length), _lib.ptr(xf_proj),
+                                                         _lib.ptr(textctx), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()))
+            else:
+                _lib.check(L.hig_denoiser_fwd(C.byref(dims), fp.param_table(), _lib.ptr(x), _lib.ptr(t),
+                                              _lib.ptr(length), _lib.ptr(xf_proj), _lib.ptr(textctx), _lib.ptr(out),
+                                              _lib.ptr(ws), 1, _lib.stream_ptr()))
+            return out, (dims, ws, textctx)
+        # inference: the LayerNorm-folded projections (derived per parameter version)
+        text = _lib.ptr(xf_out) if per_call else None
+        if bf16:
             _lib.check(L.hig_denoiser_fwd_bf16_x(C.byref(dims), fp.param_table(), fp.shadow16(self._param_version()),
                                                  self._derived16(fp), _lib.ptr(x), _lib.ptr(t), _lib.ptr(length), _lib.ptr(xf_proj),
-                                                 _lib.ptr(xf_out), _lib.ptr(textctx), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()))
-            self._pool.give("fwd_i", ws, x.device)
-            self._pool.give("textctx_i", textctx, x.device)
-            return out, None
-        textctx = self._text_context(dims, xf_out, training)
-        ws = self._pool.take("fwd_t" if training else "fwd_i", nbytes, x.device)
-        if self._bf16() and training:
-            _lib.check(L.hig_denoiser_fwd_bf16_train(C.byref(dims), fp.param_table(), fp.shadow16(self._param_version()),
-                                                     _lib.ptr(x), _lib.ptr(t), _lib.ptr(length), _lib.ptr(xf_proj),
-                                                     _lib.ptr(textctx), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()))
-            return out, (dims, ws, textctx)
-        if self._bf16():
-            _lib.check(L.hig_denoiser_fwd_bf16_x(C.byref(dims), fp.param_table(), fp.shadow16(self._param_version()),
-                                                 self._derived16(fp), _lib.ptr(x), _lib.ptr(t), _lib.ptr(length),
-                                                 _lib.ptr(xf_proj), None, _lib.ptr(textctx), _lib.ptr(out), _lib.ptr(ws),
-                                                 _lib.stream_ptr()))
-            self._pool.give("fwd_i", ws, x.device)
-            return out, None
-        if not training:   # inference: the LayerNorm-folded projections (derived per parameter version)
+                                                 text, _lib.ptr(textctx), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()))
+        else:
             _lib.check(L.hig_denoiser_fwd_x(C.byref(dims), fp.param_table(), self._derived32(fp), _lib.ptr(x), _lib.ptr(t),
-                                            _lib.ptr(length), _lib.ptr(xf_proj), None, _lib.ptr(textctx), _lib.ptr(out), _lib.ptr(ws),
-                                            0, _lib.stream_ptr()))
-            self._pool.give("fwd_i", ws, x.device)
-            return out, None
-        _lib.check(L.hig_denoiser_fwd(C.byref(dims), fp.param_table(), _lib.ptr(x), _lib.ptr(t),
-                                      _lib.ptr(length), _lib.ptr(xf_proj), _lib.ptr(textctx), _lib.ptr(out),
-                                      _lib.ptr(ws), int(training), _lib.stream_ptr()))
-        return out, (dims, ws, textctx)
+                                            _lib.ptr(length), _lib.ptr(xf_proj), text, _lib.ptr(textctx), _lib.ptr(out),
+                                            _lib.ptr(ws), 0, _lib.stream_ptr()))
+        self._pool.give("fwd_i", ws, x.device)
+        if per_call:
+            self._pool.give("textctx_i", textctx, x.device)
+        return out, None
 
     def _launch_backward(self, x, t, length, xf_out, saved, dout, want_dx=False, layer_hook=None, comm_stream=None):
         """layer_hook(l): called on the host once decoder layer l's backward is enqueued and `comm_stream` (a
@@ -915,32 +901,13 @@ class MotionTransformer(nn.Module):
         dx = torch.empty_like(x) if want_dx else None
         dxp = torch.empty(B, self.time_embed_dim, device=dev, dtype=torch.float32)
         dxo = torch.empty(B, N, self.text_latent_dim, device=dev, dtype=torch.float32)
-        if dims.storage == _lib.STORE_BF16 and layer_hook is None:
-            _lib.check(L.hig_denoiser_bwd_bf16(C.byref(dims), fp.param_table(), fp.shadow16(self._param_version()), _lib.ptr(x),
-                                               _lib.ptr(t), _lib.ptr(length), _lib.ptr(xf_out), _lib.ptr(textctx), _lib.ptr(ws),
-                                               _lib.ptr(dout), gtable, _lib.ptr(dx), _lib.ptr(dxp), _lib.ptr(dxo), _lib.ptr(bws),
-                                               _lib.stream_ptr()))
-        elif dims.storage == _lib.STORE_BF16:
-            errors = []
-
-            def _hook16(_user, layer):        # an exception must not unwind through the C frames
-                try:
-                    layer_hook(int(layer))
-                except BaseException as e:  # noqa: BLE001
-                    errors.append(e)
-
-            cb = _lib.LAYER_HOOK(_hook16)
-            _lib.check(L.hig_denoiser_bwd_bf16_hooked(
-                C.byref(dims), fp.param_table(), fp.shadow16(self._param_version()), _lib.ptr(x), _lib.ptr(t), _lib.ptr(length),
-                _lib.ptr(xf_out), _lib.ptr(textctx), _lib.ptr(ws), _lib.ptr(dout), gtable, _lib.ptr(dx), _lib.ptr(dxp), _lib.ptr(dxo),
-                _lib.ptr(bws), _lib.stream_ptr(), cb, None, None if comm_stream is None else C.c_void_p(comm_stream.cuda_stream)))
-            if errors:
-                raise errors[0]
-        elif layer_hook is None:
-            _lib.check(L.hig_denoiser_bwd(C.byref(dims), fp.param_table(), _lib.ptr(x), _lib.ptr(t),
-                                          _lib.ptr(length), _lib.ptr(xf_out), _lib.ptr(textctx), _lib.ptr(ws),
-                                          _lib.ptr(dout), gtable, _lib.ptr(dx), _lib.ptr(dxp), _lib.ptr(dxo),
-                                          _lib.ptr(bws), _lib.stream_ptr()))
+        bf16 = dims.storage == _lib.STORE_BF16
+        # the four entries take the same arguments; bf16 storage adds the weight shadow, a hooked one the hook behind the stream
+        args = [C.byref(dims), fp.param_table()] + ([fp.shadow16(self._param_version())] if bf16 else [])
+        args += [_lib.ptr(x), _lib.ptr(t), _lib.ptr(length), _lib.ptr(xf_out), _lib.ptr(textctx), _lib.ptr(ws), _lib.ptr(dout),
+                 gtable, _lib.ptr(dx), _lib.ptr(dxp), _lib.ptr(dxo), _lib.ptr(bws), _lib.stream_ptr()]
+        if layer_hook is None:      # (the hooked entries refuse a null hook)
+            _lib.check((L.hig_denoiser_bwd_bf16 if bf16 else L.hig_denoiser_bwd)(*args))
         else:
             errors = []
 
@@ -951,11 +918,8 @@ class MotionTransformer(nn.Module):
                     errors.append(e)
 
             cb = _lib.LAYER_HOOK(_hook)
-            _lib.check(L.hig_denoiser_bwd_hooked(
-                C.byref(dims), fp.param_table(), _lib.ptr(x), _lib.ptr(t), _lib.ptr(length), _lib.ptr(xf_out),
-                _lib.ptr(textctx), _lib.ptr(ws), _lib.ptr(dout), gtable, _lib.ptr(dx), _lib.ptr(dxp), _lib.ptr(dxo),
-                _lib.ptr(bws), _lib.stream_ptr(), cb, None,
-                None if comm_stream is None else C.c_void_p(comm_stream.cuda_stream)))
+            _lib.check((L.hig_denoiser_bwd_bf16_hooked if bf16 else L.hig_denoiser_bwd_hooked)(
+                *args, cb, None, None if comm_stream is None else C.c_void_p(comm_stream.cuda_stream)))
             if errors:
                 raise errors[0]
         self._pool.give("bwd", bws, dev)

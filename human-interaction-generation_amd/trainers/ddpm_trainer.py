@@ -25,21 +25,16 @@ import torch.optim as optim
 from torch.nn.utils import clip_grad_norm_
 
 from .. import _lib
-from ..models.caption_bank import expand_rows, segment_sum_rows
 from ..models.gaussian_diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType,
                                          create_named_schedule_sampler, get_named_beta_schedule)
 from ..models.guidance import ClassifierFreeGuidedModel, check_scale
 from ..models.spaced_diffusion import SpacedDiffusion, space_timesteps, space_timesteps_logsnr
 from ..parallel import (FlatGradAllReduce, OverlappedGradAllReduce, ShardedSampler, broadcast_flat, broadcast_parameters,
                         exchange_active)
+from .text_source import Banked, ClassIds, ClipFeatures, Embeddings, _core
 
 GRAD_CLIP = 0.5                    # ddpm_trainer.py:61
 ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8   # torch.optim.Adam defaults, ddpm_trainer.py:222
-
-
-def _core(encoder):
-    """The bare model under a DDP-style wrapper (the reference reaches for `.module` first, :116-119)."""
-    return getattr(encoder, "module", encoder)
 
 
 def _dist_world():
@@ -684,71 +679,44 @@ class DDPMTrainer(object):
             st["lr"].fill_(lr)
             st["lr_host"] = lr
 
-    def _text_forward(self, clip_out, eot):
-        """Text head of the fused step: CLIP features (B, N, W) + EOT indices -> xf_proj, xf_out and the saved
-        activations `_text_backward` needs."""
+    def _text_source(self, xf_proj, xf_out, clip_out, eot, caption_batch, class_ids):
+        """The text arguments of a fused step as ONE source (trainers/text_source.py).  `caption_batch=` is exclusive with
+        `clip_out=` / `eot=` and needs the model's bank; `class_ids=` (a cap_id model with class_head="hip") is exclusive with
+        every other text argument.  Embeddings passed beside a bank request or beside CLIP features are ignored."""
         core = _core(self.encoder)
-        xf_proj, xf_out, tsaved = core._launch_text_head(clip_out, eot, training=True)
-        return xf_proj, xf_out, (clip_out, eot, xf_out, tsaved)
+        if caption_batch is not None:
+            if clip_out is not None or eot is not None:
+                raise ValueError("caption_batch= and clip_out= / eot= are exclusive: the bank supplies the CLIP features")
+            if getattr(core, "caption_bank", None) is None:
+                raise RuntimeError("caption_batch= needs the model's caption bank (opt.caption_bank / enable_caption_bank)")
+        if class_ids is not None:
+            if any(a is not None for a in (xf_proj, xf_out, clip_out, eot, caption_batch)):
+                raise ValueError("class_ids= is exclusive with xf_proj= / xf_out=, clip_out= / eot= and caption_batch=: the class head "
+                                 "supplies the text embeddings")
+            core._class_head_args(class_ids)      # (refuses a model without the HIP class head, and bad ids)
+            return ClassIds(class_ids)
+        if caption_batch is not None:
+            return Banked(caption_batch)
+        if clip_out is not None:
+            return ClipFeatures(clip_out, eot)
+        return Embeddings(xf_proj, xf_out)
 
-    def _text_backward(self, tstate, dxf_proj, dxf_out):
-        clip_out, eot, xf_out, tsaved = tstate[:4]
-        if len(tstate) == 5:     # the head ran on the distinct captions: their rows' gradients, added in row order
-            cb = tstate[4]
-            dxf_proj = segment_sum_rows(dxf_proj.contiguous(), cb.order, cb.seg, cb.U_pad)
-            dxf_out = segment_sum_rows(dxf_out.contiguous(), cb.order, cb.seg, cb.U_pad)
-        _core(self.encoder)._launch_text_head_backward(clip_out, eot, xf_out, tsaved, dxf_out, dxf_proj,
-                                                       want_dclip=False, into_flat=True)
-
-    def _caption_batch_check(self, caption_batch, clip_out, eot):
-        """`caption_batch=` of the fused steps sits beside `clip_out=` / `eot=` and is exclusive with them."""
-        if caption_batch is None:
-            return
-        if clip_out is not None or eot is not None:
-            raise ValueError("caption_batch= and clip_out= / eot= are exclusive: the bank supplies the CLIP features")
-        if getattr(_core(self.encoder), "caption_bank", None) is None:
-            raise RuntimeError("caption_batch= needs the model's caption bank (opt.caption_bank / enable_caption_bank)")
-
-    def _class_ids_check(self, class_ids, xf_proj, xf_out, clip_out, eot, caption_batch):
-        """`class_ids=` of the fused steps (a cap_id model with class_head="hip") is exclusive with every other text argument."""
-        if class_ids is None:
-            return
-        if any(a is not None for a in (xf_proj, xf_out, clip_out, eot, caption_batch)):
-            raise ValueError("class_ids= is exclusive with xf_proj= / xf_out=, clip_out= / eot= and caption_batch=: the class head "
-                             "supplies the text embeddings")
-        _core(self.encoder)._class_head_args(class_ids)      # (refuses a model without the HIP class head, and bad ids)
-
-    def _text_forward_banked(self, cb):
-        """Text side of the fused step out of the caption bank: hig_caption_gather stands where the tower stood.  With
-        `text_dedup` the head runs on the U_pad distinct captions and two hig_rows_gather_f32 expand its outputs to the model
-        batch (`_text_backward` sums the upstream gradients back); without it the gather fetches every row."""
-        core = _core(self.encoder)
-        bank = core.caption_bank
-        if not core.text_dedup:
-            return self._text_forward(*bank.gather(cb.slot, cb.rows))
-        xp_u, xo_u, tstate = self._text_forward(*bank.gather(cb.uniq_slot, cb.U_pad))
-        return expand_rows(xp_u, cb.inv, cb.rows), expand_rows(xo_u, cb.inv, cb.rows), tstate + (cb,)
-
-    def _fused_fwd_bwd(self, x_start, t, length, xf_proj, xf_out, noise, clip_out=None, eot=None, exchange=None,
-                       caption_batch=None, class_ids=None):
-        """q_sample -> [text head] -> denoiser forward -> masked MSE -> denoiser backward [-> text head backward]
-        into the flat gradient.  With `clip_out` / `eot`, or with a `caption_batch` of the model's caption bank, the text
-        embeddings are computed here and the text head is trained too (the reference's full update); otherwise xf_proj /
-        xf_out are inputs.  With `class_ids` the class head stands where the text head stands (hig_class_head_fwd before the
-        denoiser, hig_class_head_bwd behind its backward).
+    def _fused_fwd_bwd(self, x_start, t, length, text, noise, exchange=None):
+        """[text head] -> q_sample -> denoiser forward -> masked MSE -> denoiser backward [-> text head backward] into the flat
+        gradient.  `text` (of `_text_source`) supplies xf_proj / xf_out -- inputs, or computed here by the text head or the class
+        head, which are then trained too (the reference's full update) -- and takes their gradients behind the denoiser's backward.
         `exchange` (an OverlappedGradAllReduce that has been begun): the gradient all-reduce of each decoder layer is
         started from inside the backward."""
+        xf_proj, xf_out = text.forward(self)
+        dxp, dxo = self._denoise_loss_backward(x_start, t, length, xf_proj, xf_out, noise, exchange)
+        text.backward(self, dxp, dxo)
+
+    def _denoise_loss_backward(self, x_start, t, length, xf_proj, xf_out, noise, exchange):
+        """The middle of `_fused_fwd_bwd`; returns the gradients of the loss with respect to xf_proj and xf_out."""
         core = _core(self.encoder)
         L = _lib.lib()
         st = self.fused_state()
         B, T, F = x_start.shape
-        tstate = None
-        if caption_batch is not None:
-            xf_proj, xf_out, tstate = self._text_forward_banked(caption_batch)
-        elif clip_out is not None:
-            xf_proj, xf_out, tstate = self._text_forward(clip_out, eot)
-        elif class_ids is not None:
-            xf_proj, xf_out = core._launch_class_head(class_ids)
         if noise is None:
             noise = torch.randn_like(x_start)
         x_t = self.diffusion.q_sample(x_start, t, noise=noise)
@@ -757,24 +725,17 @@ class DDPMTrainer(object):
         _lib.check(L.hig_masked_mse(_lib.ptr(pred), _lib.ptr(noise), _lib.ptr(length), B, T, F,
                                     _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(st["mse_scratch"]),
                                     _lib.stream_ptr()))
-        if exchange is None:
-            _, dxp, dxo = core._launch_backward(x_t, t, length, xf_out, saved, dpred, want_dx=False)
-        else:
-            _, dxp, dxo = core._launch_backward(x_t, t, length, xf_out, saved, dpred, want_dx=False,
-                                                layer_hook=exchange.layer_done, comm_stream=exchange.stream)
-        if tstate is not None:
-            self._text_backward(tstate, dxp, dxo)
-        elif class_ids is not None:
-            core._launch_class_head_backward(class_ids, dxo, dxp)
+        hook = {} if exchange is None else dict(layer_hook=exchange.layer_done, comm_stream=exchange.stream)
+        _, dxp, dxo = core._launch_backward(x_t, t, length, xf_out, saved, dpred, want_dx=False, **hook)
+        return dxp, dxo
 
-    def _fwd_bwd_overlapped_exchange(self, x_start, t, length, xf_proj, xf_out, noise, clip_out, eot, caption_batch=None,
-                                     class_ids=None):
+    def _fwd_bwd_overlapped_exchange(self, x_start, t, length, text, noise):
         """_fused_fwd_bwd with the gradient exchange of layer l issued while layers l-1 ... 0 are still in backward
         (RCCL on a side stream); returns the world size.  Capturable: see OverlappedGradAllReduce."""
         st = self.fused_state()
         core = _core(self.encoder)
         fp = core.flat_params()
-        n = self._fused_numel(clip_out is not None or caption_batch is not None or class_ids is not None)
+        n = self._fused_numel(text.trains_head)
         ex = st["overlap"]
         want = getattr(self.opt, "grad_wire", "f32")
         if want != ex.wire:      # (the option is read when the fused state is built; changing it later used to be ignored silently)
@@ -784,9 +745,7 @@ class DDPMTrainer(object):
         per_layer, tail = fp.layer_buckets(core.num_layers, nsty, core.latent_dim, core.time_embed_dim)
         assert per_layer[-1][1][1] - per_layer[0][1][0] == core.num_layers * nsty * 2 * core.latent_dim * core.time_embed_dim
         ex.begin(fp.grad, per_layer, tail)
-        self._fused_fwd_bwd(x_start, t, length, xf_proj, xf_out, noise, clip_out=clip_out, eot=eot, exchange=ex,
-                            **({} if caption_batch is None else dict(caption_batch=caption_batch)),
-                            **({} if class_ids is None else dict(class_ids=class_ids)))
+        self._fused_fwd_bwd(x_start, t, length, text, noise, exchange=ex)
         return ex.finish([(fp.core_numel, n)] if n > fp.core_numel else ())
 
     def _fused_numel(self, with_text):
@@ -819,18 +778,13 @@ class DDPMTrainer(object):
         # (fp32 master weights, no separate cast pass over the 81 M parameters)
         shadow = fp.shadow16_buffer() if bf16 else None
         ema = self.ema_state()
+        args = (_lib.ptr(fp.flat), _lib.ptr(fp.grad), _lib.ptr(st["m"]), _lib.ptr(st["v"]), n, st["lr_host"], _lib.ptr(st["lr"]),
+                ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, GRAD_CLIP, 1.0 / world, _lib.ptr(st["scratch"]), _lib.ptr(st["gnorm"]),
+                _lib.ptr(st["step"]), _lib.ptr(shadow), fp.core_numel if bf16 else 0)
         if ema is None:
-            _lib.check(L.hig_clip_adam_shadow(_lib.ptr(fp.flat), _lib.ptr(fp.grad), _lib.ptr(st["m"]), _lib.ptr(st["v"]),
-                                              n, st["lr_host"], _lib.ptr(st["lr"]), ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS,
-                                              GRAD_CLIP, 1.0 / world, _lib.ptr(st["scratch"]), _lib.ptr(st["gnorm"]),
-                                              _lib.ptr(st["step"]), _lib.ptr(shadow), fp.core_numel if bf16 else 0,
-                                              _lib.stream_ptr()))
+            _lib.check(L.hig_clip_adam_shadow(*args, _lib.stream_ptr()))
         else:   # the same pass also blends the new parameters into the EMA; its update number comes from the device counter
-            _lib.check(L.hig_clip_adam_ema(_lib.ptr(fp.flat), _lib.ptr(fp.grad), _lib.ptr(st["m"]), _lib.ptr(st["v"]),
-                                           n, st["lr_host"], _lib.ptr(st["lr"]), ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS,
-                                           GRAD_CLIP, 1.0 / world, _lib.ptr(st["scratch"]), _lib.ptr(st["gnorm"]),
-                                           _lib.ptr(st["step"]), _lib.ptr(shadow), fp.core_numel if bf16 else 0,
-                                           _lib.ptr(ema["flat"]), ema["decay"], int(ema["warmup"]), ema["origin"],
+            _lib.check(L.hig_clip_adam_ema(*args, _lib.ptr(ema["flat"]), ema["decay"], int(ema["warmup"]), ema["origin"],
                                            _lib.stream_ptr()))
         st["covered"] = max(st["covered"], n)
         core.params_changed()
@@ -852,24 +806,19 @@ class DDPMTrainer(object):
         With more than one rank the replicas must start identical: call `sync_replicas()` once (train() does).
         No host synchronisation: the loss stays on the device (`fused_state()['loss']`)."""
         self._ema_refuse_in_scope("train_step_fused")
-        self._caption_batch_check(caption_batch, clip_out, eot)
-        self._class_ids_check(class_ids, xf_proj, xf_out, clip_out, eot, caption_batch)
+        text = self._text_source(xf_proj, xf_out, clip_out, eot, caption_batch, class_ids)
         st = self.fused_state()
         ema = self.ema_state()            # (created here, from the weights before the step, when opt.ema_decay asks for one)
-        with_text = clip_out is not None or caption_batch is not None or class_ids is not None
-        n = self._fused_numel(with_text)
+        n = self._fused_numel(text.trains_head)
         self._set_lr(lr)
         core = _core(self.encoder)
         fp = core.flat_params()
-        banked = {} if caption_batch is None else dict(caption_batch=caption_batch)
-        if class_ids is not None:
-            banked = dict(class_ids=class_ids)
         if OverlappedGradAllReduce.active() and getattr(self.opt, "overlap_allreduce", True):
-            world = self._fwd_bwd_overlapped_exchange(x_start, t, length, xf_proj, xf_out, noise, clip_out, eot, **banked)
+            world = self._fwd_bwd_overlapped_exchange(x_start, t, length, text, noise)
         else:
-            self._fused_fwd_bwd(x_start, t, length, xf_proj, xf_out, noise, clip_out=clip_out, eot=eot, **banked)
+            self._fused_fwd_bwd(x_start, t, length, text, noise)
             world = st["allreduce"](fp.grad[:n])                                  # one all-reduce after the backward
-        self._fused_clip_adam(world, with_text)
+        self._fused_clip_adam(world, text.trains_head)
         if ema is not None:
             ema["num_updates"] += 1
         return st["loss"]
@@ -925,8 +874,7 @@ class DDPMTrainer(object):
         With `class_ids` the ids are the static text input, copied like `t`; the graph key carries their shape and that the
         class head is inside."""
         self._ema_refuse_in_scope("train_step_captured")
-        self._caption_batch_check(caption_batch, clip_out, eot)
-        self._class_ids_check(class_ids, xf_proj, xf_out, clip_out, eot, caption_batch)
+        text = self._text_source(xf_proj, xf_out, clip_out, eot, caption_batch, class_ids)
         st = self.fused_state()
         ema = self.ema_state()            # (created eagerly, never inside a capture)
         world = _dist_world()
@@ -934,42 +882,25 @@ class DDPMTrainer(object):
         # (gloo stages through the host: its collectives cannot be captured -- that backend always takes the split form)
         in_graph = (split and getattr(self.opt, "capture_exchange", True) and getattr(self.opt, "overlap_allreduce", True)
                     and dist.get_backend() == "nccl")
-        banked = caption_batch is not None
-        classed = class_ids is not None
-        with_text = clip_out is not None or banked or classed
-        # (banked: the one packed index buffer stands in both text slots; it is copied once per replay.  classed: so do the ids)
-        text_in = ((caption_batch.dev, caption_batch.dev) if banked else (class_ids, class_ids) if classed else
-                   (clip_out, eot) if with_text else (xf_proj, xf_out))
-        n = self._fused_numel(with_text)
+        n = self._fused_numel(text.trains_head)
         self._set_lr(lr)
-        bank = getattr(_core(self.encoder), "caption_bank", None)
-        key = (tuple(x_start.shape), tuple(text_in[0].shape), tuple(text_in[1].shape), with_text, noise is None,
-               world, split, in_graph, st["ptrs"],
-               None if ema is None else (ema["decay"], ema["warmup"], ema["origin"], ema["flat"].data_ptr()))
-        if banked:
-            key += ((caption_batch.rows, caption_batch.U_pad, bool(_core(self.encoder).text_dedup), bank.feat.data_ptr(),
-                     bank.eot.data_ptr()),)
-        if classed:
-            key += (("class_head", tuple(class_ids.shape)),)
+        statics = text.statics()
+        key = ((tuple(x_start.shape), text.kind) + tuple(tuple(a.shape) for a in statics)
+               + (noise is None, world, split, in_graph, st["ptrs"],
+                  None if ema is None else (ema["decay"], ema["warmup"], ema["origin"], ema["flat"].data_ptr()))
+               + text.key(_core(self.encoder)))
         cap = st["graphs"].get(key)
         if cap is None:
             static = {"x0": x_start.clone(), "t": t.clone(), "length": length.clone(),
-                      "ta": text_in[0].clone(), "tb": None if banked or classed else text_in[1].clone(),
-                      "noise": None if noise is None else noise.clone()}
-            sargs = ((static["x0"], static["t"], static["length"], None, None, static["noise"], None, None)
-                     if banked or classed else
-                     (static["x0"], static["t"], static["length"], None, None, static["noise"], static["ta"], static["tb"])
-                     if with_text else
-                     (static["x0"], static["t"], static["length"], static["ta"], static["tb"], static["noise"], None, None))
-            skw = (dict(caption_batch=caption_batch.on_buffer(static["ta"])) if banked else
-                   dict(class_ids=static["ta"]) if classed else {})
+                      "text": tuple(a.clone() for a in statics), "noise": None if noise is None else noise.clone()}
+            static_text = text.on(static["text"])
 
             def part_a():
-                self._fused_fwd_bwd(*sargs[:6], clip_out=sargs[6], eot=sargs[7], **skw)
+                self._fused_fwd_bwd(static["x0"], static["t"], static["length"], static_text, static["noise"])
 
             def whole_step_with_exchange():
-                w = self._fwd_bwd_overlapped_exchange(*sargs, **skw)
-                self._fused_clip_adam(w, with_text)
+                w = self._fwd_bwd_overlapped_exchange(static["x0"], static["t"], static["length"], static_text, static["noise"])
+                self._fused_clip_adam(w, text.trains_head)
 
             # warm-up (allocations, workspace pools, RCCL's communicator) on a side stream, as torch.cuda.graph requires;
             # it runs a real step, so restore parameters / moments / step counter afterwards
@@ -984,7 +915,7 @@ class DDPMTrainer(object):
                     whole_step_with_exchange()
                 else:
                     part_a()
-                    self._fused_clip_adam(1, with_text)
+                    self._fused_clip_adam(1, text.trains_head)
             torch.cuda.current_stream().wait_stream(s)
 
             def restore():
@@ -1029,13 +960,13 @@ class DDPMTrainer(object):
             if not split:
                 with torch.cuda.graph(ga, capture_error_mode="thread_local"):
                     part_a()
-                    self._fused_clip_adam(1, with_text)
+                    self._fused_clip_adam(1, text.trains_head)
             elif not in_graph:
                 with torch.cuda.graph(ga, capture_error_mode="thread_local"):
                     part_a()
                 gb = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode="thread_local"):
-                    self._fused_clip_adam(world, with_text)
+                    self._fused_clip_adam(world, text.trains_head)
             cap = st["graphs"][key] = (static, ga, gb)
             st["captured_form"] = "one graph" if not split else ("one graph, exchange inside" if in_graph
                                                                  else "graph A | all-reduce | graph B")
@@ -1045,9 +976,8 @@ class DDPMTrainer(object):
             static["x0"].copy_(x_start)
             static["t"].copy_(t)
             static["length"].copy_(length)
-            static["ta"].copy_(text_in[0])
-            if static["tb"] is not None:
-                static["tb"].copy_(text_in[1])
+            for buf, a in zip(static["text"], statics):
+                buf.copy_(a)
             if noise is not None:
                 static["noise"].copy_(noise)
         ga.replay()

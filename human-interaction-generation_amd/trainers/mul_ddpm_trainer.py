@@ -94,29 +94,18 @@ class DDPMMulTrainer(DDPMTrainer):
         return OrderedDict({'loss_mot_rec': self.loss_mot_rec.item()})
 
     # ---- MI355X fused step (inherits train_step_fused / train_step_captured) ---------------------
-    def _fused_fwd_bwd(self, x_start, t, length, xf_proj, xf_out, noise, clip_out=None, eot=None, exchange=None,
-                       caption_batch=None, class_ids=None):
-        """Two-person version of the fused forward/backward: x_start = cat([motion1, motion2]) (2B, T, F),
+    def _denoise_loss_backward(self, x_start, t, length, xf_proj, xf_out, noise, exchange):
+        """Two-person middle of the fused forward/backward: x_start = cat([motion1, motion2]) (2B, T, F),
         t (B,) or (2B,), length (B,) per pair.  PIT mode (no label file): the noised motions run twice,
         rows [m1|c1, m1|c2, m2|c2, m2|c1] -- xf_proj / xf_out must hold the 4B text embeddings in that
         order (2B rows [c1 | c2] with a label file) -- and `hig_pair_mse` picks the cheaper caption
-        assignment per pair (mul_ddpm_trainer.py:96-131, 223-247).  `caption_batch`: the captions of those rows as a
-        CaptionBatch of the model's caption bank (half of the 4B PIT rows are duplicates by construction).  `class_ids`: the
-        class ids of those rows (int32 on the device) for a cap_id model with class_head="hip": the class head runs before the
-        denoiser and its backward writes the head's gradients into the flat gradient behind the denoiser's."""
+        assignment per pair (mul_ddpm_trainer.py:96-131, 223-247).  Whatever the step's text source is (CLIP features, a
+        CaptionBatch -- half of the 4B PIT rows are duplicates by construction -- or class ids), it covers those rows."""
         if not self.multi:
-            return super()._fused_fwd_bwd(x_start, t, length, xf_proj, xf_out, noise, clip_out=clip_out, eot=eot,
-                                          exchange=exchange, caption_batch=caption_batch, class_ids=class_ids)
+            return super()._denoise_loss_backward(x_start, t, length, xf_proj, xf_out, noise, exchange)
         core = _core(self.encoder)
         L = _lib.lib()
         st = self.fused_state()
-        tstate = None
-        if caption_batch is not None:
-            xf_proj, xf_out, tstate = self._text_forward_banked(caption_batch)
-        elif clip_out is not None:     # CLIP features of the model batch's captions (4B rows in PIT mode)
-            xf_proj, xf_out, tstate = self._text_forward(clip_out, eot)
-        elif class_ids is not None:
-            xf_proj, xf_out = core._launch_class_head(class_ids)
         B2, T, F = x_start.shape
         B = B2 // 2
         t2 = t if t.numel() == B2 else torch.cat([t, t])
@@ -140,10 +129,7 @@ class DDPMMulTrainer(DDPMTrainer):
                                   _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(scr), _lib.stream_ptr()))
         hook = {} if exchange is None else dict(layer_hook=exchange.layer_done, comm_stream=exchange.stream)
         _, dxp, dxo = core._launch_backward(x_t, t2, len_rows, xf_out, saved, dpred, want_dx=False, **hook)
-        if tstate is not None:
-            self._text_backward(tstate, dxp, dxo)
-        elif class_ids is not None:
-            core._launch_class_head_backward(class_ids, dxo, dxp)
+        return dxp, dxo
 
     def train_fused_batch(self, batch_data, captured=False, noise=None):
         """forward(batch) + update() of the reference (mul_ddpm_trainer.py:90-161, 251-258) as one fused step."""

@@ -210,4 +210,4 @@ def test_the_option_left_unset_constructs_no_bank():
     assert m.caption_bank is None
     with pytest.raises(ValueError, match="exclusive"):
         on_tr = hig_amd.DDPMTrainer(types.SimpleNamespace(device="cpu", diffusion_steps=1000, is_train=False), on)
-        on_tr._caption_batch_check(on.caption_bank.batch(["a"]), torch.zeros(1), None)
+        on_tr._text_source(None, None, torch.zeros(1), None, on.caption_bank.batch(["a"]), None)

@@ -168,15 +168,18 @@ def test_trainer_refuses_class_ids_beside_other_text_arguments_and_without_the_o
     opt = types.SimpleNamespace(device="cpu", diffusion_steps=1000, is_train=False, multi=True, label_path=None, cap_id=True)
     tr = hig_amd.DDPMMulTrainer(opt, tiny(cap_id=True, class_head="hip"))
     ids = torch.zeros(4, dtype=torch.int32)
-    tr._class_ids_check(None, None, None, None, None, None)
+    tr._text_source(None, None, None, None, None, None)
     for kw in (dict(xf_proj=torch.zeros(1)), dict(xf_out=torch.zeros(1)), dict(clip_out=torch.zeros(1)), dict(eot=torch.zeros(1)),
                dict(caption_batch=object())):
         args = dict(xf_proj=None, xf_out=None, clip_out=None, eot=None, caption_batch=None)
         args.update(kw)
+        # (the steps refuse a caption_batch= without a bank before they look at the ids: a stand-in bank lets the ids' refusal show)
+        tr.encoder._caption_bank = object() if "caption_batch" in kw else None
         with pytest.raises(ValueError, match="exclusive"):
-            tr._class_ids_check(ids, **args)
+            tr._text_source(class_ids=ids, **args)
+    tr.encoder._caption_bank = None
     with pytest.raises(ValueError, match="int32"):      # (a host tensor: the ids must already be on the device)
-        tr._class_ids_check(ids, None, None, None, None, None)
+        tr._text_source(None, None, None, None, None, ids)
     off = hig_amd.DDPMMulTrainer(opt, tiny(cap_id=True))
     with pytest.raises(RuntimeError, match="class_head='hip'"):
-        off._class_ids_check(ids, None, None, None, None, None)
+        off._text_source(None, None, None, None, None, ids)

@@ -35,7 +35,8 @@ def test_two_rank_fused_training_step_matches_mean_gradient_step(dp_workers):
         total = torch.zeros(n, device="cuda")
         for r in range(world):
             sh = lambda t: dp_worker.shard(t, r, world)
-            tr._fused_fwd_bwd(sh(x0[s]), sh(gi["t"]), sh(gi["length"]), sh(gi["xf_proj"]), sh(gi["xf_out"]), sh(noise[s]))
+            text = tr._text_source(sh(gi["xf_proj"]), sh(gi["xf_out"]), None, None, None, None)
+            tr._fused_fwd_bwd(sh(x0[s]), sh(gi["t"]), sh(gi["length"]), text, sh(noise[s]))
             assert abs(tr.fused_state()["loss"].item() - got[r]["losses"][s]) <= 1e-6 * abs(got[r]["losses"][s])
             total += fp.grad[:n]
         fp.grad[:n].copy_(total)
