@@ -589,19 +589,21 @@ int stream_blocks(int64_t total) {
 // ---- two-person losses (DDPMMulTrainer.backward_G, mul_ddpm_trainer.py:223-247) ------------------------
 // Row r of the model batch, token t: l[r][t] = mean_f (pred - target)^2 over all F features, except the
 // init-pose token t == 0 which is scored on its first 4 features only.  rowloss[r] = sum_{t < len[r]} l[r][t].
-__global__ __launch_bounds__(256) void pair_rowloss_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                           const int64_t* __restrict__ length, int R, int T, int F,
-                                                           float* __restrict__ rowloss) {
+// The ONE statement of the row loss, by a block of 256 threads: row `r` of pred against row `rq` of target (the same row for
+// hig_pair_mse; hig_pair_vote scores its 4 P rows against a target of 2 P).  Wave w adds the tokens w, w + 4, .., then
+// (w0 + w1) + (w2 + w3).
+__device__ __forceinline__ void pair_rowloss_block(const float* __restrict__ pred, const float* __restrict__ target,
+                                                   const int64_t* __restrict__ length, int r, int64_t rq, int T, int F,
+                                                   float* __restrict__ rowloss) {
   __shared__ float wsum[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = blockIdx.x;
   int64_t l = length ? length[r] : T;
   l = l < 0 ? 0 : (l > T ? T : l);
   float acc = 0.f;
   for (int t = wave; t < (int)l; t += 4) {
     const int nf = t == 0 ? 4 : F;
     const float* p = pred + ((int64_t)r * T + t) * F;
-    const float* q = target + ((int64_t)r * T + t) * F;
+    const float* q = target + (rq * T + t) * F;
     float sq = 0.f;
     for (int f = lane; f < nf; f += 64) {
       const float dlt = p[f] - q[f];
@@ -613,6 +615,37 @@ __global__ __launch_bounds__(256) void pair_rowloss_kernel(const float* __restri
   if (lane == 0) wsum[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) rowloss[r] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+__global__ __launch_bounds__(256) void pair_rowloss_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                           const int64_t* __restrict__ length, int R, int T, int F,
+                                                           float* __restrict__ rowloss) {
+  pair_rowloss_block(pred, target, length, blockIdx.x, blockIdx.x, T, F, rowloss);
+}
+// hig_pair_vote, pass 1: rows [m1|c1, m1|c2, m2|c2, m2|c1] of pred (R = 4 P) against the noise in its 2 P layout [m1 | m2]:
+// group g = r / P of pred reads person g / 2 of target2.
+__global__ __launch_bounds__(256) void pair_vote_rowloss_kernel(const float* __restrict__ pred, const float* __restrict__ target2,
+                                                                const int64_t* __restrict__ length, int R, int T, int F,
+                                                                float* __restrict__ rowloss) {
+  const int P = R / 4, r = blockIdx.x;
+  pair_rowloss_block(pred, target2, length, r, (int64_t)((r / P) / 2) * P + r % P, T, F, rowloss);
+}
+// hig_pair_vote, pass 2: one thread per pair, any number of pairs.  l0 = L[p] + L[2P + p], l1 = L[P + p] + L[3P + p]; the pair
+// votes for a = (l1 < l0) (a tie: 0, as pair_select_kernel) unless a sum is NaN.  Each pair's two counters and its `first` are
+// touched by its own thread only: no atomics.
+__global__ __launch_bounds__(256) void pair_vote_select_kernel(const float* __restrict__ rowloss, int P, int32_t* __restrict__ votes,
+                                                               int32_t* __restrict__ first, float* __restrict__ assign_loss) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  const float l0 = rowloss[p] + rowloss[2 * P + p], l1 = rowloss[P + p] + rowloss[3 * P + p];
+  if (assign_loss) {
+    assign_loss[p] = l0;
+    assign_loss[P + p] = l1;
+  }
+  if (l0 != l0 || l1 != l1) return;
+  const int a = l1 < l0 ? 1 : 0;
+  const int32_t v0 = votes[2 * p], v1 = votes[2 * p + 1];
+  if (first && v0 == 0 && v1 == 0) first[p] = a;
+  votes[2 * p + a] = (a ? v1 : v0) + 1;
 }
 // One block.  pit == 0: loss = sum_r rowloss / sum(mask), every row active.  pit == 1 (rows = [m1|c1, m1|c2,
 // m2|c2, m2|c1], R = 4P): S0[p] = L[p] + L[2P + p], S1[p] = L[P + p] + L[3P + p]; loss = sum_p min(S0, S1) /
@@ -862,6 +895,70 @@ extern "C" int hig_pair_mse(const float* pred, const float* target, const int64_
                        rowscale, R, T, F, dpred);
     HIG_CHECK_LAUNCH();
   }
+  return HIG_OK;
+}
+
+// ---- the labelling pass (DDPMMulTrainer.label_votes): q_sample into the forward_twice layout, and the per-pair vote ----
+namespace {
+// x0 / noise / t: 2 P rows [m1 | m2]; xt4: 4 P rows [m1, m1, m2, m2] -- the stacked layout of cfg_cond with group = P: the
+// element i of person g = i / gp goes to i + g gp and gp further.  One read, two stores; the value is impose_elem's, which has
+// q_sample_kernel's bits (see there).  n4 float4 groups, then the scalar rest; a group that straddles a sample boundary looks
+// its coefficients up per element.
+__global__ __launch_bounds__(256) void q_sample_pit_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
+                                                           const int64_t* __restrict__ t, const float* __restrict__ tab, int nsteps,
+                                                           int64_t per_sample, int64_t total, int64_t n4, int64_t gp,
+                                                           float* __restrict__ xt4) {
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = tid; i < n4; i += stride) {
+    const int64_t o = 4 * i, oc = cfg_cond<true>(o, gp);
+    const float4 xv = reinterpret_cast<const float4*>(x0)[i], zv = reinterpret_cast<const float4*>(noise)[i];
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, zs[4] = {zv.x, zv.y, zv.z, zv.w};
+    float v[4];
+    const int64_t s0 = o / per_sample, s3 = (o + 3) / per_sample;
+    if (s0 == s3) {
+      const impose_coef c = impose_coef_at(tab, nsteps, t[s0]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = impose_elem(c, xs[k], zs[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = impose_elem(impose_coef_at(tab, nsteps, t[(o + k) / per_sample]), xs[k], zs[k]);
+    }
+    const float4 ov = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(xt4 + oc) = ov;
+    *reinterpret_cast<float4*>(xt4 + oc + gp) = ov;
+  }
+  for (int64_t i = 4 * n4 + tid; i < total; i += stride) {
+    const int64_t oc = cfg_cond<true>(i, gp);
+    const float v = impose_elem(impose_coef_at(tab, nsteps, t[i / per_sample]), x0[i], noise[i]);
+    xt4[oc] = v;
+    xt4[oc + gp] = v;
+  }
+}
+}  // namespace
+
+extern "C" int hig_q_sample_pit(const float* x0, const float* noise, const int64_t* t, const float* tab, int32_t nsteps,
+                                int32_t pairs, int64_t per_sample, float* xt4, hig_stream_t s) {
+  HIG_REQUIRE(x0 && noise && t && tab && xt4 && nsteps > 0 && pairs > 0 && pairs <= INT32_MAX / 2 && per_sample > 0,
+              "hig_q_sample_pit: bad arguments");
+  stream_plan p;
+  HIG_TRY(plan_stream("hig_q_sample_pit", ptr_bits(x0, noise, xt4), true, 2 * pairs, pairs, per_sample, &p));
+  hipLaunchKernelGGL(q_sample_pit_kernel, dim3(p.grid), dim3(256), 0, hig_stream(s), x0, noise, t, tab, nsteps, per_sample, p.total,
+                     p.n4, p.gp, xt4);
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_pair_vote(const float* pred, const float* target2, const int64_t* length, int32_t R, int32_t T, int32_t F,
+                             int32_t* votes, int32_t* first, float* assign_loss, float* scratch, hig_stream_t s) {
+  HIG_REQUIRE(pred && target2 && votes && scratch && R > 0 && R % 4 == 0 && T > 0 && F >= 4,
+              "hig_pair_vote: pred, target2, votes, scratch non-null, R > 0 a multiple of 4, T > 0 and F >= 4 required (R %d T %d F %d)",
+              (int)R, (int)T, (int)F);
+  const int P = R / 4;
+  hipLaunchKernelGGL(pair_vote_rowloss_kernel, dim3(R), dim3(256), 0, hig_stream(s), pred, target2, length, R, T, F, scratch);
+  HIG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pair_vote_select_kernel, dim3((P + 255) / 256), dim3(256), 0, hig_stream(s), scratch, P, votes, first,
+                     assign_loss);
+  HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
 

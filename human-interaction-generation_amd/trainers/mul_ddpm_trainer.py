@@ -16,6 +16,92 @@ from .. import _lib
 from .ddpm_trainer import DDPMTrainer, _core
 
 
+LABEL_STEPS = range(830, 940, 30)      # the four timesteps of the reference's labelling pass (mul_ddpm_trainer.py:411, 430)
+
+
+def label_pass_option(opt):
+    """opt.label_pass: "torch" (the default: `eval_data` loops over `label_batch`, as the reference) or "hip" (one
+    `label_votes` call per batch).  Anything else is a ValueError."""
+    v = getattr(opt, "label_pass", "torch")
+    if v not in ("torch", "hip"):
+        raise ValueError("opt.label_pass must be 'torch' or 'hip' (got %r)" % (v,))
+    return v
+
+
+def _most_common(first_value, counts):
+    """`Counter(values).most_common()[0][0]` from the counts and the value inserted first: most_common sorts by count with a
+    stable sort over insertion order, so among equal counts the value inserted first wins."""
+    best = first_value
+    for value, n in counts.items():
+        if n > counts[best]:
+            best = value
+    return best
+
+
+def learned_indices_from_votes(batches, max_class_num=42):
+    """Model mode of `eval_data` (mul_ddpm_trainer.py:405-425 of the reference) from per-batch votes.
+
+    batches: [(ids1, ids2, votes (steps, pairs, 2), first (pairs,)), ...] in the loader's order, as `label_votes` returns them
+    (assignment 0 keeps the caption order 'a_b', assignment 1 swaps it to 'b_a').  Returns `learned_indices`.
+
+    The reference merges one list per pair key 'a_b', appending timestep-outer, batch-inner, draw, pair, and takes
+    `Counter(list).most_common()[0][0]`: the larger count, and on a tie the value that entered the list first.  The counts do
+    not depend on the order, so they are the sums of `votes` over steps, batches and the pairs that carry the key.  The value
+    that entered first is reconstructed: the reference's first visit of a key is at the FIRST timestep (every batch is visited
+    under it before the second timestep starts), in the first batch of the loader that holds the key, at its first draw, at the
+    lowest pair index with that key -- and that draw's decision is `first[p]` of that batch, because `label_votes` casts the
+    first vote of every pair at steps[0], draw 0.  Being batch-outer here therefore changes nothing the winner depends on."""
+    counts, first_value = {}, {}
+    for ids1, ids2, votes, first in batches:
+        votes = np.asarray(votes).reshape(-1, len(ids1), 2).sum(axis=0)
+        for p, (a, b) in enumerate(zip(ids1, ids2)):
+            a, b = int(a), int(b)
+            key, values = '%d_%d' % (a, b), ('%d_%d' % (a, b), '%d_%d' % (b, a))
+            c = counts.setdefault(key, {})
+            if key not in first_value:
+                first_value[key] = values[int(first[p])]
+                c[first_value[key]] = 0
+            for a_, n in zip(values, votes[p]):
+                if int(n):
+                    c[a_] = c.get(a_, 0) + int(n)
+    learned_indices = []
+    for i in range(max_class_num + 1):
+        if '%d_%d' % (i - 1, i) in counts:
+            continue
+        key = '%d_%d' % (i, i + 1)
+        if key in counts:
+            num1, num2 = _most_common(first_value[key], counts[key]).split('_')
+            learned_indices += [int(num1), int(num2)]
+        else:
+            learned_indices.append(i)
+    return learned_indices
+
+
+def label_active_indices(learned_indices, ids1, ids2):
+    """Which caption of each pair the learned order puts first (label_batch: argmin over the two learned positions)."""
+    return np.argmin([[learned_indices[int(c)] for c in ids1], [learned_indices[int(c)] for c in ids2]], axis=0)
+
+
+def file_labels_from_votes(file_ids, active_indices, votes, first):
+    """Label mode of `eval_data` (mul_ddpm_trainer.py:427-440 of the reference) for one batch: {file id: 0 or 1} in the order
+    the reference's dictionary has.  A draw's output for pair p is 0 where its assignment equals active_indices[p], else 1;
+    a file's label is `Counter(outputs).most_common()[0][0]` over steps x draws: the larger count, a tie going to the output
+    of the first draw -- first[p] against active_indices[p], at the lowest pair index that carries the file id."""
+    votes = np.asarray(votes).reshape(-1, len(file_ids), 2).sum(axis=0)
+    counts, first_value = OrderedDict(), {}
+    for p, fid in enumerate(file_ids):
+        act = int(active_indices[p])
+        c = counts.setdefault(fid, {})
+        if fid not in first_value:
+            first_value[fid] = 0 if int(first[p]) == act else 1
+            c[first_value[fid]] = 0
+        for a, n in enumerate(votes[p]):
+            if int(n):
+                out = 0 if a == act else 1
+                c[out] = c.get(out, 0) + int(n)
+    return OrderedDict((fid, _most_common(first_value[fid], c)) for fid, c in counts.items())
+
+
 class DDPMMulTrainer(DDPMTrainer):
 
     def __init__(self, args, encoder):
@@ -23,6 +109,7 @@ class DDPMMulTrainer(DDPMTrainer):
         self.multi = args.multi
         self.with_label = args.label_path is not None
         self.cap_id = args.cap_id
+        label_pass_option(args)        # (a bad opt.label_pass is refused here, not at the first eval_data)
 
     # ---- one training forward ---------------------------------------------------------------
     def _pair_inputs(self, batch_data):
@@ -237,6 +324,126 @@ class DDPMMulTrainer(DDPMTrainer):
             active_list.setdefault(pair_key, []).append('%d_%d' % ((a, b) if res == 0 else (b, a)))
         return active_list
 
+    def label_votes(self, batch_data, steps=LABEL_STEPS, draws=41, noise=None, captured=True, losses=False):
+        """The votes `label_batch` would cast for one batch over `steps` x `draws` noise draws, with everything that does not
+        change between draws done once: -> dict(votes=int array (len(steps), pairs, 2), first=int array (pairs,)); votes[s, p, a]
+        counts the draws at steps[s] in which pair p scored caption assignment a cheaper (0: [c1, c2] as given, 1: swapped; a
+        tie is 0), first[p] is the assignment of the very first draw (steps[0], draw 0) -- what Counter's tie rule needs.
+
+        Once per batch: `_pair_inputs`, the ids (train_fused_batch's conversion) or captions, the text embeddings of the 4 pairs
+        rows [c1, c2, c2, c1] (hig_class_head_fwd for a class_head="hip" model, get_class_embedding otherwise, encode_text for a
+        caption model), the text context (the inference forward's cache), the lengths and the `t` buffers.  One step,
+            z.normal_() -> hig_q_sample_pit -> _launch_forward(training=False) at 4 pairs rows -> hig_pair_vote,
+        is warmed up on a side stream, captured (captured=True) and replayed `draws` times per timestep; between timesteps the
+        host refills the `t` buffers the graph reads.  The host reads `votes` once per timestep (a step's votes are the
+        difference of consecutive readings) and checks that every pair gained exactly `draws`: a pair whose loss is NaN casts
+        no vote, and the call raises naming it.  captured=False runs the same launches eagerly.
+
+        noise (len(steps), draws, 2 pairs, T, F) replaces the draws (copied into z before each step).  losses=True adds
+        `assign_loss` (len(steps), draws, 2, pairs), the two assignment sums of every draw, kept on the device until the end."""
+        if not self.multi:
+            raise RuntimeError("label_votes: the labelling pass belongs to the two-person trainer (opt.multi)")
+        steps, draws = [int(t) for t in steps], int(draws)
+        if not steps or draws <= 0:
+            raise ValueError("label_votes: at least one timestep and one draw")
+        core, L, P_ = _core(self.encoder), _lib.lib(), _lib.ptr
+        K = self.diffusion.num_timesteps
+        if any(not 0 <= t < K for t in steps):
+            raise ValueError("label_votes: steps must lie in [0, %d)" % K)
+        assert not self.diffusion.rescale_timesteps
+        with torch.no_grad():
+            caption, c1, c2, x_start, cur_len, B, T = self._pair_inputs(batch_data)
+            caption = caption + c2 + c1                     # (c1, c2, c2, c1) against (m1, m1, m2, m2)
+            x_start = x_start.contiguous()
+            dev, F = x_start.device, x_start.shape[2]
+            if self.cap_id:
+                ids = torch.cat([torch.as_tensor(c).reshape(-1).cpu() for c in caption]).to(torch.int32).to(dev)
+                if core._has_hip_class_head():
+                    xf_proj, xf_out = core._launch_class_head(ids)
+                else:
+                    xf_proj, xf_out = core.get_class_embedding([ids.long()])
+            else:
+                xf_proj, xf_out = core.encode_text(caption, dev)
+            xf_proj, xf_out = xf_proj.detach().float().contiguous(), xf_out.detach().float().contiguous()
+            len4 = torch.cat([cur_len] * 4).contiguous()
+            t2 = torch.full((2 * B,), steps[0], dtype=torch.int64, device=dev)
+            t4 = torch.full((4 * B,), steps[0], dtype=torch.int64, device=dev)
+            z = torch.zeros_like(x_start)
+            xt4 = torch.empty(4 * B, T, F, device=dev, dtype=torch.float32)
+            votes = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+            first = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            assign = torch.zeros(2, B, dtype=torch.float32, device=dev)
+            scratch = torch.zeros(4 * B, dtype=torch.float32, device=dev)
+            tab = self.diffusion.device_table(dev)
+            if noise is not None:
+                noise = torch.as_tensor(noise)
+                if tuple(noise.shape) != (len(steps), draws, 2 * B, T, F):
+                    raise ValueError("label_votes: noise must have shape %s, got %s"
+                                     % ((len(steps), draws, 2 * B, T, F), tuple(noise.shape)))
+                noise = noise.to(dev).float()
+                z.copy_(noise[0, 0])
+            kept = torch.zeros(len(steps), draws, 2, B, dtype=torch.float32, device=dev) if losses else None
+
+            def step():
+                if noise is None:
+                    z.normal_()
+                _lib.check(L.hig_q_sample_pit(P_(x_start), P_(z), P_(t2), P_(tab), K, B, T * F, P_(xt4), _lib.stream_ptr()))
+                pred, _ = core._launch_forward(xt4, t4, len4, xf_proj, xf_out, training=False)
+                _lib.check(L.hig_pair_vote(P_(pred), P_(z), P_(len4), 4 * B, T, F, P_(votes), P_(first), P_(assign), P_(scratch),
+                                           _lib.stream_ptr()))
+
+            run = step
+            if captured:    # warm-up on a side stream (allocations, text context), then undo its vote
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    step()
+                torch.cuda.current_stream().wait_stream(s)
+                votes.zero_()
+                first.fill_(-1)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    step()
+                run = graph.replay
+            out = np.zeros((len(steps), B, 2), dtype=np.int64)
+            seen = np.zeros((B, 2), dtype=np.int64)
+            for si, t in enumerate(steps):
+                t2.fill_(t)
+                t4.fill_(t)
+                for d in range(draws):
+                    if noise is not None:
+                        z.copy_(noise[si, d])
+                    run()
+                    if losses:
+                        kept[si, d].copy_(assign)
+                now = votes.cpu().numpy().astype(np.int64)
+                out[si] = now - seen
+                seen = now
+                short = np.nonzero(out[si].sum(axis=1) != draws)[0]
+                if short.size:
+                    raise RuntimeError("label_votes: pair %d of the batch cast %d of %d votes at t = %d: its loss is NaN "
+                                       "(pairs %s)" % (short[0], out[si, short[0]].sum(), draws, t, short.tolist()))
+            result = dict(votes=out, first=first.cpu().numpy().astype(np.int64))
+            if losses:
+                result["assign_loss"] = kept.cpu().numpy()
+        return result
+
+    def _eval_data_votes(self, loader, learned_indices, max_class_num, save_dir):
+        """`eval_data` under opt.label_pass == "hip": one `label_votes` call per batch, then the reference's bookkeeping as
+        pure host functions of the votes."""
+        if learned_indices is None:
+            batches = []
+            for batch_data in loader:
+                r = self.label_votes(batch_data, LABEL_STEPS, draws=5)
+                batches.append((batch_data[0][0].numpy(), batch_data[1][0].numpy(), r["votes"], r["first"]))
+            return learned_indices_from_votes(batches, max_class_num)
+        for batch_data in loader:
+            r = self.label_votes(batch_data, LABEL_STEPS, draws=41)
+            active = label_active_indices(learned_indices, batch_data[0][0].numpy(), batch_data[1][0].numpy())
+            for key, label in file_labels_from_votes(list(batch_data[5]), active, r["votes"], r["first"]).items():
+                with open(os.path.join(save_dir, key + '.txt'), 'w') as f:
+                    f.write(str(label))
+
     def eval_data(self, train_dataset, rank, world_size, learned_indices, max_class_num=42, save_dir=None):
         from ..parallel import ShardedSampler
         self.to(self.device)
@@ -244,6 +451,8 @@ class DDPMMulTrainer(DDPMTrainer):
         loader = torch.utils.data.DataLoader(train_dataset, batch_size=self.opt.batch_size, sampler=sampler,
                                              drop_last=False, num_workers=getattr(self.opt, "num_workers", 4))
         self.eval_mode()
+        if label_pass_option(self.opt) == "hip":
+            return self._eval_data_votes(loader, learned_indices, max_class_num, save_dir)
         steps = range(830, 940, 30)
         with torch.no_grad():
             if learned_indices is None:

@@ -1393,6 +1393,34 @@ int hig_masked_mse(const float* pred, const float* target, const int64_t* length
  * scratch: 2 R floats (the row losses, then d loss / d rowloss). */
 int hig_pair_mse(const float* pred, const float* target, const int64_t* length, int32_t R, int32_t T,
                  int32_t F, int32_t pit, float* loss, float* dpred, float* scratch, hig_stream_t s);
+/* The labelling pass of the two-person recipe (DDPMMulTrainer.label_votes; mul_ddpm_trainer.py:313-440 of the reference): one
+ * draw is q_sample into the forward_twice layout, the denoiser at 4 x pairs rows, and the per-pair vote.
+ *
+ * hig_q_sample_pit: x0, noise (2 pairs rows [m1 | m2] of per_sample floats) and t (2 pairs entries; a value outside
+ * [0, nsteps) reads the nearest row of `tab`, the HIG_TAB_ROWS table) -> xt4, 4 pairs rows [m1, m1, m2, m2].  Both destinations
+ * of an element receive the bits hig_q_sample gives it: one read, two stores, no copy kernel.  float4 path when x0, noise and
+ * xt4 are 16-byte aligned and pairs * per_sample % 4 == 0, scalar otherwise: the same bits.  Nothing may overlap xt4.
+ * Refused with HIG_EINVAL, nothing written: a NULL pointer, nsteps, pairs or per_sample <= 0.
+ *
+ * hig_pair_vote: pred rows are [m1|c1, m1|c2, m2|c2, m2|c1], R = 4 pairs; target2 is the noise in its 2 pairs layout: row r of
+ * pred is scored against row (g / 2) pairs + p of target2, g = r / pairs, p = r % pairs.  The row loss is hig_pair_mse's (the
+ * same device code): per-token MSE, token 0 on its first 4 features, masked by clamp(length[r], 0, T) with length (R entries)
+ * NULL for T everywhere; off the mask and on features >= 4 of token 0 neither pred nor target2 is read.  Then per pair, in fp32:
+ *   l0 = row[p] + row[2 pairs + p];  l1 = row[pairs + p] + row[3 pairs + p];  a = (l1 < l0) ? 1 : 0      (a tie takes 0)
+ *   votes[p][a] += 1;  first[p] = a where votes[p] was (0, 0) on entry;  assign_loss[0][p] = l0, assign_loss[1][p] = l1
+ * votes (pairs x 2 int32) accumulates over launches: the caller zeroes it.  first (pairs int32) and assign_loss (2 x pairs) may
+ * be NULL.  A pair with a NaN l0 or l1 casts no vote and leaves votes and first untouched (the host sees it by the count);
+ * assign_loss still receives both sums.  scratch: R floats (the row losses).  Two launches (R workgroups, then one thread per
+ * pair over ceil(pairs / 256) workgroups); no atomics, no allocation, no synchronisation: capturable.
+ * Refused with HIG_EINVAL before any HIP call, nothing written: a NULL pred / target2 / votes / scratch, R <= 0, R % 4 != 0,
+ * T <= 0, F < 4.
+ * Bound: row[r] as hig_pair_mse's rowloss (tests/boundary_bounds.py, b_row); each sum adds one rounding:
+ * |l - fp64| <= b_row[r] + b_row[r'] + u (row[r] + row[r']), u = 2^-24 (tests/label_bounds.py). */
+int hig_q_sample_pit(const float* x0, const float* noise, const int64_t* t, const float* tab, int32_t nsteps, int32_t pairs,
+                     int64_t per_sample, float* xt4, hig_stream_t s);
+int hig_pair_vote(const float* pred, const float* target2, const int64_t* length /* nullable */, int32_t R, int32_t T, int32_t F,
+                  int32_t* votes /* (R / 4, 2), accumulated */, int32_t* first /* nullable, (R / 4) */,
+                  float* assign_loss /* nullable, (2, R / 4) */, float* scratch /* R floats */, hig_stream_t s);
 int hig_sumsq_partial(const float* g, int64_t n, float inv_world, float* scratch, hig_stream_t s);
 int hig_clip_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
                   float b2, float eps, float max_norm, float inv_world, const float* scratch,
