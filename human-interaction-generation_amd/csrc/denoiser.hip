@@ -1356,6 +1356,119 @@ extern "C" int hig_shutdown(void) {
   return rc;
 }
 
+namespace {
+
+// The debug tap of the fp32 backward (hig_denoiser_bwd_debug_tap, include/hig.h): off[slot] is an absolute byte offset for the slots
+// written once and an offset from the layer's base for the per-layer ones; -1 where the model has no such buffer.
+struct Tap32Layout {
+  int64_t off[HIG_TAP32_NSLOTS], bytes[HIG_TAP32_NSLOTS];
+};
+inline int64_t wt32_floats(const Dims& D) {   // what one layer's W -> W^T launch writes of BwdLayout::wT
+  return (int64_t)(D.two == 1 ? 11 : 7) * D.d * D.d + (int64_t)2 * D.d * D.ff + (int64_t)2 * D.d * D.Lt;
+}
+Tap32Layout tap32_layout(const Dims& D) {
+  Tap32Layout t;
+  const int64_t row = D.M * D.d * 4, ctx = (int64_t)D.B * D.H * D.hd * D.hd * 4, be = (int64_t)D.B * D.E * 4;
+  const int64_t delta = (int64_t)D.B * D.H * D.T * 4, slice = (int64_t)D.B * 2 * D.d * 4;
+  const bool inter = D.two == 1;
+  for (int s = 0; s < HIG_TAP32_NSLOTS; ++s) t.bytes[s] = row;      // (most slots are one (M, d) matrix)
+  t.bytes[HIG_TAP32_DOUTM] = D.two ? D.M * D.F * 4 : -1;
+  t.bytes[HIG_TAP32_TOK0] = D.two ? (int64_t)D.B * D.d * 4 : -1;
+  t.bytes[HIG_TAP32_POSTMP] = D.two ? (int64_t)D.T * D.d * 4 : -1;
+  t.bytes[HIG_TAP32_DTMP_EMB] = t.bytes[HIG_TAP32_DTMP_TE] = be;
+  t.bytes[HIG_TAP32_WT] = wt32_floats(D) * 4;
+  t.bytes[HIG_TAP32_FFN_DSS] = t.bytes[HIG_TAP32_CA_DSS] = t.bytes[HIG_TAP32_SA_DSS] = t.bytes[HIG_TAP32_INT_DSS] = slice;
+  t.bytes[HIG_TAP32_FFN_DZ] = D.M * D.ff * 4;
+  t.bytes[HIG_TAP32_SA_DQKV] = t.bytes[HIG_TAP32_INT_DQKV] = 3 * row;
+  t.bytes[HIG_TAP32_CA_DA] = t.bytes[HIG_TAP32_SA_DA] = t.bytes[HIG_TAP32_INT_DA] = D.full ? -1 : ctx;
+  t.bytes[HIG_TAP32_CA_DELTA] = t.bytes[HIG_TAP32_SA_DELTA] = D.full ? delta : -1;
+  for (int s = HIG_TAP32_INT_T1; s <= HIG_TAP32_INT_DH; ++s)
+    if (!inter) t.bytes[s] = -1;
+  t.bytes[HIG_TAP32_CA_DKV] = D.Mt * 2 * D.d * 4;
+  t.bytes[HIG_TAP32_CA_DXFN] = t.bytes[HIG_TAP32_CA_DXF_OUT] = D.Mt * D.Lt * 4;
+  int64_t o = 0;
+  auto take = [&](int s) { t.off[s] = t.bytes[s] < 0 ? -1 : o; if (t.bytes[s] > 0) o += (t.bytes[s] + 255) & ~(int64_t)255; };
+  for (int s = 0; s < HIG_TAP32_LAYER0; ++s) take(s);
+  t.off[HIG_TAP32_LAYER0] = o;
+  o = 0;
+  for (int s = HIG_TAP32_LSTRIDE + 1; s < HIG_TAP32_TOTAL; ++s) take(s);
+  t.off[HIG_TAP32_LSTRIDE] = o;
+  t.off[HIG_TAP32_TOTAL] = t.off[HIG_TAP32_LAYER0] + o * D.L;
+  return t;
+}
+char* g_bwd32_tap = nullptr;          // diagnostic only (hig_denoiser_bwd_debug_tap): NULL in every real run
+int64_t g_bwd32_tap_bytes = 0;
+
+int require_f32_train(const Dims& D, const char* who) {
+  if (D.bf16) return hig_set_error(HIG_EINVAL, "%s: dims->storage must be HIG_STORE_F32", who);
+  return HIG_OK;
+}
+
+}  // namespace
+
+// ---- test hooks (include/hig.h): the three fp32 training layouts and the tap's, by named slot; the tap buffer ----
+extern "C" int hig_f32_train_layout(const hig_dims* dims, int32_t which, int64_t* out, int32_t n_out) {
+  Dims D;
+  HIG_TRY(check_dims(dims, D));
+  HIG_TRY(require_f32_train(D, "hig_f32_train_layout"));
+  int64_t v[HIG_FW32_NSLOTS > HIG_TAP32_NSLOTS ? HIG_FW32_NSLOTS : HIG_TAP32_NSLOTS];
+  static_assert(HIG_BW32_NSLOTS <= HIG_FW32_NSLOTS && HIG_TX32_NSLOTS <= HIG_FW32_NSLOTS, "v holds every table");
+  int n = 0;
+  const bool inter = D.two == 1, lin = !D.full;
+  auto by = [](bool have, int64_t floats) -> int64_t { return have ? floats * 4 : -1; };
+  if (which == HIG_LAYOUT32_FWD) {
+    const FwdLayout w = fwd_layout(D, 1);
+    n = HIG_FW32_NSLOTS;
+    v[HIG_FW32_TE] = w.te * 4; v[HIG_FW32_TE_H] = w.te_h * 4; v[HIG_FW32_EMB] = w.emb * 4; v[HIG_FW32_SS] = w.ss * 4; v[HIG_FW32_H0] = w.h0 * 4;
+    v[HIG_FW32_LENP] = by(D.two != 0, w.lenp); v[HIG_FW32_LAYER0] = w.layer0 * 4; v[HIG_FW32_LSTRIDE] = w.lstride * 4;
+    v[HIG_FW32_ST1] = w.st1 * 4; v[HIG_FW32_XN1] = w.xn1 * 4; v[HIG_FW32_QKV] = w.qkv * 4; v[HIG_FW32_A1] = by(lin, w.A1);
+    v[HIG_FW32_KST1] = by(lin, w.kst1); v[HIG_FW32_LSE1] = by(!lin, w.lse1); v[HIG_FW32_Y1] = w.y1 * 4; v[HIG_FW32_ST2] = w.st2 * 4;
+    v[HIG_FW32_A1S] = w.a1 * 4; v[HIG_FW32_H1] = w.h1 * 4; v[HIG_FW32_ST3] = w.st3 * 4; v[HIG_FW32_XN2] = w.xn2 * 4; v[HIG_FW32_QC] = w.qc * 4;
+    v[HIG_FW32_LSE2] = by(!lin, w.lse2); v[HIG_FW32_Y2] = w.y2 * 4; v[HIG_FW32_ST4] = w.st4 * 4; v[HIG_FW32_A2S] = w.a2 * 4; v[HIG_FW32_H2] = w.h2 * 4;
+    v[HIG_FW32_Z1] = w.z1 * 4; v[HIG_FW32_F1] = w.f1 * 4; v[HIG_FW32_Y3] = w.y3 * 4; v[HIG_FW32_ST5] = w.st5 * 4; v[HIG_FW32_A3S] = w.a3 * 4;
+    v[HIG_FW32_H3] = w.h3 * 4;
+    v[HIG_FW32_ST6] = by(inter, w.st6); v[HIG_FW32_XN3] = by(inter, w.xn3); v[HIG_FW32_IQKV] = by(inter, w.iqkv); v[HIG_FW32_AI] = by(inter, w.Ai);
+    v[HIG_FW32_KSTI] = by(inter, w.ksti); v[HIG_FW32_Y4] = by(inter, w.y4); v[HIG_FW32_ST7] = by(inter, w.st7); v[HIG_FW32_A4S] = by(inter, w.a4);
+    v[HIG_FW32_H2B] = by(inter, w.h2b);
+    v[HIG_FW32_TOTAL] = w.total * 4;
+  } else if (which == HIG_LAYOUT32_TEXT) {
+    const TextLayout t = text_layout(D, 1);
+    n = HIG_TX32_NSLOTS;
+    v[HIG_TX32_STT] = t.stt * 4; v[HIG_TX32_LAYER0] = t.layer0 * 4; v[HIG_TX32_LSTRIDE] = t.lstride * 4; v[HIG_TX32_AC] = by(lin, t.Ac);
+    v[HIG_TX32_KSTC] = by(lin, t.kstc); v[HIG_TX32_KV] = t.kv * 4; v[HIG_TX32_KV_STRIDE] = t.kv_stride * 4; v[HIG_TX32_TOTAL] = t.total * 4;
+  } else if (which == HIG_LAYOUT32_BWD) {
+    const BwdLayout w = bwd_layout(D);
+    n = HIG_BW32_NSLOTS;
+    v[HIG_BW32_DHA] = w.dhA * 4; v[HIG_BW32_DHB] = w.dhB * 4; v[HIG_BW32_T1] = w.t1 * 4; v[HIG_BW32_T2] = w.t2 * 4; v[HIG_BW32_TFF] = w.tff * 4;
+    v[HIG_BW32_DQKV] = w.dqkv * 4; v[HIG_BW32_DA] = by(lin, w.dA); v[HIG_BW32_DELTA] = by(!lin, w.delta); v[HIG_BW32_DKV] = w.dkv * 4;
+    v[HIG_BW32_DXFN] = w.dxfn * 4; v[HIG_BW32_DSS] = w.dss * 4; v[HIG_BW32_DEMB] = w.demb * 4; v[HIG_BW32_DTMP] = w.dtmp * 4;
+    v[HIG_BW32_DTE_H] = w.dte_h * 4; v[HIG_BW32_SLABS] = w.slabs * 4; v[HIG_BW32_COLPART] = w.colpart * 4; v[HIG_BW32_COLPART_W] = w.colpart_w * 4;
+    v[HIG_BW32_LNPART] = w.lnpart * 4; v[HIG_BW32_WT] = w.wT * 4; v[HIG_BW32_TA] = w.tA * 4; v[HIG_BW32_TB] = w.tB * 4; v[HIG_BW32_ATTN] = w.attn * 4;
+    v[HIG_BW32_TOK0] = by(D.two != 0, w.tok0); v[HIG_BW32_DOUTM] = by(D.two != 0, w.doutm); v[HIG_BW32_POSTMP] = by(D.two != 0, w.postmp);
+    v[HIG_BW32_GTAIL] = w.gtail * 4; v[HIG_BW32_TOTAL] = w.total * 4;
+  } else if (which == HIG_LAYOUT32_TAP) {
+    const Tap32Layout t = tap32_layout(D);
+    n = HIG_TAP32_NSLOTS;
+    for (int s = 0; s < HIG_TAP32_NSLOTS; ++s) v[s] = t.off[s];
+  } else {
+    return hig_set_error(HIG_EINVAL, "hig_f32_train_layout: no layout table %d", which);
+  }
+  for (int s = 0; out && s < n && s < n_out; ++s) out[s] = v[s];
+  return n;
+}
+extern "C" int hig_denoiser_bwd_debug_tap(void* buf, int64_t bytes) {
+  if (buf && bytes <= 0) return hig_set_error(HIG_EINVAL, "hig_denoiser_bwd_debug_tap: a tap buffer of %lld bytes", (long long)bytes);
+  g_bwd32_tap = static_cast<char*>(buf);
+  g_bwd32_tap_bytes = buf ? bytes : 0;
+  return HIG_OK;
+}
+extern "C" int64_t hig_denoiser_bwd_tap_bytes(const hig_dims* dims) {
+  Dims D;
+  HIG_TRY(check_dims(dims, D));
+  HIG_TRY(require_f32_train(D, "hig_denoiser_bwd_tap_bytes"));
+  return tap32_layout(D).off[HIG_TAP32_TOTAL];
+}
+
 extern "C" int hig_denoiser_bwd(const hig_dims* dims, const void* const* params, const float* x,
                                 const int64_t* t, const int64_t* length, const float* xf_out,
                                 const void* textctx, const void* workspace, const float* dout,
@@ -1391,6 +1504,30 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
   float* colp = b + bw.colpart;
   float* lnp = b + bw.lnpart;
   float* dss = b + bw.dss;
+  // the debug tap (include/hig.h): NULL in every real run
+  char* const tapb = g_bwd32_tap;
+  Tap32Layout tp{};
+  if (tapb) {
+    tp = tap32_layout(D);
+    if (g_bwd32_tap_bytes < tp.off[HIG_TAP32_TOTAL])
+      return hig_set_error(HIG_EINVAL, "hig_denoiser_bwd: the tap buffer has %lld bytes, these dims need %lld", (long long)g_bwd32_tap_bytes,
+                           (long long)tp.off[HIG_TAP32_TOTAL]);
+    if (is_capturing(st)) return hig_set_error(HIG_EINVAL, "hig_denoiser_bwd: a debug tap is set and the stream is capturing");
+  }
+  // copies `src` into the tap's slot (of layer l, or l < 0: a slot written once) behind the launch that wrote it, on that launch's stream
+  auto tap_dst = [&](int slot, int l) -> float* {
+    return reinterpret_cast<float*>(tapb + tp.off[slot] + (l < 0 ? 0 : tp.off[HIG_TAP32_LAYER0] + tp.off[HIG_TAP32_LSTRIDE] * l));
+  };
+  auto tap = [&](int slot, int l, const void* src) -> int { return hig_copy_async(tap_dst(slot, l), src, tp.bytes[slot], st); };
+  // the (B, 2 d) slice of d(scale, shift) that stylization block s wrote (rows ss_ld apart)
+  auto tap_dss = [&](int slot, int l, int s) -> int {
+    const int64_t n = (int64_t)D.B * 2 * D.d;
+    hipLaunchKernelGGL(copy2d_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dss + (int64_t)s * 2 * D.d, (int)ss_ld,
+                       tap_dst(slot, l), 2 * D.d, D.B, 2 * D.d);
+    HIG_CHECK_LAUNCH();
+    return HIG_OK;
+  };
+#define HIG_TAP32(slot, l, src) do { if (tapb) HIG_TRY(tap(slot, l, src)); } while (0)
 
   // data-gradient GEMMs (caller's stream) may split their tail; the weight gradients on the side stream never do
   // (reduce-slow X operand or split-R: excluded by the rule in gemm.hip), so one scratch serves the whole backward
@@ -1452,14 +1589,21 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
   // Backward of one stylization block: h_out = h_in + Lin_out(silu(LN(y)*(1+scale)+shift)).
   // `dh` is d(h_out); produces dy into `dy_out`, parameter grads, and dss columns of block s.
   auto sty_bwd = [&](int l, int s, const float* dh, const float* y, const float* a_saved, const float* stats,
-                     int norm_w, int norm_b, int out_w, int out_b, int64_t wt_off, float* dy_out) -> int {
+                     int norm_w, int norm_b, int out_w, int out_b, int64_t wt_off, float* dy_out, int tap_t1) -> int {
     const float* ssl = ws + w.ss + (int64_t)s * 2 * d;
     HIG_TRY(wgrad_act(dh, d, a_saved, d, GL(grads, l, out_w), M, nullptr, nullptr, nullptr, GL(grads, l, out_b)));
     HIG_TRY(hig_gemm_launch(G(dh, d, 0, wT + wt_off, d, 0, b + bw.t1, d, M, d, d).prec(D.prec).g, 1, nullptr, st));
-    return hig_ln_bwd(b + bw.t1, d, y, d, stats, PL(params, l, norm_w), PL(params, l, norm_b), ssl, ss_ld, d, 1,
-                      nullptr, 0, dy_out, d, M, d, D.T, GL(grads, l, norm_w), GL(grads, l, norm_b),
-                      dss + (int64_t)s * 2 * d, ss_ld, lnp, stream);
+    HIG_TAP32(tap_t1, l, b + bw.t1);
+    HIG_TRY(hig_ln_bwd(b + bw.t1, d, y, d, stats, PL(params, l, norm_w), PL(params, l, norm_b), ssl, ss_ld, d, 1,
+                       nullptr, 0, dy_out, d, M, d, D.T, GL(grads, l, norm_w), GL(grads, l, norm_b),
+                       dss + (int64_t)s * 2 * d, ss_ld, lnp, stream));
+    HIG_TAP32(tap_t1 + 1, l, dy_out);          // (T1, DY, DSS are consecutive slots of each block)
+    if (tapb) HIG_TRY(tap_dss(tap_t1 + 2, l, s));
+    return HIG_OK;
   };
+  static_assert(HIG_TAP32_FFN_DY == HIG_TAP32_FFN_T1 + 1 && HIG_TAP32_FFN_DSS == HIG_TAP32_FFN_T1 + 2 && HIG_TAP32_INT_DY == HIG_TAP32_INT_T1 + 1 &&
+                HIG_TAP32_INT_DSS == HIG_TAP32_INT_T1 + 2 && HIG_TAP32_CA_DY == HIG_TAP32_CA_T1 + 1 && HIG_TAP32_CA_DSS == HIG_TAP32_CA_T1 + 2 &&
+                HIG_TAP32_SA_DY == HIG_TAP32_SA_T1 + 1 && HIG_TAP32_SA_DSS == HIG_TAP32_SA_T1 + 2, "tap slots T1, DY, DSS of a stylization block");
 
   // ---- output projection ---------------------------------------------------------------
   const float* hL = ws + w.layer0 + w.lstride * (D.L - 1) + w.h3;
@@ -1473,6 +1617,7 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
     hipLaunchKernelGGL(tok0_kernel, dim3((D.B * F + 255) / 256), dim3(256), 0, st, dm, (int64_t)D.T * F, D.B, F,
                        (float*)nullptr, 1);
     HIG_CHECK_LAUNCH();
+    HIG_TAP32(HIG_TAP32_DOUTM, -1, dm);
     dout_m = dm;
     HIG_TRY(colsum(dout, (int64_t)D.T * F, D.B, F, GP(grads, HIG_P_OUT2_B)));
     HIG_TRY(wgrad(G(dout, (int64_t)D.T * F, 1, hL, (int64_t)D.T * d, 1, GP(grads, HIG_P_OUT2_W), d, F, d, D.B)));
@@ -1483,6 +1628,7 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
   if (D.two)  // the out-GEMM left exact zeros in the init-pose rows of dh; fill them from out2
     HIG_TRY(hig_gemm_launch(G(dout, (int64_t)D.T * F, 0, P(params, HIG_P_OUT2_W), d, 1, dh, (int64_t)D.T * d, D.B, d, F).g,
                             1, nullptr, st));
+  HIG_TAP32(HIG_TAP32_DHL, -1, dh);
 
   for (int l = D.L - 1; l >= 0; --l) {
     const float* lb = ws + w.layer0 + w.lstride * l;
@@ -1508,26 +1654,29 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
         add(HIG_L_INT_QKV_W, 3 * d, d, o_iqkv);
       }
       HIG_TRY(hig_transpose_batch(n, srcs, dsts, rws, cls, stream));
+      HIG_TAP32(HIG_TAP32_WT, l, wT);
     }
     const float* hffn = D.two == 1 ? lb + w.h2b : lb + w.h2;
     // ---- FFN --------------------------------------------------------------------------
     HIG_TRY(sty_bwd(l, D.nsty * l + D.nsty - 1, dh, lb + w.y3, lb + w.a3, lb + w.st5, HIG_L_FFN_STY_NORM_W, HIG_L_FFN_STY_NORM_B,
-                    HIG_L_FFN_STY_OUT_W, HIG_L_FFN_STY_OUT_B, o_sty3, b + bw.t2));
+                    HIG_L_FFN_STY_OUT_W, HIG_L_FFN_STY_OUT_B, o_sty3, b + bw.t2, HIG_TAP32_FFN_T1));
     const float* dy3 = b + bw.t2;
     HIG_TRY(wgrad_act(dy3, d, lb + w.f1, ff, GL(grads, l, HIG_L_FFN_W2), M, nullptr, nullptr, nullptr,
                       GL(grads, l, HIG_L_FFN_B2)));
     HIG_TRY(hig_gemm_launch(G(dy3, d, 0, wT + o_w2t, d, 0, b + bw.tff, ff, M, ff, d).prec(D.prec)
                                 .epi(HIG_EPI_DGELU).aux(const_cast<float*>(lb + w.z1), ff).g, 1, nullptr, st));
+    HIG_TAP32(HIG_TAP32_FFN_DZ, l, b + bw.tff);
     const float* dz1 = b + bw.tff;
     HIG_TRY(wgrad_act(dz1, ff, hffn, d, GL(grads, l, HIG_L_FFN_W1), M, nullptr, nullptr, nullptr,
                       GL(grads, l, HIG_L_FFN_B1)));
     HIG_TRY(hig_gemm_launch(G(dz1, ff, 0, wT + o_w1t, ff, 0, dh_alt, d, M, d, ff).prec(D.prec)
                                 .epi(HIG_EPI_RES).res(dh, d).g, 1, nullptr, st));
     { float* tmp = dh; dh = dh_alt; dh_alt = tmp; }  // dh = d(h2), or d(h2b) in the interaction model
+    HIG_TAP32(HIG_TAP32_FFN_DH, l, dh);
     if (D.two == 1) {
       // ---- person <-> person cross attention ------------------------------------------------
       HIG_TRY(sty_bwd(l, D.nsty * l + 2, dh, lb + w.y4, lb + w.a4, lb + w.st7, HIG_L_INT_STY_NORM_W, HIG_L_INT_STY_NORM_B,
-                      HIG_L_INT_STY_OUT_W, HIG_L_INT_STY_OUT_B, o_isty, b + bw.t2));
+                      HIG_L_INT_STY_OUT_W, HIG_L_INT_STY_OUT_B, o_isty, b + bw.t2, HIG_TAP32_INT_T1));
       const int64_t* len_partner = reinterpret_cast<const int64_t*>(ws + w.lenp);
       const int64_t halfA = (int64_t)Bp * D.H * D.hd * D.hd, halfM = (int64_t)Bp * D.T;
       float* dqkv = b + bw.dqkv;
@@ -1538,18 +1687,22 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
                                     dqkv + halfM * 3 * d, 3 * d, b + bw.dA, Bp, D.T, D.H, D.hd, b + bw.attn, stream));
       HIG_TRY(hig_linattn_ctx_bwd(b + bw.dA, lb + w.Ai, lb + w.iqkv + d, lb + w.iqkv + 2 * d, 3 * d, lb + w.ksti, len_partner,
                                   dqkv + d, dqkv + 2 * d, 3 * d, D.B, D.T, D.H, D.hd, b + bw.attn, stream));
+      HIG_TAP32(HIG_TAP32_INT_DA, l, b + bw.dA);
+      HIG_TAP32(HIG_TAP32_INT_DQKV, l, dqkv);
       HIG_TRY(wgrad_act(dqkv, 3 * d, lb + w.xn3, d, GL(grads, l, HIG_L_INT_QKV_W), M, nullptr, nullptr, nullptr,
                         GL(grads, l, HIG_L_INT_QKV_B)));
       HIG_TRY(hig_gemm_launch(G(dqkv, 3 * d, 0, wT + o_iqkv, 3 * d, 0, b + bw.t2, d, M, d, 3 * d).prec(D.prec).g, 1,
                               nullptr, st));
+      HIG_TAP32(HIG_TAP32_INT_T2, l, b + bw.t2);
       HIG_TRY(hig_ln_bwd(b + bw.t2, d, lb + w.h2, d, lb + w.st6, PL(params, l, HIG_L_INT_NORM_W),
                          PL(params, l, HIG_L_INT_NORM_B), nullptr, 0, 0, 0, dh, d, dh_alt, d, M, d, D.T,
                          GL(grads, l, HIG_L_INT_NORM_W), GL(grads, l, HIG_L_INT_NORM_B), nullptr, 0, lnp, stream));
       { float* tmp = dh; dh = dh_alt; dh_alt = tmp; }  // dh = d(h2)
+      HIG_TAP32(HIG_TAP32_INT_DH, l, dh);
     }
     // ---- cross attention ---------------------------------------------------------------
     HIG_TRY(sty_bwd(l, D.nsty * l + 1, dh, lb + w.y2, lb + w.a2, lb + w.st4, HIG_L_CA_STY_NORM_W, HIG_L_CA_STY_NORM_B,
-                    HIG_L_CA_STY_OUT_W, HIG_L_CA_STY_OUT_B, o_sty2, b + bw.t2));
+                    HIG_L_CA_STY_OUT_W, HIG_L_CA_STY_OUT_B, o_sty2, b + bw.t2, HIG_TAP32_CA_T1));
     const float* Ac = tc + tl.layer0 + tl.lstride * l + tl.Ac;
     const float* kstc = tc + tl.layer0 + tl.lstride * l + tl.kstc;
     const float* kv = tc + tl.kv + tl.kv_stride * l;
@@ -1561,28 +1714,41 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
       HIG_TRY(hig_linattn_apply_bwd(b + bw.t2, d, lb + w.qc, d, Ac, b + bw.t1, d, b + bw.dA, D.B, D.T, D.H, D.hd,
                                     b + bw.attn, stream));
     const float* dqc = b + bw.t1;
+    HIG_TAP32(HIG_TAP32_CA_DQ, l, dqc);
+    if (D.full) {
+      HIG_TAP32(HIG_TAP32_CA_DELTA, l, b + bw.delta);
+      HIG_TAP32(HIG_TAP32_CA_DKV, l, b + bw.dkv);
+    } else {
+      HIG_TAP32(HIG_TAP32_CA_DA, l, b + bw.dA);
+    }
     HIG_TRY(wgrad_act(dqc, d, lb + w.xn2, d, GL(grads, l, HIG_L_CA_Q_W), M, nullptr, nullptr, nullptr,
                       GL(grads, l, HIG_L_CA_Q_B)));
     HIG_TRY(hig_gemm_launch(G(dqc, d, 0, wT + o_caq, d, 0, b + bw.t2, d, M, d, d).prec(D.prec).g, 1, nullptr, st));
+    HIG_TAP32(HIG_TAP32_CA_T2, l, b + bw.t2);
     HIG_TRY(hig_ln_bwd(b + bw.t2, d, lb + w.h1, d, lb + w.st3, PL(params, l, HIG_L_CA_NORM_W),
                        PL(params, l, HIG_L_CA_NORM_B), nullptr, 0, 0, 0, dh, d, dh_alt, d, M, d, D.T,
                        GL(grads, l, HIG_L_CA_NORM_W), GL(grads, l, HIG_L_CA_NORM_B), nullptr, 0, lnp, stream));
     { float* tmp = dh; dh = dh_alt; dh_alt = tmp; }  // dh = d(h1)
+    HIG_TAP32(HIG_TAP32_CA_DH, l, dh);
     // text side of this layer: d(A_c) -> d(key,value) -> text_norm -> d(xf_out)
-    if (!D.full)
+    if (!D.full) {
       HIG_TRY(hig_linattn_ctx_bwd(b + bw.dA, Ac, kv, kv + d, 2 * d, kstc, nullptr, b + bw.dkv, b + bw.dkv + d, 2 * d, D.B,
                                   D.N, D.H, D.hd, b + bw.attn, stream));
+      HIG_TAP32(HIG_TAP32_CA_DKV, l, b + bw.dkv);
+    }
     HIG_TRY(wgrad_act(b + bw.dkv, 2 * d, xf_out, Lt, GL(grads, l, HIG_L_CA_KV_W), Mt, tc + tl.stt,
                       PL(params, l, HIG_L_CA_TNORM_W), PL(params, l, HIG_L_CA_TNORM_B), GL(grads, l, HIG_L_CA_KV_B)));
     HIG_TRY(hig_gemm_launch(G(b + bw.dkv, 2 * d, 0, wT + o_kv, 2 * d, 0, b + bw.dxfn, Lt, Mt, Lt, 2 * d).prec(D.prec).g,
                             1, nullptr, st));
+    HIG_TAP32(HIG_TAP32_CA_DXFN, l, b + bw.dxfn);
     HIG_TRY(hig_ln_bwd(b + bw.dxfn, Lt, xf_out, Lt, tc + tl.stt, PL(params, l, HIG_L_CA_TNORM_W),
                        PL(params, l, HIG_L_CA_TNORM_B), nullptr, 0, 0, 0, l == D.L - 1 ? nullptr : dxf_out, Lt,
                        dxf_out, Lt, Mt, Lt, D.N, GL(grads, l, HIG_L_CA_TNORM_W), GL(grads, l, HIG_L_CA_TNORM_B),
                        nullptr, 0, lnp, stream));
+    HIG_TAP32(HIG_TAP32_CA_DXF_OUT, l, dxf_out);
     // ---- self attention ----------------------------------------------------------------
     HIG_TRY(sty_bwd(l, D.nsty * l, dh, lb + w.y1, lb + w.a1, lb + w.st2, HIG_L_SA_STY_NORM_W, HIG_L_SA_STY_NORM_B,
-                    HIG_L_SA_STY_OUT_W, HIG_L_SA_STY_OUT_B, o_sty1, b + bw.t2));
+                    HIG_L_SA_STY_OUT_W, HIG_L_SA_STY_OUT_B, o_sty1, b + bw.t2, HIG_TAP32_SA_T1));
     float* dqkv = b + bw.dqkv;
     if (D.full) {
       HIG_TRY(hig_fullattn_bwd(b + bw.t2, d, lb + w.y1, d, lb + w.qkv, 3 * d, lb + w.qkv + d, lb + w.qkv + 2 * d, 3 * d,
@@ -1594,14 +1760,19 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
       HIG_TRY(hig_linattn_ctx_bwd(b + bw.dA, lb + w.A1, lb + w.qkv + d, lb + w.qkv + 2 * d, 3 * d, lb + w.kst1, length, dqkv + d,
                                   dqkv + 2 * d, 3 * d, D.B, D.T, D.H, D.hd, b + bw.attn, stream));
     }
+    HIG_TAP32(HIG_TAP32_SA_DQKV, l, dqkv);
+    if (D.full) HIG_TAP32(HIG_TAP32_SA_DELTA, l, b + bw.delta);
+    else HIG_TAP32(HIG_TAP32_SA_DA, l, b + bw.dA);
     HIG_TRY(wgrad_act(dqkv, 3 * d, lb + w.xn1, d, GL(grads, l, HIG_L_SA_QKV_W), M, nullptr, nullptr, nullptr,
                       GL(grads, l, HIG_L_SA_QKV_B)));
     HIG_TRY(hig_gemm_launch(G(dqkv, 3 * d, 0, wT + o_qkv, 3 * d, 0, b + bw.t2, d, M, d, 3 * d).prec(D.prec).g, 1,
                             nullptr, st));
+    HIG_TAP32(HIG_TAP32_SA_T2, l, b + bw.t2);
     HIG_TRY(hig_ln_bwd(b + bw.t2, d, hin, d, lb + w.st1, PL(params, l, HIG_L_SA_NORM_W), PL(params, l, HIG_L_SA_NORM_B),
                        nullptr, 0, 0, 0, dh, d, dh_alt, d, M, d, D.T, GL(grads, l, HIG_L_SA_NORM_W),
                        GL(grads, l, HIG_L_SA_NORM_B), nullptr, 0, lnp, stream));
     { float* tmp = dh; dh = dh_alt; dh_alt = tmp; }  // dh = d(h_in of this layer)
+    HIG_TAP32(HIG_TAP32_SA_DH, l, dh);
     if (hook) {
       // Every parameter gradient of layer l exists once this layer's stylization `emb_layers.1.weight` rows are
       // done too (they only need this layer's columns of dss): d(W_emb)[l] = dss[:, l]^T . silu(emb), one more request on
@@ -1630,6 +1801,7 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
     hipLaunchKernelGGL(tok0_kernel, dim3((D.B * d + 255) / 256), dim3(256), 0, st, dh, (int64_t)D.T * d, D.B, d,
                        b + bw.tok0, 1);
     HIG_CHECK_LAUNCH();
+    HIG_TAP32(HIG_TAP32_TOK0, -1, b + bw.tok0);
     HIG_TRY(colsum(b + bw.tok0, d, D.B, d, GP(grads, HIG_P_JOINT2_B)));
     HIG_TRY(wgrad(G(b + bw.tok0, d, 1, x, (int64_t)D.T * F, 1, GP(grads, HIG_P_JOINT2_W), 4, d, 4, D.B)));
   }
@@ -1639,6 +1811,7 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
   const int Tpos = D.two ? D.T - 1 : D.T;  // rows of sequence_embedding that were used
   if (D.two) {  // frame t used row t-1
     HIG_TRY(colsum(dh, (int64_t)D.T * d, D.B, D.T * d, b + bw.postmp));
+    HIG_TAP32(HIG_TAP32_POSTMP, -1, b + bw.postmp);
     HIG_TRY(hig_copy_async(GP(grads, HIG_P_SEQ_EMB), b + bw.postmp + d, (size_t)Tpos * d * 4, st));
   } else {
     HIG_TRY(colsum(dh, (int64_t)D.T * d, D.B, D.T * d, GP(grads, HIG_P_SEQ_EMB)));
@@ -1663,6 +1836,7 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
     int s = (int)(ss_ld / 1024);
     if (s > 16) s = 16;
     HIG_TRY(hig_gemm_launch(gd.g, s < 1 ? 1 : s, slabs, st));
+    HIG_TAP32(HIG_TAP32_DTMP_EMB, -1, b + bw.dtmp);
   }
   const int64_t nBE = (int64_t)D.B * E;
   const int eb = (int)((nBE + 255) / 256);
@@ -1672,10 +1846,12 @@ extern "C" int hig_denoiser_bwd_hooked(const hig_dims* dims, const void* const* 
   HIG_TRY(colsum(b + bw.demb, E, D.B, E, GP(grads, HIG_P_TE2_B)));
   HIG_TRY(hig_gemm_launch(G(b + bw.demb, E, 1, ws + w.te_h, E, 1, GP(grads, HIG_P_TE2_W), E, E, E, D.B).silu(1).g, 1, nullptr, st));
   HIG_TRY(hig_gemm_launch(G(b + bw.demb, E, 0, P(params, HIG_P_TE2_W), E, 1, b + bw.dtmp, E, D.B, E, E).g, 1, nullptr, st));
+  HIG_TAP32(HIG_TAP32_DTMP_TE, -1, b + bw.dtmp);
   hipLaunchKernelGGL(mul_dsilu_kernel, dim3(eb), dim3(256), 0, st, b + bw.dtmp, ws + w.te_h, nBE, b + bw.dte_h);
   HIG_CHECK_LAUNCH();
   HIG_TRY(colsum(b + bw.dte_h, E, D.B, E, GP(grads, HIG_P_TE0_B)));
   HIG_TRY(hig_gemm_launch(G(b + bw.dte_h, E, 1, ws + w.te, d, 1, GP(grads, HIG_P_TE0_W), d, E, d, D.B).g, 1, nullptr, st));
+#undef HIG_TAP32
   return HIG_OK;
 }
 

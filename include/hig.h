@@ -14,7 +14,7 @@
  *   - No global mutable state except (a) what hig_shutdown() releases (the per-thread weight-gradient stream below),
  *     (b) the diagnostic stamp pointers of hig_gemm_debug_stamps / hig_gemm_bf16_debug_stamps /
  *     hig_gemm_ws16_debug_stamps / hig_linattn16_debug_stamps (NULL unless a profiling tool sets them; never set during a timed or captured run),
- *     and the tap buffers of hig_denoiser_bwd_bf16_debug_tap and hig_enc_bwd_debug_tap (NULL unless a test sets them; a captured
+ *     and the tap buffers of hig_denoiser_bwd_debug_tap, hig_denoiser_bwd_bf16_debug_tap and hig_enc_bwd_debug_tap (NULL unless a test sets them; a captured
  *     backward refuses them),
  *     and (c) tuning knobs read ONCE from the environment (HIG_*: DESIGN.md section 5 lists them) into function-local
  *     constants on first use -- after that first call they never change, so calls stay re-entrant.
@@ -1051,6 +1051,50 @@ enum {
 int hig_bf16_train_layout(const hig_dims* dims, int32_t which, int64_t* out, int32_t n_out);
 int hig_denoiser_bwd_bf16_debug_tap(void* buf, int64_t bytes);
 int64_t hig_denoiser_bwd_bf16_tap_bytes(const hig_dims* dims);
+/* The same hooks for the fp32-storage training step (hig_text_context / hig_denoiser_fwd with training = 1, hig_denoiser_bwd[_hooked]).
+ * hig_f32_train_layout: byte offsets as above; HIG_LAYOUT32_FWD: `workspace` (fwd_layout, training), _TEXT: `textctx`, _BWD:
+ *   `bwd_workspace`, _TAP: the tap buffer.  HIG_EINVAL for bf16 storage.  Per-layer members of _FWD, _TEXT (AC, KSTC) and _TAP are offsets
+ *   from LAYER0 + l * LSTRIDE; the key / value rows of layer l are at KV + l * KV_STRIDE.  -1: a buffer this model's step never touches --
+ *   the person <-> person block unless two_person == 1, LENP / TOK0 / DOUTM / POSTMP outside the two-person model, LSE* and DELTA unless
+ *   attn_kind is full, A* / KST* / AI / AC / KSTC / DA unless it is linear (the layouts keep the room either way).
+ * hig_denoiser_bwd_debug_tap(buf, bytes): while buf != NULL every hig_denoiser_bwd[_hooked] call of the process copies each transient
+ *   result into its slot directly behind the launch that wrote it, on the stream that wrote it; no buffer moves, no launch is added to,
+ *   taken from or reordered on the step's own sequence.  NULL switches it off.  buf != NULL with bytes <= 0 is HIG_EINVAL; a backward
+ *   whose tap is shorter than hig_denoiser_bwd_tap_bytes(dims) is refused with HIG_EINVAL (the message names both sizes) before any HIP
+ *   call, one on a capturing stream with a tap set before any launch.  Never set during a timed or captured run.
+ * Tap slots.  Once: DHL d(h_L), DOUTM / TOK0 / POSTMP (two-person), DTMP_EMB and DTMP_TE (the two values of `dtmp`).  Per layer: WT (the
+ * layer's transposed weights); per stylization block T1 (d(a)), DY and DSS (its (B, 2 d) slice of d(scale, shift)); FFN_DZ, FFN_DH
+ * (d(h2), or d(h2b)); INT_ / SA_ DQKV, DA, T2 (the gradient in front of the pre-norm), DH; CA_DQ, CA_DA, CA_T2, CA_DH (d(h1)), CA_DKV,
+ * CA_DXFN, CA_DXF_OUT (dxf_out as it stands behind this layer); CA_DELTA / SA_DELTA (full attention). */
+#define HIG_LAYOUT32_FWD 0
+#define HIG_LAYOUT32_TEXT 1
+#define HIG_LAYOUT32_BWD 2
+#define HIG_LAYOUT32_TAP 3
+enum {
+  HIG_FW32_TE = 0, HIG_FW32_TE_H, HIG_FW32_EMB, HIG_FW32_SS, HIG_FW32_H0, HIG_FW32_LENP, HIG_FW32_LAYER0, HIG_FW32_LSTRIDE,
+  HIG_FW32_ST1, HIG_FW32_XN1, HIG_FW32_QKV, HIG_FW32_A1, HIG_FW32_KST1, HIG_FW32_LSE1, HIG_FW32_Y1, HIG_FW32_ST2, HIG_FW32_A1S, HIG_FW32_H1,
+  HIG_FW32_ST3, HIG_FW32_XN2, HIG_FW32_QC, HIG_FW32_LSE2, HIG_FW32_Y2, HIG_FW32_ST4, HIG_FW32_A2S, HIG_FW32_H2, HIG_FW32_Z1, HIG_FW32_F1,
+  HIG_FW32_Y3, HIG_FW32_ST5, HIG_FW32_A3S, HIG_FW32_H3, HIG_FW32_ST6, HIG_FW32_XN3, HIG_FW32_IQKV, HIG_FW32_AI, HIG_FW32_KSTI, HIG_FW32_Y4,
+  HIG_FW32_ST7, HIG_FW32_A4S, HIG_FW32_H2B, HIG_FW32_TOTAL, HIG_FW32_NSLOTS
+};
+enum { HIG_TX32_STT = 0, HIG_TX32_LAYER0, HIG_TX32_LSTRIDE, HIG_TX32_AC, HIG_TX32_KSTC, HIG_TX32_KV, HIG_TX32_KV_STRIDE, HIG_TX32_TOTAL, HIG_TX32_NSLOTS };
+enum {
+  HIG_BW32_DHA = 0, HIG_BW32_DHB, HIG_BW32_T1, HIG_BW32_T2, HIG_BW32_TFF, HIG_BW32_DQKV, HIG_BW32_DA, HIG_BW32_DELTA, HIG_BW32_DKV, HIG_BW32_DXFN,
+  HIG_BW32_DSS, HIG_BW32_DEMB, HIG_BW32_DTMP, HIG_BW32_DTE_H, HIG_BW32_SLABS, HIG_BW32_COLPART, HIG_BW32_COLPART_W, HIG_BW32_LNPART, HIG_BW32_WT,
+  HIG_BW32_TA, HIG_BW32_TB, HIG_BW32_ATTN, HIG_BW32_TOK0, HIG_BW32_DOUTM, HIG_BW32_POSTMP, HIG_BW32_GTAIL, HIG_BW32_TOTAL, HIG_BW32_NSLOTS
+};
+enum {
+  HIG_TAP32_DHL = 0, HIG_TAP32_DOUTM, HIG_TAP32_TOK0, HIG_TAP32_POSTMP, HIG_TAP32_DTMP_EMB, HIG_TAP32_DTMP_TE, HIG_TAP32_LAYER0, HIG_TAP32_LSTRIDE,
+  HIG_TAP32_WT, HIG_TAP32_FFN_T1, HIG_TAP32_FFN_DY, HIG_TAP32_FFN_DSS, HIG_TAP32_FFN_DZ, HIG_TAP32_FFN_DH,
+  HIG_TAP32_INT_T1, HIG_TAP32_INT_DY, HIG_TAP32_INT_DSS, HIG_TAP32_INT_DQKV, HIG_TAP32_INT_DA, HIG_TAP32_INT_T2, HIG_TAP32_INT_DH,
+  HIG_TAP32_CA_T1, HIG_TAP32_CA_DY, HIG_TAP32_CA_DSS, HIG_TAP32_CA_DQ, HIG_TAP32_CA_DA, HIG_TAP32_CA_DELTA, HIG_TAP32_CA_T2, HIG_TAP32_CA_DH,
+  HIG_TAP32_CA_DKV, HIG_TAP32_CA_DXFN, HIG_TAP32_CA_DXF_OUT,
+  HIG_TAP32_SA_T1, HIG_TAP32_SA_DY, HIG_TAP32_SA_DSS, HIG_TAP32_SA_DQKV, HIG_TAP32_SA_DA, HIG_TAP32_SA_DELTA, HIG_TAP32_SA_T2, HIG_TAP32_SA_DH,
+  HIG_TAP32_TOTAL, HIG_TAP32_NSLOTS
+};
+int hig_f32_train_layout(const hig_dims* dims, int32_t which, int64_t* out, int32_t n_out);
+int hig_denoiser_bwd_debug_tap(void* buf, int64_t bytes);
+int64_t hig_denoiser_bwd_tap_bytes(const hig_dims* dims);
 /* dst[i] = bf16(src[i]) (round to nearest even): builds the bf16 shadow of the flat fp32 parameter buffer. */
 /* joint_embed + sequence_embedding of the bf16-storage forward (transformer.py:418-419) as its own kernel pair:
  * out[m][:] = bf16( x[m][:F] . W^T + bias + pos[(m % T) - pos_shift] ), x fp32 with F (e.g. 150, 263) features per

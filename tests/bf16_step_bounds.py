@@ -189,8 +189,9 @@ def swap_halves(x):
 # ----------------------------------------------------------------------------------------------------------------------
 # the attention backward with bf16 rows (hig_linattn_apply_bwd_bf16, hig_linattn_ctx_bwd_bf16)
 # ----------------------------------------------------------------------------------------------------------------------
-def apply_bwd(dy, q, A, want_bound):
-    """dy, q (B, T, H, hd), A (B, H, hd, hd) [c][l] -> dq like q, dA like A, and their fp32 bounds."""
+def apply_bwd(dy, q, A, want_bound, u16=U16):
+    """dy, q (B, T, H, hd), A (B, H, hd, hd) [c][l] -> dq like q, dA like A, and their fp32 bounds (u16 = 0: the fp32 rows of
+    hig_linattn_apply_bwd, tests/f32_step_bounds.py)."""
     p = torch.softmax(q, -1)
     t = torch.einsum("bnhl,bhcl->bnhc", dy, A)
     dq = p * (t - (p * t).sum(-1, keepdim=True))
@@ -204,10 +205,10 @@ def apply_bwd(dy, q, A, want_bound):
     Tm = torch.einsum("bnhl,bhcl->bnhc", dy.abs(), A.abs())
     MdQ = p * (Tm + (p * Tm).sum(-1, keepdim=True))
     MdA = torch.einsum("bnhc,bnhl->bhcl", p, dy.abs())
-    return dq, dA, (g["dQ"] * U + 2 * U16) * MdQ + FLOOR, (g["dA"] * U + 2 * U16) * MdA + FLOOR
+    return dq, dA, (g["dQ"] * U + 2 * u16) * MdQ + FLOOR, (g["dA"] * U + 2 * u16) * MdA + FLOOR
 
 
-def ctx_bwd(dA, A, K, V, kst, lens, want_bound):
+def ctx_bwd(dA, A, K, V, kst, lens, want_bound, u16=U16):
     """dA, A (B, H, hd, hd); K, V (B, T, H, hd); kst (B, H, hd, 2) = (column maximum, denominator) as the forward left them;
     -> dK, dV like K (exact zeros at and beyond the length) and their fp32 bounds."""
     B, T, H, hd = K.shape
@@ -228,7 +229,7 @@ def ctx_bwd(dA, A, K, V, kst, lens, want_bound):
     Sm = torch.einsum("bnhl,bhcl->bnhc", v.abs(), dA.abs())
     MdK = k * (Sm + (A.abs() * dA.abs()).sum(-1)[:, None])
     MdV = torch.einsum("bnhc,bhcl->bnhl", k, dA.abs()) * lm
-    return dK, dV, (g["dK"] * U + 2 * U16) * MdK + FLOOR, (g["dV"] * U + 2 * U16) * MdV + FLOOR
+    return dK, dV, (g["dK"] * U + 2 * u16) * MdK + FLOOR, (g["dV"] * U + 2 * u16) * MdV + FLOOR
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -238,6 +239,7 @@ class Walk:
     """See the module docstring.  trace None: a chain in arithmetic `ar` (its buffers end up in self.out); else a check of
     `trace` (ar is REF), self.worst = {stage kind: (largest |error| / bound, the buffer that gave it)}.
     forms: joint_kernel, ffn_wsp16, fuse_front, ctx_mm16, edge16 (booleans: the forms the call took)."""
+    u16 = U16           # what a product on bf16 rows adds to the attention backward's bounds (0 in the fp32 walk that subclasses this)
 
     def __init__(self, P, D, inp, forms, ar=REF, trace=None, mutant=None, te=None):
         assert mutant is None or (mutant in MUTANTS and trace is None)
@@ -548,12 +550,12 @@ class Walk:
         """apply_bwd (dq, dA) and ctx_bwd (dk, dv) of one attention; swap: the person <-> person routing of A and dA."""
         D, ar, d = self.D, self.ar, self.D.d
         hv = lambda t, r: heads(t, D.B, r, D.H, D.hd)      # noqa: E731
-        dq, dA, bq, bA = apply_bwd(hv(dy, D.T), hv(q, D.T), swap_halves(A) if swap else A, self.check)
+        dq, dA, bq, bA = apply_bwd(hv(dy, D.T), hv(q, D.T), swap_halves(A) if swap else A, self.check, self.u16)
         if swap:
             dA, bA = swap_halves(dA), (swap_halves(bA) if self.check else None)
         self.put("apply_bwd", (pre + "_dA", l), dA, (lambda: bA) if self.check else None)
         dAb = self.get((pre + "_dA", l))
-        dK, dV, bK, bV = ctx_bwd(dAb, A, hv(K, rows), hv(V, rows), kst, lens, self.check)
+        dK, dV, bK, bV = ctx_bwd(dAb, A, hv(K, rows), hv(V, rows), kst, lens, self.check, self.u16)
         R = D.B * rows
         if pre == "ca":
             self.put("apply_bwd", ("ca_dq", l), dq.reshape(D.M, d), (lambda: bq.reshape(D.M, d)) if self.check else None, bf16=True)
@@ -715,7 +717,11 @@ class Walk:
                 b[first] = torch.cat([b4(), b[first][:, 4:]], 1)
                 return b
         self.put("gemm32", "dx", dx, bdx)
-        # ---- time / text embedding path (fp32) ----
+        self.time_path_bwd()
+
+    def time_path_bwd(self):
+        """The time / text embedding path (fp32 in either storage): from dss to the gradients of the embedding chain and dxf_proj."""
+        D, L, mut, d = self.D, _lib, self.mut, self.D.d
         dss, emb, te_h, te = self.get("dss"), self.get("emb"), self.get("te_h"), self.get("te")
         self.put("colsum", ("g", L.P_STY_EMB_B), dss.sum(0), lambda: rb.colsum_bound(dss)[1])
         dsrc = dss

@@ -401,6 +401,50 @@ int main() {
     EXPECT(hig_last_error(msg, sizeof(msg)) >= 0 && strstr(msg, "tap buffer") != nullptr);
     EXPECT(hig_denoiser_bwd_bf16_debug_tap(nullptr, 0) == HIG_OK);
   }
+  // ---- the same for the fp32 training step (hig_f32_train_layout, hig_denoiser_bwd_debug_tap) ----
+  {
+    hig_dims T32 = dims(4, 21, 12, 128, 2, 96, 2, 1, 0, 0, 0);       // two-person, fp32 storage, linear attention
+    hig_dims B16 = dims(4, 21, 12, 128, 2, 96, 2, 1, 1, 0, 0);
+    int64_t v[64];
+    const int tables[][2] = {{HIG_LAYOUT32_FWD, HIG_FW32_NSLOTS}, {HIG_LAYOUT32_TEXT, HIG_TX32_NSLOTS}, {HIG_LAYOUT32_BWD, HIG_BW32_NSLOTS},
+                             {HIG_LAYOUT32_TAP, HIG_TAP32_NSLOTS}};
+    for (const auto& t : tables) {
+      for (int64_t& x : v) x = -7;
+      EXPECT(hig_f32_train_layout(&T32, t[0], v, 64) == t[1]);
+      for (int s = t[1]; s < 64; ++s) EXPECT(v[s] == -7);
+      for (int64_t& x : v) x = -7;
+      EXPECT(hig_f32_train_layout(&T32, t[0], v, 3) == t[1] && v[2] >= 0 && v[3] == -7);   // n_out is respected
+      EXPECT(hig_f32_train_layout(&T32, t[0], nullptr, 64) == t[1]);
+    }
+    EXPECT(hig_f32_train_layout(&T32, HIG_LAYOUT32_FWD, v, 64) == HIG_FW32_NSLOTS && v[HIG_FW32_TOTAL] == hig_workspace_bytes(&T32, 1) &&
+           v[HIG_FW32_H2B] > 0 && v[HIG_FW32_LSE1] == -1);
+    EXPECT(hig_f32_train_layout(&T32, HIG_LAYOUT32_TEXT, v, 64) == HIG_TX32_NSLOTS && v[HIG_TX32_TOTAL] == hig_textctx_bytes(&T32, 1));
+    EXPECT(hig_f32_train_layout(&T32, HIG_LAYOUT32_BWD, v, 64) == HIG_BW32_NSLOTS && v[HIG_BW32_TOTAL] == hig_bwd_workspace_bytes(&T32) &&
+           v[HIG_BW32_DELTA] == -1 && v[HIG_BW32_TOK0] > 0);
+    EXPECT(hig_f32_train_layout(&T32, HIG_LAYOUT32_TAP, v, 64) == HIG_TAP32_NSLOTS && v[HIG_TAP32_TOTAL] == hig_denoiser_bwd_tap_bytes(&T32) &&
+           v[HIG_TAP32_INT_DA] >= 0 && v[HIG_TAP32_SA_DELTA] == -1);
+    hig_dims one = T32; one.two_person = 0;
+    EXPECT(hig_f32_train_layout(&one, HIG_LAYOUT32_TAP, v, 64) == HIG_TAP32_NSLOTS && v[HIG_TAP32_INT_DA] == -1 && v[HIG_TAP32_TOK0] == -1 &&
+           v[HIG_TAP32_SA_DH] > 0);
+    EXPECT(hig_f32_train_layout(&one, HIG_LAYOUT32_FWD, v, 64) == HIG_FW32_NSLOTS && v[HIG_FW32_H2B] == -1 && v[HIG_FW32_LENP] == -1);
+    EXPECT(hig_f32_train_layout(&T32, 4, v, 64) == HIG_EINVAL && hig_f32_train_layout(&T32, -1, v, 64) == HIG_EINVAL);
+    EXPECT(hig_f32_train_layout(nullptr, HIG_LAYOUT32_FWD, v, 64) < 0 && hig_f32_train_layout(&B16, HIG_LAYOUT32_FWD, v, 64) == HIG_EINVAL);
+    EXPECT(hig_denoiser_bwd_tap_bytes(nullptr) < 0 && hig_denoiser_bwd_tap_bytes(&B16) == HIG_EINVAL);
+    const int64_t need = hig_denoiser_bwd_tap_bytes(&T32);
+    EXPECT(need > 0 && need % 256 == 0);
+    void* fake = reinterpret_cast<void*>((uintptr_t)1 << 32);
+    EXPECT(hig_denoiser_bwd_debug_tap(fake, 0) == HIG_EINVAL && hig_denoiser_bwd_debug_tap(fake, -1) == HIG_EINVAL);
+    // a tap buffer one byte short: the backward is refused before it touches the device or any of its arguments
+    EXPECT(hig_denoiser_bwd_debug_tap(fake, need - 1) == HIG_OK);
+    const void* tab[1] = {nullptr};
+    void* gtab[1] = {nullptr};
+    const float* ff = static_cast<const float*>(fake);
+    const int64_t* fi = static_cast<const int64_t*>(fake);
+    EXPECT(hig_denoiser_bwd(&T32, tab, ff, fi, fi, ff, fake, fake, ff, gtab, nullptr, static_cast<float*>(fake), static_cast<float*>(fake), fake,
+                            nullptr) == HIG_EINVAL);
+    EXPECT(hig_last_error(msg, sizeof(msg)) >= 0 && strstr(msg, "tap buffer") != nullptr);
+    EXPECT(hig_denoiser_bwd_debug_tap(nullptr, 0) == HIG_OK);
+  }
   if (failures) {
     fprintf(stderr, "%d expectation(s) failed\n", failures);
     return 1;
