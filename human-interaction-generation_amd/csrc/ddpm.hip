@@ -355,12 +355,24 @@ __global__ __launch_bounds__(256) void impose_known_kernel(float* x, const float
     }
 }
 
+// A per-timestep weight: row tt of the table, a step outside [0, nsteps) reading its nearest row.
+__device__ __forceinline__ float step_weight(const float* __restrict__ wtab, int nsteps, int64_t t) {
+  return wtab[t < 0 ? 0 : (t >= nsteps ? nsteps - 1 : (int)t)];
+}
+
 // One wave per (b, t) row: row mean of squared error, masked; dpred written in the same pass.
+// W = false: hig_masked_mse as it always was.  W = true (hig_masked_mse_w): the row of sample b counts w = wtab[t[b]] times --
+// `w * (s / F)` into the partial sum and `(gscale * w) * dlt` into dpred, which at w == 1 are the unweighted bits (a product
+// with 1 is exact, and so is an fma of it) -- and, with rowval, the row's unweighted mean (0 off the mask) is kept for the
+// per-sample losses.
+template <bool W>
 __global__ __launch_bounds__(256) void masked_mse_kernel(const float* __restrict__ pred,
                                                          const float* __restrict__ target,
-                                                         const int64_t* __restrict__ length, int B,
+                                                         const int64_t* __restrict__ length,
+                                                         const int64_t* __restrict__ t, const float* __restrict__ wtab,
+                                                         int nsteps, int B,
                                                          int T, int F, float* __restrict__ dpred,
-                                                         float* __restrict__ partial) {
+                                                         float* __restrict__ partial, float* __restrict__ rowval) {
   __shared__ float wsum[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // sum(mask) = sum_b clamp(length[b], 0, T)
@@ -380,23 +392,52 @@ __global__ __launch_bounds__(256) void masked_mse_kernel(const float* __restrict
     const bool on = tt < l;
     const float* p = pred + row * F;
     const float* q = target + row * F;
+    float gs = gscale, w = 1.0f;
+    if constexpr (W) {
+      w = step_weight(wtab, nsteps, t[b]);
+      gs = gscale * w;
+    }
     float s = 0.f;
     for (int f = lane; f < F; f += 64) {
       const float dlt = p[f] - q[f];
       s += dlt * dlt;
-      if (dpred) dpred[row * F + f] = on ? gscale * dlt : 0.f;
+      if (dpred) dpred[row * F + f] = on ? gs * dlt : 0.f;
     }
     s = wave_sum(s);
-    if (on) acc += s / (float)F;
+    if constexpr (W) {
+      const float m = s / (float)F;
+      if (on) acc += w * m;
+      if (rowval && lane == 0) rowval[row] = on ? m : 0.f;
+    } else {
+      if (on) acc += s / (float)F;
+    }
   }
   if (lane == 0) wsum[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
   if (blockIdx.x == 0 && threadIdx.x == 0) partial[gridDim.x] = cnt;
 }
+// Workgroup 0: the loss.  W = true with sample_loss: workgroups 1 .. ceil(B / 256) hold one thread per sample, which adds the
+// sample's row means in frame order (one thread, one order: the bits repeat) and divides by max(clamp(len), 1).
+template <bool W>
 __global__ void masked_mse_final_kernel(const float* __restrict__ partial, int nblk,
-                                        float* __restrict__ loss) {
+                                        float* __restrict__ loss, const float* __restrict__ rowval,
+                                        const int64_t* __restrict__ length, int B, int T,
+                                        float* __restrict__ sample_loss) {
   __shared__ float red[256];
+  if constexpr (W) {
+    if (blockIdx.x > 0) {
+      const int b = (int)(blockIdx.x - 1) * 256 + (int)threadIdx.x;
+      if (b < B) {
+        int64_t l = length ? length[b] : T;
+        l = l < 0 ? 0 : (l > T ? T : l);
+        float a = 0.f;
+        for (int tt = 0; tt < (int)l; ++tt) a += rowval[(int64_t)b * T + tt];
+        sample_loss[b] = a / (float)(l > 0 ? l : 1);
+      }
+      return;
+    }
+  }
   float s = 0.f;
   for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
   red[threadIdx.x] = s;
@@ -651,9 +692,17 @@ __global__ __launch_bounds__(256) void pair_vote_select_kernel(const float* __re
 // m2|c2, m2|c1], R = 4P): S0[p] = L[p] + L[2P + p], S1[p] = L[P + p] + L[3P + p]; loss = sum_p min(S0, S1) /
 // (sum(mask) / 2); only the rows of the cheaper caption assignment of each pair get a gradient (ties: the first).
 // rowscale[r] = d loss / d rowloss[r].
+// W = false: hig_pair_mse as it always was.  W = true (hig_pair_mse_w): row r counts w = wtab[t[r]] times (the rows of a pair
+// share t: its weight is read at row p).  The comparison stays on the unweighted S0, S1; `w * S` enters the sum and
+// `w * (1 / denom)` the row scale, the unweighted bits at w == 1.  sample_loss (nullable): min(S0, S1) / (2 max(len_p, 1)) per
+// pair, rowloss[r] / max(len_r, 1) per row without PIT, len clamped to [0, T]: one thread each, no reduction.
+template <bool W>
 __global__ __launch_bounds__(256) void pair_select_kernel(const float* __restrict__ rowloss,
-                                                          const int64_t* __restrict__ length, int R, int T, int pit,
-                                                          float* __restrict__ loss, float* __restrict__ rowscale) {
+                                                          const int64_t* __restrict__ length,
+                                                          const int64_t* __restrict__ t, const float* __restrict__ wtab,
+                                                          int nsteps, int R, int T, int pit,
+                                                          float* __restrict__ loss, float* __restrict__ rowscale,
+                                                          float* __restrict__ sample_loss) {
   __shared__ float red[256];
   __shared__ float scnt;
   float cnt = 0.f;
@@ -676,14 +725,38 @@ __global__ __launch_bounds__(256) void pair_select_kernel(const float* __restric
     for (int p = threadIdx.x; p < P; p += 256) {
       const float s0 = rowloss[p] + rowloss[2 * P + p], s1 = rowloss[P + p] + rowloss[3 * P + p];
       const bool first = s0 <= s1;
-      part += first ? s0 : s1;
-      rowscale[p] = rowscale[2 * P + p] = first ? 1.0f / denom : 0.f;
-      rowscale[P + p] = rowscale[3 * P + p] = first ? 0.f : 1.0f / denom;
+      if constexpr (W) {
+        const float w = step_weight(wtab, nsteps, t[p]);
+        const float sel = first ? s0 : s1, ws = w * (1.0f / denom);
+        part += w * sel;
+        rowscale[p] = rowscale[2 * P + p] = first ? ws : 0.f;
+        rowscale[P + p] = rowscale[3 * P + p] = first ? 0.f : ws;
+        if (sample_loss) {
+          int64_t l = length ? length[p] : T;
+          l = l < 1 ? 1 : (l > T ? T : l);
+          sample_loss[p] = sel / (2.0f * (float)l);
+        }
+      } else {
+        part += first ? s0 : s1;
+        rowscale[p] = rowscale[2 * P + p] = first ? 1.0f / denom : 0.f;
+        rowscale[P + p] = rowscale[3 * P + p] = first ? 0.f : 1.0f / denom;
+      }
     }
   } else {
     for (int r = threadIdx.x; r < R; r += 256) {
-      part += rowloss[r];
-      rowscale[r] = 1.0f / denom;
+      if constexpr (W) {
+        const float w = step_weight(wtab, nsteps, t[r]);
+        part += w * rowloss[r];
+        rowscale[r] = w * (1.0f / denom);
+        if (sample_loss) {
+          int64_t l = length ? length[r] : T;
+          l = l < 1 ? 1 : (l > T ? T : l);
+          sample_loss[r] = rowloss[r] / (float)l;
+        }
+      } else {
+        part += rowloss[r];
+        rowscale[r] = 1.0f / denom;
+      }
     }
   }
   __syncthreads();
@@ -695,6 +768,73 @@ __global__ __launch_bounds__(256) void pair_select_kernel(const float* __restric
   }
   if (threadIdx.x == 0) loss[0] = red[0] / denom;
 }
+
+// ---- the loss history of the loss-aware timestep sampler (include/hig.h, 'Per-timestep loss weights') ----
+// ONE workgroup of 1024 threads; thread i owns the timesteps i, i + 1024, ..: it scans the batch in order and pushes the entries
+// of its timesteps into their rings (so entries that share a timestep land in batch order, with no atomics), then takes the
+// root mean square of each ring.  "Every ring is full" and sum_t m_t are reduced over the block: a thread adds its own
+// timesteps in ascending order, then red[i] += red[i + o], o = 512 .. 1.  m_t waits in p_out[t] between the two phases, written
+// and read back by the same thread.
+__global__ __launch_bounds__(1024) void loss_history_kernel(const int64_t* __restrict__ t, const float* __restrict__ sample_loss,
+                                                            int n, float* __restrict__ hist, int32_t* __restrict__ counts,
+                                                            const float* __restrict__ base_w, int nsteps, int H,
+                                                            float uniform_prob, float* __restrict__ p_out,
+                                                            float* __restrict__ w_out) {
+#pragma clang fp contract(off)
+  __shared__ float red[1024];
+  __shared__ int full[1024];
+  float msum = 0.f;
+  int all_full = 1;
+  for (int k = threadIdx.x; k < nsteps; k += 1024) {
+    float* ring = hist + (int64_t)k * H;
+    int c = counts[k];
+    c = c < 0 ? 0 : (c > H ? H : c);
+    const float bw = base_w[k];
+    for (int i = 0; i < n; ++i) {
+      if (t[i] != (int64_t)k) continue;
+      const float v = bw * sample_loss[i];
+      if (!(fabsf(v) <= 3.402823466e+38f)) continue;   // (NaN and +-inf are not pushed)
+      if (c == H) {
+        for (int h = 0; h + 1 < H; ++h) ring[h] = ring[h + 1];
+        ring[H - 1] = v;
+      } else {
+        ring[c++] = v;
+      }
+    }
+    counts[k] = c;
+    float sq = 0.f;
+    for (int h = 0; h < H; ++h) sq = sq + ring[h] * ring[h];
+    const float m = sqrtf(sq / (float)H);
+    p_out[k] = m;
+    msum = msum + m;
+    all_full &= c == H;
+  }
+  red[threadIdx.x] = msum;
+  full[threadIdx.x] = all_full;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + o];
+      full[threadIdx.x] &= full[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  const float total = red[0];
+  // (a total that is 0, NaN or infinite -- every recorded loss 0, or an overflow -- would make p unusable: stay uniform)
+  const bool warm = full[0] != 0 && total > 0.f && total <= 3.402823466e+38f;
+  const float fn = (float)nsteps, unif = 1.0f / fn;
+  for (int k = threadIdx.x; k < nsteps; k += 1024) {
+    if (warm) {
+      const float p = (1.0f - uniform_prob) * (p_out[k] / total) + uniform_prob / fn;
+      p_out[k] = p;
+      w_out[k] = base_w[k] / (fn * p);
+    } else {
+      p_out[k] = unif;
+      w_out[k] = base_w[k];
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void pair_grad_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                         const int64_t* __restrict__ length,
                                                         const float* __restrict__ rowscale, int R, int T, int F,
@@ -878,16 +1018,18 @@ extern "C" int hig_advance_timesteps(int64_t* t, const int64_t* map, int32_t nst
   return HIG_OK;
 }
 
-extern "C" int hig_pair_mse(const float* pred, const float* target, const int64_t* length, int32_t R, int32_t T,
-                            int32_t F, int32_t pit, float* loss, float* dpred, float* scratch, hig_stream_t s) {
-  HIG_REQUIRE(pred && target && loss && scratch && R > 0 && T > 0 && F >= 4, "hig_pair_mse: bad arguments");
-  HIG_REQUIRE(!pit || R % 4 == 0, "hig_pair_mse: PIT needs 4 groups of rows (got %d rows)", R);
+namespace {
+// hig_pair_mse and hig_pair_mse_w: the row losses, the selection (weighted or not), the gradient.
+template <bool W>
+int pair_mse_launch(const float* pred, const float* target, const int64_t* length, const int64_t* t, const float* wtab,
+                    int32_t nsteps, int32_t R, int32_t T, int32_t F, int32_t pit, float* loss, float* dpred, float* sample_loss,
+                    float* scratch, hig_stream_t s) {
   float* rowloss = scratch;          // [R]
   float* rowscale = scratch + R;     // [R]
   hipLaunchKernelGGL(pair_rowloss_kernel, dim3(R), dim3(256), 0, hig_stream(s), pred, target, length, R, T, F, rowloss);
   HIG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(pair_select_kernel, dim3(1), dim3(256), 0, hig_stream(s), rowloss, length, R, T, pit, loss,
-                     rowscale);
+  hipLaunchKernelGGL(pair_select_kernel<W>, dim3(1), dim3(256), 0, hig_stream(s), rowloss, length, t, wtab, nsteps, R, T, pit,
+                     loss, rowscale, sample_loss);
   HIG_CHECK_LAUNCH();
   if (dpred) {
     const int64_t n = (int64_t)R * T * F;
@@ -895,6 +1037,38 @@ extern "C" int hig_pair_mse(const float* pred, const float* target, const int64_
                        rowscale, R, T, F, dpred);
     HIG_CHECK_LAUNCH();
   }
+  return HIG_OK;
+}
+}  // namespace
+
+extern "C" int hig_pair_mse(const float* pred, const float* target, const int64_t* length, int32_t R, int32_t T,
+                            int32_t F, int32_t pit, float* loss, float* dpred, float* scratch, hig_stream_t s) {
+  HIG_REQUIRE(pred && target && loss && scratch && R > 0 && T > 0 && F >= 4, "hig_pair_mse: bad arguments");
+  HIG_REQUIRE(!pit || R % 4 == 0, "hig_pair_mse: PIT needs 4 groups of rows (got %d rows)", R);
+  return pair_mse_launch<false>(pred, target, length, nullptr, nullptr, 0, R, T, F, pit, loss, dpred, nullptr, scratch, s);
+}
+
+extern "C" int hig_pair_mse_w(const float* pred, const float* target, const int64_t* length, const int64_t* t, const float* wtab,
+                              int32_t nsteps, int32_t R, int32_t T, int32_t F, int32_t pit, float* loss, float* dpred,
+                              float* sample_loss, float* scratch, hig_stream_t s) {
+  HIG_REQUIRE(pred && target && t && wtab && loss && scratch && nsteps > 0 && R > 0 && T > 0 && F >= 4,
+              "hig_pair_mse_w: pred, target, t, wtab, loss, scratch non-null, nsteps > 0, R > 0, T > 0 and F >= 4 required "
+              "(nsteps %d R %d T %d F %d)", (int)nsteps, (int)R, (int)T, (int)F);
+  HIG_REQUIRE(!pit || R % 4 == 0, "hig_pair_mse_w: PIT needs 4 groups of rows (got %d rows)", R);
+  return pair_mse_launch<true>(pred, target, length, t, wtab, nsteps, R, T, F, pit, loss, dpred, sample_loss, scratch, s);
+}
+
+extern "C" int hig_loss_history_update(const int64_t* t, const float* sample_loss, int32_t n, float* hist, int32_t* counts,
+                                       const float* base_w, int32_t nsteps, int32_t H, float uniform_prob, float* p_out,
+                                       float* w_out, hig_stream_t s) {
+  HIG_REQUIRE(hist && counts && base_w && p_out && w_out && nsteps > 0 && H > 0 && n >= 0 && (n == 0 || (t && sample_loss)),
+              "hig_loss_history_update: hist, counts, base_w, p_out, w_out non-null, nsteps > 0, H > 0, n >= 0 and, with n > 0, "
+              "t and sample_loss required (n %d nsteps %d H %d)", (int)n, (int)nsteps, (int)H);
+  HIG_REQUIRE(uniform_prob >= 0.f && uniform_prob <= 1.f, "hig_loss_history_update: 0 <= uniform_prob <= 1 required, got %g",
+              (double)uniform_prob);
+  hipLaunchKernelGGL(loss_history_kernel, dim3(1), dim3(1024), 0, hig_stream(s), t, sample_loss, (int)n, hist, counts, base_w,
+                     (int)nsteps, (int)H, uniform_prob, p_out, w_out);
+  HIG_CHECK_LAUNCH();
   return HIG_OK;
 }
 
@@ -962,17 +1136,42 @@ extern "C" int hig_pair_vote(const float* pred, const float* target2, const int6
   return HIG_OK;
 }
 
+namespace {
+int masked_mse_blocks(int32_t B, int32_t T) {
+  const int64_t rows = (int64_t)B * T;
+  const int64_t nblk = (rows + 3) / 4;
+  return (int)(nblk > HIG_NORM_BLOCKS - 1 ? HIG_NORM_BLOCKS - 1 : nblk);
+}
+}  // namespace
+
 extern "C" int hig_masked_mse(const float* pred, const float* target, const int64_t* length, int32_t B,
                               int32_t T, int32_t F, float* loss, float* dpred, float* scratch,
                               hig_stream_t s) {
   HIG_REQUIRE(pred && target && loss && scratch && B > 0 && T > 0 && F > 0, "hig_masked_mse: bad arguments");
-  const int64_t rows = (int64_t)B * T;
-  int nblk = (int)((rows + 3) / 4);
-  if (nblk > HIG_NORM_BLOCKS - 1) nblk = HIG_NORM_BLOCKS - 1;
-  hipLaunchKernelGGL(masked_mse_kernel, dim3(nblk), dim3(256), 0, hig_stream(s), pred, target, length, B, T,
-                     F, dpred, scratch);
+  const int nblk = masked_mse_blocks(B, T);
+  hipLaunchKernelGGL(masked_mse_kernel<false>, dim3(nblk), dim3(256), 0, hig_stream(s), pred, target, length,
+                     static_cast<const int64_t*>(nullptr), static_cast<const float*>(nullptr), 0, B, T,
+                     F, dpred, scratch, static_cast<float*>(nullptr));
   HIG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(masked_mse_final_kernel, dim3(1), dim3(256), 0, hig_stream(s), scratch, nblk, loss);
+  hipLaunchKernelGGL(masked_mse_final_kernel<false>, dim3(1), dim3(256), 0, hig_stream(s), scratch, nblk, loss,
+                     static_cast<const float*>(nullptr), static_cast<const int64_t*>(nullptr), 0, 0, static_cast<float*>(nullptr));
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+
+extern "C" int hig_masked_mse_w(const float* pred, const float* target, const int64_t* length, const int64_t* t,
+                                const float* wtab, int32_t nsteps, int32_t B, int32_t T, int32_t F, float* loss, float* dpred,
+                                float* sample_loss, float* scratch, hig_stream_t s) {
+  HIG_REQUIRE(pred && target && t && wtab && loss && scratch && nsteps > 0 && B > 0 && T > 0 && F > 0,
+              "hig_masked_mse_w: pred, target, t, wtab, loss, scratch non-null and nsteps, B, T, F > 0 required "
+              "(nsteps %d B %d T %d F %d)", (int)nsteps, (int)B, (int)T, (int)F);
+  const int nblk = masked_mse_blocks(B, T);
+  float* rowval = sample_loss ? scratch + HIG_NORM_BLOCKS : nullptr;      // [B T] behind the partial sums
+  hipLaunchKernelGGL(masked_mse_kernel<true>, dim3(nblk), dim3(256), 0, hig_stream(s), pred, target, length, t, wtab,
+                     (int)nsteps, B, T, F, dpred, scratch, rowval);
+  HIG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(masked_mse_final_kernel<true>, dim3(1 + (sample_loss ? (B + 255) / 256 : 0)), dim3(256), 0, hig_stream(s),
+                     scratch, nblk, loss, static_cast<const float*>(rowval), length, (int)B, (int)T, sample_loss);
   HIG_CHECK_LAUNCH();
   return HIG_OK;
 }

@@ -41,6 +41,8 @@ def create_named_schedule_sampler(name, diffusion):
     """gaussian_diffusion.py:16-27."""
     if name == "uniform":
         return UniformSampler(diffusion)
+    if name == "loss-second-moment":
+        return LossSecondMomentResampler(diffusion)
     raise NotImplementedError(f"unknown schedule sampler: {name}")
 
 
@@ -68,6 +70,120 @@ class UniformSampler(ScheduleSampler):
 
     def weights(self):
         return self._weights
+
+
+class LossAwareSampler(ScheduleSampler):
+    """gaussian_diffusion.py:74-120 without update_with_local_losses: the cross-rank gather of (t, loss) is not built."""
+
+    @abstractmethod
+    def update_with_all_losses(self, ts, losses):
+        """ts: int timesteps, losses: one float per timestep; deterministic, no synchronisation."""
+
+
+class LossSecondMomentResampler(LossAwareSampler):
+    """gaussian_diffusion.py:123-153 on the host, in float64 (the reference's `np.int` is `int` here): the host mirror of
+    hig_loss_history_update, which the trainers use through DeviceLossSecondMomentResampler."""
+
+    def __init__(self, diffusion, history_per_term=10, uniform_prob=0.001):
+        self.diffusion = diffusion
+        self.history_per_term = history_per_term
+        self.uniform_prob = uniform_prob
+        self._loss_history = np.zeros([diffusion.num_timesteps, history_per_term], dtype=np.float64)
+        self._loss_counts = np.zeros([diffusion.num_timesteps], dtype=int)
+
+    def weights(self):
+        if not self._warmed_up():
+            return np.ones([self.diffusion.num_timesteps], dtype=np.float64)
+        weights = np.sqrt(np.mean(self._loss_history ** 2, axis=-1))
+        weights /= np.sum(weights)
+        weights *= 1 - self.uniform_prob
+        weights += self.uniform_prob / len(weights)
+        return weights
+
+    def update_with_all_losses(self, ts, losses):
+        for t, loss in zip(ts, losses):
+            if self._loss_counts[t] == self.history_per_term:
+                self._loss_history[t, :-1] = self._loss_history[t, 1:]      # shift out the oldest loss term
+                self._loss_history[t, -1] = loss
+            else:
+                self._loss_history[t, self._loss_counts[t]] = loss
+                self._loss_counts[t] += 1
+
+    def _warmed_up(self):
+        return (self._loss_counts == self.history_per_term).all()
+
+
+def min_snr_weights(alphas_cumprod, gamma):
+    """min-SNR-gamma weights of an eps-prediction loss, w_t = min(SNR_t, gamma) / SNR_t with SNR_t = ac_t / (1 - ac_t), in
+    float64; gamma = inf gives all ones.  ValueError unless gamma > 0 (NaN fails)."""
+    gamma = float(gamma)
+    if not gamma > 0.0:
+        raise ValueError("min_snr_weights: gamma must be a number > 0, got %r" % (gamma,))
+    ac = np.asarray(alphas_cumprod, dtype=np.float64)
+    snr = ac / (1.0 - ac)
+    return np.minimum(snr, gamma) / snr
+
+
+class DeviceLossSecondMomentResampler:
+    """The loss-second-moment sampler with its state on the device (include/hig.h, hig_loss_history_update): `hist`
+    (nsteps, H) and `counts` (int32), the sampling probabilities `p` and the loss-weight table `w` = base_w / (N p), all fp32
+    (the reference's history is float64).  base_w: the static per-timestep weights the importance weights are folded into
+    (None: all ones).  `sample` draws on the device and reads nothing back; `update` is one kernel launch, capturable.
+    Deviations from the reference: fp32 history, and a non-finite loss is skipped instead of recorded."""
+
+    def __init__(self, num_timesteps, device, base_w=None, history_per_term=10, uniform_prob=0.001):
+        n, H = int(num_timesteps), int(history_per_term)
+        if n <= 0 or H <= 0 or not 0.0 <= float(uniform_prob) <= 1.0:
+            raise ValueError("DeviceLossSecondMomentResampler: num_timesteps > 0, history_per_term > 0 and uniform_prob in [0, 1] "
+                             "required, got %r, %r, %r" % (num_timesteps, history_per_term, uniform_prob))
+        self.num_timesteps, self.history_per_term, self.uniform_prob = n, H, float(uniform_prob)
+        base = np.ones(n) if base_w is None else np.asarray(base_w, dtype=np.float64)
+        if base.shape != (n,) or not (np.isfinite(base).all() and (base > 0).all()):
+            raise ValueError("DeviceLossSecondMomentResampler: base_w must be %d finite positive weights" % n)
+        self.base_w = th.from_numpy(base.astype(np.float32)).to(device)
+        self.hist = th.zeros(n, H, device=device, dtype=th.float32)
+        self.counts = th.zeros(n, device=device, dtype=th.int32)
+        self.p = th.empty(n, device=device, dtype=th.float32)
+        self.w = th.empty(n, device=device, dtype=th.float32)
+        self.refresh()
+
+    def _launch(self, t, sample_loss, n):
+        _lib.check(_lib.lib().hig_loss_history_update(
+            _lib.ptr(t), _lib.ptr(sample_loss), n, _lib.ptr(self.hist), _lib.ptr(self.counts), _lib.ptr(self.base_w),
+            self.num_timesteps, self.history_per_term, self.uniform_prob, _lib.ptr(self.p), _lib.ptr(self.w), _lib.stream_ptr()))
+
+    def refresh(self):
+        """p and w from the history as it stands (what a launch with an empty batch does)."""
+        self._launch(None, None, 0)
+
+    def update(self, t, sample_loss):
+        """Pushes base_w[t_i] * sample_loss[i] for the first len(sample_loss) entries of t (int64) in order, then refreshes p
+        and w."""
+        n = sample_loss.numel()
+        if t.dtype != th.int64 or sample_loss.dtype != th.float32 or t.numel() < n or not (t.is_contiguous() and sample_loss.is_contiguous()):
+            raise ValueError("DeviceLossSecondMomentResampler.update: t int64 and sample_loss fp32, contiguous, len(t) >= len(sample_loss)")
+        self._launch(t, sample_loss, n)
+
+    def sample(self, batch_size, device=None):
+        """(t, weights): t ~ p drawn on the device by torch.multinomial, weights = w[t] (with base_w folded in)."""
+        t = th.multinomial(self.p, int(batch_size), replacement=True)
+        return t, self.w[t]
+
+    def state_dict(self):
+        return {"history": self.hist.cpu(), "counts": self.counts.cpu(), "history_per_term": self.history_per_term,
+                "uniform_prob": self.uniform_prob}
+
+    def load_state_dict(self, sd):
+        if tuple(sd["history"].shape) != tuple(self.hist.shape):
+            raise ValueError("schedule sampler state: history is %s, this sampler's is %s"
+                             % (tuple(sd["history"].shape), tuple(self.hist.shape)))
+        self.hist.copy_(sd["history"].to(self.hist.device, th.float32))
+        self.counts.copy_(sd["counts"].to(self.counts.device, th.int32))
+        self.refresh()
+
+    def tensors(self):
+        """The four state tensors (what a captured step's warm-up saves and restores)."""
+        return (self.hist, self.counts, self.p, self.w)
 
 
 def get_named_beta_schedule(schedule_name, num_diffusion_timesteps):

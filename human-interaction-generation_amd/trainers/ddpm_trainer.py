@@ -16,6 +16,7 @@ step (and under the reference's trainer).
 """
 import contextlib
 import time
+import warnings
 from collections import OrderedDict
 from os.path import join as pjoin
 
@@ -25,8 +26,8 @@ import torch.optim as optim
 from torch.nn.utils import clip_grad_norm_
 
 from .. import _lib
-from ..models.gaussian_diffusion import (GaussianDiffusion, LossType, ModelMeanType, ModelVarType,
-                                         create_named_schedule_sampler, get_named_beta_schedule)
+from ..models.gaussian_diffusion import (DeviceLossSecondMomentResampler, GaussianDiffusion, LossType, ModelMeanType,
+                                         ModelVarType, create_named_schedule_sampler, get_named_beta_schedule, min_snr_weights)
 from ..models.guidance import ClassifierFreeGuidedModel, check_scale
 from ..models.spaced_diffusion import SpacedDiffusion, space_timesteps, space_timesteps_logsnr
 from ..parallel import (FlatGradAllReduce, OverlappedGradAllReduce, ShardedSampler, broadcast_flat, broadcast_parameters,
@@ -55,6 +56,32 @@ def ema_options(opt):
     return float(d), bool(getattr(opt, "ema_warmup", True))
 
 
+def loss_options(opt):
+    """(loss_weighting, min_snr_gamma, sampler) that `opt` asks for.  opt.loss_weighting: None (the default: the unweighted
+    masked MSE) or "min_snr", w_t = min(SNR_t, gamma) / SNR_t with opt.min_snr_gamma (default 5.0, a number > 0, inf allowed);
+    opt.sampler: "uniform" (the default) or "loss-second-moment", t ~ sqrt(E[loss_t^2]) with each term weighted by
+    1 / (N p_t) (include/hig.h, 'Per-timestep loss weights').  Anything else is a ValueError."""
+    weighting = getattr(opt, "loss_weighting", None)
+    if weighting not in (None, "min_snr"):
+        raise ValueError("opt.loss_weighting must be None or 'min_snr', got %r" % (weighting,))
+    gamma = getattr(opt, "min_snr_gamma", 5.0)
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not float(gamma) > 0.0:
+        raise ValueError("opt.min_snr_gamma must be a number > 0, got %r" % (gamma,))
+    sampler = getattr(opt, "sampler", "uniform")
+    if sampler not in ("uniform", "loss-second-moment"):
+        raise ValueError("opt.sampler must be 'uniform' or 'loss-second-moment', got %r" % (sampler,))
+    return weighting, float(gamma), sampler
+
+
+def check_loss_sampler_world(sampler, world):
+    """The loss-aware sampler keeps one history per process: with more than one rank every rank would have to see every
+    rank's (t, loss) pairs, and that gather is not built."""
+    if sampler == "loss-second-moment" and world > 1:
+        raise NotImplementedError("opt.sampler = 'loss-second-moment' with %d ranks: the cross-rank gather of (t, loss) that keeps "
+                                  "the ranks' loss histories identical is not built -- train with one rank, or with "
+                                  "opt.sampler = 'uniform' (opt.loss_weighting = 'min_snr' needs no exchange)" % world)
+
+
 class _RunningMean:
     """Sums per-key values (host floats or device scalars -- the latter without any host sync) and hands back their
     means when the ITERATION COUNT is a multiple of `period` -- the reference prints at `it % log_every == 0`
@@ -78,16 +105,21 @@ class _RunningMean:
 
 
 class DDPMTrainer(object):
+    # both loss options unset (what a trainer assembled without __init__ gets): every route is the unweighted one
+    _loss_cfg, _loss_dev = (None, 5.0, "uniform"), None
 
     def __init__(self, args, encoder):
         self.opt, self.device, self.encoder = args, args.device, encoder
         self.multi = False
         self.diffusion_steps = args.diffusion_steps
-        self.sampler_name = 'uniform'
+        self._loss_cfg = loss_options(args)      # (a bad option is refused here, not at the first step)
+        self.sampler_name = self._loss_cfg[2]
+        self._loss_dev = None          # _loss_state: the device weight table and, loss-aware, the device sampler (lazy)
         # the one diffusion every reference tool builds: linear betas, eps-prediction, fixed small variance, MSE
         self.diffusion = GaussianDiffusion(betas=get_named_beta_schedule('linear', self.diffusion_steps),
                                            model_mean_type=ModelMeanType.EPSILON,
                                            model_var_type=ModelVarType.FIXED_SMALL, loss_type=LossType.MSE)
+        # the host sampler of that name; a loss-aware trainer replaces it by the device one at its first step (_loss_state)
         self.sampler = create_named_schedule_sampler(self.sampler_name, self.diffusion)
         if args.is_train:
             self.mse_criterion = torch.nn.MSELoss(reduction='none')
@@ -158,6 +190,80 @@ class DDPMTrainer(object):
             return caption
         return [c if k else "" for c, k in zip(caption, keep)]
 
+    # ---- per-timestep loss weights (include/hig.h, 'Per-timestep loss weights') --------------------------------------
+    def _loss_state(self, device):
+        """(wtab, sampler): the device table of per-timestep weights the losses index by t and, under
+        opt.sampler = "loss-second-moment", the device sampler that keeps it -- (None, None) with both options unset, where
+        every route is the unweighted one.  min-SNR alone: a static table.  Loss-aware: the sampler's `w`, into which the
+        static table (or ones) is folded; `self.sampler` becomes that sampler."""
+        weighting, gamma, name = self._loss_cfg
+        if weighting is None and name == "uniform":
+            return None, None
+        check_loss_sampler_world(name, _dist_world())
+        st = self._loss_dev
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:      # ("cuda" is the current device: not a reason to rebuild)
+            device = torch.device("cuda", torch.cuda.current_device())
+        if st is None or st["base"].device != device:
+            base = min_snr_weights(self.diffusion.alphas_cumprod, gamma) if weighting == "min_snr" else None
+            smp = None
+            if name == "loss-second-moment":
+                smp = DeviceLossSecondMomentResampler(self.diffusion.num_timesteps, device, base_w=base)
+                if st is not None and st["sampler"] is not None:
+                    smp.load_state_dict(st["sampler"].state_dict())
+                self.sampler = smp
+                tab = smp.base_w
+            else:
+                tab = torch.from_numpy(base).float().to(device)
+            st = self._loss_dev = {"base": tab, "sampler": smp}
+            if self._fused is not None:
+                self._fused["graphs"] = {}
+        smp = st["sampler"]
+        return (st["base"] if smp is None else smp.w), smp
+
+    def _draw_t(self, n, device):
+        """n timesteps from the trainer's sampler: the host sampler's (numpy's generator), or the device sampler's
+        torch.multinomial, which reads nothing back."""
+        self._loss_state(device)
+        return self.sampler.sample(n, device)[0]
+
+    def _weighted(self, per_sample, count, t, lens, device):
+        """The autograd route's objective: sum_i w[t_i] per_sample[i] / count (what the weighted loss kernels compute) and,
+        under the loss-aware sampler, the history update with per_sample[i] / lens[i] behind it -- lens: the frames an entry
+        was summed over, at least 1.  wtab None: the plain sum / count."""
+        wtab, smp = self._loss_state(device)
+        if wtab is None:
+            return per_sample.sum() / count
+        w = wtab[t[:per_sample.shape[0]].clamp(0, wtab.numel() - 1)]
+        loss = (w * per_sample).sum() / count
+        if smp is not None:
+            smp.update(t.contiguous(), (per_sample.detach() / lens).float().contiguous())
+        return loss
+
+    def _loss_load(self, ent):
+        """The 'schedule_sampler' entry of a checkpoint.  The history is restored only into a loss-aware trainer whose static
+        table is the one it was recorded under (the rings hold base_w[t] * loss); any other difference between the
+        checkpoint's loss options and this trainer's is a warning, never silence: the run then continues under this
+        trainer's options, and is not the uninterrupted one."""
+        weighting, gamma, name = self._loss_cfg
+        if ent is None:
+            if name == "loss-second-moment":
+                warnings.warn("the checkpoint has no 'schedule_sampler' entry: the loss-aware sampler starts from an empty history")
+            return
+        theirs = (ent.get('loss_weighting'), ent.get('min_snr_gamma'), ent.get('sampler'))
+        same_base = theirs[0] == weighting and (weighting is None or theirs[1] == gamma)
+        if theirs[2] != name or not same_base:
+            warnings.warn("the checkpoint was written under loss options (loss_weighting, min_snr_gamma, sampler) = %r, this "
+                          "trainer has %r: training continues under this trainer's options%s"
+                          % (theirs, (weighting, gamma, name),
+                             ", from an empty loss history" if name == "loss-second-moment" else ""))
+        if name == "loss-second-moment" and theirs[2] == name and same_base and 'history' in ent:
+            self._loss_state(_core(self.encoder).flat_params().flat.device)[1].load_state_dict(ent)
+
+    def _loss_key(self, device):
+        wtab, _ = self._loss_state(device)
+        return None if wtab is None else self._loss_cfg + (wtab.data_ptr(),)
+
     # ---- the reference's step: forward() then update() --------------------------------------------------------
     def forward(self, batch_data, eval_mode=False):
         """Noises the batch at sampled timesteps and runs the denoiser (ddpm_trainer.py:97-119); leaves
@@ -165,7 +271,7 @@ class DDPMTrainer(object):
         caption, x_start, cur_len = self._stage_batch(batch_data)
         caption = self._drop_captions(caption)
         self.caption, self.motions = caption, x_start
-        t, _unit_weights = self.sampler.sample(x_start.shape[0], x_start.device)
+        t = self._t = self._draw_t(x_start.shape[0], x_start.device)
         terms = self.diffusion.training_losses(model=self.encoder, x_start=x_start, t=t,
                                                model_kwargs=dict(text=caption, length=cur_len))
         self.real_noise, self.fake_noise = terms['target'], terms['pred']
@@ -174,7 +280,11 @@ class DDPMTrainer(object):
     def backward_G(self):
         """Masked mean over valid frames of the per-frame feature-mean squared error (ddpm_trainer.py:172-178)."""
         per_frame = self.mse_criterion(self.fake_noise, self.real_noise).mean(dim=-1)
-        self.loss_mot_rec = (per_frame * self.src_mask).sum() / self.src_mask.sum()
+        if self._loss_cfg[0] is None and self._loss_cfg[2] == "uniform":
+            self.loss_mot_rec = (per_frame * self.src_mask).sum() / self.src_mask.sum()
+        else:   # sum_b w[t_b] sum_frames / sum(mask): what hig_masked_mse_w computes
+            self.loss_mot_rec = self._weighted((per_frame * self.src_mask).sum(dim=1), self.src_mask.sum(), self._t,
+                                               self.src_mask.sum(dim=1).clamp_min(1), per_frame.device)
         return OrderedDict(loss_mot_rec=self.loss_mot_rec.item())
 
     def update(self):
@@ -546,6 +656,13 @@ class DDPMTrainer(object):
         if ema is not None:
             ck['encoder_ema'] = self._ema_state_dict(ema)
             ck['ema'] = {k: ema[k] for k in ('decay', 'warmup', 'origin', 'num_updates')}
+        weighting, gamma, name = self._loss_cfg
+        if weighting is not None or name != "uniform":
+            # the loss options and, loss-aware, the history the next draw depends on (the reference's `load` ignores the key)
+            ent = {'sampler': name, 'loss_weighting': weighting, 'min_snr_gamma': gamma}
+            if name == "loss-second-moment":
+                ent.update(self._loss_state(_core(self.encoder).flat_params().flat.device)[1].state_dict())
+            ck['schedule_sampler'] = ent
         torch.save(ck, file_name)
 
     def load(self, model_dir):
@@ -559,6 +676,7 @@ class DDPMTrainer(object):
             if getattr(self.opt, "fused_step", False) or self._fused is not None:
                 self._adopt_optimizer_state(ck['opt_encoder'])
         self._ema_load(ck)       # (also with is_train False: an inference-only trainer can sample from the average)
+        self._loss_load(ck.get('schedule_sampler'))
         return ck['ep'], ck.get('total_it', 0)
 
     # ---- the epoch loop (ddpm_trainer.py:220-266: logging and checkpoint cadence) ----------------------------------
@@ -722,12 +840,35 @@ class DDPMTrainer(object):
         x_t = self.diffusion.q_sample(x_start, t, noise=noise)
         pred, saved = core._launch_forward(x_t, t, length, xf_proj, xf_out, training=True)
         dpred = torch.empty_like(pred)
-        _lib.check(L.hig_masked_mse(_lib.ptr(pred), _lib.ptr(noise), _lib.ptr(length), B, T, F,
-                                    _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(st["mse_scratch"]),
-                                    _lib.stream_ptr()))
+        wtab, smp = self._loss_state(pred.device)
+        if wtab is None:
+            _lib.check(L.hig_masked_mse(_lib.ptr(pred), _lib.ptr(noise), _lib.ptr(length), B, T, F,
+                                        _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(st["mse_scratch"]),
+                                        _lib.stream_ptr()))
+        else:   # the weighted twin; loss-aware: the per-sample losses, then the history update BEHIND the loss launch, so
+            # this step's loss has read the table its t was drawn under
+            sl = None if smp is None else self._loss_buffer(st, "sample_loss", B, pred.device)
+            scr = self._loss_buffer(st, "mse_w_scratch", _lib.NORM_BLOCKS + (0 if smp is None else B * T), pred.device)
+            _lib.check(L.hig_masked_mse_w(_lib.ptr(pred), _lib.ptr(noise), _lib.ptr(length), _lib.ptr(t), _lib.ptr(wtab),
+                                          wtab.numel(), B, T, F, _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(sl),
+                                          _lib.ptr(scr), _lib.stream_ptr()))
+            if smp is not None:
+                smp.update(t, sl)
         hook = {} if exchange is None else dict(layer_hook=exchange.layer_done, comm_stream=exchange.stream)
         _, dxp, dxo = core._launch_backward(x_t, t, length, xf_out, saved, dpred, want_dx=False, **hook)
         return dxp, dxo
+
+    @staticmethod
+    def _loss_buffer(st, name, n, device):
+        """The fp32 buffer of n floats that the fused state keeps under (name, n, device).  One buffer per size, never replaced
+        and never freed while the state lives: every captured graph holds the raw pointer of the buffer of ITS shape and mode,
+        and graphs of several shapes and modes live side by side in st["graphs"]."""
+        bufs = st.setdefault("loss_buffers", {})
+        key = (name, int(n), torch.device(device))
+        buf = bufs.get(key)
+        if buf is None:
+            buf = bufs[key] = torch.zeros(int(n), device=device, dtype=torch.float32)
+        return buf
 
     def _fwd_bwd_overlapped_exchange(self, x_start, t, length, text, noise):
         """_fused_fwd_bwd with the gradient exchange of layer l issued while layers l-1 ... 0 are still in backward
@@ -830,7 +971,7 @@ class DDPMTrainer(object):
         train_step_captured with captured=True (two graph launches per step, no other host work)."""
         caption, x_start, cur_len = self._stage_batch(batch_data)
         caption = self._drop_captions(caption)
-        t, _ = self.sampler.sample(x_start.shape[0], x_start.device)
+        t = self._draw_t(x_start.shape[0], x_start.device)
         step = self.train_step_captured if captured else self.train_step_fused
         return step(x_start.contiguous(), t, cur_len, noise=noise, **self._text_inputs(caption))
 
@@ -865,7 +1006,10 @@ class DDPMTrainer(object):
         collectives fails: graph A = ... + backward, the all-reduce of the flat gradient enqueued eagerly on the same
         stream, graph B = clip + Adam.  Inputs are copied into static device buffers; `t` arrives from the host
         sampler through the same staging copy (the reference draws it with numpy, gaussian_diffusion.py:47-62), the
-        learning rate through a device scalar (`_set_lr`).  A graph is keyed on the shapes AND on the flat parameter /
+        learning rate through a device scalar (`_set_lr`).  With opt.loss_weighting / opt.sampler set the weight table, the
+        loss history and p are fixed device buffers, the history update is a node of the graph, `t` (drawn on the device by
+        `train_fused_batch`) is filled device to device, and the graph key carries the mode and the table.
+        A graph is keyed on the shapes AND on the flat parameter /
         gradient buffers it was captured against.  Text inputs as in `train_step_fused`: embeddings, or CLIP
         features.  The EMA of the weights rides in the same update kernel (its update number comes from the device step
         counter, its origin is a constant of the graph); the graph key carries its configuration.
@@ -887,7 +1031,8 @@ class DDPMTrainer(object):
         statics = text.statics()
         key = ((tuple(x_start.shape), text.kind) + tuple(tuple(a.shape) for a in statics)
                + (noise is None, world, split, in_graph, st["ptrs"],
-                  None if ema is None else (ema["decay"], ema["warmup"], ema["origin"], ema["flat"].data_ptr()))
+                  None if ema is None else (ema["decay"], ema["warmup"], ema["origin"], ema["flat"].data_ptr()),
+                  self._loss_key(x_start.device))
                + text.key(_core(self.encoder)))
         cap = st["graphs"].get(key)
         if cap is None:
@@ -908,6 +1053,8 @@ class DDPMTrainer(object):
             fp = core.flat_params()
             keep = (fp.flat.clone(), st["m"].clone(), st["v"].clone(), st["step"].clone(), st["covered"],
                     None if ema is None else (ema["flat"].clone(), ema["num_updates"]))
+            loss_smp = self._loss_state(x_start.device)[1]      # (the warm-up's step also pushes into the loss history)
+            keep_smp = None if loss_smp is None else [a.clone() for a in loss_smp.tensors()]
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
@@ -927,6 +1074,9 @@ class DDPMTrainer(object):
                     if ema is not None:     # the warm-up's update also moved the EMA
                         ema["flat"].copy_(keep[5][0])
                         ema["num_updates"] = keep[5][1]
+                    if loss_smp is not None:
+                        for a, b in zip(loss_smp.tensors(), keep_smp):
+                            a.copy_(b)
                 st["covered"] = keep[4]
                 core.params_changed()
                 if getattr(core, "storage", "f32") == "bf16":   # the warm-up's update also wrote the bf16 shadow: re-derive it

@@ -139,8 +139,8 @@ class DDPMMulTrainer(DDPMTrainer):
         caption, caption1, caption2, x_start, cur_len, B, T = self._pair_inputs(batch_data)
         caption1, caption2 = self._drop_pair_captions(caption1, caption2)
         caption = caption1 + caption2
-        t, _ = self.sampler.sample(B, x_start.device)
-        t = torch.cat([t, t], dim=0)
+        t = self._draw_t(B, x_start.device)
+        t = self._t = torch.cat([t, t], dim=0)
         if not self.with_label:
             caption = caption + caption2 + caption1      # (c1, c2, c2, c1) against (m1, m1, m2, m2)
             cur_len = torch.cat([cur_len] * 4, dim=0)
@@ -165,6 +165,8 @@ class DDPMMulTrainer(DDPMTrainer):
         """mul_ddpm_trainer.py:223-249."""
         if not self.multi:
             return super().backward_G()
+        if self._loss_cfg[0] is not None or self._loss_cfg[2] != "uniform":
+            return self._backward_G_weighted()
         if self.with_label:
             if _core(self.encoder).two_embed:
                 loss = self._token_loss()
@@ -178,6 +180,21 @@ class DDPMMulTrainer(DDPMTrainer):
             per_assign = (loss * self.src_mask).sum(dim=1).view(2, rows // 2).sum(dim=0)
             loss_mot_rec = per_assign.view(2, rows // 4).min(dim=0).values.sum() / (self.src_mask.sum() / 2)
         self.loss_mot_rec = loss_mot_rec
+        return OrderedDict({'loss_mot_rec': self.loss_mot_rec.item()})
+
+    def _backward_G_weighted(self):
+        """backward_G under opt.loss_weighting / opt.sampler: what hig_pair_mse_w computes.  Labelled: row r counts w[t_r]
+        times.  PIT: the assignment is chosen on the unweighted sums, the chosen sum of pair p counts w[t_p] times."""
+        mask = self.src_mask
+        if self.with_label:
+            loss = self._token_loss() if _core(self.encoder).two_embed else self.mse_criterion(self.fake_noise, self.real_noise).mean(dim=-1)
+            self.loss_mot_rec = self._weighted((loss * mask).sum(dim=1), mask.sum(), self._t, mask.sum(dim=1).clamp_min(1), loss.device)
+        else:
+            loss = self._token_loss()
+            rows = loss.shape[0]
+            per_assign = (loss * mask).sum(dim=1).view(2, rows // 2).sum(dim=0)
+            chosen = per_assign.view(2, rows // 4).min(dim=0).values
+            self.loss_mot_rec = self._weighted(chosen, mask.sum() / 2, self._t, 2 * mask[:rows // 4].sum(dim=1).clamp_min(1), loss.device)
         return OrderedDict({'loss_mot_rec': self.loss_mot_rec.item()})
 
     # ---- MI355X fused step (inherits train_step_fused / train_step_captured) ---------------------
@@ -209,11 +226,20 @@ class DDPMMulTrainer(DDPMTrainer):
         assert xf_proj.shape[0] == rows and xf_out.shape[0] == rows, "text embeddings must cover the model batch"
         pred, saved = core._launch_forward(x_t, t2, len_rows, xf_proj, xf_out, training=True)
         dpred = torch.empty_like(pred)
-        scr = st.get("pair_scratch")
-        if scr is None or scr.numel() < 2 * rows:
-            scr = st["pair_scratch"] = torch.zeros(2 * rows, device=pred.device, dtype=torch.float32)
-        _lib.check(L.hig_pair_mse(_lib.ptr(pred), _lib.ptr(noise.contiguous()), _lib.ptr(len_rows), rows, T, F, int(pit),
-                                  _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(scr), _lib.stream_ptr()))
+        scr = self._loss_buffer(st, "pair_scratch", 2 * rows, pred.device)      # (one per size: captured graphs keep theirs)
+        wtab, smp = self._loss_state(pred.device)
+        if wtab is None:
+            _lib.check(L.hig_pair_mse(_lib.ptr(pred), _lib.ptr(noise.contiguous()), _lib.ptr(len_rows), rows, T, F, int(pit),
+                                      _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(scr), _lib.stream_ptr()))
+        else:   # the weighted twin (row r counts w[t2[r]] times); loss-aware: one loss per pair (PIT) or per row, pushed under
+            # the first entries of t2, behind the loss launch
+            t2 = t2.contiguous()
+            sl = None if smp is None else self._loss_buffer(st, "sample_loss", rows // 4 if pit else rows, pred.device)
+            _lib.check(L.hig_pair_mse_w(_lib.ptr(pred), _lib.ptr(noise.contiguous()), _lib.ptr(len_rows), _lib.ptr(t2), _lib.ptr(wtab),
+                                        wtab.numel(), rows, T, F, int(pit), _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(sl),
+                                        _lib.ptr(scr), _lib.stream_ptr()))
+            if smp is not None:
+                smp.update(t2, sl)
         hook = {} if exchange is None else dict(layer_hook=exchange.layer_done, comm_stream=exchange.stream)
         _, dxp, dxo = core._launch_backward(x_t, t2, len_rows, xf_out, saved, dpred, want_dx=False, **hook)
         return dxp, dxo
@@ -227,7 +253,7 @@ class DDPMMulTrainer(DDPMTrainer):
         caption = caption1 + caption2
         if not self.with_label:
             caption = caption + caption2 + caption1
-        t, _ = self.sampler.sample(B, x_start.device)
+        t = self._draw_t(B, x_start.device)
         step = self.train_step_captured if captured else self.train_step_fused
         if self.cap_id:
             if not _core(self.encoder)._has_hip_class_head():

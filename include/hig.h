@@ -1437,6 +1437,59 @@ int hig_masked_mse(const float* pred, const float* target, const int64_t* length
  * scratch: 2 R floats (the row losses, then d loss / d rowloss). */
 int hig_pair_mse(const float* pred, const float* target, const int64_t* length, int32_t R, int32_t T,
                  int32_t F, int32_t pit, float* loss, float* dpred, float* scratch, hig_stream_t s);
+/* ------------------------------------------------------------------------------------------
+ * Per-timestep loss weights: a table `wtab` of nsteps fp32 weights on the device that the loss kernels index by each sample's
+ * timestep, and the device-side loss history that keeps such a table for loss-aware timestep sampling.  A t outside
+ * [0, nsteps) reads the nearest row of wtab, as the other DDPM entries do.
+ *
+ * hig_masked_mse_w: hig_masked_mse with sample b counted w[t[b]] times (t: B entries),
+ *     loss = sum_b w[t_b] sum_{tau < len_b} mean_f (p - q)^2 / sum(mask),      dpred = d loss / d pred  (nullable),
+ *   and, with sample_loss (nullable, B floats), the UNWEIGHTED per-sample mean a loss-aware sampler is fed:
+ *     sample_loss[b] = sum_{tau < len_b} mean_f (p - q)^2 / max(len_b, 1),     len_b = clamp(length[b], 0, T)
+ *   added by one thread per sample in frame order.  scratch: HIG_NORM_BLOCKS floats, and B T more behind them when
+ *   sample_loss is given (the row means).  Off the mask pred and target may hold anything (the row's own sum is discarded).
+ * hig_pair_mse_w: hig_pair_mse with row r counted w[t[r]] times (t: R entries; the rows of a pair carry the same t -- the
+ *   reference does t = cat([t, t]) -- and under PIT the weight of pair p is read at row p).  PIT still compares the unweighted
+ *   sums S0, S1: the weight is positive and common to both assignments, so the choice does not move.
+ *     pit == 1: loss = sum_p w[t_p] min(S0, S1) / (sum(mask) / 2);   sample_loss[p] = min(S0, S1) / (2 max(len_p, 1)), R / 4 floats
+ *     pit == 0: loss = sum_r w[t_r] rowloss[r] / sum(mask);          sample_loss[r] = rowloss[r] / max(len_r, 1),      R floats
+ *   scratch: 2 R floats (the row losses, then d loss / d rowloss = w / denom or 0), as hig_pair_mse.
+ * Each weighted kernel and its unweighted twin are one template over a flag; hig_masked_mse / hig_pair_mse launch the flag-off
+ * instance.  The weight enters as one product (w x the row's term into the sum, w x the gradient scale), so with wtab == 1.0f
+ * everywhere loss and dpred are the unweighted entries' bits.  No atomics, no allocation, no synchronisation: capturable; two
+ * calls give the same bits.  Refused with HIG_EINVAL before any HIP call, nothing written: a NULL pred / target / t / wtab /
+ * loss / scratch, nsteps, B (R), T or F <= 0 (hig_pair_mse_w: F < 4, and R % 4 != 0 under PIT).
+ * Bound (tests/loss_weight_bounds.py), u = 2^-24, wtab's fp32 entries taken as exact: the weighted sums carry one rounding more
+ * per term than the unweighted ones; dpred gam(5) |dpred|; sample_loss gam(F + 4 + len + 1) of itself (single person), b_row /
+ * len + gam(3) of itself (pairs).
+ *
+ * hig_loss_history_update: the state of the reference's LossSecondMomentResampler (gaussian_diffusion.py:123-153) on the
+ * device, one launch, two phases.
+ *   (a) push: for i = 0 .. n - 1 in batch order, v = base_w[t_i] * sample_loss[i] goes into the ring hist[t_i][0 .. H): while
+ *       counts[t] < H it is appended and the count grows; a full ring shifts out its oldest entry (hist[t][h] = hist[t][h + 1])
+ *       and stores v last, as update_with_all_losses does.  An entry with t outside [0, nsteps) is ignored.  An entry whose v
+ *       is NaN or infinite is ignored too -- a deviation from the reference, where one NaN would poison p for good.
+ *   (b) refresh: if every count equals H,
+ *         m_t = sqrt(mean_h hist[t][h]^2);   p_t = (1 - u) m_t / sum_t m_t + u / N;   w_t = base_w[t] / (N p_t),   N = nsteps,
+ *       the sampling probabilities (weights() of the reference, normalised) and the importance weights 1 / (N p_t) folded into
+ *       the static table base_w (all ones, or the min-SNR table); otherwise p_t = fp32(1 / N) and w_t = base_w[t] exactly.  A
+ *       sum_t m_t that is 0, NaN or infinite also leaves the uniform result (the reference would return NaN).
+ *   History, p and w are fp32 (the reference's history is float64); counts are int32 and saturate at H.  n == 0 (t and
+ *   sample_loss may then be NULL) is the refresh alone.  One workgroup: a thread owns the timesteps i, i + 1024, .. and scans the
+ *   batch for them, so entries that share a timestep are pushed in batch order; "all full" and sum m are block reductions in a
+ *   fixed order.  No atomics, no allocation, no synchronisation: capturable.  Refused with HIG_EINVAL before any HIP call: a
+ *   NULL hist / counts / base_w / p_out / w_out, nsteps or H <= 0, n < 0, n > 0 with a NULL t or sample_loss, uniform_prob
+ *   outside [0, 1].  hist: nsteps x H floats; counts, base_w, p_out, w_out: nsteps entries. */
+int hig_masked_mse_w(const float* pred, const float* target, const int64_t* length /* nullable */, const int64_t* t,
+                     const float* wtab, int32_t nsteps, int32_t B, int32_t T, int32_t F, float* loss /* device scalar */,
+                     float* dpred /* nullable */, float* sample_loss /* nullable, B */,
+                     float* scratch /* HIG_NORM_BLOCKS (+ B T with sample_loss) floats */, hig_stream_t s);
+int hig_pair_mse_w(const float* pred, const float* target, const int64_t* length /* nullable */, const int64_t* t, const float* wtab,
+                   int32_t nsteps, int32_t R, int32_t T, int32_t F, int32_t pit, float* loss, float* dpred /* nullable */,
+                   float* sample_loss /* nullable, R / 4 (pit) or R */, float* scratch /* 2 R floats */, hig_stream_t s);
+int hig_loss_history_update(const int64_t* t /* nullable iff n == 0 */, const float* sample_loss /* nullable iff n == 0 */, int32_t n,
+                            float* hist, int32_t* counts, const float* base_w, int32_t nsteps, int32_t H, float uniform_prob,
+                            float* p_out, float* w_out, hig_stream_t s);
 /* The labelling pass of the two-person recipe (DDPMMulTrainer.label_votes; mul_ddpm_trainer.py:313-440 of the reference): one
  * draw is q_sample into the forward_twice layout, the denoiser at 4 x pairs rows, and the per-pair vote.
  *
