@@ -435,17 +435,17 @@ extern "C" int hig_clip_text_fwd_train(const int32_t* dims, const void* const* p
   return hig_layernorm(xin, W, M, W, CP(params, HIG_CT_LNF_W), CP(params, HIG_CT_LNF_B), out, W, ws + w.stf, stream);
 }
 
-extern "C" int hig_clip_text_bwd(const int32_t* dims, const void* const* params, const int32_t* index, int32_t n_live, int32_t n_chunks,
-                                 int32_t n_ids, const float* dout, const void* saved, void* const* grads, void* bwd_workspace,
-                                 hig_stream_t stream) {
-  CDims D;
-  HIG_REQUIRE(params && grads, "hig_clip_text_bwd: null table");
-  HIG_TRY(check_train(dims, D, "hig_clip_text_bwd"));
-  HIG_REQUIRE(index && dout && saved && bwd_workspace, "hig_clip_text_bwd: null argument");
-  HIG_REQUIRE(n_live >= 0 && n_live <= D.M && n_chunks >= 0 && n_chunks <= n_live && n_ids >= 0 && n_ids <= n_chunks && (n_live == 0) == (n_ids == 0),
-              "hig_clip_text_bwd: index counts (live %d, chunks %d, ids %d) that no %lld rows give", n_live, n_chunks, n_ids, (long long)D.M);
+namespace {
+// Everything of the adjoint in front of the embedding pass, shared by hig_clip_text_bwd and hig_clip_text_bwd_dev: checks the
+// tables and buffers, runs ln_final and the layers in reverse, and leaves d(x0) (B N, W) at *dx0 and the embedding pass's
+// scratch at *emb.
+int text_bwd_front(const char* who, const int32_t* dims, const void* const* params, const float* dout, const void* saved, void* const* grads,
+                   void* bwd_workspace, hig_stream_t stream, CDims& D, const float** dx0, float** emb) {
+  HIG_REQUIRE(params && grads, "%s: null table", who);
+  HIG_TRY(check_train(dims, D, who));
+  HIG_REQUIRE(dout && saved && bwd_workspace, "%s: null argument", who);
   for (int i = 0; i < HIG_CT_NGLOBAL + D.L * HIG_CTL_NLAYER; ++i)
-    HIG_REQUIRE(params[i] && grads[i], "hig_clip_text_bwd: null parameter or gradient %d", i);
+    HIG_REQUIRE(params[i] && grads[i], "%s: null parameter or gradient %d", who, i);
   const CTrain w = ctrain_layout(D);
   const CBwd bw = cbwd_layout(D);
   const float* ws = static_cast<const float*>(saved);
@@ -497,6 +497,38 @@ extern "C" int hig_clip_text_bwd(const int32_t* dims, const void* const* params,
     HIG_TRY(hig_ln_bwd(t1, W, xin, W, lb + w.st1, p(HIG_CTL_LN1_W), p(HIG_CTL_LN1_B), nullptr, 0, 0, 0, t2, W, d, W, M, W, D.N,
                        g(HIG_CTL_LN1_W), g(HIG_CTL_LN1_B), nullptr, 0, e.lnp, stream));    // d = d(xin) = d(x1) + the norm's
   }
-  return hig_clip_embed_bwd(d, D.B, D.N, W, D.vocab, index, n_live, n_chunks, n_ids, b + bw.emb, CG(grads, HIG_CT_TOK_EMB),
+  *dx0 = d;
+  *emb = b + bw.emb;
+  return HIG_OK;
+}
+}  // namespace
+
+extern "C" int hig_clip_text_bwd(const int32_t* dims, const void* const* params, const int32_t* index, int32_t n_live, int32_t n_chunks,
+                                 int32_t n_ids, const float* dout, const void* saved, void* const* grads, void* bwd_workspace,
+                                 hig_stream_t stream) {
+  CDims D;
+  HIG_REQUIRE(params && grads, "hig_clip_text_bwd: null table");
+  HIG_TRY(check_train(dims, D, "hig_clip_text_bwd"));
+  HIG_REQUIRE(index && dout && saved && bwd_workspace, "hig_clip_text_bwd: null argument");
+  HIG_REQUIRE(n_live >= 0 && n_live <= D.M && n_chunks >= 0 && n_chunks <= n_live && n_ids >= 0 && n_ids <= n_chunks && (n_live == 0) == (n_ids == 0),
+              "hig_clip_text_bwd: index counts (live %d, chunks %d, ids %d) that no %lld rows give", n_live, n_chunks, n_ids, (long long)D.M);
+  const float* d;
+  float* emb;
+  HIG_TRY(text_bwd_front("hig_clip_text_bwd", dims, params, dout, saved, grads, bwd_workspace, stream, D, &d, &emb));
+  return hig_clip_embed_bwd(d, D.B, D.N, D.W, D.vocab, index, n_live, n_chunks, n_ids, emb, CG(grads, HIG_CT_TOK_EMB),
                             CG(grads, HIG_CT_POS_EMB), stream);
+}
+
+// the same launches up to d(x0), then the embedding pass on the device-built index (hig_clip_embed_index_build)
+extern "C" int hig_clip_text_bwd_dev(const int32_t* dims, const void* const* params, const int32_t* index, const int32_t* counts,
+                                     const float* dout, const void* saved, void* const* grads, void* bwd_workspace, hig_stream_t stream) {
+  CDims D;
+  HIG_REQUIRE(params && grads, "hig_clip_text_bwd_dev: null table");
+  HIG_TRY(check_train(dims, D, "hig_clip_text_bwd_dev"));
+  HIG_REQUIRE(index && counts && dout && saved && bwd_workspace, "hig_clip_text_bwd_dev: null argument");
+  HIG_REQUIRE(((reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(counts)) & 3) == 0, "hig_clip_text_bwd_dev: unaligned buffer");
+  const float* d;
+  float* emb;
+  HIG_TRY(text_bwd_front("hig_clip_text_bwd_dev", dims, params, dout, saved, grads, bwd_workspace, stream, D, &d, &emb));
+  return hig_clip_embed_bwd_dev(d, D.B, D.N, D.W, D.vocab, index, counts, emb, CG(grads, HIG_CT_TOK_EMB), CG(grads, HIG_CT_POS_EMB), stream);
 }

@@ -198,8 +198,14 @@ __global__ __launch_bounds__(256) void quick_gelu_bwd_kernel(const float* __rest
 }
 
 // ---- dst[ids[u]][:] = src[u][:], u < n_ids; an id outside [0, vocab) writes nothing ---------------------------------------------
-__global__ __launch_bounds__(256) void scatter_rows_kernel(const float* __restrict__ src, const int32_t* __restrict__ ids, int n_ids, int W,
-                                                            int vocab, float* __restrict__ dst) {
+// DEVN: n_ids is a capacity (it sizes the grid) and *n_dev the count, kept on the device; rows at or past it are not touched.
+template <bool DEVN>
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const float* __restrict__ src, const int32_t* __restrict__ ids, int n_ids,
+                                                            const int32_t* __restrict__ n_dev, int W, int vocab, float* __restrict__ dst) {
+  if constexpr (DEVN) {
+    const int live = *n_dev;
+    n_ids = live < n_ids ? (live < 0 ? 0 : live) : n_ids;
+  }
   for (int u = blockIdx.x; u < n_ids; u += gridDim.x) {
     const int id = ids[u];
     if (id < 0 || id >= vocab) continue;
@@ -295,8 +301,41 @@ extern "C" int hig_clip_embed_bwd(const float* dx0, int32_t B, int32_t N, int32_
   HIG_TRY(hig_rows_segment_sum_f32(partial, n_chunks, chunk_order, id_seg, n_ids, W, usum, stream));
   if (n_ids > 0) {
     const int cap = hig_chip_cus() * 8;
-    hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)(n_ids < cap ? n_ids : cap)), dim3(256), 0, st, usum, ids, n_ids, W, vocab, dtok);
+    hipLaunchKernelGGL(scatter_rows_kernel<false>, dim3((unsigned)(n_ids < cap ? n_ids : cap)), dim3(256), 0, st, usum, ids, n_ids,
+                       (const int32_t*)nullptr, W, vocab, dtok);
     HIG_CHECK_LAUNCH();
   }
   return hig_rows_segment_sum_f32(dx0, (int32_t)M, pos_order, pos_seg, N, W, dpos, stream);
+}
+
+extern "C" int64_t hig_clip_embed_bwd_dev_scratch_floats(int32_t B, int32_t N, int32_t W, int32_t vocab) {
+  if (B < 0 || N <= 0 || W <= 0 || vocab <= 0 || (int64_t)B * N > 0x7fffffff) return -1;
+  const hig_clip_index_layout_t l = hig_clip_index_layout(B, N, vocab);
+  return (l.part_rows + l.cap_ids) * W;
+}
+
+// hig_clip_embed_bwd on the capacity layout: the same four launches on grids sized by the capacities, each reading its count
+// from `counts` on the device.
+extern "C" int hig_clip_embed_bwd_dev(const float* dx0, int32_t B, int32_t N, int32_t W, int32_t vocab, const int32_t* index,
+                                      const int32_t* counts, float* scratch, float* dtok, float* dpos, hig_stream_t stream) {
+  HIG_REQUIRE(dx0 && index && counts && scratch && dtok && dpos, "hig_clip_embed_bwd_dev: null argument");
+  HIG_REQUIRE(B >= 0 && N > 0 && W > 0 && vocab > 0, "hig_clip_embed_bwd_dev: bad extent (B=%d N=%d W=%d vocab=%d)", B, N, W, vocab);
+  HIG_REQUIRE((int64_t)B * N <= 0x7fffffff, "hig_clip_embed_bwd_dev: B * N beyond an int32 row index");
+  HIG_REQUIRE(((reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(scratch)) & 3) == 0,
+              "hig_clip_embed_bwd_dev: unaligned buffer");
+  const hig_clip_index_layout_t l = hig_clip_index_layout(B, N, vocab);
+  HIG_REQUIRE(l.cap_chunks <= 0x7fffffff, "hig_clip_embed_bwd_dev: chunk capacity beyond int32");
+  hipStream_t st = hig_stream(stream);
+  const int32_t M = (int32_t)l.M, cap_chunks = (int32_t)l.part_rows, cap_ids = (int32_t)l.cap_ids;
+  float* partial = scratch;                              // (part_rows, W)
+  float* usum = scratch + l.part_rows * W;               // (cap_ids, W)
+  HIG_TRY(hig_zero_async(dtok, (int64_t)vocab * W * 4, st));
+  if (B == 0) return hig_zero_async(dpos, (int64_t)N * W * 4, st);
+  HIG_TRY(hig_rows_segment_sum_dev(dx0, M, index + l.order, index + l.chunk_seg, cap_chunks, counts + 1, W, partial, stream));
+  HIG_TRY(hig_rows_segment_sum_dev(partial, cap_chunks, index + l.chunk_order, index + l.id_seg, cap_ids, counts + 2, W, usum, stream));
+  const int cap = hig_chip_cus() * 8;
+  hipLaunchKernelGGL(scatter_rows_kernel<true>, dim3((unsigned)(cap_ids < cap ? cap_ids : cap)), dim3(256), 0, st, usum, index + l.ids,
+                     cap_ids, counts + 2, W, vocab, dtok);
+  HIG_CHECK_LAUNCH();
+  return hig_rows_segment_sum_f32(dx0, M, index + l.pos_order, index + l.pos_seg, N, W, dpos, stream);
 }

@@ -236,6 +236,31 @@ bool hig_gemm_wsp32_active();   // that kernel is switched on and the chip has t
 // rowops.hip: fill / copy as kernels (never hipMemsetAsync / hipMemcpyAsync on a stream that may be under capture: see there)
 int hig_zero_async(void* p, int64_t bytes, hipStream_t st);
 int hig_copy_async(void* dst, const void* src, int64_t bytes, hipStream_t st);
+// textrows.hip: hig_rows_segment_sum_f32 over the first *n_seg_dev of cap_seg segments (a count kept on the device)
+int hig_rows_segment_sum_dev(const float* src, int32_t n_src, const int32_t* order, const int32_t* seg, int32_t cap_seg,
+                             const int32_t* n_seg_dev, int64_t row_floats, float* dst, hig_stream_t stream);
+// The capacity layout of the embedding index built on the device (include/hig.h, hig_clip_embed_index_build): int32 offsets of
+// the seven arrays, a function of (B, N, vocab) only.  part_rows: the rows the chunk partials can take (n_chunks <= n_live <= M).
+struct hig_clip_index_layout_t {
+  int64_t M, cap_ids, cap_chunks, part_rows;
+  int64_t order, chunk_seg, chunk_order, id_seg, ids, pos_order, pos_seg, total;
+};
+inline hig_clip_index_layout_t hig_clip_index_layout(int64_t B, int64_t N, int64_t vocab) {
+  hig_clip_index_layout_t l;
+  l.M = B * N;
+  l.cap_ids = l.M < vocab ? l.M : vocab;
+  l.cap_chunks = (l.M + HIG_CLIP_EMBED_CHUNK - 1) / HIG_CLIP_EMBED_CHUNK + l.cap_ids;
+  l.part_rows = l.cap_chunks < l.M ? l.cap_chunks : l.M;
+  l.order = 0;
+  l.chunk_seg = l.order + l.M;
+  l.chunk_order = l.chunk_seg + l.cap_chunks + 1;
+  l.id_seg = l.chunk_order + l.cap_chunks;
+  l.ids = l.id_seg + l.cap_ids + 1;
+  l.pos_order = l.ids + l.cap_ids;
+  l.pos_seg = l.pos_order + l.M;
+  l.total = l.pos_seg + N + 1;
+  return l;
+}
 // the buffer of hig_enc_bwd_debug_tap (texthead.hip; include/hig.h): NULL, 0 in every real run
 void hig_enc_tap_buffer(float** buf, int64_t* bytes);
 

@@ -60,11 +60,18 @@ __global__ __launch_bounds__(TR_NT) void rows_gather_kernel(const float* __restr
 // lists here are short and even (at most about 1 300 rows over 44 segments, the captions of one step), so the chunked form
 // that splits long lists over several waves would buy nothing: one walker per column it is.  An entry of `order` outside
 // [0, n_src) reads nothing and contributes NaN.
-template <bool VEC>
+// DEVN: n_seg is a capacity (it sizes the launch) and *n_dev the number of segments, a count that lives on the device
+// (hig_clip_embed_index_build); items at or past it exit without a read or a write.  A segment's sum does not depend on the flag.
+template <bool VEC, bool DEVN>
 __global__ __launch_bounds__(TR_NT) void rows_segment_sum_kernel(const float* __restrict__ src, int n_src,
                                                                  const int32_t* __restrict__ order, const int32_t* __restrict__ seg,
-                                                                 int n_seg, int64_t nvec, int parts, float* __restrict__ dst) {
+                                                                 int n_seg, const int32_t* __restrict__ n_dev, int64_t nvec, int parts,
+                                                                 float* __restrict__ dst) {
   using E = typename RowElem<VEC>::type;
+  if constexpr (DEVN) {
+    const int live = *n_dev;
+    n_seg = live < n_seg ? (live < 0 ? 0 : live) : n_seg;
+  }
   const int64_t items = (int64_t)n_seg * parts;
   for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
     const int u = (int)(item / parts), part = (int)(item % parts);
@@ -195,6 +202,22 @@ extern "C" int hig_caption_gather(const float* feat, const int64_t* eot_src, int
   return gather_launch("hig_caption_gather", feat, n_slots, slot, rows, row_floats, clip_out, eot_src, eot, stream);
 }
 
+namespace {
+// the one launch site of rows_segment_sum_kernel: n_dev == NULL is hig_rows_segment_sum_f32, else hig_rows_segment_sum_dev
+int segment_sum_launch(const float* src, int32_t n_src, const int32_t* order, const int32_t* seg, int32_t n_seg, const int32_t* n_dev,
+                       int64_t row_floats, float* dst, hig_stream_t stream) {
+  const RowSplit s = row_split(src, dst, n_seg, row_floats);
+#define TR_SEG(VECV, DEVV)                                                                                                        \
+  hipLaunchKernelGGL((rows_segment_sum_kernel<VECV, DEVV>), dim3(s.grid), dim3(TR_NT), 0, hig_stream(stream), src, (int)n_src, order, seg, \
+                     (int)n_seg, n_dev, s.nvec, s.parts, dst)
+  if (n_dev) { if (s.vec) TR_SEG(true, true); else TR_SEG(false, true); }
+  else { if (s.vec) TR_SEG(true, false); else TR_SEG(false, false); }
+#undef TR_SEG
+  HIG_CHECK_LAUNCH();
+  return HIG_OK;
+}
+}  // namespace
+
 extern "C" int hig_rows_segment_sum_f32(const float* src, int32_t n_src, const int32_t* order, const int32_t* seg, int32_t n_seg,
                                         int64_t row_floats, float* dst, hig_stream_t stream) {
   HIG_REQUIRE(src && order && seg && dst, "hig_rows_segment_sum_f32: src, order, seg and dst must be non-null");
@@ -204,15 +227,17 @@ extern "C" int hig_rows_segment_sum_f32(const float* src, int32_t n_src, const i
                 reinterpret_cast<uintptr_t>(seg)) & 3) == 0, "hig_rows_segment_sum_f32: pointers must be 4-byte aligned");
   HIG_REQUIRE(row_floats < ((int64_t)1 << 40), "hig_rows_segment_sum_f32: row_floats %lld is out of range", (long long)row_floats);
   if (n_seg == 0 || row_floats == 0) return HIG_OK;
-  const RowSplit s = row_split(src, dst, n_seg, row_floats);
-  if (s.vec)
-    hipLaunchKernelGGL(rows_segment_sum_kernel<true>, dim3(s.grid), dim3(TR_NT), 0, hig_stream(stream), src, (int)n_src, order, seg,
-                       (int)n_seg, s.nvec, s.parts, dst);
-  else
-    hipLaunchKernelGGL(rows_segment_sum_kernel<false>, dim3(s.grid), dim3(TR_NT), 0, hig_stream(stream), src, (int)n_src, order, seg,
-                       (int)n_seg, s.nvec, s.parts, dst);
-  HIG_CHECK_LAUNCH();
-  return HIG_OK;
+  return segment_sum_launch(src, n_src, order, seg, n_seg, nullptr, row_floats, dst, stream);
+}
+
+// hig_host.h: the same sum over the first *n_seg_dev of cap_seg segments; the grid is sized by cap_seg, so the launch does not
+// depend on the count and a captured graph serves every batch.  Arguments are the caller's (cliptext_bwd.hip), checked there.
+int hig_rows_segment_sum_dev(const float* src, int32_t n_src, const int32_t* order, const int32_t* seg, int32_t cap_seg,
+                             const int32_t* n_seg_dev, int64_t row_floats, float* dst, hig_stream_t stream) {
+  HIG_REQUIRE(src && order && seg && n_seg_dev && dst && n_src >= 0 && cap_seg >= 0 && row_floats >= 0,
+              "hig_rows_segment_sum_dev: null argument or negative size");
+  if (cap_seg == 0 || row_floats == 0) return HIG_OK;
+  return segment_sum_launch(src, n_src, order, seg, cap_seg, n_seg_dev, row_floats, dst, stream);
 }
 
 // The only parallelism is keys x columns (a key's rows are added in order by one lane per column), so the column range of an

@@ -11,7 +11,11 @@ package brings the tower as stock torch ops; this module has
     a given tower, its pointer table, and the call;
   * `TrainTowerTable` / `EmbedIndex` / `tower_forward_train` / `tower_backward` / `_ClipTowerFn`: the same for a TRAINABLE tower
     (`MotionInteractionTransformer(no_clip=True, clip_tower_train="hip")`) through hig_clip_text_fwd_train / hig_clip_text_bwd,
-    with the embedding gradient's inverted index built on the host from the tokenizer's CPU tokens.
+    with the embedding gradient's inverted index built on the host from the tokenizer's CPU tokens;
+  * `TokenBatch` / `DeviceEmbedIndex` / `tower_backward_dev`: the tower inside the fused / captured training step
+    (`clip_tower_train="flat"`, trainers/text_source.py: Tokens): the distinct captions' tokens with their row maps as one
+    packed upload, the index built on the device by hig_clip_embed_index_build, and hig_clip_text_bwd_dev writing the
+    gradients into the flat gradient buffer.
 
 The BPE vocabulary is data this repository does not carry: without the `clip` package the caller supplies the tokenizer
 (`MotionTransformer(clip_model=..., clip_tokenize=...)`).
@@ -428,3 +432,168 @@ class _ClipTowerFn(torch.autograd.Function):
         ctx.saved = None
         ctx.owner.clip_train_stats["native_backwards"] += 1
         return (None, None, None, None) + tuple(g if p.requires_grad else None for g, p in zip(grads, ctx.table.tensors))
+
+
+# ---- the trainable tower inside the fused / captured step ------------------------------------------------------------------------
+class TokenBatch:
+    """The text input of a fused step that trains the tower (trainers/text_source.py: Tokens), built on the host: the tokens of
+    the step's DISTINCT captions and the row maps that expand the text side's output to the model batch and sum its upstream
+    gradients back -- `inv`, `order`, `seg` exactly as the caption bank's CaptionBatch builds them (distinct captions in order
+    of first appearance, U rounded up by `padded_unique`).  Padding entries repeat the first distinct caption's tokens and have
+    empty segments, so their upstream gradient is exactly zero.  dedup=False: the identity maps over all rows (U = U_pad = rows).
+    Everything is int32 words of ONE packed buffer (`host`; `to(device)` uploads it from pinned memory):
+        tokens (U_pad, N) int64 | eot (U_pad,) int64 | inv (rows,) | order (rows,) | seg (U_pad + 1,) | U
+    whose layout depends on (rows, U_pad, N) alone: a captured step copies `dev` into its static twin.
+    `cache`: a dict caption -> (token row, eot) kept by the caller, so that the tokenizer never runs on a caption twice."""
+
+    def __init__(self, captions, tokenize, dedup=True, cache=None):
+        from .caption_bank import padded_unique
+        captions = list(captions)
+        rows = len(captions)
+        if rows == 0:
+            raise ValueError("TokenBatch: no captions")
+        if not all(isinstance(c, str) for c in captions):
+            raise TypeError("TokenBatch: captions must be strings")
+        cache = {} if cache is None else cache
+        missing = [c for c in dict.fromkeys(captions) if c not in cache]
+        self.tokenizer_rows = len(missing)
+        if missing:
+            tok = tokenize(missing).to("cpu", torch.int64)      # (the model's `_tokenize`: one call for all of them)
+            for c, row in zip(missing, tok):
+                cache[c] = (row.clone(), int(row.argmax()))
+        if dedup:
+            index, uniq, inv = {}, [], []
+            for c in captions:
+                u = index.get(c)
+                if u is None:
+                    u = index[c] = len(uniq)
+                    uniq.append(c)
+                inv.append(u)
+            U, U_pad = len(uniq), padded_unique(len(uniq))
+        else:
+            uniq, inv, U, U_pad = captions, list(range(rows)), rows, rows
+        count = [0] * U
+        for u in inv:
+            count[u] += 1
+        seg = [0] * (U_pad + 1)
+        for u in range(U):
+            seg[u + 1] = seg[u] + count[u]
+        for u in range(U, U_pad):
+            seg[u + 1] = rows
+        order, cursor = [0] * rows, seg[:U]
+        for r, u in enumerate(inv):
+            order[cursor[u]] = r
+            cursor[u] += 1
+        padded = uniq + [uniq[0]] * (U_pad - U)
+        tokens = torch.stack([cache[c][0] for c in padded])
+        eot = torch.tensor([cache[c][1] for c in padded], dtype=torch.int64)
+        self.rows, self.U, self.U_pad, self.N, self.dedup = rows, U, U_pad, int(tokens.shape[1]), bool(dedup)
+        host = torch.cat([tokens.reshape(-1).view(torch.int32), eot.view(torch.int32),
+                          torch.tensor(inv + order + seg + [U], dtype=torch.int32)])
+        assert host.numel() == self.numel(rows, U_pad, self.N)
+        self._bind(host, None)
+
+    @staticmethod
+    def layout(rows, U_pad, N):
+        """name -> (first int32 word, one past the last); tokens and eot are int64, two words each."""
+        out, o = {}, 0
+        for name, n in (("tokens", 2 * U_pad * N), ("eot", 2 * U_pad), ("inv", rows), ("order", rows), ("seg", U_pad + 1)):
+            out[name] = (o, o + n)
+            o += n
+        return out
+
+    @staticmethod
+    def numel(rows, U_pad, N):
+        return 2 * U_pad * N + 2 * U_pad + 2 * rows + U_pad + 2
+
+    def _bind(self, host, dev):
+        self.host, self.dev = host, dev
+        for name, (lo, hi) in self.layout(self.rows, self.U_pad, self.N).items():
+            for suffix, buf in (("_host", host), ("", dev)):
+                v = None if buf is None else buf[lo:hi]
+                if v is not None and name in ("tokens", "eot"):
+                    v = v.view(torch.int64)
+                    v = v.view(self.U_pad, self.N) if name == "tokens" else v
+                setattr(self, name + suffix, v)
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type == "cuda" and not self.host.is_pinned():
+            self.host = self.host.pin_memory()
+        self._bind(self.host, self.host.to(device, non_blocking=True))
+        return self
+
+    def on_buffer(self, dev):
+        """The same request read from another device buffer of the same layout (the static input of a captured step)."""
+        assert dev.shape == self.host.shape and dev.dtype == torch.int32
+        twin = object.__new__(TokenBatch)
+        twin.rows, twin.U, twin.U_pad, twin.N, twin.dedup, twin.tokenizer_rows = self.rows, self.U, self.U_pad, self.N, self.dedup, 0
+        twin._bind(self.host, dev)
+        return twin
+
+
+def index_capacity(B, N, vocab, chunk=None):
+    """The capacity layout of hig_clip_embed_index_build (include/hig.h) restated: {name: (first int32, entries)}, the total, and
+    (cap_ids, cap_chunks)."""
+    chunk = embed_chunk() if chunk is None else int(chunk)
+    M = B * N
+    cap_ids = min(M, vocab)
+    cap_chunks = (M + chunk - 1) // chunk + cap_ids
+    out, o = {}, 0
+    for name, n in zip(EmbedIndex.FIELDS, (M, cap_chunks + 1, cap_chunks, cap_ids + 1, cap_ids, M, N + 1)):
+        out[name] = (o, n)
+        o += n
+    return out, o, (cap_ids, cap_chunks)
+
+
+class DeviceEmbedIndex:
+    """The buffers of hig_clip_embed_index_build for one (B, N, vocab): `index` (the capacity layout), `counts` (n_live, n_chunks,
+    n_ids) and the sort's scratch, allocated once -- a captured step holds their pointers.  `build(tokens)` launches the entry on
+    the current stream; `live()` reads the live prefix of every array back (tests and tools only: it synchronises)."""
+
+    def __init__(self, B, N, vocab, device):
+        from .. import _lib
+        L = _lib.lib()
+        ints, nbytes = L.hig_clip_embed_index_cap_ints(B, N, vocab), L.hig_clip_embed_index_scratch_bytes(B, N, vocab)
+        if ints < 0 or nbytes < 0:
+            raise RuntimeError("libhig: %s" % _lib.last_error())
+        self.B, self.N, self.vocab, self.device = B, N, vocab, torch.device(device)
+        self.index = torch.zeros(ints, dtype=torch.int32, device=device)
+        self.counts = torch.zeros(3, dtype=torch.int32, device=device)
+        self.scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+    def build(self, tokens):
+        from .. import _lib
+        assert tokens.shape == (self.B, self.N) and tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.device == self.index.device
+        _lib.check(_lib.lib().hig_clip_embed_index_build(_lib.ptr(tokens), self.B, self.N, self.vocab, _lib.ptr(self.index),
+                                                         _lib.ptr(self.counts), _lib.ptr(self.scratch), _lib.stream_ptr()))
+        return self
+
+    def live(self):
+        lay = index_capacity(self.B, self.N, self.vocab)[0]
+        n_live, n_chunks, n_ids = (int(v) for v in self.counts.cpu())
+        host = self.index.cpu().numpy()
+        lens = (n_live, n_chunks + 1, n_chunks, n_ids + 1, n_ids, self.B * self.N, self.N + 1)
+        return (n_live, n_chunks, n_ids), {name: host[lay[name][0]:lay[name][0] + n] for name, n in zip(EmbedIndex.FIELDS, lens)}
+
+
+def tower_backward_dev(table, dindex, dout, saved, gtable, pool=None):
+    """hig_clip_text_bwd_dev: upstream dout (B, N, W) -> the gradients of table.tensors written through `gtable` (a c_void_p table in
+    that order: the fused step points it into the flat gradient buffer), with the embedding pass on the device-built index."""
+    from .. import _lib
+    dims, ws, B = saved
+    dev = table.device
+    if (dindex.B, dindex.N, dindex.vocab) != (B, table.N, table.vocab) or dindex.index.device != dev:
+        raise RuntimeError("CLIP text tower: the embedding index does not belong to these tokens")
+    dout = dout.contiguous()
+    assert dout.shape == (B, table.N, table.W) and dout.dtype == torch.float32
+    L = _lib.lib()
+    nb = L.hig_clip_text_bwd_workspace_bytes(dims)
+    if nb < 0:
+        raise RuntimeError("libhig: %s" % _lib.last_error())
+    bws = pool.take("clip_bwd", nb, dev) if pool is not None else torch.empty(nb, dtype=torch.uint8, device=dev)
+    _lib.check(L.hig_clip_text_bwd_dev(dims, table.table, _lib.ptr(dindex.index), _lib.ptr(dindex.counts), _lib.ptr(dout), _lib.ptr(ws),
+                                       gtable, _lib.ptr(bws), _lib.stream_ptr()))
+    if pool is not None:
+        pool.give("clip_bwd", bws, dev)
+        pool.give("clip_t", ws, dev)

@@ -129,9 +129,15 @@ class MotionInteractionTransformer(MotionTransformer):
         self._init_clip_route(kargs)
         # `clip_tower_train` (with `no_clip`): "hip" runs a qualifying TRAINABLE tower through hig_clip_text_fwd_train /
         # hig_clip_text_bwd (clip_text.tower_refusal(trainable=True) is the rule), "torch" (the default) keeps it on torch ops.
+        # "flat" does what "hip" does and also places the tower's parameters behind the text head in the flat parameter buffer
+        # (transformer._FlatParams), so that the fused / captured training step trains them (`token_batch=` of the trainer's
+        # steps); it needs a `no_clip` model and a tower the rule accepts, and raises otherwise.
         self.clip_tower_train = kargs.get("clip_tower_train", os.environ.get("HIG_CLIP_TOWER_TRAIN", "torch"))
-        if self.clip_tower_train not in ("hip", "torch"):
-            raise ValueError("clip_tower_train must be 'hip' or 'torch' (got %r)" % (self.clip_tower_train,))
+        if self.clip_tower_train not in ("hip", "torch", "flat"):
+            raise ValueError("clip_tower_train must be 'hip', 'torch' or 'flat' (got %r)" % (self.clip_tower_train,))
+        if self.clip_tower_train == "flat" and (self.cap_id or not getattr(self, "no_clip", False)):
+            raise ValueError("clip_tower_train='flat' needs a model that trains its CLIP text tower (no_clip=True, not cap_id): this "
+                             "one's tower is %s" % ("absent (cap_id)" if self.cap_id else "frozen"))
         self._clip_train_table = None
         self.clip_train_stats = {"native_forwards": 0, "native_backwards": 0, "native_inference": 0}
         # `class_head` (with `cap_id`): "hip" puts cap_embedding and text_proj into the flat buffer behind the core and lets the
@@ -158,10 +164,12 @@ class MotionInteractionTransformer(MotionTransformer):
         """The pointer table of the trainable tower when `encode_text` takes the native route for these tokens, else None: the
         model is `no_clip`, the option is "hip", the tokens are on a ROCm device and clip_text.tower_refusal(trainable=True)
         finds nothing (asked once; a tower that did not qualify is asked again only after `_apply` or a load)."""
-        if self.clip_tower_train != "hip" or not tokens.is_cuda or not getattr(self, "no_clip", False):
+        if self.clip_tower_train not in ("hip", "flat") or not tokens.is_cuda or not getattr(self, "no_clip", False):
             return None
         if not hasattr(getattr(self.clip, "transformer", None), "resblocks"):
             return None
+        if self.clip_tower_train == "flat":
+            self.flat_params()      # (re-homes the tower first: the table below holds the flat buffer's pointers)
         t = self._clip_train_table
         if isinstance(t, clip_text.TrainTowerTable) and (t.device != tokens.device or t.stale()):
             t = None
@@ -220,6 +228,20 @@ class MotionInteractionTransformer(MotionTransformer):
         x = self.clip.transformer(x)
         x = self.clip.ln_final(x).type(self.clip.d_type)
         return self._text_head(text, x)
+
+    def flat_tower_table(self):
+        """The TrainTowerTable of a tower that lives in the flat parameter buffer (clip_tower_train="flat"), its pointers the
+        buffer's: what the fused / captured step's Tokens source runs the tower through.  No fallback: raises when the model has
+        no such tower."""
+        fp = self.flat_params()
+        if not fp.tower_params:
+            raise RuntimeError("token_batch= needs a no_clip model built with clip_tower_train='flat' (or HIG_CLIP_TOWER_TRAIN=flat): "
+                               "this model's CLIP text tower is not in the flat parameter buffer")
+        t = self._clip_train_table
+        if not isinstance(t, clip_text.TrainTowerTable) or t.device != fp.flat.device or t.stale():
+            t = self._clip_train_table = clip_text.TrainTowerTable(self.clip, fp.flat.device)
+        assert all(a is b for a, b in zip(t.tensors, fp.tower_params))
+        return t
 
     def get_class_embedding(self, text):
         """:558-563: caption ids -> learned class embeddings (cap_id models)."""

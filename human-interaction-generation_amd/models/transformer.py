@@ -178,7 +178,9 @@ class _FlatParams:
     The nn.Parameters become views into it; state-dict names/shapes are untouched.
     The text-head parameters (when the model has a HIP text head) follow the core in the same
     buffer -- `[0, core_numel)` core, `[core_numel, numel)` text head -- so the fused training step
-    can update everything that is trainable with one all-reduce and one clip+Adam."""
+    can update everything that is trainable with one all-reduce and one clip+Adam.  With
+    `clip_tower_train="flat"` (a `no_clip` model) the trainable CLIP text tower follows the text head:
+    `tower_params` / `tower_offsets`.  The bf16 weight shadow stays core-only."""
 
     ALIGN = 64  # floats (256 B)
 
@@ -209,18 +211,42 @@ class _FlatParams:
         for p in self.text_params:
             self.text_offsets.append(o)
             o += (p.numel() + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        # the trainable CLIP tower (clip_tower_train="flat"; clip_text._tower_tensors order), one aligned group per tensor, behind
+        # the text head: `[core_numel + head, numel)`.  A new option does not fall back: what cannot be placed raises.
+        self.tower_params, self.tower_offsets = [], []
+        if getattr(model, "clip_tower_train", None) == "flat":
+            why = None if self.text_params and model._has_hip_text_head() else "the text head is not on the HIP path"
+            # (on the host only the layout exists -- the CPU tests read it -- and the rule's device clause has nothing to say)
+            why = why or clip_text.tower_refusal(model.clip, dev if dev.type == "cuda" else None, trainable=True)
+            if why is not None:
+                raise RuntimeError("clip_tower_train='flat': the CLIP text tower cannot join the flat parameter buffer: " + why)
+            self.tower_params = list(clip_text._tower_tensors(model.clip))
+            for p in self.tower_params:
+                self.tower_offsets.append(o)
+                o += (p.numel() + self.ALIGN - 1) // self.ALIGN * self.ALIGN
         self.numel = o
         self.flat = torch.zeros(self.numel, device=dev, dtype=torch.float32)
         with torch.no_grad():
-            for p, off in zip(self.params + self.text_params, offs + self.text_offsets):
+            for p, off in self.members():
                 view = self.flat[off:off + p.numel()].view(p.shape)
                 view.copy_(p.data)
                 p.data = view
+        if self.tower_params:
+            model._clip_train_table = None      # (its pointers were the tensors' old homes)
         self.grad = None
         self.grad_views = None
         self._ptr_key = None
         self._ptable = None
         self._gtable = None
+
+    def members(self):
+        """[(parameter, flat offset)] of everything that lives in the buffer: the core, the text (or class) head, the tower."""
+        return list(zip(self.params + self.text_params + self.tower_params, self.offsets + self.text_offsets + self.tower_offsets))
+
+    def tower_grad_table(self):
+        """Pointer table (clip_text._tower_tensors order) into the flat GRADIENT buffer."""
+        self.ensure_grad()
+        return (C.c_void_p * len(self.tower_offsets))(*[self.grad.data_ptr() + 4 * o for o in self.tower_offsets])
 
     def table(self, base_ptr):
         n = len(self.group_offsets)
@@ -305,7 +331,8 @@ class _FlatParams:
         base, end = self.flat.data_ptr(), self.flat.data_ptr() + 4 * self.numel
         return all(p.is_cuda and base <= p.data_ptr() < end for p in self.params[:3] + self.params[-3:]) \
             and all(p.data_ptr() == base + 4 * o for p, o in zip(self.params[:8], self.offsets[:8])) \
-            and all(p.data_ptr() == base + 4 * o for p, o in zip(self.text_params, self.text_offsets))
+            and all(p.data_ptr() == base + 4 * o for p, o in zip(self.text_params, self.text_offsets)) \
+            and all(p.data_ptr() == base + 4 * o for p, o in zip(self.tower_params, self.tower_offsets))
 
 
 class _DerivedTable:

@@ -32,7 +32,7 @@ from ..models.guidance import ClassifierFreeGuidedModel, check_scale
 from ..models.spaced_diffusion import SpacedDiffusion, space_timesteps, space_timesteps_logsnr
 from ..parallel import (FlatGradAllReduce, OverlappedGradAllReduce, ShardedSampler, broadcast_flat, broadcast_parameters,
                         exchange_active)
-from .text_source import Banked, ClassIds, ClipFeatures, Embeddings, _core
+from .text_source import Banked, ClassIds, ClipFeatures, Embeddings, Tokens, _core
 
 GRAD_CLIP = 0.5                    # ddpm_trainer.py:61
 ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8   # torch.optim.Adam defaults, ddpm_trainer.py:222
@@ -344,10 +344,11 @@ class DDPMTrainer(object):
     # ---- EMA of the weights (include/hig.h, 'EMA weights') -------------------------------------------------------
     def _ema_outside_params(self):
         """[(state-dict name, parameter)] of what trains outside the flat buffer: a torch text head, a trainable CLIP tower
-        (no_clip=True), the class head of a cap_id model built with class_head="torch" (with "hip" it is in the buffer)."""
+        (no_clip=True; with clip_tower_train="flat" it is in the buffer), the class head of a cap_id model built with
+        class_head="torch" (with "hip" it is in the buffer)."""
         core = _core(self.encoder)
         fp = core.flat_params()
-        in_flat = {id(p) for p in fp.params + fp.text_params}
+        in_flat = {id(p) for p, _ in fp.members()}
         return [(k, p) for k, p in core.named_parameters() if p.requires_grad and id(p) not in in_flat]
 
     def _ema_new(self, decay, warmup, origin, num_updates):
@@ -450,7 +451,7 @@ class DDPMTrainer(object):
     def _ema_state_dict(self, st):
         """state-dict name -> averaged tensor, trainable parameters only (a frozen CLIP tower is not duplicated)."""
         fp = _core(self.encoder).flat_params()
-        off = {id(p): o for p, o in zip(fp.params + fp.text_params, fp.offsets + fp.text_offsets)}
+        off = {id(p): o for p, o in fp.members()}
         out = OrderedDict()
         for k, p in _core(self.encoder).named_parameters():
             if id(p) in off:
@@ -470,7 +471,7 @@ class DDPMTrainer(object):
             decay, warmup = cfg if cfg is not None else (info['decay'], info['warmup'])
             st = self._ema_new(decay, warmup, info['origin'], info['num_updates'])
             fp = _core(self.encoder).flat_params()
-            off = {id(p): o for p, o in zip(fp.params + fp.text_params, fp.offsets + fp.text_offsets)}
+            off = {id(p): o for p, o in fp.members()}
             with torch.no_grad():
                 for k, p in _core(self.encoder).named_parameters():
                     if k not in ck['encoder_ema']:
@@ -609,8 +610,7 @@ class DDPMTrainer(object):
         fp = _core(self.encoder).flat_params()
         index = {id(p): i for i, p in enumerate(self.encoder.parameters())}
         covered = self._fused["covered"] if self._fused else 0
-        slots = zip(fp.params + fp.text_params, fp.offsets + fp.text_offsets)
-        return [(index[id(p)], off, p) for p, off in slots if off < covered and id(p) in index]
+        return [(index[id(p)], off, p) for p, off in fp.members() if off < covered and id(p) in index]
 
     def _optimizer_state_dict(self):
         """torch.optim.Adam.state_dict() of the optimizer that is really in use: when the fused step has run, its
@@ -633,7 +633,7 @@ class DDPMTrainer(object):
         index = {id(p): i for i, p in enumerate(self.encoder.parameters())}
         steps, covered = [], 0
         with torch.no_grad():
-            for p, off in zip(fp.params + fp.text_params, fp.offsets + fp.text_offsets):
+            for p, off in fp.members():
                 ent = sd['state'].get(index.get(id(p)))
                 if ent is None:
                     continue
@@ -694,7 +694,7 @@ class DDPMTrainer(object):
         core = _core(self.encoder)
         fp = core.flat_params()
         broadcast_flat(fp.flat)
-        in_flat = {id(p) for p in fp.params + fp.text_params}
+        in_flat = {id(p) for p, _ in fp.members()}
         for p in core.parameters():
             if p.requires_grad and id(p) not in in_flat:
                 dist.broadcast(p.data, src=0)
@@ -797,11 +797,20 @@ class DDPMTrainer(object):
             st["lr"].fill_(lr)
             st["lr_host"] = lr
 
-    def _text_source(self, xf_proj, xf_out, clip_out, eot, caption_batch, class_ids):
+    def _text_source(self, xf_proj, xf_out, clip_out, eot, caption_batch, class_ids, token_batch=None):
         """The text arguments of a fused step as ONE source (trainers/text_source.py).  `caption_batch=` is exclusive with
         `clip_out=` / `eot=` and needs the model's bank; `class_ids=` (a cap_id model with class_head="hip") is exclusive with
-        every other text argument.  Embeddings passed beside a bank request or beside CLIP features are ignored."""
+        every other text argument, and so is `token_batch=` (a no_clip model with clip_tower_train="flat").  Embeddings passed
+        beside a bank request or beside CLIP features are ignored."""
         core = _core(self.encoder)
+        if token_batch is not None:
+            if any(a is not None for a in (xf_proj, xf_out, clip_out, eot, caption_batch, class_ids)):
+                raise ValueError("token_batch= is exclusive with xf_proj= / xf_out=, clip_out= / eot=, caption_batch= and class_ids=: "
+                                 "the tower and the text head inside the step supply the text embeddings")
+            if getattr(core, "clip_tower_train", None) != "flat":
+                raise ValueError("token_batch= needs a no_clip model built with clip_tower_train='flat' (or "
+                                 "HIG_CLIP_TOWER_TRAIN=flat): this model's CLIP text tower is not in the flat parameter buffer")
+            return Tokens(token_batch)
         if caption_batch is not None:
             if clip_out is not None or eot is not None:
                 raise ValueError("caption_batch= and clip_out= / eot= are exclusive: the bank supplies the CLIP features")
@@ -876,7 +885,7 @@ class DDPMTrainer(object):
         st = self.fused_state()
         core = _core(self.encoder)
         fp = core.flat_params()
-        n = self._fused_numel(text.trains_head)
+        n = self._fused_numel(text)
         ex = st["overlap"]
         want = getattr(self.opt, "grad_wire", "f32")
         if want != ex.wire:      # (the option is read when the fused state is built; changing it later used to be ignored silently)
@@ -889,10 +898,22 @@ class DDPMTrainer(object):
         self._fused_fwd_bwd(x_start, t, length, text, noise, exchange=ex)
         return ex.finish([(fp.core_numel, n)] if n > fp.core_numel else ())
 
-    def _fused_numel(self, with_text):
-        """Floats of the flat buffers one fused step covers: the core, or core + text head."""
+    def _fused_numel(self, text):
+        """Floats of the flat buffers one fused step covers: the core, core + text head or, for a source that runs the tower
+        (Tokens), everything.  text: the step's source, or a bool = its `trains_head`."""
         core = _core(self.encoder)
         fp = core.flat_params()
+        with_text = bool(getattr(text, "trains_head", text))
+        if getattr(text, "trains_tower", False):
+            if not fp.tower_params:
+                raise RuntimeError("token_batch= needs a no_clip model built with clip_tower_train='flat': this model's CLIP text "
+                                   "tower is not in the flat parameter buffer")
+            return fp.numel
+        if fp.tower_params:
+            # the tower's parameters lie behind the head in the buffers: any other source leaves them without a gradient
+            raise NotImplementedError("the CLIP text tower is trainable (no_clip=True) and lives in the flat parameter buffer "
+                                      "(clip_tower_train='flat'): a step from %s would silently freeze it -- pass token_batch= "
+                                      "(or use forward() + update())" % (getattr(text, "kind", "these inputs"),))
         if with_text:
             if not fp.text_params:
                 raise RuntimeError("this model's text head is not on the HIP path (text_head='torch', cap_id without "
@@ -905,7 +926,7 @@ class DDPMTrainer(object):
                                           "silently freeze it -- use forward() + update() for this configuration")
         return fp.numel if with_text else fp.core_numel
 
-    def _fused_clip_adam(self, world, with_text=False):
+    def _fused_clip_adam(self, world, with_text=False):   # (with_text: the step's source, or a bool = its `trains_head`)
         """g /= world; clip_grad_norm_(0.5); Adam -- one norm pass + one update pass over the flat buffers."""
         core = _core(self.encoder)
         L = _lib.lib()
@@ -933,7 +954,7 @@ class DDPMTrainer(object):
             fp.shadow16_mark_current(core._param_version())
 
     def train_step_fused(self, x_start, t, length, xf_proj=None, xf_out=None, noise=None, lr=None, clip_out=None,
-                         eot=None, caption_batch=None, class_ids=None):
+                         eot=None, caption_batch=None, class_ids=None, token_batch=None):
         """One DDPM training step on device tensors, reference semantics (ddpm_trainer.py:97-119,172-187):
           x_t = q_sample(x0, t, noise); pred = denoiser(x_t, t); loss = masked MSE(pred, noise);
           backward; grads = all_reduce(grads) / world; clip_grad_norm_(0.5); Adam.
@@ -943,14 +964,16 @@ class DDPMTrainer(object):
         CaptionBatch of the model's caption bank, exclusive with clip_out / eot) is that same update with the CLIP features
         fetched from the bank by hig_caption_gather.  `class_ids` (int32 on the device, one class id per model-batch row --
         4 B rows in the order c1, c2, c2, c1 in PIT mode; exclusive with every other text argument) is the full update of a
-        cap_id model built with class_head="hip": the class head runs inside the step.
+        cap_id model built with class_head="hip": the class head runs inside the step.  `token_batch` (a clip_text.TokenBatch on
+        the device; exclusive with every other text argument) is the full update of a no_clip model built with
+        clip_tower_train="flat": the CLIP text tower runs inside the step, once per distinct caption, and is trained too.
         With more than one rank the replicas must start identical: call `sync_replicas()` once (train() does).
         No host synchronisation: the loss stays on the device (`fused_state()['loss']`)."""
         self._ema_refuse_in_scope("train_step_fused")
-        text = self._text_source(xf_proj, xf_out, clip_out, eot, caption_batch, class_ids)
+        text = self._text_source(xf_proj, xf_out, clip_out, eot, caption_batch, class_ids, token_batch)
         st = self.fused_state()
         ema = self.ema_state()            # (created here, from the weights before the step, when opt.ema_decay asks for one)
-        n = self._fused_numel(text.trains_head)
+        n = self._fused_numel(text)
         self._set_lr(lr)
         core = _core(self.encoder)
         fp = core.flat_params()
@@ -959,7 +982,7 @@ class DDPMTrainer(object):
         else:
             self._fused_fwd_bwd(x_start, t, length, text, noise)
             world = st["allreduce"](fp.grad[:n])                                  # one all-reduce after the backward
-        self._fused_clip_adam(world, text.trains_head)
+        self._fused_clip_adam(world, text)
         if ema is not None:
             ema["num_updates"] += 1
         return st["loss"]
@@ -976,9 +999,19 @@ class DDPMTrainer(object):
         return step(x_start.contiguous(), t, cur_len, noise=noise, **self._text_inputs(caption))
 
     def _text_inputs(self, caption):
-        """The text arguments of a fused step for these captions: a CaptionBatch when the model has a caption bank (the tower
-        runs for captions the bank has not met, and only for them), else the tower's output for every row."""
-        bank = getattr(_core(self.encoder), "caption_bank", None)
+        """The text arguments of a fused step for these captions: a TokenBatch for a model whose trainable tower lives in the flat
+        buffer (clip_tower_train="flat"), a CaptionBatch when the model has a caption bank (the tower runs for captions the bank
+        has not met, and only for them), else the tower's output for every row."""
+        core = _core(self.encoder)
+        if getattr(core, "clip_tower_train", None) == "flat":
+            # the tower trains inside the step: its only text input is the distinct captions' tokens (opt.text_dedup, default on)
+            from ..models.clip_text import TokenBatch
+            cache = core.__dict__.setdefault("_token_cache", (core._clip_tokenize, {}))
+            if cache[0] is not core._clip_tokenize:
+                cache = core.__dict__["_token_cache"] = (core._clip_tokenize, {})
+            return dict(token_batch=TokenBatch(caption, core._tokenize, dedup=bool(getattr(self.opt, "text_dedup", True)),
+                                               cache=cache[1]).to(self.device))
+        bank = getattr(core, "caption_bank", None)
         if bank is not None:
             return dict(caption_batch=bank.batch(caption, self.device))
         clip_out, eot = self.clip_inputs(caption)
@@ -997,7 +1030,7 @@ class DDPMTrainer(object):
         return clip_out, tokens.argmax(dim=-1).contiguous()
 
     def train_step_captured(self, x_start, t, length, xf_proj=None, xf_out=None, noise=None, lr=None, clip_out=None,
-                            eot=None, caption_batch=None, class_ids=None):
+                            eot=None, caption_batch=None, class_ids=None, token_batch=None):
         """The same step as hipGraphs.  Captured once per batch shape.  One rank: ONE graph (q_sample [+ text head] +
         forward + loss + backward + clip + Adam).  With a gradient exchange (more than one rank, or HIG_FORCE_EXCHANGE)
         still ONE graph: the per-layer RCCL all-reduces of `OverlappedGradAllReduce` are captured with the backward they
@@ -1016,9 +1049,10 @@ class DDPMTrainer(object):
         With `caption_batch` the packed int32 index buffer is the static text input, copied like `t`; the graph is keyed on
         its layout (rows, U_pad), on `text_dedup` and on the bank's buffers, which are allocated once and never move.
         With `class_ids` the ids are the static text input, copied like `t`; the graph key carries their shape and that the
-        class head is inside."""
+        class head is inside.  With `token_batch` the packed token buffer is the static text input, copied like `t`; the embedding
+        index is rebuilt from it by a node of the graph, its counts stay on the device, and the key carries (rows, U_pad, dedup)."""
         self._ema_refuse_in_scope("train_step_captured")
-        text = self._text_source(xf_proj, xf_out, clip_out, eot, caption_batch, class_ids)
+        text = self._text_source(xf_proj, xf_out, clip_out, eot, caption_batch, class_ids, token_batch)
         st = self.fused_state()
         ema = self.ema_state()            # (created eagerly, never inside a capture)
         world = _dist_world()
@@ -1026,7 +1060,7 @@ class DDPMTrainer(object):
         # (gloo stages through the host: its collectives cannot be captured -- that backend always takes the split form)
         in_graph = (split and getattr(self.opt, "capture_exchange", True) and getattr(self.opt, "overlap_allreduce", True)
                     and dist.get_backend() == "nccl")
-        n = self._fused_numel(text.trains_head)
+        n = self._fused_numel(text)
         self._set_lr(lr)
         statics = text.statics()
         key = ((tuple(x_start.shape), text.kind) + tuple(tuple(a.shape) for a in statics)
@@ -1045,7 +1079,7 @@ class DDPMTrainer(object):
 
             def whole_step_with_exchange():
                 w = self._fwd_bwd_overlapped_exchange(static["x0"], static["t"], static["length"], static_text, static["noise"])
-                self._fused_clip_adam(w, text.trains_head)
+                self._fused_clip_adam(w, text)
 
             # warm-up (allocations, workspace pools, RCCL's communicator) on a side stream, as torch.cuda.graph requires;
             # it runs a real step, so restore parameters / moments / step counter afterwards
@@ -1062,7 +1096,7 @@ class DDPMTrainer(object):
                     whole_step_with_exchange()
                 else:
                     part_a()
-                    self._fused_clip_adam(1, text.trains_head)
+                    self._fused_clip_adam(1, text)
             torch.cuda.current_stream().wait_stream(s)
 
             def restore():
@@ -1110,13 +1144,13 @@ class DDPMTrainer(object):
             if not split:
                 with torch.cuda.graph(ga, capture_error_mode="thread_local"):
                     part_a()
-                    self._fused_clip_adam(1, text.trains_head)
+                    self._fused_clip_adam(1, text)
             elif not in_graph:
                 with torch.cuda.graph(ga, capture_error_mode="thread_local"):
                     part_a()
                 gb = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode="thread_local"):
-                    self._fused_clip_adam(world, text.trains_head)
+                    self._fused_clip_adam(world, text)
             cap = st["graphs"][key] = (static, ga, gb)
             st["captured_form"] = "one graph" if not split else ("one graph, exchange inside" if in_graph
                                                                  else "graph A | all-reduce | graph B")

@@ -556,6 +556,41 @@ int hig_clip_text_bwd(const int32_t* dims, const void* const* params, const int3
                       hig_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The embedding index on the device (csrc/clipindex.hip): what a captured training step needs, because the host index above has
+ * three host counts that size launches and a graph would freeze one batch's.
+ * hig_clip_embed_index_build: tokens (B, N) int64 on the device -> the seven arrays above in a CAPACITY layout, whose offsets
+ * depend on (B, N, vocab) only, and counts[3] = n_live, n_chunks, n_ids (int32, on the device).  With M = B N,
+ * cap_ids = min(M, vocab) and cap_chunks = ceil(M / HIG_CLIP_EMBED_CHUNK) + cap_ids, the int32 buffer `index` holds
+ *     order[M] | chunk_seg[cap_chunks + 1] | chunk_order[cap_chunks] | id_seg[cap_ids + 1] | ids[cap_ids] | pos_order[M] | pos_seg[N + 1]
+ * (hig_clip_embed_index_cap_ints gives the total; -1 for a bad extent).  The live prefix of every array -- n_live, n_chunks + 1,
+ * n_chunks, n_ids + 1, n_ids, M, N + 1 entries -- equals the host index of the same tokens exactly; entries beyond it are
+ * unspecified and never read.  An id outside [0, vocab) is not live.
+ * One workgroup of 1024: the rows are sorted by the key id << 16 | row (a bitonic network, 32 768 keys at a time in 128 KiB of
+ * LDS and the merges across those tiles through `scratch`), then three block scans give the id boundaries, the chunk cuts and
+ * the counts.  All live keys are distinct, so the order is the defined one whatever the network does with equal (dead) keys.
+ * Integer work only: no atomics, no host read-back, no allocation, no synchronisation; the launch is a function of (B, N, vocab),
+ * so the entry is capturable and one graph serves every batch of a shape.  scratch: hig_clip_embed_index_scratch_bytes (the padded
+ * key count, 4 bytes each; -1 outside the covered range).
+ * Covered: B N <= 65 535 and vocab <= 65 536 (the key's two halves; 65535 << 16 | 65535 is the dead key).  Beyond that:
+ * HIG_EUNSUPPORTED before any HIP call, nothing written.  Bad arguments: HIG_EINVAL before any HIP call. */
+int64_t hig_clip_embed_index_cap_ints(int32_t B, int32_t N, int32_t vocab);
+int64_t hig_clip_embed_index_scratch_bytes(int32_t B, int32_t N, int32_t vocab);
+int hig_clip_embed_index_build(const int64_t* tokens, int32_t B, int32_t N, int32_t vocab, int32_t* index, int32_t* counts,
+                               void* scratch, hig_stream_t stream);
+/* hig_clip_embed_bwd reading the capacity layout and the device counts: the same three segment sums and the row scatter, on grids
+ * sized by the capacities; an item at or past its device count exits without a read or a write.  The result is the same fp32
+ * sum, so dtok (zero fill and +0.0 rows of unused ids included) and dpos have the bits hig_clip_embed_bwd gives under the host
+ * index of the same tokens.  scratch: hig_clip_embed_bwd_dev_scratch_floats = (min(cap_chunks, M) + cap_ids) W floats, at most
+ * 2 M W (-1 for a bad extent). */
+int64_t hig_clip_embed_bwd_dev_scratch_floats(int32_t B, int32_t N, int32_t W, int32_t vocab);
+int hig_clip_embed_bwd_dev(const float* dx0, int32_t B, int32_t N, int32_t W, int32_t vocab, const int32_t* index,
+                           const int32_t* counts, float* scratch, float* dtok, float* dpos, hig_stream_t stream);
+/* hig_clip_text_bwd with (index, counts) of hig_clip_embed_index_build in place of the host index and its three counts: the same
+ * launch sequence up to d(x0) (one function serves both), then hig_clip_embed_bwd_dev.  Same workspace, same bits. */
+int hig_clip_text_bwd_dev(const int32_t* dims, const void* const* params, const int32_t* index, const int32_t* counts,
+                          const float* dout, const void* saved, void* const* grads, void* bwd_workspace, hig_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Evaluator feature extraction: the two classifiers that score generated pairs,
  * `MotionEncoder` (interaction_transformer.py:641-741: class logits + the pooled feature FID /
  * diversity are computed on) and `MotionConsistencyEvalModel` (:743-829: real/fake logits from a
