@@ -2,14 +2,21 @@
 
 The header stays inside a small, closed subset of C (its opening comment lists the forms).  parse_header() takes the header's
 text and returns its constants, structs, callback typedefs and prototypes; bind() turns those into ctypes Structures, CFUNCTYPEs
-and (restype, argtypes) pairs.  A declaration outside the subset raises HeaderError naming it: nothing ever falls back to ctypes'
-default `int` conversion.  Pure functions: no file is read, no library loaded, torch is not imported.
+and (restype, argtypes) pairs; gateway() turns the prototypes into what every parameter of every function takes from Python and
+what every result means, and convert() applies that to one call's arguments.  A declaration outside the subset raises HeaderError
+naming it: nothing ever falls back to ctypes' default `int` conversion.  Pure functions: no file is read, no library loaded, torch
+is not imported (a tensor is known by its attributes).
 """
 import ctypes as C
+import numbers
 import re
 
 # `#define HIG_*` names whose body is not an integer: the include guard and the two function-like table-size macros
 IGNORED_DEFINES = ("HIG_H", "HIG_D32_COUNT", "HIG_D16_COUNT")
+# `int` functions whose result is a value and not a status: a version, a length, a count of chunks or of table slots, a yes / no.
+# Every other `int` function returns HIG_OK or an error code (each one that takes a hig_stream_t is a launcher and does)
+NOT_STATUS = ("hig_version", "hig_last_error", "hig_text_head_layout", "hig_eval_encoder_layout", "hig_gemm_bf16_lnfold_plan",
+              "hig_bf16_train_layout", "hig_f32_train_layout", "hig_colsum_chunks")
 
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "hig_stream_t": C.c_void_p}
 _INT = re.compile(r"\(?\s*(-?\d+)\s*\)?$")
@@ -54,7 +61,9 @@ def _declarator(decl):
 
 def _params(text):
     text = text.strip()
-    return [] if text in ("", "void") else [_declarator(p)[0] for p in text.split(",")]
+    if text in ("", "void"):
+        return []
+    return [(name or "arg%d" % i, ctype) for i, (ctype, name) in enumerate(_declarator(p) for p in text.split(","))]
 
 
 def _fields(struct, body):
@@ -72,8 +81,9 @@ def parse_header(text):
     """(constants, structs, callbacks, prototypes) of the header `text`:
     constants  {name: int}: every `#define HIG_X <integer>` and every enum member (implicit values count on from the previous one)
     structs    {name: [(field, C type), ...]} of every `typedef struct hig_x { ... } hig_x;`
-    callbacks  {name: (return C type, [parameter C types])} of every `typedef ret (*name)(...);`
-    prototypes {name: (return C type, [parameter C types])} of every function, in the header's order"""
+    callbacks  {name: (return C type, [(parameter, C type), ...])} of every `typedef ret (*name)(...);`
+    prototypes {name: (return C type, [(parameter, C type), ...])} of every function, in the header's order
+    An unnamed parameter goes by `arg<i>`, i its position."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     constants, structs, callbacks, prototypes = {}, {}, {}, {}
 
@@ -157,6 +167,136 @@ def bind(structs, callbacks, prototypes, struct_names):
             raise HeaderError("%s: a struct of the header without a Python name" % name)
         classes[name] = type(struct_names[name], (C.Structure,), {"_fields_": [(f, ctype(t, "%s.%s" % (name, f))) for f, t in fields]})
     for name, (ret, params) in callbacks.items():
-        hooks[name] = C.CFUNCTYPE(ctype(ret, name, True), *[ctype(p, name) for p in params])
-    signatures = {name: (ctype(ret, name, True), [ctype(p, name) for p in params]) for name, (ret, params) in prototypes.items()}
+        hooks[name] = C.CFUNCTYPE(ctype(ret, name, True), *[ctype(t, name) for _, t in params])
+    signatures = {name: (ctype(ret, name, True), [ctype(t, name) for _, t in params]) for name, (ret, params) in prototypes.items()}
     return {struct_names[n]: c for n, c in classes.items()}, hooks, signatures
+
+
+# ---- the gateway: what each parameter of each prototype accepts, and what each result means ----------------------------------
+
+_TENSOR_OF = {"float": "torch.float32", "int32_t": "torch.int32", "int64_t": "torch.int64", "uint8_t": "torch.uint8"}
+_DTYPE_NAMES = {}                                           # torch dtype -> its name, as the calls meet them
+# what ctypes itself takes for a pointer: references (POINTER instances, byref() results), c_void_p / c_char buffers, arrays
+_REF = (C._Pointer, type(C.byref(C.c_int32())))
+_RAW = (C._SimpleCData, C.Array) + _REF
+
+
+def _is_tensor(v):
+    return hasattr(v, "data_ptr") and hasattr(v, "is_cuda")
+
+
+def _got(v):
+    return "a %s tensor of %s" % (v.device.type, v.dtype) if _is_tensor(v) else "%s (%s)" % (repr(v)[:60], type(v).__name__)
+
+
+def _converter(fn, name, ctype, classes, hooks):
+    """What turns one Python argument into what ctypes passes for parameter `name` of `fn`, declared `ctype`."""
+    where = "%s: parameter `%s` (%s)" % (fn, name, ctype)
+    bare = re.sub(r"^const ", "", ctype)
+
+    def refuse(v, takes):
+        return TypeError("%s takes %s, got %s" % (where, takes, _got(v)))
+
+    if bare in ("int", "int32_t", "int64_t", "float"):
+        kind, cast = (numbers.Real, float) if bare == "float" else (numbers.Integral, int)
+
+        def scalar(v):
+            if type(v) is cast:
+                return v
+            if isinstance(v, kind):
+                return cast(v)
+            raise refuse(v, "a Python number (reading a tensor here would be a hidden synchronisation)" if _is_tensor(v) else "a Python number")
+        return scalar
+    if bare == "hig_stream_t":
+        def stream(v):
+            if v is None or type(v) is int or isinstance(v, C.c_void_p):
+                return v
+            if hasattr(v, "cuda_stream"):
+                return v.cuda_stream
+            raise refuse(v, "a torch.cuda.Stream, a c_void_p, an address or None")
+        return stream
+    if bare in hooks:
+        def callback(v):
+            if v is None or isinstance(v, hooks[bare]):
+                return v
+            raise refuse(v, "a %s instance or None" % bare)
+        return callback
+    if not bare.endswith("*"):
+        raise HeaderError("%s, which the gateway does not pass" % where)
+    pointee = bare[:-1]
+    if pointee in classes:
+        def struct(v):
+            if isinstance(v, classes[pointee]):
+                return C.byref(v)
+            if isinstance(v, _REF):
+                return v
+            raise refuse(v, "a %s (passed by reference)" % classes[pointee].__name__)
+        return struct
+    if "*" in pointee:                                      # `void* const*`, `const float* const*`, ...
+        def table(v):
+            if v is None or isinstance(v, _RAW):
+                return v
+            raise refuse(v, "a ctypes array of pointers or None")
+        return table
+    if pointee == "char":
+        def chars(v):
+            if isinstance(v, _RAW):
+                return v
+            raise refuse(v, "a ctypes character buffer")
+        return chars
+    if pointee != "void" and pointee not in _TENSOR_OF:
+        raise HeaderError("%s, which the gateway does not pass" % where)
+    dtype = _TENSOR_OF.get(pointee)
+    takes = "a ROCm device tensor%s, None, or a raw ctypes value / address" % (" of %s" % dtype if dtype else "")
+
+    def pointer(v):
+        if v is None:
+            return None
+        got = getattr(v, "dtype", None)
+        if got is not None and hasattr(v, "data_ptr"):      # a tensor
+            if dtype is not None and (_DTYPE_NAMES.get(got) or _DTYPE_NAMES.setdefault(got, str(got))) != dtype:
+                raise refuse(v, takes)
+            if not v.is_cuda:
+                raise RuntimeError("%s: libhig needs ROCm device tensors (got a %s tensor); there is no CPU fallback" % (where, v.device.type))
+            return v.data_ptr()
+        if type(v) is int or isinstance(v, _RAW):
+            return v
+        raise refuse(v, takes)
+    return pointer
+
+
+def gateway(prototypes, classes, hooks):
+    """{function: (names, C types, converters, result rule)} for every prototype of a parse; classes / hooks: {header name:
+    Structure / CFUNCTYPE}.  One converter per parameter takes what the declared type admits and refuses the rest by name:
+      float, int, int32_t, int64_t     Python numbers (bool as int); a tensor is refused
+      T* / const T*                    T in float, int32_t, int64_t, uint8_t: a ROCm device tensor of exactly that dtype, None for
+                                       NULL; a ctypes object or a plain integer address passes unchecked (raw workspace bytes given to
+                                       a typed parameter on purpose, and host arrays an entry reads before it returns)
+      void* / const void*              any device tensor, None, or a raw value as above
+      pointer to pointer               ctypes arrays or None
+      const hig_x*                     the Structure itself (passed by reference), or a reference
+      a callback type                  its CFUNCTYPE instance or None
+      hig_stream_t                     c_void_p, an address, None, or a torch.cuda.Stream
+    Contiguity, shape and alignment are not checked: the header does not state them, the entry points take leading dimensions, and
+    strided views are legitimate operands.  The result rule is "status" (an `int` that is HIG_OK or an error code), "size" (an
+    int64_t count of bytes / floats / ints, negative on refusal) or "value".  A type outside these raises HeaderError."""
+    out = {}
+    for fn, (ret, params) in prototypes.items():
+        rule = "status" if ret == "int" and fn not in NOT_STATUS else \
+               "size" if ret == "int64_t" and fn.endswith(("_bytes", "_floats", "_ints")) else "value"
+        out[fn] = (tuple(n for n, _ in params), tuple(t for _, t in params),
+                   tuple(_converter(fn, n, t, classes, hooks) for n, t in params), rule)
+    return out
+
+
+def convert(fn, entry, args, current_stream):
+    """The ctypes arguments of one call of `fn` (entry: its gateway() value).  The declared count is accepted, and one fewer when
+    the last parameter is a hig_stream_t, which then is current_stream(), read now."""
+    names, ctypes_, converters, _ = entry
+    if len(args) != len(names):
+        if len(args) != len(names) - 1 or not names or ctypes_[-1] != "hig_stream_t":
+            raise TypeError("%s takes %d arguments%s, got %d: (%s)" % (
+                fn, len(names), " (or %d, without the stream)" % (len(names) - 1) if names and ctypes_[-1] == "hig_stream_t" else "",
+                len(args), ", ".join("%s %s" % (t, n) for n, t in zip(names, ctypes_))))
+        return [c(a) for c, a in zip(converters, args)] + [current_stream()]
+    return [c(a) for c, a in zip(converters, args)]

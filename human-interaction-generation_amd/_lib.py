@@ -84,14 +84,14 @@ def denoiser_plan(dims, entry, training=0, has_xf_out=0, facts=0, capturing=0, c
         assert not unknown, unknown
         sw = (C.c_int32 * DN_NSWITCHES)(*[switches.get(n, v) for n, v in zip(DN_SWITCHES, DN_SWITCH_DEFAULTS)])
     out = (C.c_int32 * DN_PLAN_NSLOTS)()
-    check(lib().hig_denoiser_plan(C.byref(dims), entry, training, has_xf_out, facts, capturing, chip_cus, wsp32_active, sw, out, DN_PLAN_NSLOTS))
+    api.hig_denoiser_plan(dims, entry, training, has_xf_out, facts, capturing, chip_cus, wsp32_active, sw, out, DN_PLAN_NSLOTS)
     return dict(zip(DN_PLAN_SLOTS, out))
 
 
 def denoiser_last_schedule():
     """What the most recent denoiser entry point on this thread ran, as {slot name: value} (None: none yet)."""
     out = (C.c_int32 * DN_PLAN_NSLOTS)()
-    return dict(zip(DN_PLAN_SLOTS, out)) if lib().hig_denoiser_last_schedule(out, DN_PLAN_NSLOTS) >= 0 else None
+    return dict(zip(DN_PLAN_SLOTS, out)) if api.hig_denoiser_last_schedule(out, DN_PLAN_NSLOTS) >= 0 else None
 
 
 def stream_ptr():
@@ -107,3 +107,36 @@ def ptr(t):
         raise RuntimeError("libhig needs ROCm device tensors (got a %s tensor); there is no CPU fallback"
                            % t.device.type)
     return C.c_void_p(t.data_ptr())
+
+
+def _current_stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+class _Api:
+    """The package's way into libhig.so: api.<name>(*args) under the header's own names, every argument held to the type the header
+    declares for it (_abi.gateway states what each type takes), all of it on the host before anything is launched.  A trailing
+    hig_stream_t may be left out and is then torch's current stream at the time of the call, so a call under torch.cuda.graph is
+    captured.  A status other than HIG_OK raises as check() does, a negative size raises with the library's message, the functions
+    of _abi.NOT_STATUS and every other integer return their value.  Contiguity is not checked: the entry points take leading
+    dimensions, and strided views are legitimate operands.  A name the header does not declare is an AttributeError."""
+
+    def __getattr__(self, name):
+        if name not in _GATEWAY:
+            raise AttributeError("include/hig.h declares no %s" % name)
+        entry, rule, convert = _GATEWAY[name], _GATEWAY[name][3], _abi.convert
+
+        def call(*args):                                    # (the entry is asked of lib() at every call, as a raw call asks it)
+            result = getattr(lib(), name)(*convert(name, entry, args, _current_stream))
+            if rule == "status" and result != 0:
+                raise RuntimeError("libhig error %d: %s" % (result, last_error()))
+            if rule == "size" and result < 0:
+                raise RuntimeError("libhig: " + last_error())
+            return None if rule == "status" else result
+        call.__name__ = call.__qualname__ = name
+        setattr(self, name, call)                           # (the next lookup finds it without coming here)
+        return call
+
+
+_GATEWAY = _abi.gateway(_prototypes, {c: _classes[py] for c, py in STRUCT_NAMES.items()}, _hooks)
+api = _Api()

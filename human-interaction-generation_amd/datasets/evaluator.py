@@ -258,10 +258,10 @@ class GeneratedMotionSet(object):
         """One launch: items [start, start + n) of the tables -> (2 n, frames + 1, F)."""
         out = torch.empty(2 * n, self.frames + 1, self.F, device=self.device, dtype=torch.float32)
         (off_h, len_h, shift_h), (off_d, len_d, shift_d) = host, dev
-        _lib.check(_lib.lib().hig_eval_pairs_build(
-            _lib.C.c_void_p(self._base), _lib.ptr(off_d[2 * start:]), _lib.ptr(len_d[start:]), _lib.ptr(shift_d[start:]),
-            _host_ptr(off_h[2 * start:]), _host_ptr(len_h[start:]), _host_ptr(shift_h[start:]), self._src_floats, n, self.F,
-            self.F, self.frames + 1, _lib.ptr(out), _lib.stream_ptr()))
+        # (src is the lowest address among the generated motions, not a tensor; the host tables are read before the call returns)
+        _lib.api.hig_eval_pairs_build(_lib.C.c_void_p(self._base), off_d[2 * start:], len_d[start:], shift_d[start:],
+                                      _host_ptr(off_h[2 * start:]), _host_ptr(len_h[start:]), _host_ptr(shift_h[start:]),
+                                      self._src_floats, n, self.F, self.F, self.frames + 1, out)
         return out
 
     def _groups(self, batch_size, drop_last):

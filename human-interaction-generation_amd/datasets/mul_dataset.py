@@ -239,7 +239,5 @@ class DeviceMotionBank(object):
         off_d = torch.from_numpy(seq_off).to(self.device, non_blocking=True)
         fix_d = torch.from_numpy(frame_ix).to(self.device, non_blocking=True)
         out = torch.empty(2 * B, T, F, device=self.device, dtype=torch.float32)
-        _lib.check(_lib.lib().hig_gather_frames(
-            _lib.ptr(self.bank), _lib.ptr(off_d), _lib.ptr(fix_d), _lib.ptr(self.stats), int(self.stat_f64),
-            2 * B, T, F, _lib.ptr(out), _lib.stream_ptr()))
+        _lib.api.hig_gather_frames(self.bank, off_d, fix_d, self.stats, self.stat_f64, 2 * B, T, F, out)
         return cap1, cap2, out[:B], out[B:], torch.tensor(lens), ids

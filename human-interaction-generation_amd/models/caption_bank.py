@@ -189,8 +189,7 @@ class CaptionBank:
         """hig_caption_gather: (clip_out (n, N, W), eot (n,)) of the n bank slots in the device int32 array `slot`."""
         clip_out = torch.empty(n, self.N, self.W, device=self.feat.device, dtype=torch.float32)
         eot = torch.empty(n, device=self.feat.device, dtype=torch.int64)
-        _lib.check(_lib.lib().hig_caption_gather(_lib.ptr(self.feat), _lib.ptr(self.eot), self.feat.shape[0], _lib.ptr(slot), n,
-                                                 self.N * self.W, _lib.ptr(clip_out), _lib.ptr(eot), _lib.stream_ptr()))
+        _lib.api.hig_caption_gather(self.feat, self.eot, self.feat.shape[0], slot, n, self.N * self.W, clip_out, eot)
         return clip_out, eot
 
 
@@ -198,8 +197,7 @@ def expand_rows(src, idx, n_out):
     """hig_rows_gather_f32: out[r] = src[idx[r]] over the leading dimension (src contiguous fp32, idx device int32)."""
     assert src.is_contiguous() and src.dtype == torch.float32
     out = torch.empty((n_out,) + tuple(src.shape[1:]), device=src.device, dtype=torch.float32)
-    _lib.check(_lib.lib().hig_rows_gather_f32(_lib.ptr(src), src.shape[0], _lib.ptr(idx), n_out, src[0].numel(), _lib.ptr(out),
-                                              _lib.stream_ptr()))
+    _lib.api.hig_rows_gather_f32(src, src.shape[0], idx, n_out, src[0].numel(), out)
     return out
 
 
@@ -207,6 +205,5 @@ def segment_sum_rows(src, order, seg, n_seg):
     """hig_rows_segment_sum_f32: out[u] = the rows order[seg[u]:seg[u + 1]] of src added in that order."""
     assert src.is_contiguous() and src.dtype == torch.float32
     out = torch.empty((n_seg,) + tuple(src.shape[1:]), device=src.device, dtype=torch.float32)
-    _lib.check(_lib.lib().hig_rows_segment_sum_f32(_lib.ptr(src), src.shape[0], _lib.ptr(order), _lib.ptr(seg), n_seg,
-                                                   src[0].numel(), _lib.ptr(out), _lib.stream_ptr()))
+    _lib.api.hig_rows_segment_sum_f32(src, src.shape[0], order, seg, n_seg, src[0].numel(), out)
     return out

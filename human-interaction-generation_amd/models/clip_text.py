@@ -265,13 +265,10 @@ def tower_forward(table, tokens, pool=None, precision="f32"):
     tokens = tokens.contiguous()
     B = tokens.shape[0]
     dims = clip_dims(B, table.N, table.W, table.H, table.L, table.vocab, _PREC[precision])
-    L = _lib.lib()
-    nbytes = L.hig_clip_text_workspace_bytes(dims)
-    if nbytes < 0:
-        raise RuntimeError("libhig: %s (clip_tower='torch' selects stock PyTorch ops)" % _lib.last_error())
+    nbytes = _lib.api.hig_clip_text_workspace_bytes(dims)
     ws = pool.take("clip", nbytes, table.device) if pool is not None else torch.empty(nbytes, dtype=torch.uint8, device=table.device)
     out = torch.empty(B, table.N, table.W, device=table.device, dtype=torch.float32)
-    _lib.check(L.hig_clip_text_fwd(dims, table.table, _lib.ptr(tokens), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()))
+    _lib.api.hig_clip_text_fwd(dims, table.table, tokens, out, ws)
     if pool is not None:
         pool.give("clip", ws, table.device)
     return out
@@ -375,13 +372,10 @@ def tower_forward_train(table, tokens, pool=None):
     tokens = tokens.contiguous()
     B = tokens.shape[0]
     dims = _train_dims(table, B)
-    L = _lib.lib()
-    nbytes = L.hig_clip_text_train_bytes(dims)
-    if nbytes < 0:
-        raise RuntimeError("libhig: %s (clip_tower_train='torch' selects stock PyTorch ops)" % _lib.last_error())
+    nbytes = _lib.api.hig_clip_text_train_bytes(dims)
     ws = pool.take("clip_t", nbytes, table.device) if pool is not None else torch.empty(nbytes, dtype=torch.uint8, device=table.device)
     out = torch.empty(B, table.N, table.W, device=table.device, dtype=torch.float32)
-    _lib.check(L.hig_clip_text_fwd_train(dims, table.table, _lib.ptr(tokens), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()))
+    _lib.api.hig_clip_text_fwd_train(dims, table.table, tokens, out, ws)
     return out, (dims, ws, B)
 
 
@@ -401,13 +395,9 @@ def tower_backward(table, index, dout, saved, pool=None):
     gflat = torch.empty(o, device=dev, dtype=torch.float32)
     grads = [gflat[off:off + p.numel()].view(p.shape) for p, off in zip(table.tensors, offs)]
     gtable = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
-    L = _lib.lib()
-    nb = L.hig_clip_text_bwd_workspace_bytes(dims)
-    if nb < 0:
-        raise RuntimeError("libhig: %s" % _lib.last_error())
+    nb = _lib.api.hig_clip_text_bwd_workspace_bytes(dims)
     bws = pool.take("clip_bwd", nb, dev) if pool is not None else torch.empty(nb, dtype=torch.uint8, device=dev)
-    _lib.check(L.hig_clip_text_bwd(dims, table.table, _lib.ptr(index.dev), index.n_live, index.n_chunks, index.n_ids, _lib.ptr(dout),
-                                   _lib.ptr(ws), gtable, _lib.ptr(bws), _lib.stream_ptr()))
+    _lib.api.hig_clip_text_bwd(dims, table.table, index.dev, index.n_live, index.n_chunks, index.n_ids, dout, ws, gtable, bws)
     if pool is not None:
         pool.give("clip_bwd", bws, dev)
         pool.give("clip_t", ws, dev)
@@ -553,10 +543,7 @@ class DeviceEmbedIndex:
 
     def __init__(self, B, N, vocab, device):
         from .. import _lib
-        L = _lib.lib()
-        ints, nbytes = L.hig_clip_embed_index_cap_ints(B, N, vocab), L.hig_clip_embed_index_scratch_bytes(B, N, vocab)
-        if ints < 0 or nbytes < 0:
-            raise RuntimeError("libhig: %s" % _lib.last_error())
+        ints, nbytes = _lib.api.hig_clip_embed_index_cap_ints(B, N, vocab), _lib.api.hig_clip_embed_index_scratch_bytes(B, N, vocab)
         self.B, self.N, self.vocab, self.device = B, N, vocab, torch.device(device)
         self.index = torch.zeros(ints, dtype=torch.int32, device=device)
         self.counts = torch.zeros(3, dtype=torch.int32, device=device)
@@ -565,8 +552,7 @@ class DeviceEmbedIndex:
     def build(self, tokens):
         from .. import _lib
         assert tokens.shape == (self.B, self.N) and tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.device == self.index.device
-        _lib.check(_lib.lib().hig_clip_embed_index_build(_lib.ptr(tokens), self.B, self.N, self.vocab, _lib.ptr(self.index),
-                                                         _lib.ptr(self.counts), _lib.ptr(self.scratch), _lib.stream_ptr()))
+        _lib.api.hig_clip_embed_index_build(tokens, self.B, self.N, self.vocab, self.index, self.counts, self.scratch)
         return self
 
     def live(self):
@@ -587,13 +573,9 @@ def tower_backward_dev(table, dindex, dout, saved, gtable, pool=None):
         raise RuntimeError("CLIP text tower: the embedding index does not belong to these tokens")
     dout = dout.contiguous()
     assert dout.shape == (B, table.N, table.W) and dout.dtype == torch.float32
-    L = _lib.lib()
-    nb = L.hig_clip_text_bwd_workspace_bytes(dims)
-    if nb < 0:
-        raise RuntimeError("libhig: %s" % _lib.last_error())
+    nb = _lib.api.hig_clip_text_bwd_workspace_bytes(dims)
     bws = pool.take("clip_bwd", nb, dev) if pool is not None else torch.empty(nb, dtype=torch.uint8, device=dev)
-    _lib.check(L.hig_clip_text_bwd_dev(dims, table.table, _lib.ptr(dindex.index), _lib.ptr(dindex.counts), _lib.ptr(dout), _lib.ptr(ws),
-                                       gtable, _lib.ptr(bws), _lib.stream_ptr()))
+    _lib.api.hig_clip_text_bwd_dev(dims, table.table, dindex.index, dindex.counts, dout, ws, gtable, bws)
     if pool is not None:
         pool.give("clip_bwd", bws, dev)
         pool.give("clip_t", ws, dev)

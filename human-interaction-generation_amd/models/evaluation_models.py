@@ -56,8 +56,7 @@ def softmax_xent(logits, labels, want_dlogits=True, loss=None):
     dlogits = torch.empty_like(logits) if want_dlogits else None
     pred = torch.empty(B, device=dev, dtype=torch.int64)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().hig_softmax_xent(_lib.ptr(logits), _lib.ptr(labels), B, Cn, _lib.ptr(loss),
-                                               _lib.ptr(dlogits), _lib.ptr(pred), _lib.stream_ptr()))
+        _lib.api.hig_softmax_xent(logits, labels, B, Cn, loss, dlogits, pred)
     return loss, dlogits, pred
 
 
@@ -176,17 +175,12 @@ class _EvalEncoderBase(nn.Module):
                                       "EvaluatorModelWrapper does" % type(self).__name__)
         x1, x2, length, dims = self._prepare(x1, x2, length, class_num)
         B, dev = x1.shape[0], x1.device
-        L = _lib.lib()
-        nbytes = L.hig_eval_encoder_workspace_bytes(C.byref(dims))
-        if nbytes < 0:
-            raise RuntimeError("libhig: " + _lib.last_error())
-        ws = self._pool.take("eval_ws", nbytes, dev)
+        ws = self._pool.take("eval_ws", _lib.api.hig_eval_encoder_workspace_bytes(dims), dev)
         logits = torch.empty(B, class_num, device=dev, dtype=torch.float32)
         feature = torch.empty(B, self.latent_dim, device=dev, dtype=torch.float32) if want_feature else None
         table = self._table()
         with torch.cuda.device(dev):
-            _lib.check(L.hig_eval_encoder_fwd(C.byref(dims), table, _lib.ptr(x1), _lib.ptr(x2), _lib.ptr(length),
-                                              _lib.ptr(logits), _lib.ptr(feature), _lib.ptr(ws), _lib.stream_ptr()))
+            _lib.api.hig_eval_encoder_fwd(dims, table, x1, x2, length, logits, feature, ws)
         self._pool.give("eval_ws", ws, dev)   # stream-ordered reuse: the next call launches behind this one
         return logits, feature
 
@@ -220,16 +214,11 @@ class _EvalEncoderBase(nn.Module):
                                       % (type(self).__name__, self.precision))
         x1, x2, length, dims = self._prepare(x1, x2, length, class_num, shape_error=ValueError)
         B, dev = x1.shape[0], x1.device
-        L = _lib.lib()
-        nbytes = L.hig_eval_encoder_train_workspace_bytes(C.byref(dims))
-        if nbytes < 0:
-            raise RuntimeError("libhig: " + _lib.last_error())
-        ws = self._pool.take("eval_train_ws", nbytes, dev)
+        ws = self._pool.take("eval_train_ws", _lib.api.hig_eval_encoder_train_workspace_bytes(dims), dev)
         logits = torch.empty(B, class_num, device=dev, dtype=torch.float32)
         feature = None if self._cls_token else torch.empty(B, self.latent_dim, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            _lib.check(L.hig_eval_encoder_fwd_train(C.byref(dims), self._table(), _lib.ptr(x1), _lib.ptr(x2), _lib.ptr(length),
-                                                    _lib.ptr(logits), _lib.ptr(feature), _lib.ptr(ws), _lib.stream_ptr()))
+            _lib.api.hig_eval_encoder_fwd_train(dims, self._table(), x1, x2, length, logits, feature, ws)
         return logits, feature, (dims, x1, x2, length, ws, [p._version for p in self.trained_parameters()])
 
     def _release(self, saved):
@@ -260,12 +249,9 @@ class _EvalEncoderBase(nn.Module):
         dlogits = dlogits.detach().float().contiguous()
         if dfeature is not None:
             dfeature = dfeature.detach().float().contiguous()
-        L = _lib.lib()
-        bws = self._pool.take("eval_bwd_ws", L.hig_eval_encoder_bwd_workspace_bytes(C.byref(dims)), dev)
+        bws = self._pool.take("eval_bwd_ws", _lib.api.hig_eval_encoder_bwd_workspace_bytes(dims), dev)
         with torch.cuda.device(dev):
-            _lib.check(L.hig_eval_encoder_bwd(C.byref(dims), self._table(), _lib.ptr(x1), _lib.ptr(x2), _lib.ptr(length),
-                                              _lib.ptr(ws), _lib.ptr(dlogits), _lib.ptr(dfeature), self._table(grads),
-                                              _lib.ptr(bws), _lib.stream_ptr()))
+            _lib.api.hig_eval_encoder_bwd(dims, self._table(), x1, x2, length, ws, dlogits, dfeature, self._table(grads), bws)
         self._pool.give("eval_bwd_ws", bws, dev)
         return grads
 

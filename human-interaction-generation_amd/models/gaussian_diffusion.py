@@ -148,9 +148,8 @@ class DeviceLossSecondMomentResampler:
         self.refresh()
 
     def _launch(self, t, sample_loss, n):
-        _lib.check(_lib.lib().hig_loss_history_update(
-            _lib.ptr(t), _lib.ptr(sample_loss), n, _lib.ptr(self.hist), _lib.ptr(self.counts), _lib.ptr(self.base_w),
-            self.num_timesteps, self.history_per_term, self.uniform_prob, _lib.ptr(self.p), _lib.ptr(self.w), _lib.stream_ptr()))
+        _lib.api.hig_loss_history_update(t, sample_loss, n, self.hist, self.counts, self.base_w, self.num_timesteps,
+                                         self.history_per_term, self.uniform_prob, self.p, self.w)
 
     def refresh(self):
         """p and w from the history as it stands (what a launch with an empty batch does)."""
@@ -315,7 +314,7 @@ _Update = collections.namedtuple("_Update", "entry table needs_z history tail")
 
 
 def _launch_update(L, upd, x, eps, aux, t, tab, K, B, per, stream, scale=None, group=None, x_prev=None, pred=None):
-    """ONE launch of the fused update `upd` through the library handle L; every tensor argument is a device pointer already.
+    """ONE launch of the fused update `upd` through the gateway L (_lib.api), which holds every argument to its declared type.
         unguided (group None):  (x, eps, aux, t, tab, K, B, per, *tail, [x_prev, pred,] stream)
         guided:                 (xx, eps2, scale, aux, t2, tab, K, B, group, per, *tail, [pred,] stream), in place on xx
     aux is z (None where the update reads none) or the history; the bracketed outputs exist where upd.history is false."""
@@ -323,13 +322,13 @@ def _launch_update(L, upd, x, eps, aux, t, tab, K, B, per, stream, scale=None, g
     args = (x, eps) + ((scale,) if guided else ()) + (aux, t, tab, K, B) + ((group,) if guided else ()) + (per,) + tuple(upd.tail)
     if not upd.history:
         args += (pred,) if guided else (x_prev, pred)
-    _lib.check(getattr(L, upd.entry + ("_cfg" if guided else ""))(*args, stream))
+    getattr(L, upd.entry + ("_cfg" if guided else ""))(*args, stream)
 
 
 def _launch_impose_known(L, x, known, mask, z, t, tab, K, B, per, stream, group=None):
     """ONE hig_impose_known launch (group None) or hig_impose_known_cfg launch (`group` goes in before per) through L."""
     args = (x, known, mask, z, t, tab, K, B) + (() if group is None else (group,)) + (per, stream)
-    _lib.check(getattr(L, "hig_impose_known" + ("" if group is None else "_cfg"))(*args))
+    getattr(L, "hig_impose_known" + ("" if group is None else "_cfg"))(*args)
 
 
 def _last_sample(steps):
@@ -397,15 +396,15 @@ class GaussianDiffusion:
 
     def _fused_update(self, upd, x, eps, aux, t, B, scale=None, group=None, x_prev=None, pred=None):
         """ONE launch of `upd` on contiguous fp32 ROCm tensors of B samples (x, eps and t stacked to 2 B rows when guided)."""
-        P, rows = _lib.ptr, (B if group is None else 2 * B)
-        _launch_update(_lib.lib(), upd, P(x), P(eps), P(aux), P(t), P(upd.table(x.device)), self.num_timesteps, B,
-                       x.numel() // rows, _lib.stream_ptr(), scale, group, P(x_prev), P(pred))
+        rows = B if group is None else 2 * B
+        _launch_update(_lib.api, upd, x, eps, aux, t, upd.table(x.device), self.num_timesteps, B, x.numel() // rows,
+                       th.cuda.current_stream(), scale, group, x_prev, pred)
 
     def _impose_known(self, x, known, mask, z, t, B, group=None):
         """ONE imposition launch on contiguous tensors of B samples, in place on x (x and t stacked to 2 B rows when guided)."""
-        P, rows = _lib.ptr, (B if group is None else 2 * B)
-        _launch_impose_known(_lib.lib(), P(x), P(known), P(mask), P(z), P(t), P(self.device_table(x.device)), self.num_timesteps,
-                             B, x.numel() // rows, _lib.stream_ptr(), group)
+        rows = B if group is None else 2 * B
+        _launch_impose_known(_lib.api, x, known, mask, z, t, self.device_table(x.device), self.num_timesteps, B, x.numel() // rows,
+                             th.cuda.current_stream(), group)
 
     # ---- q(x_t | x_0) ---------------------------------------------------------------------
     def q_mean_variance(self, x_start, t):
@@ -424,9 +423,7 @@ class GaussianDiffusion:
             x0, nz = x_start.contiguous(), noise.contiguous()
             out = th.empty_like(x0)
             B = x0.shape[0]
-            _lib.check(_lib.lib().hig_q_sample(_lib.ptr(x0), _lib.ptr(nz), _lib.ptr(t.long().contiguous()),
-                                              _lib.ptr(self.device_table(x0.device)), self.num_timesteps, B,
-                                              x0.numel() // B, _lib.ptr(out), _lib.stream_ptr()))
+            _lib.api.hig_q_sample(x0, nz, t.long().contiguous(), self.device_table(x0.device), self.num_timesteps, B, x0.numel() // B, out)
             return out
         return (_extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
                 + _extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
@@ -690,10 +687,9 @@ class GaussianDiffusion:
                     z.normal_()
                 self._fused_update(upd, state, eps, hist if upd.history else z, t_dev, B, x_prev=state, **guide)
                 if tmap is None:
-                    _lib.check(_lib.lib().hig_dec_timesteps(_lib.ptr(t_dev), rows, _lib.stream_ptr()))
+                    _lib.api.hig_dec_timesteps(t_dev, rows)
                 else:
-                    _lib.check(_lib.lib().hig_advance_timesteps(_lib.ptr(t_dev), _lib.ptr(tmap), K, rows, _lib.ptr(t_model),
-                                                                _lib.stream_ptr()))
+                    _lib.api.hig_advance_timesteps(t_dev, tmap, K, rows, t_model)
 
             # warm-up on a side stream (allocations, text context), then undo its effect
             img0 = state.clone()

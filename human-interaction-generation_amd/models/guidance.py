@@ -143,8 +143,7 @@ class ClassifierFreeGuidedModel:
         if out2.is_cuda and out2.dtype == th.float32 and not out2.requires_grad:
             o2 = out2.contiguous()
             out = th.empty(B, *o2.shape[1:], device=o2.device, dtype=th.float32)
-            _lib.check(_lib.lib().hig_cfg_combine(_lib.ptr(o2), self.scale, B, group, o2.numel() // (2 * B), _lib.ptr(out),
-                                                  _lib.stream_ptr()))
+            _lib.api.hig_cfg_combine(o2, self.scale, B, group, o2.numel() // (2 * B), out)
             return out
         c, u = split_rows(out2, group)
         d = c - u

@@ -274,31 +274,26 @@ class MotionInteractionTransformer(MotionTransformer):
     def _launch_class_head(self, ids):
         """ids (rows,) int32 -> xf_proj (rows, E), xf_out (rows, 1, Lt): text_proj once per class, rows fetched by id."""
         tp, classes, Lt, E, rows = self._class_head_args(ids)
-        L = _lib.lib()
         dev = ids.device
-        ws = self._pool.take("cls_f", L.hig_class_head_workspace_bytes(classes, Lt, E, 0), dev)
+        ws = self._pool.take("cls_f", _lib.api.hig_class_head_workspace_bytes(classes, Lt, E, 0), dev)
         xf_out = torch.empty(rows, 1, Lt, device=dev, dtype=torch.float32)
         xf_proj = torch.empty(rows, E, device=dev, dtype=torch.float32)
-        _lib.check(L.hig_class_head_fwd(classes, Lt, E, rows, _lib.ptr(tp[0]), _lib.ptr(tp[1]), _lib.ptr(tp[2]), _lib.ptr(ids),
-                                        _lib.ptr(xf_out), _lib.ptr(xf_proj), _lib.ptr(ws), _lib.stream_ptr()))
+        _lib.api.hig_class_head_fwd(classes, Lt, E, rows, tp[0], tp[1], tp[2], ids, xf_out, xf_proj, ws)
         self._pool.give("cls_f", ws, dev)
         return xf_proj, xf_out
 
     def _launch_class_head_backward(self, ids, dxf_out, dxf_proj):
         """Writes the gradients of cap_embedding, text_proj.0.weight and text_proj.0.bias into the flat gradient buffer."""
         tp, classes, Lt, E, rows = self._class_head_args(ids)
-        L = _lib.lib()
         dev = ids.device
         fp = self.flat_params()
         fp.ensure_grad()
         assert len(fp.text_params) == 3 and all(a is b for a, b in zip(fp.text_params, tp)), \
             "the class head is not part of the flat parameter buffer"
         g_emb, g_w, g_b = (C.c_void_p(fp.grad.data_ptr() + 4 * o) for o in fp.text_offsets)
-        ws = self._pool.take("cls_b", L.hig_class_head_workspace_bytes(classes, Lt, E, 1), dev)
-        _lib.check(L.hig_class_head_bwd(classes, Lt, E, rows, _lib.ptr(tp[0]), _lib.ptr(tp[1]), _lib.ptr(ids),
-                                        _lib.ptr(None if dxf_out is None else dxf_out.contiguous()),
-                                        _lib.ptr(None if dxf_proj is None else dxf_proj.contiguous()),
-                                        g_emb, g_w, g_b, _lib.ptr(ws), _lib.stream_ptr()))
+        ws = self._pool.take("cls_b", _lib.api.hig_class_head_workspace_bytes(classes, Lt, E, 1), dev)
+        _lib.api.hig_class_head_bwd(classes, Lt, E, rows, tp[0], tp[1], ids, None if dxf_out is None else dxf_out.contiguous(),
+                                    None if dxf_proj is None else dxf_proj.contiguous(), g_emb, g_w, g_b, ws)
         self._pool.give("cls_b", ws, dev)
 
     def dims(self, B, T, N):

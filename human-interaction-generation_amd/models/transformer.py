@@ -31,8 +31,7 @@ def timestep_embedding(timesteps, dim, max_period=10000):
     if timesteps.is_cuda:
         t = timesteps.long().contiguous()
         out = torch.empty(t.shape[0], dim, device=t.device, dtype=torch.float32)
-        _lib.check(_lib.lib().hig_timestep_embedding(_lib.ptr(t), t.shape[0], dim, _lib.ptr(out),
-                                                    _lib.stream_ptr()))
+        _lib.api.hig_timestep_embedding(t, t.shape[0], dim, out)
         return out
     raise RuntimeError("timestep_embedding: ROCm device tensor required (no CPU fallback)")
 
@@ -312,8 +311,7 @@ class _FlatParams:
                 self._stable[i] = None if off is None else self._shadow_ptr + 2 * off
             self._shadow_version = None
         if self._shadow_version != (version, self.flat.data_ptr()):
-            _lib.check(_lib.lib().hig_cast_bf16(_lib.ptr(self.flat), _lib.ptr(self._shadow), self.core_numel,
-                                                _lib.stream_ptr()))
+            _lib.api.hig_cast_bf16(self.flat, self._shadow, self.core_numel)
             self._shadow_version = (version, self.flat.data_ptr())
         return self._stable
 
@@ -734,10 +732,7 @@ class MotionTransformer(nn.Module):
                    fp.flat._version, self._textctx_param_version(), self.precision, self.storage)
             if self._textctx_cache is not None and self._textctx_cache[0] == key:
                 return self._textctx_cache[1]
-        L = _lib.lib()
-        nbytes = L.hig_textctx_bytes(C.byref(dims), int(training))
-        if nbytes < 0:
-            raise RuntimeError("libhig: " + _lib.last_error())
+        nbytes = _lib.api.hig_textctx_bytes(dims, training)
         if training:
             buf = self._pool.take("textctx_t", nbytes, xf_out.device)
         elif use_cache:
@@ -746,14 +741,11 @@ class MotionTransformer(nn.Module):
             buf = self._pool.take("textctx_i", nbytes, xf_out.device)
             self._pool.give("textctx_i", buf, xf_out.device)
         if self._bf16() and training:
-            _lib.check(L.hig_text_context_bf16_train(C.byref(dims), fp.param_table(), fp.shadow16(self._param_version()),
-                                                     _lib.ptr(xf_out), _lib.ptr(buf), _lib.stream_ptr()))
+            _lib.api.hig_text_context_bf16_train(dims, fp.param_table(), fp.shadow16(self._param_version()), xf_out, buf)
         elif self._bf16():
-            _lib.check(L.hig_text_context_bf16(C.byref(dims), fp.param_table(), fp.shadow16(self._param_version()),
-                                               _lib.ptr(xf_out), _lib.ptr(buf), _lib.stream_ptr()))
+            _lib.api.hig_text_context_bf16(dims, fp.param_table(), fp.shadow16(self._param_version()), xf_out, buf)
         else:
-            _lib.check(L.hig_text_context(C.byref(dims), fp.param_table(), _lib.ptr(xf_out), _lib.ptr(buf),
-                                          int(training), _lib.stream_ptr()))
+            _lib.api.hig_text_context(dims, fp.param_table(), xf_out, buf, training)
         if use_cache:
             self._textctx_cache = (key, buf, xf_out)  # keep xf_out alive so the key stays unique
         return buf
@@ -866,14 +858,12 @@ class MotionTransformer(nn.Module):
     def _launch_forward(self, x, t, length, xf_proj, xf_out, training):
         B, T, N = x.shape[0], x.shape[1], xf_out.shape[1]
         assert xf_out.shape == (B, N, self.text_latent_dim) and xf_proj.shape == (B, self.time_embed_dim)
-        L = _lib.lib()
+        api = _lib.api
         fp = self.flat_params()
         dims = self.dims(B, T, N)
         if training:
             self._check_bf16_training()
-        nbytes = L.hig_workspace_bytes(C.byref(dims), int(training))
-        if nbytes < 0:
-            raise RuntimeError("libhig: " + _lib.last_error())
+        nbytes = api.hig_workspace_bytes(dims, training)
         out = torch.empty(B, T, self.input_feats, device=x.device, dtype=torch.float32)
         bf16 = self._bf16()
         # per call: the reference's forward (text side recomputed every call, transformer.py:144-150) as ONE library call, which
@@ -881,33 +871,24 @@ class MotionTransformer(nn.Module):
         # bf16 storage: embedding chain and text side next to the frame-row launches)
         per_call = not training and not self.cache_text_context
         if per_call:
-            tbytes = L.hig_textctx_bytes(C.byref(dims), 0)
-            if tbytes < 0:
-                raise RuntimeError("libhig: " + _lib.last_error())
-            textctx = self._pool.take("textctx_i", tbytes, x.device)
+            textctx = self._pool.take("textctx_i", api.hig_textctx_bytes(dims, 0), x.device)
         else:
             textctx = self._text_context(dims, xf_out, training)
         ws = self._pool.take("fwd_t" if training else "fwd_i", nbytes, x.device)
         if training:
             if bf16:
-                _lib.check(L.hig_denoiser_fwd_bf16_train(C.byref(dims), fp.param_table(), fp.shadow16(self._param_version()),
-                                                         _lib.ptr(x), _lib.ptr(t), _lib.ptr(length), _lib.ptr(xf_proj),
-                                                         _lib.ptr(textctx), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()))
+                api.hig_denoiser_fwd_bf16_train(dims, fp.param_table(), fp.shadow16(self._param_version()), x, t, length, xf_proj,
+                                                textctx, out, ws)
             else:
-                _lib.check(L.hig_denoiser_fwd(C.byref(dims), fp.param_table(), _lib.ptr(x), _lib.ptr(t),
-                                              _lib.ptr(length), _lib.ptr(xf_proj), _lib.ptr(textctx), _lib.ptr(out),
-                                              _lib.ptr(ws), 1, _lib.stream_ptr()))
+                api.hig_denoiser_fwd(dims, fp.param_table(), x, t, length, xf_proj, textctx, out, ws, 1)
             return out, (dims, ws, textctx)
         # inference: the LayerNorm-folded projections (derived per parameter version)
-        text = _lib.ptr(xf_out) if per_call else None
+        text = xf_out if per_call else None
         if bf16:
-            _lib.check(L.hig_denoiser_fwd_bf16_x(C.byref(dims), fp.param_table(), fp.shadow16(self._param_version()),
-                                                 self._derived16(fp), _lib.ptr(x), _lib.ptr(t), _lib.ptr(length), _lib.ptr(xf_proj),
-                                                 text, _lib.ptr(textctx), _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr()))
+            api.hig_denoiser_fwd_bf16_x(dims, fp.param_table(), fp.shadow16(self._param_version()), self._derived16(fp), x, t, length,
+                                        xf_proj, text, textctx, out, ws)
         else:
-            _lib.check(L.hig_denoiser_fwd_x(C.byref(dims), fp.param_table(), self._derived32(fp), _lib.ptr(x), _lib.ptr(t),
-                                            _lib.ptr(length), _lib.ptr(xf_proj), text, _lib.ptr(textctx), _lib.ptr(out),
-                                            _lib.ptr(ws), 0, _lib.stream_ptr()))
+            api.hig_denoiser_fwd_x(dims, fp.param_table(), self._derived32(fp), x, t, length, xf_proj, text, textctx, out, ws, 0)
         self._pool.give("fwd_i", ws, x.device)
         if per_call:
             self._pool.give("textctx_i", textctx, x.device)
@@ -918,23 +899,21 @@ class MotionTransformer(nn.Module):
         torch.cuda.Stream) has been made to wait for it -- the data-parallel exchange of layer l's gradients can start
         there while the earlier layers are still in backward (hig_denoiser_bwd_hooked)."""
         dims, ws, textctx = saved
-        L = _lib.lib()
+        api = _lib.api
         fp = self.flat_params()
         gtable = fp.ensure_grad()
         B, T, N = dims.B, dims.T, dims.N
         dev = x.device
-        nb = L.hig_bwd_workspace_bytes(C.byref(dims))
-        bws = self._pool.take("bwd", nb, dev)
+        bws = self._pool.take("bwd", api.hig_bwd_workspace_bytes(dims), dev)
         dx = torch.empty_like(x) if want_dx else None
         dxp = torch.empty(B, self.time_embed_dim, device=dev, dtype=torch.float32)
         dxo = torch.empty(B, N, self.text_latent_dim, device=dev, dtype=torch.float32)
         bf16 = dims.storage == _lib.STORE_BF16
         # the four entries take the same arguments; bf16 storage adds the weight shadow, a hooked one the hook behind the stream
-        args = [C.byref(dims), fp.param_table()] + ([fp.shadow16(self._param_version())] if bf16 else [])
-        args += [_lib.ptr(x), _lib.ptr(t), _lib.ptr(length), _lib.ptr(xf_out), _lib.ptr(textctx), _lib.ptr(ws), _lib.ptr(dout),
-                 gtable, _lib.ptr(dx), _lib.ptr(dxp), _lib.ptr(dxo), _lib.ptr(bws), _lib.stream_ptr()]
+        args = [dims, fp.param_table()] + ([fp.shadow16(self._param_version())] if bf16 else []) + \
+               [x, t, length, xf_out, textctx, ws, dout, gtable, dx, dxp, dxo, bws, torch.cuda.current_stream()]
         if layer_hook is None:      # (the hooked entries refuse a null hook)
-            _lib.check((L.hig_denoiser_bwd_bf16 if bf16 else L.hig_denoiser_bwd)(*args))
+            (api.hig_denoiser_bwd_bf16 if bf16 else api.hig_denoiser_bwd)(*args)
         else:
             errors = []
 
@@ -945,8 +924,7 @@ class MotionTransformer(nn.Module):
                     errors.append(e)
 
             cb = _lib.LAYER_HOOK(_hook)
-            _lib.check((L.hig_denoiser_bwd_bf16_hooked if bf16 else L.hig_denoiser_bwd_hooked)(
-                *args, cb, None, None if comm_stream is None else C.c_void_p(comm_stream.cuda_stream)))
+            (api.hig_denoiser_bwd_bf16_hooked if bf16 else api.hig_denoiser_bwd_hooked)(*args, cb, None, comm_stream)
             if errors:
                 raise errors[0]
         self._pool.give("bwd", bws, dev)
@@ -998,22 +976,17 @@ class MotionTransformer(nn.Module):
 
     def _launch_text_head(self, clip_out, eot, training):
         B, N, W = clip_out.shape
-        L = _lib.lib()
         tp = self._text_params()
         for p in tp:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 raise RuntimeError("text head: parameters must be contiguous fp32 ROCm tensors")
         dims = self._text_dims(B, N, W)
-        nbytes = L.hig_text_head_workspace_bytes(C.byref(dims), int(training))
-        if nbytes < 0:
-            raise RuntimeError("libhig: %s (text_head='torch' selects stock PyTorch ops)" % _lib.last_error())
+        nbytes = _lib.api.hig_text_head_workspace_bytes(dims, training)
         dev = clip_out.device
         ws = self._pool.take("txt_t" if training else "txt_i", nbytes, dev)
         xf_out = torch.empty(B, N, self.text_latent_dim, device=dev, dtype=torch.float32)
         xf_proj = torch.empty(B, self.time_embed_dim, device=dev, dtype=torch.float32)
-        _lib.check(L.hig_text_head_fwd(C.byref(dims), self._text_table(tp), _lib.ptr(clip_out), _lib.ptr(eot),
-                                       _lib.ptr(xf_out), _lib.ptr(xf_proj), _lib.ptr(ws), int(training),
-                                       _lib.stream_ptr()))
+        _lib.api.hig_text_head_fwd(dims, self._text_table(tp), clip_out, eot, xf_out, xf_proj, ws, training)
         if not training:
             self._pool.give("txt_i", ws, dev)
             return xf_proj, xf_out, None
@@ -1024,7 +997,6 @@ class MotionTransformer(nn.Module):
         """into_flat: write the parameter gradients into the flat gradient buffer (fused training step)
         instead of a fresh scratch buffer (autograd path)."""
         dims, ws = saved
-        L = _lib.lib()
         tp = self._text_params()
         dev = clip_out.device
         if into_flat:
@@ -1040,12 +1012,10 @@ class MotionTransformer(nn.Module):
             grads = [gflat[off:off + p.numel()].view(p.shape) for p, off in zip(tp, offs)]
             gtable = self._text_table(grads)
         dclip = torch.empty_like(clip_out) if want_dclip else None
-        bws = self._pool.take("txt_bwd", L.hig_text_head_bwd_workspace_bytes(C.byref(dims)), dev)
-        _lib.check(L.hig_text_head_bwd(
-            C.byref(dims), self._text_table(tp), _lib.ptr(clip_out), _lib.ptr(eot), _lib.ptr(xf_out), _lib.ptr(ws),
-            _lib.ptr(None if dxf_out is None else dxf_out.contiguous()),
-            _lib.ptr(None if dxf_proj is None else dxf_proj.contiguous()),
-            gtable, _lib.ptr(dclip), _lib.ptr(bws), _lib.stream_ptr()))
+        bws = self._pool.take("txt_bwd", _lib.api.hig_text_head_bwd_workspace_bytes(dims), dev)
+        _lib.api.hig_text_head_bwd(dims, self._text_table(tp), clip_out, eot, xf_out, ws,
+                                   None if dxf_out is None else dxf_out.contiguous(),
+                                   None if dxf_proj is None else dxf_proj.contiguous(), gtable, dclip, bws)
         self._pool.give("txt_bwd", bws, dev)
         self._pool.give("txt_t", ws, dev)
         return grads, dclip

@@ -100,10 +100,9 @@ class OverlappedGradAllReduce:
                 dist.all_reduce(self.grad[a:b], op=dist.ReduceOp.SUM, group=self.group)
                 continue
             from . import _lib
-            sp = _lib.stream_ptr()
-            _lib.check(_lib.lib().hig_cast_bf16(_lib.ptr(self.grad[a:b]), _lib.ptr(self.stage[a:b]), b - a, sp))
+            _lib.api.hig_cast_bf16(self.grad[a:b], self.stage[a:b], b - a)
             dist.all_reduce(self.stage[a:b], op=dist.ReduceOp.SUM, group=self.group)      # (self.stream waits for RCCL's)
-            _lib.check(_lib.lib().hig_cast_f32(_lib.ptr(self.stage[a:b]), _lib.ptr(self.grad[a:b]), b - a, sp))
+            _lib.api.hig_cast_f32(self.stage[a:b], self.grad[a:b], b - a)
 
     def layer_done(self, layer):
         with torch.cuda.stream(self.stream):       # (the library already made this stream wait for the layer)

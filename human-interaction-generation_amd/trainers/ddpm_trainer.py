@@ -401,26 +401,24 @@ class DDPMTrainer(object):
 
     def _ema_update_after_torch_step(self, st):
         """Route 3: torch.optim.Adam has stepped; one hig_ema_update over the flat buffer, one per outside tensor."""
-        L = _lib.lib()
         fp = _core(self.encoder).flat_params()
         n_host = st["num_updates"] + 1
-        args = (st["decay"], int(st["warmup"]), None, st["origin"], n_host, _lib.stream_ptr())
-        _lib.check(L.hig_ema_update(_lib.ptr(st["flat"]), _lib.ptr(fp.flat), fp.numel, *args))
+        args = (st["decay"], int(st["warmup"]), None, st["origin"], n_host)
+        _lib.api.hig_ema_update(st["flat"], fp.flat, fp.numel, *args)
         now = dict(self._ema_outside_params())
         for k, e in st["outside"].items():
-            _lib.check(L.hig_ema_update(_lib.ptr(e), _lib.ptr(now[k].data), e.numel(), *args))
+            _lib.api.hig_ema_update(e, now[k].data, e.numel(), *args)
         st["num_updates"] = n_host
 
     def _ema_exchange(self, st):
         """Weights <-> EMA in place (hig_swap_f32): no pointer moves, so parameter tables, derived-operand caches and captured
         training graphs stay valid; what is DERIVED from the weights (bf16 shadow, text context) follows params_changed()."""
-        L = _lib.lib()
         core = _core(self.encoder)
         fp = core.flat_params()
-        _lib.check(L.hig_swap_f32(_lib.ptr(fp.flat), _lib.ptr(st["flat"]), fp.numel, _lib.stream_ptr()))
+        _lib.api.hig_swap_f32(fp.flat, st["flat"], fp.numel)
         now = dict(self._ema_outside_params())
         for k, e in st["outside"].items():
-            _lib.check(L.hig_swap_f32(_lib.ptr(now[k].data), _lib.ptr(e), e.numel(), _lib.stream_ptr()))
+            _lib.api.hig_swap_f32(now[k].data, e, e.numel())
         core.params_changed()
         if getattr(core, "storage", "f32") == "bf16" and getattr(fp, "_shadow", None) is not None:
             fp.shadow16(core._param_version())      # eagerly: a captured training graph reads the shadow without re-deriving it
@@ -841,7 +839,6 @@ class DDPMTrainer(object):
     def _denoise_loss_backward(self, x_start, t, length, xf_proj, xf_out, noise, exchange):
         """The middle of `_fused_fwd_bwd`; returns the gradients of the loss with respect to xf_proj and xf_out."""
         core = _core(self.encoder)
-        L = _lib.lib()
         st = self.fused_state()
         B, T, F = x_start.shape
         if noise is None:
@@ -851,16 +848,12 @@ class DDPMTrainer(object):
         dpred = torch.empty_like(pred)
         wtab, smp = self._loss_state(pred.device)
         if wtab is None:
-            _lib.check(L.hig_masked_mse(_lib.ptr(pred), _lib.ptr(noise), _lib.ptr(length), B, T, F,
-                                        _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(st["mse_scratch"]),
-                                        _lib.stream_ptr()))
+            _lib.api.hig_masked_mse(pred, noise, length, B, T, F, st["loss"], dpred, st["mse_scratch"])
         else:   # the weighted twin; loss-aware: the per-sample losses, then the history update BEHIND the loss launch, so
             # this step's loss has read the table its t was drawn under
             sl = None if smp is None else self._loss_buffer(st, "sample_loss", B, pred.device)
             scr = self._loss_buffer(st, "mse_w_scratch", _lib.NORM_BLOCKS + (0 if smp is None else B * T), pred.device)
-            _lib.check(L.hig_masked_mse_w(_lib.ptr(pred), _lib.ptr(noise), _lib.ptr(length), _lib.ptr(t), _lib.ptr(wtab),
-                                          wtab.numel(), B, T, F, _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(sl),
-                                          _lib.ptr(scr), _lib.stream_ptr()))
+            _lib.api.hig_masked_mse_w(pred, noise, length, t, wtab, wtab.numel(), B, T, F, st["loss"], dpred, sl, scr)
             if smp is not None:
                 smp.update(t, sl)
         hook = {} if exchange is None else dict(layer_hook=exchange.layer_done, comm_stream=exchange.stream)
@@ -929,25 +922,21 @@ class DDPMTrainer(object):
     def _fused_clip_adam(self, world, with_text=False):   # (with_text: the step's source, or a bool = its `trains_head`)
         """g /= world; clip_grad_norm_(0.5); Adam -- one norm pass + one update pass over the flat buffers."""
         core = _core(self.encoder)
-        L = _lib.lib()
         st = self.fused_state()
         fp = core.flat_params()
         n = self._fused_numel(with_text)
-        _lib.check(L.hig_sumsq_partial(_lib.ptr(fp.grad), n, 1.0 / world, _lib.ptr(st["scratch"]),
-                                       _lib.stream_ptr()))
+        _lib.api.hig_sumsq_partial(fp.grad, n, 1.0 / world, st["scratch"])
         bf16 = getattr(core, "storage", "f32") == "bf16"
         # bf16 storage: the update kernel also writes bf16(new parameters) into the weight shadow the next forward reads
         # (fp32 master weights, no separate cast pass over the 81 M parameters)
         shadow = fp.shadow16_buffer() if bf16 else None
         ema = self.ema_state()
-        args = (_lib.ptr(fp.flat), _lib.ptr(fp.grad), _lib.ptr(st["m"]), _lib.ptr(st["v"]), n, st["lr_host"], _lib.ptr(st["lr"]),
-                ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, GRAD_CLIP, 1.0 / world, _lib.ptr(st["scratch"]), _lib.ptr(st["gnorm"]),
-                _lib.ptr(st["step"]), _lib.ptr(shadow), fp.core_numel if bf16 else 0)
+        args = (fp.flat, fp.grad, st["m"], st["v"], n, st["lr_host"], st["lr"], ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, GRAD_CLIP,
+                1.0 / world, st["scratch"], st["gnorm"], st["step"], shadow, fp.core_numel if bf16 else 0)
         if ema is None:
-            _lib.check(L.hig_clip_adam_shadow(*args, _lib.stream_ptr()))
+            _lib.api.hig_clip_adam_shadow(*args)
         else:   # the same pass also blends the new parameters into the EMA; its update number comes from the device counter
-            _lib.check(L.hig_clip_adam_ema(*args, _lib.ptr(ema["flat"]), ema["decay"], int(ema["warmup"]), ema["origin"],
-                                           _lib.stream_ptr()))
+            _lib.api.hig_clip_adam_ema(*args, ema["flat"], ema["decay"], int(ema["warmup"]), ema["origin"])
         st["covered"] = max(st["covered"], n)
         core.params_changed()
         if bf16:

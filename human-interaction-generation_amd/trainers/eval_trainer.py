@@ -122,9 +122,8 @@ class EvalModelTrainer:
             raise
         model._launch_bwd(saved, dlogits, None, grads=st["gviews"])
         with torch.cuda.device(st["flat"].device):
-            _lib.check(_lib.lib().hig_clip_adam(_lib.ptr(st["flat"]), _lib.ptr(st["grad"]), _lib.ptr(st["m"]), _lib.ptr(st["v"]),
-                                                st["n"], self.lr, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS, 0.0, 1.0,
-                                                _lib.ptr(st["scratch"]), None, _lib.ptr(st["step"]), _lib.stream_ptr()))
+            _lib.api.hig_clip_adam(st["flat"], st["grad"], st["m"], st["v"], st["n"], self.lr, ADAM_BETAS[0], ADAM_BETAS[1], ADAM_EPS,
+                                   0.0, 1.0, st["scratch"], None, st["step"])
         return loss.clone(), pred
 
     # ---- the loop --------------------------------------------------------------------------------------------------------

@@ -208,7 +208,6 @@ class DDPMMulTrainer(DDPMTrainer):
         if not self.multi:
             return super()._denoise_loss_backward(x_start, t, length, xf_proj, xf_out, noise, exchange)
         core = _core(self.encoder)
-        L = _lib.lib()
         st = self.fused_state()
         B2, T, F = x_start.shape
         B = B2 // 2
@@ -229,15 +228,12 @@ class DDPMMulTrainer(DDPMTrainer):
         scr = self._loss_buffer(st, "pair_scratch", 2 * rows, pred.device)      # (one per size: captured graphs keep theirs)
         wtab, smp = self._loss_state(pred.device)
         if wtab is None:
-            _lib.check(L.hig_pair_mse(_lib.ptr(pred), _lib.ptr(noise.contiguous()), _lib.ptr(len_rows), rows, T, F, int(pit),
-                                      _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(scr), _lib.stream_ptr()))
+            _lib.api.hig_pair_mse(pred, noise.contiguous(), len_rows, rows, T, F, pit, st["loss"], dpred, scr)
         else:   # the weighted twin (row r counts w[t2[r]] times); loss-aware: one loss per pair (PIT) or per row, pushed under
             # the first entries of t2, behind the loss launch
             t2 = t2.contiguous()
             sl = None if smp is None else self._loss_buffer(st, "sample_loss", rows // 4 if pit else rows, pred.device)
-            _lib.check(L.hig_pair_mse_w(_lib.ptr(pred), _lib.ptr(noise.contiguous()), _lib.ptr(len_rows), _lib.ptr(t2), _lib.ptr(wtab),
-                                        wtab.numel(), rows, T, F, int(pit), _lib.ptr(st["loss"]), _lib.ptr(dpred), _lib.ptr(sl),
-                                        _lib.ptr(scr), _lib.stream_ptr()))
+            _lib.api.hig_pair_mse_w(pred, noise.contiguous(), len_rows, t2, wtab, wtab.numel(), rows, T, F, pit, st["loss"], dpred, sl, scr)
             if smp is not None:
                 smp.update(t2, sl)
         hook = {} if exchange is None else dict(layer_hook=exchange.layer_done, comm_stream=exchange.stream)
@@ -372,7 +368,7 @@ class DDPMMulTrainer(DDPMTrainer):
         steps, draws = [int(t) for t in steps], int(draws)
         if not steps or draws <= 0:
             raise ValueError("label_votes: at least one timestep and one draw")
-        core, L, P_ = _core(self.encoder), _lib.lib(), _lib.ptr
+        core = _core(self.encoder)
         K = self.diffusion.num_timesteps
         if any(not 0 <= t < K for t in steps):
             raise ValueError("label_votes: steps must lie in [0, %d)" % K)
@@ -413,10 +409,9 @@ class DDPMMulTrainer(DDPMTrainer):
             def step():
                 if noise is None:
                     z.normal_()
-                _lib.check(L.hig_q_sample_pit(P_(x_start), P_(z), P_(t2), P_(tab), K, B, T * F, P_(xt4), _lib.stream_ptr()))
+                _lib.api.hig_q_sample_pit(x_start, z, t2, tab, K, B, T * F, xt4)
                 pred, _ = core._launch_forward(xt4, t4, len4, xf_proj, xf_out, training=False)
-                _lib.check(L.hig_pair_vote(P_(pred), P_(z), P_(len4), 4 * B, T, F, P_(votes), P_(first), P_(assign), P_(scratch),
-                                           _lib.stream_ptr()))
+                _lib.api.hig_pair_vote(pred, z, len4, 4 * B, T, F, votes, first, assign, scratch)
 
             run = step
             if captured:    # warm-up on a side stream (allocations, text context), then undo its vote

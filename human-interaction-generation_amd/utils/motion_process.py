@@ -15,8 +15,7 @@ def _launch(motion, stats, joints_num, init_first):
     motion = motion.float().contiguous()
     R, T1, F = motion.shape
     pos = torch.empty(R, T1 - 1, joints_num, 3, device=motion.device, dtype=torch.float32)
-    _lib.check(_lib.lib().hig_recover_joints(_lib.ptr(motion), _lib.ptr(stats), R, T1 - 1, F, joints_num,
-                                             int(init_first), _lib.ptr(pos), _lib.stream_ptr()))
+    _lib.api.hig_recover_joints(motion, stats, R, T1 - 1, F, joints_num, init_first, pos)
     return pos
 
 

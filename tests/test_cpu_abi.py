@@ -42,6 +42,8 @@ def test_reader_on_literal_declarations():
                             float* loss /* device scalar, (nullable); */, int64_t* pred,
                             float scale, hig_stream_t stream, hig_layer_hook hook, char* buf);
         void hig_nothing(int32_t);
+        typedef int (*hig_progress)(void*, int64_t done);   /* a callback with an unnamed parameter */
+        int hig_mixed(const float*, int64_t n, hig_progress, const int64_t* const*);
         #ifdef __cplusplus
         }
         #endif
@@ -50,18 +52,33 @@ def test_reader_on_literal_declarations():
     assert consts == {"HIG_OK": 0, "HIG_X": -3, "HIG_A": 4, "HIG_B": 5, "HIG_C": -2, "HIG_D": -1, "HIG_E": 0, "HIG_F": 0, "HIG_G": 1,
                       "HIG_H2": 2}
     assert structs == {"hig_pt": [("B", "int32_t"), ("N", "int32_t"), ("X", "const float*"), ("ldx", "int64_t"), ("Y", "void*")]}
-    assert callbacks == {"hig_layer_hook": ("void", ["void*", "int32_t"])}
-    assert list(protos) == ["hig_version", "hig_bytes", "hig_three_lines", "hig_nothing"]            # the header's order
-    assert protos["hig_version"] == ("int", []) and protos["hig_bytes"] == ("int64_t", ["const hig_pt*", "int"])
-    assert protos["hig_three_lines"] == ("int", ["const hig_pt*", "const void* const*", "float*", "int64_t*", "float", "hig_stream_t",
-                                                 "hig_layer_hook", "char*"])
-    assert protos["hig_nothing"] == ("void", ["int32_t"])
+    def types(decl):                                     # (return C type, [parameter C types]); the names are held to below
+        return decl[0], [t for _, t in decl[1]]
+
+    def names(decl):
+        return [n for n, _ in decl[1]]
+
+    assert {n: types(d) for n, d in callbacks.items()} == {"hig_layer_hook": ("void", ["void*", "int32_t"]),
+                                                           "hig_progress": ("int", ["void*", "int64_t"])}
+    assert list(protos) == ["hig_version", "hig_bytes", "hig_three_lines", "hig_nothing", "hig_mixed"]  # the header's order
+    assert types(protos["hig_version"]) == ("int", []) and types(protos["hig_bytes"]) == ("int64_t", ["const hig_pt*", "int"])
+    assert types(protos["hig_three_lines"]) == ("int", ["const hig_pt*", "const void* const*", "float*", "int64_t*", "float", "hig_stream_t",
+                                                        "hig_layer_hook", "char*"])
+    assert types(protos["hig_nothing"]) == ("void", ["int32_t"])
+    assert types(protos["hig_mixed"]) == ("int", ["const float*", "int64_t", "hig_progress", "const int64_t* const*"])
+    # the names: the header's own, `arg<i>` by position where it gives none
+    assert names(callbacks["hig_layer_hook"]) == ["user", "layer"] and names(callbacks["hig_progress"]) == ["arg0", "done"]
+    assert names(protos["hig_version"]) == [] and names(protos["hig_bytes"]) == ["p", "training"]
+    assert names(protos["hig_three_lines"]) == ["p", "params", "loss", "pred", "scale", "stream", "hook", "buf"]
+    assert names(protos["hig_nothing"]) == ["arg0"] and names(protos["hig_mixed"]) == ["arg0", "n", "arg2", "arg3"]
 
     classes, hooks, sigs = _abi.bind(structs, callbacks, protos, {"hig_pt": "Pt"})
     Pt, hook = classes["Pt"], hooks["hig_layer_hook"]
     assert Pt.__name__ == "Pt" and Pt._fields_ == [("B", C.c_int32), ("N", C.c_int32), ("X", C.c_void_p), ("ldx", C.c_int64), ("Y", C.c_void_p)]
     assert Pt(B=3, ldx=1 << 40).ldx == 1 << 40
     assert (hook._restype_, hook._argtypes_) == (None, (C.c_void_p, C.c_int32))
+    assert (hooks["hig_progress"]._restype_, hooks["hig_progress"]._argtypes_) == (C.c_int32, (C.c_void_p, C.c_int64))
+    assert sigs["hig_mixed"] == (C.c_int32, [C.c_void_p, C.c_int64, hooks["hig_progress"], C.c_void_p])
     assert sigs["hig_version"] == (C.c_int32, []) and sigs["hig_nothing"] == (None, [C.c_int32])
     assert sigs["hig_bytes"] == (C.c_int64, [C.POINTER(Pt), C.c_int32])
     assert sigs["hig_three_lines"] == (C.c_int32, [C.POINTER(Pt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, hook, C.c_char_p])
