@@ -6,7 +6,7 @@
 // Three kernels live here -- the embedding front, QuickGELU and the causal attention -- and the launch sequence, which is host
 // code in the style of texthead.hip: GEMMs through hig_gemm_launch, norms through hig_layernorm, hipGraph-capturable.
 #include "hig_common.h"
-#include "hig_host.h"
+#include "enc_layers.h"
 
 namespace {
 
@@ -157,6 +157,7 @@ __global__ __launch_bounds__(CA_NT) void causal_attn_kernel(const float* __restr
 struct CDims {
   int B, N, W, H, L, vocab, prec;
   int64_t M;
+  EncShape enc() const { return {B, N, W, 4 * W, H, CA_HD}; }
 };
 
 int check_cdims(const int32_t* p, CDims& D) {
@@ -170,13 +171,17 @@ int check_cdims(const int32_t* p, CDims& D) {
   if (D.N > CA_NMAX)
     return hig_set_error(HIG_EUNSUPPORTED, "hig clip text tower: N=%d tokens, the causal attention covers N <= %d", D.N, CA_NMAX);
   if (D.W > 1024) return hig_set_error(HIG_EUNSUPPORTED, "hig clip text tower: W=%d, hig_layernorm covers rows of <= 1024", D.W);
-  if (D.prec != HIG_PREC_F32 && D.prec != HIG_PREC_BF16X3 && D.prec != HIG_PREC_BF16)
-    return hig_set_error(HIG_EINVAL, "hig: unknown prec=%d", D.prec);
+  HIG_TRY(hig_enc_check_prec(D.prec));
   D.M = (int64_t)D.B * D.N;
   return HIG_OK;
 }
+int check_train(const int32_t* dims, CDims& D, const char* who) {
+  HIG_TRY(check_cdims(dims, D));
+  if (D.prec != HIG_PREC_F32) return hig_set_error(HIG_EUNSUPPORTED, "%s: prec=%d, the tower trains with exact fp32 products only", who, D.prec);
+  return HIG_OK;
+}
 
-// Workspace (floats): the embedded rows and ln_final's statistics, then two layer blocks.
+// Inference workspace (floats): the embedded rows and ln_final's statistics, then two layer blocks.
 struct CFwd {
   int64_t x0, stf, layer0, block;
   int64_t h, st, qkv, att, x1, f, x2;
@@ -203,9 +208,100 @@ CFwd cfwd_layout(const CDims& D) {
   return w;
 }
 
-inline const float* CP(const void* const* t, int idx) { return static_cast<const float*>(t[idx]); }
-inline const float* CPL(const void* const* t, int l, int idx) {
-  return static_cast<const float*>(t[HIG_CT_NGLOBAL + l * HIG_CTL_NLAYER + idx]);
+// What hig_clip_text_fwd_train keeps (floats): the embedded rows and ln_final's statistics, then per layer the two LayerNorms'
+// statistics, qkv, lse, the attention output, x1, the FFN's pre-activation z and x2 (the next layer's input).  The LayerNorm
+// outputs and quick_gelu(z) are not kept: the adjoint rebuilds them (hig_layernorm, hig_quick_gelu_to), bit for bit.  Behind the
+// layers: the two buffers the forward itself rebuilds per layer (h, f).
+struct CTrain {
+  int64_t x0, stf, layer0, lstride;
+  int64_t st1, qkv, lse, att, x1, st2, z, x2;
+  int64_t h, f, total;
+};
+CTrain ctrain_layout(const CDims& D) {
+  CTrain w;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { int64_t r = o; o += al(n); return r; };
+  w.x0 = take(D.M * D.W);
+  w.stf = take(D.M * 2);
+  w.layer0 = o;
+  o = 0;
+  w.st1 = take(D.M * 2);
+  w.qkv = take(D.M * 3 * D.W);
+  w.lse = take((int64_t)D.B * D.H * D.N);
+  w.att = take(D.M * D.W);
+  w.x1 = take(D.M * D.W);
+  w.st2 = take(D.M * 2);
+  w.z = take(D.M * 4 * D.W);
+  w.x2 = take(D.M * D.W);
+  w.lstride = o;
+  o = w.layer0 + w.lstride * D.L;
+  w.h = take(D.M * D.W);
+  w.f = take(D.M * 4 * D.W);
+  w.total = o;
+  return w;
+}
+
+// The adjoint's workspace (floats): d / t1 / t2 / h (M, W), h's statistics, f (M, 4 W), the shared backward scratch, and the
+// embedding pass's chunk partials and per-id sums (at most B N rows each).  An array by slot, unlike CFwd and CTrain above,
+// because the shared scratch layout and EncBwd's binding (enc_layers.h) address a chain's table by slot.
+enum { CBW_D = 0, CBW_T1, CBW_T2, CBW_H, CBW_HST, CBW_F, CBW_DFF, CBW_DQKV, CBW_DELTA, CBW_WT, CBW_SLABS, CBW_SLAB_FLOATS, CBW_COLPART,
+       CBW_LNPART, CBW_EMB, CBW_TOTAL, CBW_NSLOTS };
+using CBwd = std::array<int64_t, CBW_NSLOTS>;
+constexpr EncScratchSlots CBW_SCRATCH = {CBW_DFF, CBW_DQKV, CBW_DELTA, CBW_WT, -1, -1, CBW_SLABS, CBW_SLAB_FLOATS, CBW_COLPART, CBW_LNPART};
+CBwd cbwd_layout(const CDims& D) {
+  CBwd w;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { int64_t r = o; o += al(n); return r; };
+  const int64_t ff = 4 * (int64_t)D.W;
+  for (int s : {CBW_D, CBW_T1, CBW_T2, CBW_H}) w[s] = take(D.M * D.W);
+  w[CBW_HST] = take(D.M * 2);
+  w[CBW_F] = take(D.M * ff);
+  hig_enc_scratch_grads(take, w.data(), CBW_SCRATCH, D.enc());
+  hig_enc_scratch_work(take, w.data(), CBW_SCRATCH, D.enc(), ff * D.W /* c_fc / c_proj */, {{D.M, ff}});
+  w[CBW_EMB] = take(2 * D.M * D.W);
+  w[CBW_TOTAL] = o;
+  return w;
+}
+
+// Where one layer of the tower works: ln_1 / ln_2's output h and their statistics, qkv, the attention's row log-sum-exps, its
+// output, x1, the FFN's pre-activation z, f = quick_gelu(z), x2.
+struct CLayer {
+  float *h, *st1, *st2, *qkv, *lse, *att, *x1, *z, *f, *x2;
+};
+// The forward both entry points launch; they differ in where layer l works (layer_of(l)), in whether lse is kept (lse != NULL:
+// hig_causal_attn_fwd_train) and in whether z is (z != f: hig_quick_gelu_to, else QuickGELU in place).
+template <class LayerOf>
+int clip_forward(const CDims& D, const void* const* params, const int64_t* tokens, float* out, float* x0, float* stf, LayerOf layer_of,
+                 hig_stream_t stream) {
+  const Tab P(params, HIG_CT_NGLOBAL, HIG_CTL_NLAYER);
+  hipStream_t st = hig_stream(stream);
+  const int W = D.W, ff = 4 * D.W;
+  const int64_t M = D.M;
+  HIG_TRY(hig_clip_embed(P[HIG_CT_TOK_EMB], P[HIG_CT_POS_EMB], tokens, D.B, D.N, W, D.vocab, x0, W, stream));
+  const float* xin = x0;
+  for (int l = 0; l < D.L; ++l) {
+    const CLayer a = layer_of(l);
+    HIG_TRY(hig_layernorm(xin, W, M, W, P(l, HIG_CTL_LN1_W), P(l, HIG_CTL_LN1_B), a.h, W, a.st1, stream));
+    HIG_TRY(hig_gemm_launch(G(a.h, W, 0, P(l, HIG_CTL_IN_W), W, 0, a.qkv, 3 * W, M, 3 * W, W)
+                                .epi(HIG_EPI_BIAS, P(l, HIG_CTL_IN_B)).prec(D.prec).g, 1, nullptr, st));
+    if (a.lse)
+      HIG_TRY(hig_causal_attn_fwd_train(a.qkv, 3 * W, a.qkv + W, a.qkv + 2 * W, 3 * W, D.B, D.N, D.H, a.att, W, a.lse, stream));
+    else
+      HIG_TRY(hig_causal_attn_fwd(a.qkv, 3 * W, a.qkv + W, a.qkv + 2 * W, 3 * W, D.B, D.N, D.H, a.att, W, stream));
+    HIG_TRY(hig_gemm_launch(G(a.att, W, 0, P(l, HIG_CTL_OUT_W), W, 0, a.x1, W, M, W, W)
+                                .epi(HIG_EPI_BIAS_RES, P(l, HIG_CTL_OUT_B)).res(xin, W).prec(D.prec).g, 1, nullptr, st));
+    HIG_TRY(hig_layernorm(a.x1, W, M, W, P(l, HIG_CTL_LN2_W), P(l, HIG_CTL_LN2_B), a.h, W, a.st2, stream));
+    HIG_TRY(hig_gemm_launch(G(a.h, W, 0, P(l, HIG_CTL_FC_W), W, 0, a.z, ff, M, ff, W)
+                                .epi(HIG_EPI_BIAS, P(l, HIG_CTL_FC_B)).prec(D.prec).g, 1, nullptr, st));
+    if (a.z != a.f)
+      HIG_TRY(hig_quick_gelu_to(a.z, a.f, M * ff, stream));
+    else
+      HIG_TRY(hig_quick_gelu(a.f, M * ff, stream));
+    HIG_TRY(hig_gemm_launch(G(a.f, ff, 0, P(l, HIG_CTL_PROJ_W), ff, 0, a.x2, W, M, W, ff)
+                                .epi(HIG_EPI_BIAS_RES, P(l, HIG_CTL_PROJ_B)).res(a.x1, W).prec(D.prec).g, 1, nullptr, st));
+    xin = a.x2;
+  }
+  return hig_layernorm(xin, W, M, W, P[HIG_CT_LNF_W], P[HIG_CT_LNF_B], out, W, stf, stream);
 }
 
 }  // namespace
@@ -276,6 +372,16 @@ extern "C" int64_t hig_clip_text_workspace_bytes(const int32_t* dims) {
   if (check_cdims(dims, D) != HIG_OK) return -1;
   return cfwd_layout(D).total * 4;
 }
+extern "C" int64_t hig_clip_text_train_bytes(const int32_t* dims) {
+  CDims D;
+  if (check_train(dims, D, "hig_clip_text_train_bytes") != HIG_OK) return -1;
+  return ctrain_layout(D).total * 4;
+}
+extern "C" int64_t hig_clip_text_bwd_workspace_bytes(const int32_t* dims) {
+  CDims D;
+  if (check_train(dims, D, "hig_clip_text_bwd_workspace_bytes") != HIG_OK) return -1;
+  return cbwd_layout(D)[CBW_TOTAL] * 4;
+}
 
 extern "C" int hig_clip_text_fwd(const int32_t* dims, const void* const* params, const int64_t* tokens, float* out, void* workspace,
                                  hig_stream_t stream) {
@@ -286,117 +392,15 @@ extern "C" int hig_clip_text_fwd(const int32_t* dims, const void* const* params,
   for (int i = 0; i < HIG_CT_NGLOBAL + D.L * HIG_CTL_NLAYER; ++i) HIG_REQUIRE(params[i], "hig_clip_text_fwd: null parameter %d", i);
   const CFwd w = cfwd_layout(D);
   float* ws = static_cast<float*>(workspace);
-  hipStream_t st = hig_stream(stream);
-  const int W = D.W, ff = 4 * D.W;
-  const int64_t M = D.M;
-  HIG_TRY(hig_clip_embed(CP(params, HIG_CT_TOK_EMB), CP(params, HIG_CT_POS_EMB), tokens, D.B, D.N, W, D.vocab, ws + w.x0, W, stream));
-  const float* xin = ws + w.x0;
-  for (int l = 0; l < D.L; ++l) {
+  // one statistics buffer, no lse, QuickGELU in place on f
+  auto layer_of = [&](int l) {
     float* lb = ws + w.layer0 + (l & 1) * w.block;
-    HIG_TRY(hig_layernorm(xin, W, M, W, CPL(params, l, HIG_CTL_LN1_W), CPL(params, l, HIG_CTL_LN1_B), lb + w.h, W, lb + w.st, stream));
-    HIG_TRY(hig_gemm_launch(G(lb + w.h, W, 0, CPL(params, l, HIG_CTL_IN_W), W, 0, lb + w.qkv, 3 * W, M, 3 * W, W)
-                                .epi(HIG_EPI_BIAS, CPL(params, l, HIG_CTL_IN_B)).prec(D.prec).g, 1, nullptr, st));
-    HIG_TRY(hig_causal_attn_fwd(lb + w.qkv, 3 * W, lb + w.qkv + W, lb + w.qkv + 2 * W, 3 * W, D.B, D.N, D.H, lb + w.att, W, stream));
-    HIG_TRY(hig_gemm_launch(G(lb + w.att, W, 0, CPL(params, l, HIG_CTL_OUT_W), W, 0, lb + w.x1, W, M, W, W)
-                                .epi(HIG_EPI_BIAS_RES, CPL(params, l, HIG_CTL_OUT_B)).res(xin, W).prec(D.prec).g, 1, nullptr, st));
-    HIG_TRY(hig_layernorm(lb + w.x1, W, M, W, CPL(params, l, HIG_CTL_LN2_W), CPL(params, l, HIG_CTL_LN2_B), lb + w.h, W, lb + w.st, stream));
-    HIG_TRY(hig_gemm_launch(G(lb + w.h, W, 0, CPL(params, l, HIG_CTL_FC_W), W, 0, lb + w.f, ff, M, ff, W)
-                                .epi(HIG_EPI_BIAS, CPL(params, l, HIG_CTL_FC_B)).prec(D.prec).g, 1, nullptr, st));
-    HIG_TRY(hig_quick_gelu(lb + w.f, M * ff, stream));
-    HIG_TRY(hig_gemm_launch(G(lb + w.f, ff, 0, CPL(params, l, HIG_CTL_PROJ_W), ff, 0, lb + w.x2, W, M, W, ff)
-                                .epi(HIG_EPI_BIAS_RES, CPL(params, l, HIG_CTL_PROJ_B)).res(lb + w.x1, W).prec(D.prec).g, 1, nullptr, st));
-    xin = lb + w.x2;
-  }
-  return hig_layernorm(xin, W, M, W, CP(params, HIG_CT_LNF_W), CP(params, HIG_CT_LNF_B), out, W, ws + w.stf, stream);
+    return CLayer{lb + w.h, lb + w.st, lb + w.st, lb + w.qkv, nullptr, lb + w.att, lb + w.x1, lb + w.f, lb + w.f, lb + w.x2};
+  };
+  return clip_forward(D, params, tokens, out, ws + w.x0, ws + w.stf, layer_of, stream);
 }
 
 // ---- training: the forward that keeps what the adjoint needs, and the adjoint ---------------------------------------------------
-namespace {
-
-// What hig_clip_text_fwd_train keeps (floats): the embedded rows and ln_final's statistics, then per layer the two LayerNorms'
-// statistics, qkv, lse, the attention output, x1, the FFN's pre-activation z and x2 (the next layer's input).  The LayerNorm
-// outputs and quick_gelu(z) are not kept: the adjoint rebuilds them (hig_layernorm, hig_quick_gelu_to), bit for bit.  Behind the
-// layers: the two buffers the forward itself rebuilds per layer (h, f).
-struct CTrain {
-  int64_t x0, stf, layer0, lstride;
-  int64_t st1, qkv, lse, att, x1, st2, z, x2;
-  int64_t h, f, total;
-};
-CTrain ctrain_layout(const CDims& D) {
-  CTrain w;
-  int64_t o = 0;
-  auto take = [&](int64_t n) { int64_t r = o; o += al(n); return r; };
-  w.x0 = take(D.M * D.W);
-  w.stf = take(D.M * 2);
-  w.layer0 = o;
-  o = 0;
-  w.st1 = take(D.M * 2);
-  w.qkv = take(D.M * 3 * D.W);
-  w.lse = take((int64_t)D.B * D.H * D.N);
-  w.att = take(D.M * D.W);
-  w.x1 = take(D.M * D.W);
-  w.st2 = take(D.M * 2);
-  w.z = take(D.M * 4 * D.W);
-  w.x2 = take(D.M * D.W);
-  w.lstride = o;
-  o = w.layer0 + w.lstride * D.L;
-  w.h = take(D.M * D.W);
-  w.f = take(D.M * 4 * D.W);
-  w.total = o;
-  return w;
-}
-
-struct CBwd {
-  int64_t d, t1, t2, h, hst, f, dff, dqkv, delta, wT, slabs, slab_floats, colpart, lnpart, emb, total;
-};
-CBwd cbwd_layout(const CDims& D) {
-  CBwd w;
-  int64_t o = 0;
-  auto take = [&](int64_t n) { int64_t r = o; o += al(n); return r; };
-  const int64_t ff = 4 * (int64_t)D.W;
-  w.d = take(D.M * D.W);
-  w.t1 = take(D.M * D.W);
-  w.t2 = take(D.M * D.W);
-  w.h = take(D.M * D.W);
-  w.hst = take(D.M * 2);
-  w.f = take(D.M * ff);
-  w.dff = take(D.M * ff);
-  w.dqkv = take(D.M * 3 * D.W);
-  w.delta = take((int64_t)D.B * D.H * D.N);
-  const int64_t big = ff * D.W;   // the largest weight: c_fc / c_proj
-  w.wT = take(big);
-  w.slab_floats = big * 16 > (int64_t)1536 * 128 * 128 ? big * 16 : (int64_t)1536 * 128 * 128;
-  w.slabs = take(w.slab_floats);
-  w.colpart = take((int64_t)hig_colsum_chunks(D.M) * ff);
-  w.lnpart = take(hig_ln_bwd_partial_floats(D.M, D.W, D.N));
-  w.emb = take(2 * D.M * D.W);   // chunk partials and per-id sums: at most B N rows each
-  w.total = o;
-  return w;
-}
-
-int check_train(const int32_t* dims, CDims& D, const char* who) {
-  HIG_TRY(check_cdims(dims, D));
-  if (D.prec != HIG_PREC_F32) return hig_set_error(HIG_EUNSUPPORTED, "%s: prec=%d, the tower trains with exact fp32 products only", who, D.prec);
-  return HIG_OK;
-}
-
-inline float* CG(void* const* t, int idx) { return static_cast<float*>(t[idx]); }
-inline float* CGL(void* const* t, int l, int idx) { return static_cast<float*>(t[HIG_CT_NGLOBAL + l * HIG_CTL_NLAYER + idx]); }
-
-}  // namespace
-
-extern "C" int64_t hig_clip_text_train_bytes(const int32_t* dims) {
-  CDims D;
-  if (check_train(dims, D, "hig_clip_text_train_bytes") != HIG_OK) return -1;
-  return ctrain_layout(D).total * 4;
-}
-
-extern "C" int64_t hig_clip_text_bwd_workspace_bytes(const int32_t* dims) {
-  CDims D;
-  if (check_train(dims, D, "hig_clip_text_bwd_workspace_bytes") != HIG_OK) return -1;
-  return cbwd_layout(D).total * 4;
-}
-
 extern "C" int hig_clip_text_fwd_train(const int32_t* dims, const void* const* params, const int64_t* tokens, float* out, void* saved,
                                        hig_stream_t stream) {
   CDims D;
@@ -406,33 +410,13 @@ extern "C" int hig_clip_text_fwd_train(const int32_t* dims, const void* const* p
   for (int i = 0; i < HIG_CT_NGLOBAL + D.L * HIG_CTL_NLAYER; ++i) HIG_REQUIRE(params[i], "hig_clip_text_fwd_train: null parameter %d", i);
   const CTrain w = ctrain_layout(D);
   float* ws = static_cast<float*>(saved);
-  hipStream_t st = hig_stream(stream);
-  const int W = D.W, ff = 4 * D.W;
-  const int64_t M = D.M;
-  float* h = ws + w.h;
-  float* f = ws + w.f;
   // the launches of hig_clip_text_fwd on the same operand values: the attention also writes lse, and QuickGELU goes from z to
   // f instead of overwriting z
-  HIG_TRY(hig_clip_embed(CP(params, HIG_CT_TOK_EMB), CP(params, HIG_CT_POS_EMB), tokens, D.B, D.N, W, D.vocab, ws + w.x0, W, stream));
-  const float* xin = ws + w.x0;
-  for (int l = 0; l < D.L; ++l) {
+  auto layer_of = [&](int l) {
     float* lb = ws + w.layer0 + l * w.lstride;
-    HIG_TRY(hig_layernorm(xin, W, M, W, CPL(params, l, HIG_CTL_LN1_W), CPL(params, l, HIG_CTL_LN1_B), h, W, lb + w.st1, stream));
-    HIG_TRY(hig_gemm_launch(G(h, W, 0, CPL(params, l, HIG_CTL_IN_W), W, 0, lb + w.qkv, 3 * W, M, 3 * W, W)
-                                .epi(HIG_EPI_BIAS, CPL(params, l, HIG_CTL_IN_B)).g, 1, nullptr, st));
-    HIG_TRY(hig_causal_attn_fwd_train(lb + w.qkv, 3 * W, lb + w.qkv + W, lb + w.qkv + 2 * W, 3 * W, D.B, D.N, D.H, lb + w.att, W,
-                                      lb + w.lse, stream));
-    HIG_TRY(hig_gemm_launch(G(lb + w.att, W, 0, CPL(params, l, HIG_CTL_OUT_W), W, 0, lb + w.x1, W, M, W, W)
-                                .epi(HIG_EPI_BIAS_RES, CPL(params, l, HIG_CTL_OUT_B)).res(xin, W).g, 1, nullptr, st));
-    HIG_TRY(hig_layernorm(lb + w.x1, W, M, W, CPL(params, l, HIG_CTL_LN2_W), CPL(params, l, HIG_CTL_LN2_B), h, W, lb + w.st2, stream));
-    HIG_TRY(hig_gemm_launch(G(h, W, 0, CPL(params, l, HIG_CTL_FC_W), W, 0, lb + w.z, ff, M, ff, W)
-                                .epi(HIG_EPI_BIAS, CPL(params, l, HIG_CTL_FC_B)).g, 1, nullptr, st));
-    HIG_TRY(hig_quick_gelu_to(lb + w.z, f, M * ff, stream));
-    HIG_TRY(hig_gemm_launch(G(f, ff, 0, CPL(params, l, HIG_CTL_PROJ_W), ff, 0, lb + w.x2, W, M, W, ff)
-                                .epi(HIG_EPI_BIAS_RES, CPL(params, l, HIG_CTL_PROJ_B)).res(lb + w.x1, W).g, 1, nullptr, st));
-    xin = lb + w.x2;
-  }
-  return hig_layernorm(xin, W, M, W, CP(params, HIG_CT_LNF_W), CP(params, HIG_CT_LNF_B), out, W, ws + w.stf, stream);
+    return CLayer{ws + w.h, lb + w.st1, lb + w.st2, lb + w.qkv, lb + w.lse, lb + w.att, lb + w.x1, lb + w.z, ws + w.f, lb + w.x2};
+  };
+  return clip_forward(D, params, tokens, out, ws + w.x0, ws + w.stf, layer_of, stream);
 }
 
 namespace {
@@ -448,31 +432,28 @@ int text_bwd_front(const char* who, const int32_t* dims, const void* const* para
     HIG_REQUIRE(params[i] && grads[i], "%s: null parameter or gradient %d", who, i);
   const CTrain w = ctrain_layout(D);
   const CBwd bw = cbwd_layout(D);
+  const Tab P(params, HIG_CT_NGLOBAL, HIG_CTL_NLAYER);
+  const Tab Gr(grads, HIG_CT_NGLOBAL, HIG_CTL_NLAYER);
   const float* ws = static_cast<const float*>(saved);
   float* b = static_cast<float*>(bwd_workspace);
   const int W = D.W, ff = 4 * D.W;
   const int64_t M = D.M;
-  EncBwd e;
-  e.B = D.B; e.S = D.N; e.n = W; e.ff = ff; e.H = D.H; e.hd = CA_HD; e.prec = HIG_PREC_F32; e.M = M;
-  e.slabs = b + bw.slabs; e.slab_floats = bw.slab_floats;
-  e.colp = b + bw.colpart; e.lnp = b + bw.lnpart; e.wT = b + bw.wT; e.tA = nullptr; e.tB = nullptr;   // (tA / tB: bf16 product modes only)
-  e.dff = b + bw.dff; e.dqkv = b + bw.dqkv; e.delta = b + bw.delta;
-  e.stream = stream;
-  float* d = b + bw.d;      // d(x2 of layer l), then d(its input)
-  float* t1 = b + bw.t1;
-  float* t2 = b + bw.t2;
-  float* h = b + bw.h;
-  float* hst = b + bw.hst;
-  float* f = b + bw.f;
+  const EncBwd e(D.enc(), HIG_PREC_F32, b, bw.data(), CBW_SCRATCH, stream);
+  float* d = b + bw[CBW_D];      // d(x2 of layer l), then d(its input)
+  float* t1 = b + bw[CBW_T1];
+  float* t2 = b + bw[CBW_T2];
+  float* h = b + bw[CBW_H];
+  float* hst = b + bw[CBW_HST];
+  float* f = b + bw[CBW_F];
   // ---- ln_final --------------------------------------------------------------------------------------------------------------
   const float* xL = ws + w.layer0 + w.lstride * (D.L - 1) + w.x2;
-  HIG_TRY(hig_ln_bwd(dout, W, xL, W, ws + w.stf, CP(params, HIG_CT_LNF_W), CP(params, HIG_CT_LNF_B), nullptr, 0, 0, 0, nullptr, 0, d, W, M,
-                     W, D.N, CG(grads, HIG_CT_LNF_W), CG(grads, HIG_CT_LNF_B), nullptr, 0, e.lnp, stream));
+  HIG_TRY(hig_ln_bwd(dout, W, xL, W, ws + w.stf, P[HIG_CT_LNF_W], P[HIG_CT_LNF_B], nullptr, 0, 0, 0, nullptr, 0, d, W, M,
+                     W, D.N, Gr[HIG_CT_LNF_W], Gr[HIG_CT_LNF_B], nullptr, 0, e.lnp, stream));
   for (int l = D.L - 1; l >= 0; --l) {
     const float* lb = ws + w.layer0 + w.lstride * l;
     const float* xin = l == 0 ? ws + w.x0 : ws + w.layer0 + w.lstride * (l - 1) + w.x2;
-    auto p = [&](int i) { return CPL(params, l, i); };
-    auto g = [&](int i) { return CGL(grads, l, i); };
+    auto p = [&](int i) { return P(l, i); };
+    auto g = [&](int i) { return Gr(l, i); };
     // x2 = x1 + c_proj(f), f = quick_gelu(z)
     HIG_TRY(hig_quick_gelu_to(lb + w.z, f, M * ff, stream));
     HIG_TRY(e.wgrad_act(d, W, f, ff, g(HIG_CTL_PROJ_W), M, g(HIG_CTL_PROJ_B)));
@@ -498,7 +479,7 @@ int text_bwd_front(const char* who, const int32_t* dims, const void* const* para
                        g(HIG_CTL_LN1_W), g(HIG_CTL_LN1_B), nullptr, 0, e.lnp, stream));    // d = d(xin) = d(x1) + the norm's
   }
   *dx0 = d;
-  *emb = b + bw.emb;
+  *emb = b + bw[CBW_EMB];
   return HIG_OK;
 }
 }  // namespace
@@ -515,8 +496,8 @@ extern "C" int hig_clip_text_bwd(const int32_t* dims, const void* const* params,
   const float* d;
   float* emb;
   HIG_TRY(text_bwd_front("hig_clip_text_bwd", dims, params, dout, saved, grads, bwd_workspace, stream, D, &d, &emb));
-  return hig_clip_embed_bwd(d, D.B, D.N, D.W, D.vocab, index, n_live, n_chunks, n_ids, emb, CG(grads, HIG_CT_TOK_EMB),
-                            CG(grads, HIG_CT_POS_EMB), stream);
+  return hig_clip_embed_bwd(d, D.B, D.N, D.W, D.vocab, index, n_live, n_chunks, n_ids, emb, static_cast<float*>(grads[HIG_CT_TOK_EMB]),
+                            static_cast<float*>(grads[HIG_CT_POS_EMB]), stream);
 }
 
 // the same launches up to d(x0), then the embedding pass on the device-built index (hig_clip_embed_index_build)
@@ -530,5 +511,6 @@ extern "C" int hig_clip_text_bwd_dev(const int32_t* dims, const void* const* par
   const float* d;
   float* emb;
   HIG_TRY(text_bwd_front("hig_clip_text_bwd_dev", dims, params, dout, saved, grads, bwd_workspace, stream, D, &d, &emb));
-  return hig_clip_embed_bwd_dev(d, D.B, D.N, D.W, D.vocab, index, counts, emb, CG(grads, HIG_CT_TOK_EMB), CG(grads, HIG_CT_POS_EMB), stream);
+  return hig_clip_embed_bwd_dev(d, D.B, D.N, D.W, D.vocab, index, counts, emb, static_cast<float*>(grads[HIG_CT_TOK_EMB]),
+                                static_cast<float*>(grads[HIG_CT_POS_EMB]), stream);
 }

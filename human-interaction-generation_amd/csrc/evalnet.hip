@@ -13,15 +13,16 @@
 //                  feature = sum_valid o / #valid;  logits = fin_proj(feature)
 //   Consistency:   logits = cls_output(h[cls token])
 // Host code + a few small row kernels; the GEMMs, LayerNorm and attention are the shared ones, and the backward of a layer is
-// the text head's (hig_enc_layer_bwd, hig_host.h).
+// the text head's (hig_enc_layer_fwd / hig_enc_layer_bwd, enc_layers.h).
 #include "hig_common.h"
-#include "hig_host.h"
+#include "enc_layers.h"
 
 namespace {
 
 struct EDims {
   int B, T, F, d, H, ff, L, C, cls, hd, prec, S;
   int64_t M;
+  EncShape enc() const { return {B, S, d, ff, H, hd}; }
 };
 
 int check_edims(const hig_eval_dims* p, EDims& D) {
@@ -32,11 +33,9 @@ int check_edims(const hig_eval_dims* p, EDims& D) {
               "hig_eval_dims: every extent must be positive (T >= 2, F >= 4)");
   HIG_REQUIRE(D.d % D.H == 0, "hig_eval_dims: d=%d not divisible by H=%d", D.d, D.H);
   D.hd = D.d / D.H;
-  if (!(D.hd == 8 || D.hd == 16 || D.hd == 32 || D.hd == 64 || D.hd == 128))
-    return hig_set_error(HIG_EUNSUPPORTED, "hig eval encoder: head dim %d not in {8,16,32,64,128}", D.hd);
+  HIG_TRY(hig_enc_check_hd("hig eval encoder", D.hd));
   HIG_REQUIRE(D.d % 4 == 0 && D.ff % 4 == 0 && D.d <= 1024, "hig_eval_dims: d, ff must be multiples of 4 and d <= 1024");
-  if (p->prec != HIG_PREC_F32 && p->prec != HIG_PREC_BF16X3 && p->prec != HIG_PREC_BF16)
-    return hig_set_error(HIG_EINVAL, "hig: unknown prec=%d", p->prec);
+  HIG_TRY(hig_enc_check_prec(p->prec));
   D.prec = p->prec;
   D.S = D.cls + 2 * D.T;
   D.M = (int64_t)D.B * D.S;
@@ -68,10 +67,8 @@ EWs ews_layout(const EDims& D) {
   return w;
 }
 
-inline const float* EP(const void* const* t, int idx) { return static_cast<const float*>(t[idx]); }
-inline const float* EPL(const void* const* t, int l, int idx) {
-  return static_cast<const float*>(t[HIG_EV_NGLOBAL + l * HIG_TL_NLAYER + idx]);
-}
+using ETab = Tab<const void>;   // a parameter table: P[HIG_EV_*], P(l, HIG_TL_*)
+inline ETab etab(const void* const* t) { return ETab(t, HIG_EV_NGLOBAL, HIG_TL_NLAYER); }
 
 // Row (b, s) of h: the [cls] vector, or row (p, b, t) of the per-person embeddings; also the key padding byte.
 __global__ __launch_bounds__(128) void assemble_kernel(const float* __restrict__ emb, const float* __restrict__ cls_in,
@@ -114,81 +111,52 @@ __global__ __launch_bounds__(256) void masked_mean_kernel(const float* __restric
 
 
 // ---- training ---------------------------------------------------------------------------------------------------------
-// Forward workspace (floats): the inference prefix, then one activation block per layer (as the text head's training layout).
-struct ETrain {
-  int64_t emb, h, kpad, o, feat, layer0, lstride;
-  int64_t qkv, lse, att, r1, st1, x1, z, f, r2, st2, x2;
-  int64_t total;
-};
+// Forward workspace (floats) by HIG_EFW_* slot: the inference prefix, then one activation block per layer (the text head's).
+using ETrain = std::array<int64_t, HIG_EFW_NSLOTS>;
 ETrain etrain_layout(const EDims& D) {
   ETrain w;
   int64_t o = 0;
   auto take = [&](int64_t n) { int64_t r = o; o += al(n); return r; };
-  w.emb = take((int64_t)2 * D.B * D.T * D.d);
-  w.h = take(D.M * D.d);
-  w.kpad = take((D.M + 3) / 4);
-  w.o = take(D.cls ? 0 : D.M * D.d);
-  w.feat = take((int64_t)D.B * D.d);
-  w.layer0 = o;
+  w[HIG_EFW_EMB] = take((int64_t)2 * D.B * D.T * D.d);
+  w[HIG_EFW_H] = take(D.M * D.d);
+  w[HIG_EFW_KPAD] = take((D.M + 3) / 4);
+  w[HIG_EFW_O] = take(D.cls ? 0 : D.M * D.d);
+  w[HIG_EFW_FEAT] = take((int64_t)D.B * D.d);
+  w[HIG_EFW_LAYER0] = o;
   o = 0;
-  w.qkv = take(D.M * 3 * D.d);
-  w.lse = take((int64_t)D.B * D.H * D.S);
-  w.att = take(D.M * D.d);
-  w.r1 = take(D.M * D.d);
-  w.st1 = take(D.M * 2);
-  w.x1 = take(D.M * D.d);
-  w.z = take(D.M * D.ff);
-  w.f = take(D.M * D.ff);
-  w.r2 = take(D.M * D.d);
-  w.st2 = take(D.M * 2);
-  w.x2 = take(D.M * D.d);
-  w.lstride = o;
-  w.total = w.layer0 + o * D.L;
+  hig_enc_block_layout(take, &w[HIG_EFW_QKV], D.enc());
+  w[HIG_EFW_LSTRIDE] = o;
+  w[HIG_EFW_TOTAL] = w[HIG_EFW_LAYER0] + o * D.L;
   return w;
 }
 
-struct EBwd {
-  int64_t dA, dB, dC, dff, dqkv, delta, wT, slabs, slab_floats, colpart, lnpart;
-  int64_t dft, g, gn, g2, pool1, pool2, u1, u2;   // MotionEncoder head, (B, d) each
-  int64_t xcat, dmove, dinit, postmp;             // embedding
-  int64_t total;
-};
+// Backward workspace (floats) by HIG_EBW_* slot: the layers' scratch, the MotionEncoder head ((B, d) each), the embedding.
+using EBwd = std::array<int64_t, HIG_EBW_NSLOTS>;
+constexpr EncScratchSlots EBW_SCRATCH = {HIG_EBW_DFF,   HIG_EBW_DQKV,        HIG_EBW_DELTA,   HIG_EBW_WT,    -1, -1,
+                                         HIG_EBW_SLABS, HIG_EBW_SLAB_FLOATS, HIG_EBW_COLPART, HIG_EBW_LNPART};
+constexpr int EBW_HEAD[] = {HIG_EBW_DFT, HIG_EBW_G, HIG_EBW_GN, HIG_EBW_G2, HIG_EBW_POOL1, HIG_EBW_POOL2, HIG_EBW_U1, HIG_EBW_U2};
 EBwd ebwd_layout(const EDims& D) {
   EBwd w;
   int64_t o = 0;
   auto take = [&](int64_t n) { int64_t r = o; o += al(n); return r; };
-  const int64_t d = D.d, Bd = (int64_t)D.B * d, R = (int64_t)2 * D.B * D.T;
-  w.dA = take(D.M * d);
-  w.dB = take(D.M * d);
-  w.dC = take(D.M * d);
-  w.dff = take(D.M * D.ff);
-  w.dqkv = take(D.M * 3 * d);
-  w.delta = take((int64_t)D.B * D.H * D.S);
+  const int64_t d = D.d, R = (int64_t)2 * D.B * D.T;
+  w[HIG_EBW_DA] = take(D.M * d);
+  w[HIG_EBW_DB] = take(D.M * d);
+  w[HIG_EBW_DC] = take(D.M * d);
+  hig_enc_scratch_grads(take, w.data(), EBW_SCRATCH, D.enc());
   int64_t big = 3 * d * d;
   if ((int64_t)D.ff * d > big) big = (int64_t)D.ff * d;
   if ((int64_t)d * D.F > big) big = (int64_t)d * D.F;
-  w.wT = take(big);
-  w.slab_floats = big * 16 > (int64_t)1536 * 128 * 128 ? big * 16 : (int64_t)1536 * 128 * 128;
-  w.slabs = take(w.slab_floats);
-  int64_t colp = 0;
-  const int64_t uses[][2] = {{D.M, 3 * d}, {D.M, D.ff}, {D.B, D.C}, {D.B, d}, {R, d}, {2 * D.B, (int64_t)D.T * d}};
-  for (auto& u : uses) {
-    const int64_t v = (int64_t)hig_colsum_chunks(u[0]) * u[1];
-    colp = v > colp ? v : colp;
-  }
-  w.colpart = take(colp);
-  w.lnpart = take(hig_ln_bwd_partial_floats(D.M, D.d, D.S));
-  w.dft = take(Bd); w.g = take(Bd); w.gn = take(Bd); w.g2 = take(Bd);
-  w.pool1 = take(Bd); w.pool2 = take(Bd); w.u1 = take(Bd); w.u2 = take(Bd);
-  w.xcat = take(R * D.F);
-  w.dmove = take(R * d);
-  w.dinit = take((int64_t)2 * D.B * d);
-  w.postmp = take((int64_t)D.T * d);
-  w.total = o;
+  hig_enc_scratch_work(take, w.data(), EBW_SCRATCH, D.enc(), big,
+                       {{D.M, 3 * d}, {D.M, D.ff}, {D.B, D.C}, {D.B, d}, {R, d}, {2 * D.B, (int64_t)D.T * d}});
+  for (int s : EBW_HEAD) w[s] = take((int64_t)D.B * d);
+  w[HIG_EBW_XCAT] = take(R * D.F);
+  w[HIG_EBW_DMOVE] = take(R * d);
+  w[HIG_EBW_DINIT] = take((int64_t)2 * D.B * d);
+  w[HIG_EBW_POSTMP] = take((int64_t)D.T * d);
+  w[HIG_EBW_TOTAL] = o;
   return w;
 }
-
-inline float* EG(void* const* t, int idx) { return static_cast<float*>(t[idx]); }
 
 __device__ __forceinline__ int clamp_len(const int64_t* length, int b, int T) {
   int64_t len = length[b];
@@ -307,84 +275,70 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
 }
 
 // what both training entry points ask of a table (parameters or gradients) before the first launch
-int check_train(const EDims& D, const void* const* params, const char* who) {
+int check_train(const EDims& D, const void* const* table, const char* who) {
+  const ETab P = etab(table);
   if (D.prec != HIG_PREC_F32)
     return hig_set_error(HIG_EUNSUPPORTED, "%s: training the evaluation classifiers runs exact-fp32 products only (prec f32)", who);
-  HIG_REQUIRE(EP(params, HIG_EV_SEQ_EMB) && EP(params, HIG_EV_JOINT1_W) && EP(params, HIG_EV_JOINT1_B) && EP(params, HIG_EV_JOINT2_W) &&
-                  EP(params, HIG_EV_JOINT2_B) && EP(params, HIG_EV_HEAD_W) && EP(params, HIG_EV_HEAD_B),
+  HIG_REQUIRE(P[HIG_EV_SEQ_EMB] && P[HIG_EV_JOINT1_W] && P[HIG_EV_JOINT1_B] && P[HIG_EV_JOINT2_W] &&
+                  P[HIG_EV_JOINT2_B] && P[HIG_EV_HEAD_W] && P[HIG_EV_HEAD_B],
               "%s: missing embedding / head slots", who);
   if (D.cls)
-    HIG_REQUIRE(EP(params, HIG_EV_CLS_IN), "%s: consistency model needs cls_input", who);
+    HIG_REQUIRE(P[HIG_EV_CLS_IN], "%s: consistency model needs cls_input", who);
   else
-    HIG_REQUIRE(EP(params, HIG_EV_OUT1_W) && EP(params, HIG_EV_OUT1_B) && EP(params, HIG_EV_OUT2_W) && EP(params, HIG_EV_OUT2_B),
+    HIG_REQUIRE(P[HIG_EV_OUT1_W] && P[HIG_EV_OUT1_B] && P[HIG_EV_OUT2_W] && P[HIG_EV_OUT2_B],
                 "%s: MotionEncoder needs out1 / out2", who);
   for (int l = 0; l < D.L; ++l)
-    for (int i = 0; i < HIG_TL_NLAYER; ++i) HIG_REQUIRE(EPL(params, l, i), "%s: layer %d lacks slot %d", who, l, i);
+    for (int i = 0; i < HIG_TL_NLAYER; ++i) HIG_REQUIRE(P(l, i), "%s: layer %d lacks slot %d", who, l, i);
   return HIG_OK;
 }
 
 // The forward both entry points launch; they differ in where a layer's activations live (layer_of(l)) and in whether the GELU
 // pre-activation is kept (z != NULL).  o: (M, d) scratch of the MotionEncoder head; feat: where its pooled feature goes.
-struct EFwdLayer {
-  float *qkv, *lse, *att, *r1, *st1, *x1, *z, *f, *r2, *st2, *x2;
-};
 template <class LayerOf>
 int eval_forward(const EDims& D, const void* const* params, const float* x1, const float* x2, const int64_t* length,
                  float* logits, float* emb, float* h, uint8_t* kpad, float* o, float* feat, int prec, LayerOf layer_of,
                  hig_stream_t stream) {
+  const ETab P = etab(params);
   hipStream_t st = hig_stream(stream);
-  const int d = D.d, ff = D.ff, T = D.T, S = D.S;
+  const int d = D.d, T = D.T, S = D.S;
   const int64_t M = D.M, BT = (int64_t)D.B * T;
   // per-person embeddings: every row through joint_embed1 (+ sequence_embedding[t-1]), then the init-pose rows
   // (t = 0) overwritten with joint_embed2 of their first 4 features (:717-720 / :814-817)
   const float* xs[2] = {x1, x2};
   for (int p = 0; p < 2; ++p) {
     float* e = emb + p * BT * d;
-    G ge(xs[p], D.F, 0, EP(params, HIG_EV_JOINT1_W), D.F, 0, e, d, BT, d, D.F);
-    ge.epi(HIG_EPI_BIAS_POS, EP(params, HIG_EV_JOINT1_B)).pos(EP(params, HIG_EV_SEQ_EMB), d, T).prec(prec);
+    G ge(xs[p], D.F, 0, P[HIG_EV_JOINT1_W], D.F, 0, e, d, BT, d, D.F);
+    ge.epi(HIG_EPI_BIAS_POS, P[HIG_EV_JOINT1_B]).pos(P[HIG_EV_SEQ_EMB], d, T).prec(prec);
     ge.g.pos_shift = 1;
     HIG_TRY(hig_gemm_launch(ge.g, 1, nullptr, st));
-    HIG_TRY(hig_gemm_launch(G(xs[p], (int64_t)T * D.F, 0, EP(params, HIG_EV_JOINT2_W), 4, 0, e, (int64_t)T * d, D.B, d, 4)
-                                .epi(HIG_EPI_BIAS, EP(params, HIG_EV_JOINT2_B)).g, 1, nullptr, st));
+    HIG_TRY(hig_gemm_launch(G(xs[p], (int64_t)T * D.F, 0, P[HIG_EV_JOINT2_W], 4, 0, e, (int64_t)T * d, D.B, d, 4)
+                                .epi(HIG_EPI_BIAS, P[HIG_EV_JOINT2_B]).g, 1, nullptr, st));
   }
-  hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)M), dim3(128), 0, st, emb, EP(params, HIG_EV_CLS_IN), length, h, kpad, D.B,
+  hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)M), dim3(128), 0, st, emb, P[HIG_EV_CLS_IN], length, h, kpad, D.B,
                      T, d, D.cls);
   HIG_CHECK_LAUNCH();
 
   const float* xin = h;
   for (int l = 0; l < D.L; ++l) {
-    const EFwdLayer a = layer_of(l);
-    HIG_TRY(hig_gemm_launch(G(xin, d, 0, EPL(params, l, HIG_TL_IN_W), d, 0, a.qkv, 3 * d, M, 3 * d, d)
-                                .epi(HIG_EPI_BIAS, EPL(params, l, HIG_TL_IN_B)).prec(prec).g, 1, nullptr, st));
-    HIG_TRY(hig_fullattn_fwd_kpad(a.qkv, 3 * d, a.qkv + d, a.qkv + 2 * d, 3 * d, D.B, S, S, D.H, D.hd, nullptr, kpad, a.att, d,
-                                  a.lse, stream));
-    HIG_TRY(hig_gemm_launch(G(a.att, d, 0, EPL(params, l, HIG_TL_OUT_W), d, 0, a.r1, d, M, d, d)
-                                .epi(HIG_EPI_BIAS_RES, EPL(params, l, HIG_TL_OUT_B)).res(xin, d).prec(prec).g, 1, nullptr, st));
-    HIG_TRY(hig_layernorm(a.r1, d, M, d, EPL(params, l, HIG_TL_N1_W), EPL(params, l, HIG_TL_N1_B), a.x1, d, a.st1, stream));
-    G g1(a.x1, d, 0, EPL(params, l, HIG_TL_FF1_W), d, 0, a.f, ff, M, ff, d);
-    g1.epi(HIG_EPI_BIAS_GELU, EPL(params, l, HIG_TL_FF1_B)).prec(prec);
-    if (a.z) g1.aux(a.z, ff);
-    HIG_TRY(hig_gemm_launch(g1.g, 1, nullptr, st));
-    HIG_TRY(hig_gemm_launch(G(a.f, ff, 0, EPL(params, l, HIG_TL_FF2_W), ff, 0, a.r2, d, M, d, ff)
-                                .epi(HIG_EPI_BIAS_RES, EPL(params, l, HIG_TL_FF2_B)).res(a.x1, d).prec(prec).g, 1, nullptr, st));
-    HIG_TRY(hig_layernorm(a.r2, d, M, d, EPL(params, l, HIG_TL_N2_W), EPL(params, l, HIG_TL_N2_B), a.x2, d, a.st2, stream));
+    const EncLayer a = layer_of(l);
+    HIG_TRY(hig_enc_layer_fwd(D.enc(), P.layer(l), a, xin, kpad, prec, stream));
     xin = a.x2;
   }
 
   if (D.cls) {  // logits from the [cls] token's row of each pair
-    return hig_gemm_launch(G(xin, (int64_t)S * d, 0, EP(params, HIG_EV_HEAD_W), d, 0, logits, D.C, D.B, D.C, d)
-                               .epi(HIG_EPI_BIAS, EP(params, HIG_EV_HEAD_B)).g, 1, nullptr, st);
+    return hig_gemm_launch(G(xin, (int64_t)S * d, 0, P[HIG_EV_HEAD_W], d, 0, logits, D.C, D.B, D.C, d)
+                               .epi(HIG_EPI_BIAS, P[HIG_EV_HEAD_B]).g, 1, nullptr, st);
   }
-  HIG_TRY(hig_gemm_launch(G(xin, d, 0, EP(params, HIG_EV_OUT1_W), d, 0, o, d, M, d, d)
-                              .epi(HIG_EPI_BIAS, EP(params, HIG_EV_OUT1_B)).prec(prec).g, 1, nullptr, st));
+  HIG_TRY(hig_gemm_launch(G(xin, d, 0, P[HIG_EV_OUT1_W], d, 0, o, d, M, d, d)
+                              .epi(HIG_EPI_BIAS, P[HIG_EV_OUT1_B]).prec(prec).g, 1, nullptr, st));
   for (int p = 0; p < 2; ++p)
-    HIG_TRY(hig_gemm_launch(G(xin + (int64_t)p * T * d, (int64_t)S * d, 0, EP(params, HIG_EV_OUT2_W), d, 0,
+    HIG_TRY(hig_gemm_launch(G(xin + (int64_t)p * T * d, (int64_t)S * d, 0, P[HIG_EV_OUT2_W], d, 0,
                               o + (int64_t)p * T * d, (int64_t)S * d, D.B, d, d)
-                                .epi(HIG_EPI_BIAS, EP(params, HIG_EV_OUT2_B)).g, 1, nullptr, st));
+                                .epi(HIG_EPI_BIAS, P[HIG_EV_OUT2_B]).g, 1, nullptr, st));
   hipLaunchKernelGGL(masked_mean_kernel, dim3(D.B, (d + 255) / 256), dim3(256), 0, st, o, length, feat, T, D.cls, d);
   HIG_CHECK_LAUNCH();
-  return hig_gemm_launch(G(feat, d, 0, EP(params, HIG_EV_HEAD_W), d, 0, logits, D.C, D.B, D.C, d)
-                             .epi(HIG_EPI_BIAS, EP(params, HIG_EV_HEAD_B)).g, 1, nullptr, st);
+  return hig_gemm_launch(G(feat, d, 0, P[HIG_EV_HEAD_W], d, 0, logits, D.C, D.B, D.C, d)
+                             .epi(HIG_EPI_BIAS, P[HIG_EV_HEAD_B]).g, 1, nullptr, st);
 }
 
 }  // namespace
@@ -401,19 +355,19 @@ extern "C" int hig_eval_encoder_fwd(const hig_eval_dims* dims, const void* const
   EDims D;
   HIG_TRY(check_edims(dims, D));
   HIG_REQUIRE(params && x1 && x2 && length && logits && workspace, "hig_eval_encoder_fwd: null argument");
-  HIG_REQUIRE(EP(params, HIG_EV_SEQ_EMB) && EP(params, HIG_EV_JOINT1_W) && EP(params, HIG_EV_JOINT2_W) &&
-                  EP(params, HIG_EV_HEAD_W),
+  const ETab P = etab(params);
+  HIG_REQUIRE(P[HIG_EV_SEQ_EMB] && P[HIG_EV_JOINT1_W] && P[HIG_EV_JOINT2_W] && P[HIG_EV_HEAD_W],
               "hig_eval_encoder_fwd: missing embedding / head parameters");
   if (D.cls)
-    HIG_REQUIRE(EP(params, HIG_EV_CLS_IN), "hig_eval_encoder_fwd: consistency model needs cls_input");
+    HIG_REQUIRE(P[HIG_EV_CLS_IN], "hig_eval_encoder_fwd: consistency model needs cls_input");
   else
-    HIG_REQUIRE(EP(params, HIG_EV_OUT1_W) && EP(params, HIG_EV_OUT2_W), "hig_eval_encoder_fwd: MotionEncoder needs out1 / out2");
+    HIG_REQUIRE(P[HIG_EV_OUT1_W] && P[HIG_EV_OUT2_W], "hig_eval_encoder_fwd: MotionEncoder needs out1 / out2");
   const EWs w = ews_layout(D);
   float* ws = static_cast<float*>(workspace);
   // one activation block, the layer output ping-ponging between xa and xb so that a layer never overwrites its own input; the
   // head's o reuses r1
   auto layer_of = [&](int l) {
-    return EFwdLayer{ws + w.qkv, ws + w.lse, ws + w.att, ws + w.r1, ws + w.st, ws + w.x1, nullptr, ws + w.f, ws + w.r2, ws + w.st,
+    return EncLayer{ws + w.qkv, ws + w.lse, ws + w.att, ws + w.r1, ws + w.st, ws + w.x1, nullptr, ws + w.f, ws + w.r2, ws + w.st,
                      ws + ((l & 1) ? w.xb : w.xa)};
   };
   return eval_forward(D, params, x1, x2, length, logits, ws + w.emb, ws + w.h, reinterpret_cast<uint8_t*>(ws + w.kpad), ws + w.r1,
@@ -423,51 +377,35 @@ extern "C" int hig_eval_encoder_fwd(const hig_eval_dims* dims, const void* const
 extern "C" int64_t hig_eval_encoder_train_workspace_bytes(const hig_eval_dims* dims) {
   EDims D;
   if (check_edims(dims, D) != HIG_OK) return -1;
-  return etrain_layout(D).total * 4;
+  return etrain_layout(D)[HIG_EFW_TOTAL] * 4;
 }
 extern "C" int64_t hig_eval_encoder_bwd_workspace_bytes(const hig_eval_dims* dims) {
   EDims D;
   if (check_edims(dims, D) != HIG_OK) return -1;
-  return ebwd_layout(D).total * 4;
+  return ebwd_layout(D)[HIG_EBW_TOTAL] * 4;
 }
 // ---- test hooks (include/hig.h): the training layouts above and the tap's, by named slot ----
 extern "C" int64_t hig_eval_encoder_bwd_tap_bytes(const hig_eval_dims* dims) {
   EDims D;
   if (check_edims(dims, D) != HIG_OK) return HIG_EINVAL;
-  return hig_enc_tap_layout(false, D.B, D.S, D.d, D.ff, D.H, D.L).off[HIG_ETAP_TOTAL] * 4;
+  return hig_enc_tap_layout(false, D.enc(), D.L).off[HIG_ETAP_TOTAL] * 4;
 }
 extern "C" int hig_eval_encoder_layout(const hig_eval_dims* dims, int32_t which, int64_t* out, int32_t n_out) {
   EDims D;
   if (check_edims(dims, D) != HIG_OK) return HIG_EINVAL;   // (the message is check_edims's)
-  int64_t v[HIG_EBW_NSLOTS];
-  static_assert(HIG_EFW_NSLOTS <= HIG_EBW_NSLOTS && HIG_ETAP_NSLOTS <= HIG_EBW_NSLOTS, "v holds the longest table");
-  int n = 0;
   if (which == HIG_ENC_LAYOUT_FWD) {
-    const ETrain w = etrain_layout(D);
-    n = HIG_EFW_NSLOTS;
-    v[HIG_EFW_EMB] = w.emb; v[HIG_EFW_H] = w.h; v[HIG_EFW_KPAD] = w.kpad; v[HIG_EFW_O] = D.cls ? -1 : w.o; v[HIG_EFW_FEAT] = D.cls ? -1 : w.feat;
-    v[HIG_EFW_LAYER0] = w.layer0; v[HIG_EFW_LSTRIDE] = w.lstride;
-    v[HIG_EFW_QKV] = w.qkv; v[HIG_EFW_LSE] = w.lse; v[HIG_EFW_ATT] = w.att; v[HIG_EFW_R1] = w.r1; v[HIG_EFW_ST1] = w.st1; v[HIG_EFW_X1] = w.x1;
-    v[HIG_EFW_Z] = w.z; v[HIG_EFW_F] = w.f; v[HIG_EFW_R2] = w.r2; v[HIG_EFW_ST2] = w.st2; v[HIG_EFW_X2] = w.x2; v[HIG_EFW_TOTAL] = w.total;
-  } else if (which == HIG_ENC_LAYOUT_BWD) {
-    const EBwd w = ebwd_layout(D);
-    n = HIG_EBW_NSLOTS;
-    v[HIG_EBW_DA] = w.dA; v[HIG_EBW_DB] = w.dB; v[HIG_EBW_DC] = w.dC; v[HIG_EBW_DFF] = w.dff; v[HIG_EBW_DQKV] = w.dqkv; v[HIG_EBW_DELTA] = w.delta;
-    v[HIG_EBW_WT] = w.wT; v[HIG_EBW_SLABS] = w.slabs; v[HIG_EBW_SLAB_FLOATS] = w.slab_floats; v[HIG_EBW_COLPART] = w.colpart;
-    v[HIG_EBW_LNPART] = w.lnpart;
-    const int64_t head[][2] = {{HIG_EBW_DFT, w.dft}, {HIG_EBW_G, w.g}, {HIG_EBW_GN, w.gn}, {HIG_EBW_G2, w.g2}, {HIG_EBW_POOL1, w.pool1},
-                               {HIG_EBW_POOL2, w.pool2}, {HIG_EBW_U1, w.u1}, {HIG_EBW_U2, w.u2}};
-    for (auto& h : head) v[h[0]] = D.cls ? -1 : h[1];      // (the MotionEncoder head)
-    v[HIG_EBW_XCAT] = w.xcat; v[HIG_EBW_DMOVE] = w.dmove; v[HIG_EBW_DINIT] = w.dinit; v[HIG_EBW_POSTMP] = w.postmp; v[HIG_EBW_TOTAL] = w.total;
-  } else if (which == HIG_ENC_LAYOUT_TAP) {
-    const EncTap t = hig_enc_tap_layout(false, D.B, D.S, D.d, D.ff, D.H, D.L);
-    n = HIG_ETAP_NSLOTS;
-    for (int s = 0; s < HIG_ETAP_NSLOTS; ++s) v[s] = t.off[s];
-  } else {
-    return hig_set_error(HIG_EINVAL, "hig_eval_encoder_layout: no layout table %d", which);
+    ETrain w = etrain_layout(D);
+    if (D.cls) w[HIG_EFW_O] = w[HIG_EFW_FEAT] = -1;      // (the MotionEncoder head)
+    return hig_enc_publish(w.data(), HIG_EFW_NSLOTS, out, n_out);
   }
-  for (int s = 0; out && s < n && s < n_out; ++s) out[s] = v[s];
-  return n;
+  if (which == HIG_ENC_LAYOUT_BWD) {
+    EBwd w = ebwd_layout(D);
+    if (D.cls)
+      for (int s : EBW_HEAD) w[s] = -1;
+    return hig_enc_publish(w.data(), HIG_EBW_NSLOTS, out, n_out);
+  }
+  if (which == HIG_ENC_LAYOUT_TAP) return hig_enc_publish(hig_enc_tap_layout(false, D.enc(), D.L).off, HIG_ETAP_NSLOTS, out, n_out);
+  return hig_set_error(HIG_EINVAL, "hig_eval_encoder_layout: no layout table %d", which);
 }
 
 extern "C" int hig_eval_encoder_fwd_train(const hig_eval_dims* dims, const void* const* params, const float* x1,
@@ -479,15 +417,13 @@ extern "C" int hig_eval_encoder_fwd_train(const hig_eval_dims* dims, const void*
   HIG_TRY(check_train(D, params, "hig_eval_encoder_fwd_train"));
   const ETrain w = etrain_layout(D);
   float* ws = static_cast<float*>(workspace);
-  auto layer_of = [&](int l) {   // one block per layer, the GELU pre-activation z kept
-    float* lb = ws + w.layer0 + w.lstride * l;
-    return EFwdLayer{lb + w.qkv, lb + w.lse, lb + w.att, lb + w.r1, lb + w.st1, lb + w.x1, lb + w.z, lb + w.f, lb + w.r2, lb + w.st2,
-                     lb + w.x2};
-  };
+  // one block per layer, the GELU pre-activation z kept
+  auto layer_of = [&](int l) { return hig_enc_block_at(ws + w[HIG_EFW_LAYER0] + w[HIG_EFW_LSTRIDE] * l, &w[HIG_EFW_QKV]); };
   // the pooled feature is kept in the workspace (the backward's fin_proj weight gradient reads it) and copied out
-  HIG_TRY(eval_forward(D, params, x1, x2, length, logits, ws + w.emb, ws + w.h, reinterpret_cast<uint8_t*>(ws + w.kpad), ws + w.o,
-                       ws + w.feat, HIG_PREC_F32, layer_of, stream));
-  if (!D.cls && feature) HIG_TRY(hig_copy_async(feature, ws + w.feat, (int64_t)D.B * D.d * 4, hig_stream(stream)));
+  HIG_TRY(eval_forward(D, params, x1, x2, length, logits, ws + w[HIG_EFW_EMB], ws + w[HIG_EFW_H],
+                       reinterpret_cast<uint8_t*>(ws + w[HIG_EFW_KPAD]), ws + w[HIG_EFW_O], ws + w[HIG_EFW_FEAT], HIG_PREC_F32, layer_of,
+                       stream));
+  if (!D.cls && feature) HIG_TRY(hig_copy_async(feature, ws + w[HIG_EFW_FEAT], (int64_t)D.B * D.d * 4, hig_stream(stream)));
   return HIG_OK;
 }
 
@@ -502,81 +438,80 @@ extern "C" int hig_eval_encoder_bwd(const hig_eval_dims* dims, const void* const
   HIG_REQUIRE(!(D.cls && dfeature), "hig_eval_encoder_bwd: the consistency model has no feature output");
   const ETrain w = etrain_layout(D);
   const EBwd bw = ebwd_layout(D);
+  const ETab P = etab(params);
+  const Tab Gr(grads, HIG_EV_NGLOBAL, HIG_TL_NLAYER);
   const float* ws = static_cast<const float*>(workspace);
   float* b = static_cast<float*>(bwd_workspace);
   hipStream_t st = hig_stream(stream);
   const int d = D.d, T = D.T, S = D.S, C = D.C, F = D.F;
   const int64_t M = D.M, BT = (int64_t)D.B * T;
-  const uint8_t* kpad = reinterpret_cast<const uint8_t*>(ws + w.kpad);
-  EncBwd e;
-  e.B = D.B; e.S = S; e.n = d; e.ff = D.ff; e.H = D.H; e.hd = D.hd; e.prec = HIG_PREC_F32; e.M = M;
-  e.slabs = b + bw.slabs; e.slab_floats = bw.slab_floats;
-  e.colp = b + bw.colpart; e.lnp = b + bw.lnpart; e.wT = b + bw.wT; e.tA = nullptr; e.tB = nullptr;   // (tA / tB: bf16 product modes only)
-  e.dff = b + bw.dff; e.dqkv = b + bw.dqkv; e.delta = b + bw.delta;
-  e.stream = stream;
+  const uint8_t* kpad = reinterpret_cast<const uint8_t*>(ws + w[HIG_EFW_KPAD]);
+  EncBwd e(D.enc(), HIG_PREC_F32, b, bw.data(), EBW_SCRATCH, stream);
   HIG_TRY(e.tap_begin(false, D.L, "hig_eval_encoder_bwd"));
 
-  float* dA = b + bw.dA;
-  float* dB = b + bw.dB;
-  float* dC = b + bw.dC;
-  const float* xL = ws + w.layer0 + w.lstride * (D.L - 1) + w.x2;
+  float* dA = b + bw[HIG_EBW_DA];
+  float* dB = b + bw[HIG_EBW_DB];
+  float* dC = b + bw[HIG_EBW_DC];
+  float *dft = b + bw[HIG_EBW_DFT], *g = b + bw[HIG_EBW_G], *gn = b + bw[HIG_EBW_GN], *g2 = b + bw[HIG_EBW_G2];
+  float *pool1 = b + bw[HIG_EBW_POOL1], *pool2 = b + bw[HIG_EBW_POOL2], *u1 = b + bw[HIG_EBW_U1], *u2 = b + bw[HIG_EBW_U2];
+  float* postmp = b + bw[HIG_EBW_POSTMP];
+  const float* feat = ws + w[HIG_EFW_FEAT];
+  auto layer = [&](int l) { return hig_enc_block_at(ws + w[HIG_EFW_LAYER0] + w[HIG_EFW_LSTRIDE] * l, &w[HIG_EFW_QKV]); };
+  const float* xL = layer(D.L - 1).x2;
   // ---- head: d(h of the last layer) into dB ---------------------------------------------------------------------------
-  HIG_TRY(e.colsum(dlogits, C, D.B, C, EG(grads, HIG_EV_HEAD_B)));
+  HIG_TRY(e.colsum(dlogits, C, D.B, C, Gr[HIG_EV_HEAD_B]));
   if (D.cls) {
     // logits = cls_output(h[b][0])
-    HIG_TRY(hig_gemm_launch(G(dlogits, C, 1, xL, (int64_t)S * d, 1, EG(grads, HIG_EV_HEAD_W), d, C, d, D.B).g, 1, nullptr, st));
+    HIG_TRY(hig_gemm_launch(G(dlogits, C, 1, xL, (int64_t)S * d, 1, Gr[HIG_EV_HEAD_W], d, C, d, D.B).g, 1, nullptr, st));
     HIG_TRY(hig_zero_async(dB, M * d * 4, st));
-    HIG_TRY(hig_gemm_launch(G(dlogits, C, 0, EP(params, HIG_EV_HEAD_W), d, 1, dB, (int64_t)S * d, D.B, d, C).g, 1, nullptr, st));
+    HIG_TRY(hig_gemm_launch(G(dlogits, C, 0, P[HIG_EV_HEAD_W], d, 1, dB, (int64_t)S * d, D.B, d, C).g, 1, nullptr, st));
   } else {
-    HIG_TRY(hig_gemm_launch(G(dlogits, C, 1, ws + w.feat, d, 1, EG(grads, HIG_EV_HEAD_W), d, C, d, D.B).g, 1, nullptr, st));
+    HIG_TRY(hig_gemm_launch(G(dlogits, C, 1, feat, d, 1, Gr[HIG_EV_HEAD_W], d, C, d, D.B).g, 1, nullptr, st));
     // d(feature) total = upstream + dlogits . fin_proj.weight
-    G gf(dlogits, C, 0, EP(params, HIG_EV_HEAD_W), d, 1, b + bw.dft, d, D.B, d, C);
+    G gf(dlogits, C, 0, P[HIG_EV_HEAD_W], d, 1, dft, d, D.B, d, C);
     if (dfeature) gf.epi(HIG_EPI_RES).res(dfeature, d);
     HIG_TRY(hig_gemm_launch(gf.g, 1, nullptr, st));
     const dim3 gb(D.B, (d + 255) / 256);
-    hipLaunchKernelGGL(head_scale_kernel, gb, dim3(256), 0, st, b + bw.dft, length, b + bw.g, b + bw.gn, b + bw.g2, T, d);
+    hipLaunchKernelGGL(head_scale_kernel, gb, dim3(256), 0, st, dft, length, g, gn, g2, T, d);
     HIG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pool_kernel, gb, dim3(256), 0, st, xL, length, b + bw.pool1, b + bw.pool2, T, d);
+    hipLaunchKernelGGL(pool_kernel, gb, dim3(256), 0, st, xL, length, pool1, pool2, T, d);
     HIG_CHECK_LAUNCH();
-    HIG_TRY(hig_gemm_launch(G(b + bw.g, d, 1, b + bw.pool1, d, 1, EG(grads, HIG_EV_OUT1_W), d, d, d, D.B).g, 1, nullptr, st));
-    HIG_TRY(hig_gemm_launch(G(b + bw.g, d, 1, b + bw.pool2, d, 1, EG(grads, HIG_EV_OUT2_W), d, d, d, D.B).g, 1, nullptr, st));
-    HIG_TRY(e.colsum(b + bw.gn, d, D.B, d, EG(grads, HIG_EV_OUT1_B)));
-    HIG_TRY(e.colsum(b + bw.g2, d, D.B, d, EG(grads, HIG_EV_OUT2_B)));
-    HIG_TRY(hig_gemm_launch(G(b + bw.g, d, 0, EP(params, HIG_EV_OUT1_W), d, 1, b + bw.u1, d, D.B, d, d).g, 1, nullptr, st));
-    HIG_TRY(hig_gemm_launch(G(b + bw.g, d, 0, EP(params, HIG_EV_OUT2_W), d, 1, b + bw.u2, d, D.B, d, d).g, 1, nullptr, st));
-    hipLaunchKernelGGL(unpool_kernel, dim3((unsigned)M), dim3(128), 0, st, b + bw.u1, b + bw.u2, length, dB, T, d);
+    HIG_TRY(hig_gemm_launch(G(g, d, 1, pool1, d, 1, Gr[HIG_EV_OUT1_W], d, d, d, D.B).g, 1, nullptr, st));
+    HIG_TRY(hig_gemm_launch(G(g, d, 1, pool2, d, 1, Gr[HIG_EV_OUT2_W], d, d, d, D.B).g, 1, nullptr, st));
+    HIG_TRY(e.colsum(gn, d, D.B, d, Gr[HIG_EV_OUT1_B]));
+    HIG_TRY(e.colsum(g2, d, D.B, d, Gr[HIG_EV_OUT2_B]));
+    HIG_TRY(hig_gemm_launch(G(g, d, 0, P[HIG_EV_OUT1_W], d, 1, u1, d, D.B, d, d).g, 1, nullptr, st));
+    HIG_TRY(hig_gemm_launch(G(g, d, 0, P[HIG_EV_OUT2_W], d, 1, u2, d, D.B, d, d).g, 1, nullptr, st));
+    hipLaunchKernelGGL(unpool_kernel, dim3((unsigned)M), dim3(128), 0, st, u1, u2, length, dB, T, d);
     HIG_CHECK_LAUNCH();
   }
   HIG_TRY(e.tap_copy(HIG_ETAP_DH_L, -1, dB));
   // ---- layers ------------------------------------------------------------------------------------------------------------
   float* dh = dB;
   for (int l = D.L - 1; l >= 0; --l) {
-    const float* lb = ws + w.layer0 + w.lstride * l;
-    const float* xin = l == 0 ? ws + w.h : ws + w.layer0 + w.lstride * (l - 1) + w.x2;
-    const EncLayerAct a = {lb + w.qkv, lb + w.lse, lb + w.att, lb + w.r1, lb + w.st1, lb + w.x1, lb + w.z, lb + w.f, lb + w.r2, lb + w.st2};
-    HIG_TRY(hig_enc_layer_bwd(e, l, params + HIG_EV_NGLOBAL + l * HIG_TL_NLAYER, grads + HIG_EV_NGLOBAL + l * HIG_TL_NLAYER, a, xin, kpad, dh, dA,
-                              dC));
+    const float* xin = l == 0 ? ws + w[HIG_EFW_H] : layer(l - 1).x2;
+    HIG_TRY(hig_enc_layer_bwd(e, l, P.layer(l), Gr.layer(l), layer(l), xin, kpad, dh, dA, dC));
   }
   HIG_TRY(e.tap_copy(HIG_ETAP_DH_0, -1, dh));
   // ---- embedding -----------------------------------------------------------------------------------------------------------
-  if (D.cls) HIG_TRY(e.colsum(dh, (int64_t)S * d, D.B, d, EG(grads, HIG_EV_CLS_IN)));   // the [cls] rows, summed over the batch
-  float* dmove = b + bw.dmove;
-  float* dinit = b + bw.dinit;
-  float* xcat = b + bw.xcat;
+  if (D.cls) HIG_TRY(e.colsum(dh, (int64_t)S * d, D.B, d, Gr[HIG_EV_CLS_IN]));   // the [cls] rows, summed over the batch
+  float* dmove = b + bw[HIG_EBW_DMOVE];
+  float* dinit = b + bw[HIG_EBW_DINIT];
+  float* xcat = b + bw[HIG_EBW_XCAT];
   hipLaunchKernelGGL(unassemble_kernel, dim3((unsigned)(2 * BT)), dim3(128), 0, st, dh, dmove, dinit, D.B, T, d, D.cls);
   HIG_CHECK_LAUNCH();
   HIG_TRY(hig_copy_async(xcat, x1, BT * F * 4, st));
   HIG_TRY(hig_copy_async(xcat + BT * F, x2, BT * F * 4, st));
   // joint_embed2: the init-pose rows (t = 0), first 4 features
-  HIG_TRY(e.colsum(dinit, d, 2 * D.B, d, EG(grads, HIG_EV_JOINT2_B)));
-  HIG_TRY(e.wgrad(G(dinit, d, 1, xcat, (int64_t)T * F, 1, EG(grads, HIG_EV_JOINT2_W), 4, d, 4, 2 * D.B)));
+  HIG_TRY(e.colsum(dinit, d, 2 * D.B, d, Gr[HIG_EV_JOINT2_B]));
+  HIG_TRY(e.wgrad(G(dinit, d, 1, xcat, (int64_t)T * F, 1, Gr[HIG_EV_JOINT2_W], 4, d, 4, 2 * D.B)));
   // joint_embed1: the rows t >= 1 (the forward overwrote its t = 0 rows: they are zero in dmove)
-  HIG_TRY(e.colsum(dmove, d, 2 * BT, d, EG(grads, HIG_EV_JOINT1_B)));
-  HIG_TRY(e.wgrad(G(dmove, d, 1, xcat, F, 1, EG(grads, HIG_EV_JOINT1_W), F, d, F, 2 * BT)));
+  HIG_TRY(e.colsum(dmove, d, 2 * BT, d, Gr[HIG_EV_JOINT1_B]));
+  HIG_TRY(e.wgrad(G(dmove, d, 1, xcat, F, 1, Gr[HIG_EV_JOINT1_W], F, d, F, 2 * BT)));
   // d(sequence_embedding)[t - 1] = sum over persons and samples of row t: column sums of dmove viewed as (2 B, T d), row 0 dropped
   // (the table's rows at or beyond T - 1 were never read: the caller zeroes their gradient, include/hig.h)
-  HIG_TRY(e.colsum(dmove, (int64_t)T * d, 2 * D.B, T * d, b + bw.postmp));
-  HIG_TRY(hig_copy_async(EG(grads, HIG_EV_SEQ_EMB), b + bw.postmp + d, (int64_t)(T - 1) * d * 4, st));
+  HIG_TRY(e.colsum(dmove, (int64_t)T * d, 2 * D.B, T * d, postmp));
+  HIG_TRY(hig_copy_async(Gr[HIG_EV_SEQ_EMB], postmp + d, (int64_t)(T - 1) * d * 4, st));
   return HIG_OK;
 }
 

@@ -1,4 +1,4 @@
-// Host-side helpers shared by the orchestration translation units (denoiser.hip, texthead.hip, evalnet.hip).
+// Host-side helpers shared by the orchestration translation units (denoiser.hip and, through enc_layers.h, the encoder chains).
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -315,150 +315,6 @@ inline int wgrad_splits(int64_t I, int64_t J, int64_t R, int64_t slab_floats, in
   while (s > 1 && s * (I * J + I) > slab_floats) --s;   // slabs + the per-split column sums of X behind them
   if ((I * J) % 4 != 0) s = 1;
   return (int)(s < 1 ? 1 : s);
-}
-
-
-// ---- backward of one post-norm nn.TransformerEncoderLayer (gelu, dropout 0), shared by the text head and the evaluator ----
-//     x1 = norm1(xin + out_proj(att(in_proj(xin))));   x2 = norm2(x1 + linear2(gelu(linear1(x1))))
-// The debug tap of the two backwards (hig_enc_bwd_debug_tap, include/hig.h), in floats: off[slot] is an absolute offset for the
-// slots written once and an offset from the layer's base for the per-layer ones; -1 where the chain has no such buffer.
-struct EncTap {
-  int64_t off[HIG_ETAP_NSLOTS], floats[HIG_ETAP_NSLOTS];
-};
-// text: the text head (DXF_TOTAL, DGATH) or the evaluator (DH_L, DH_0); S tokens per sample, n the model width
-inline EncTap hig_enc_tap_layout(bool text, int64_t B, int64_t S, int64_t n, int64_t ff, int64_t H, int64_t L) {
-  EncTap t;
-  const int64_t row = B * S * n;
-  for (int s = 0; s < HIG_ETAP_NSLOTS; ++s) t.floats[s] = row;      // (most slots are one (M, n) matrix)
-  t.floats[HIG_ETAP_DXF_TOTAL] = text ? row : -1;
-  t.floats[HIG_ETAP_DGATH] = text ? B * n : -1;
-  t.floats[HIG_ETAP_DH_L] = t.floats[HIG_ETAP_DH_0] = text ? -1 : row;
-  t.floats[HIG_ETAP_DZ] = B * S * ff;
-  t.floats[HIG_ETAP_DQKV] = 3 * row;
-  t.floats[HIG_ETAP_DELTA] = B * H * S;
-  int64_t o = 0;
-  auto take = [&](int s) { t.off[s] = t.floats[s] < 0 ? -1 : o; if (t.floats[s] > 0) o += al(t.floats[s]); };
-  for (int s = 0; s < HIG_ETAP_LAYER0; ++s) take(s);
-  t.off[HIG_ETAP_LAYER0] = o;
-  o = 0;
-  for (int s = HIG_ETAP_LSTRIDE + 1; s < HIG_ETAP_TOTAL; ++s) take(s);
-  t.off[HIG_ETAP_LSTRIDE] = o;
-  t.off[HIG_ETAP_TOTAL] = t.off[HIG_ETAP_LAYER0] + o * L;
-  return t;
-}
-
-// The scratch a backward sequence owns (sized by its own layout), plus the three GEMM forms every such sequence is made of.
-struct EncBwd {
-  int B, S, n, ff, H, hd, prec;       // samples, tokens per sample, model width, FFN width, heads, head dim, HIG_PREC_*
-  int64_t M;                          // B * S rows
-  float *slabs; int64_t slab_floats;  // split-R slabs of the weight-gradient GEMMs
-  float *colp, *lnp, *wT, *tA, *tB;   // column-sum partials, LayerNorm partials, W^T, the two transposed operands (bf16 product modes)
-  float *dff, *dqkv, *delta;          // (M, ff), (M, 3n), (B, H, S)
-  hig_stream_t stream;
-  float* tap = nullptr;               // the debug tap (tap_begin): NULL in every real run
-  EncTap tl;
-  hipStream_t st() const { return hig_stream(stream); }
-
-  // Before the first launch of a backward: takes the process's tap buffer, if one is set; a buffer too short for these dims is
-  // refused before any HIP call, a capturing stream before any launch.
-  int tap_begin(bool text, int L, const char* who) {
-    float* buf = nullptr;
-    int64_t bytes = 0;
-    hig_enc_tap_buffer(&buf, &bytes);
-    tap = nullptr;
-    if (!buf) return HIG_OK;
-    tl = hig_enc_tap_layout(text, B, S, n, ff, H, L);
-    if (bytes < tl.off[HIG_ETAP_TOTAL] * 4)
-      return hig_set_error(HIG_EINVAL, "%s: the tap buffer has %lld bytes, these dims need %lld", who, (long long)bytes,
-                           (long long)(tl.off[HIG_ETAP_TOTAL] * 4));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st(), &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-      return hig_set_error(HIG_EINVAL, "%s: a debug tap is set and the stream is capturing", who);
-    tap = buf;
-    return HIG_OK;
-  }
-  // copies `src` into the tap's slot (of layer l, or l < 0: a slot written once) behind the launch that wrote it
-  int tap_copy(int slot, int l, const float* src) const {
-    if (!tap) return HIG_OK;
-    float* dst = tap + tl.off[slot] + (l < 0 ? 0 : tl.off[HIG_ETAP_LAYER0] + tl.off[HIG_ETAP_LSTRIDE] * l);
-    return hig_copy_async(dst, src, tl.floats[slot] * 4, st());
-  }
-
-  int wgrad(G gd) const {
-    const int s = wgrad_splits(gd.g.I, gd.g.J, gd.g.R, slab_floats, gd.g.prec);
-    return hig_gemm_launch(gd.g, s, slabs, st());
-  }
-  // dW[n][k] = sum_m dC[m][n] * act[m][k]; bf16 product modes transpose both operands first
-  // dbias = column sums of dC (the bias gradient): from the wgrad GEMM itself in the exact-fp32 path
-  int wgrad_act(const float* dC, int n_out, const float* act, int k_in, float* out, int64_t rows, float* dbias) const {
-    if (prec != HIG_PREC_F32 && rows % 32 == 0) {
-      HIG_TRY(hig_colsum(dC, n_out, rows, n_out, dbias, colp, stream));
-      HIG_TRY(hig_transpose(dC, n_out, (int)rows, n_out, tA, rows, nullptr, nullptr, nullptr, stream));
-      HIG_TRY(hig_transpose(act, k_in, (int)rows, k_in, tB, rows, nullptr, nullptr, nullptr, stream));
-      return wgrad(G(tA, rows, 0, tB, rows, 0, out, k_in, n_out, k_in, rows).prec(prec));
-    }
-    G gd(dC, n_out, 1, act, k_in, 1, out, k_in, n_out, k_in, rows);
-    if (n_out % 4 == 0) gd.xsum(dbias);
-    else HIG_TRY(hig_colsum(dC, n_out, rows, n_out, dbias, colp, stream));
-    return wgrad(gd);
-  }
-  // dX = dC . W with W (out_f, in_f) transposed first, so both operands are reduce-contiguous
-  int dgrad(const float* dC, const float* W, int out_f, int in_f, int64_t rows, float* dX, int epi, const float* res,
-            float* aux) const {
-    HIG_TRY(hig_transpose(W, in_f, out_f, in_f, wT, out_f, nullptr, nullptr, nullptr, stream));
-    G gd(dC, out_f, 0, wT, out_f, 0, dX, in_f, rows, in_f, out_f);
-    gd.prec(prec);
-    if (epi == HIG_EPI_RES) gd.epi(HIG_EPI_RES).res(res, in_f);
-    if (epi == HIG_EPI_DGELU) gd.epi(HIG_EPI_DGELU).aux(aux, in_f);
-    return hig_gemm_launch(gd.g, 1, nullptr, st());
-  }
-  int colsum(const float* src, int64_t ld, int64_t rows, int n_, float* dst) const {
-    return hig_colsum(src, ld, rows, n_, dst, colp, stream);
-  }
-};
-// what the training forward kept of one layer
-struct EncLayerAct {
-  const float *qkv, *lse, *att, *r1, *st1, *x1, *z, *f, *r2, *st2;
-};
-// P / Gr: the layer's HIG_TL_* block of the parameter / gradient table.  d: in d(x2), out d(xin); t1, t2: (M, n) scratch.
-// kpad: the forward's key-padding bytes (B, S), or NULL.
-// l: the layer's index (names the tap's per-layer block).
-inline int hig_enc_layer_bwd(const EncBwd& e, int l, const void* const* P, void* const* Gr, const EncLayerAct& a, const float* xin,
-                             const uint8_t* kpad, float* d, float* t1, float* t2) {
-  auto p = [&](int i) { return static_cast<const float*>(P[i]); };
-  auto g = [&](int i) { return static_cast<float*>(Gr[i]); };
-  const int n = e.n, ff = e.ff;
-  const int64_t M = e.M;
-  HIG_TRY(e.tap_copy(HIG_ETAP_DH_IN, l, d));
-  // norm2: x2 = LN(r2)
-  HIG_TRY(hig_ln_bwd(d, n, a.r2, n, a.st2, p(HIG_TL_N2_W), p(HIG_TL_N2_B), nullptr, 0, 0, 0, nullptr, 0, t1, n, M, n, e.S,
-                     g(HIG_TL_N2_W), g(HIG_TL_N2_B), nullptr, 0, e.lnp, e.stream));
-  const float* dr2 = t1;
-  HIG_TRY(e.tap_copy(HIG_ETAP_DR2, l, dr2));
-  // r2 = x1 + linear2(gelu(z)),  z = linear1(x1)
-  HIG_TRY(e.wgrad_act(dr2, n, a.f, ff, g(HIG_TL_FF2_W), M, g(HIG_TL_FF2_B)));
-  HIG_TRY(e.dgrad(dr2, p(HIG_TL_FF2_W), n, ff, M, e.dff, HIG_EPI_DGELU, nullptr, const_cast<float*>(a.z)));
-  const float* dz = e.dff;
-  HIG_TRY(e.tap_copy(HIG_ETAP_DZ, l, dz));
-  HIG_TRY(e.wgrad_act(dz, ff, a.x1, n, g(HIG_TL_FF1_W), M, g(HIG_TL_FF1_B)));
-  HIG_TRY(e.dgrad(dz, p(HIG_TL_FF1_W), ff, n, M, t2, HIG_EPI_RES, dr2, nullptr));  // t2 = d(x1)
-  HIG_TRY(e.tap_copy(HIG_ETAP_DX1, l, t2));
-  // norm1: x1 = LN(r1)
-  HIG_TRY(hig_ln_bwd(t2, n, a.r1, n, a.st1, p(HIG_TL_N1_W), p(HIG_TL_N1_B), nullptr, 0, 0, 0, nullptr, 0, t1, n, M, n, e.S,
-                     g(HIG_TL_N1_W), g(HIG_TL_N1_B), nullptr, 0, e.lnp, e.stream));
-  const float* dr1 = t1;
-  HIG_TRY(e.tap_copy(HIG_ETAP_DR1, l, dr1));
-  // r1 = xin + out_proj(att)
-  HIG_TRY(e.wgrad_act(dr1, n, a.att, n, g(HIG_TL_OUT_W), M, g(HIG_TL_OUT_B)));
-  HIG_TRY(e.dgrad(dr1, p(HIG_TL_OUT_W), n, n, M, t2, HIG_EPI_NONE, nullptr, nullptr));  // t2 = d(att)
-  HIG_TRY(e.tap_copy(HIG_ETAP_DATT, l, t2));
-  float* dqkv = e.dqkv;
-  HIG_TRY(hig_fullattn_bwd_kpad(t2, n, a.att, n, a.qkv, 3 * n, a.qkv + n, a.qkv + 2 * n, 3 * n, e.B, e.S, e.S, e.H, e.hd, nullptr,
-                                a.lse, e.delta, dqkv, 3 * n, dqkv + n, dqkv + 2 * n, 3 * n, kpad, e.stream));
-  HIG_TRY(e.tap_copy(HIG_ETAP_DQKV, l, dqkv));
-  HIG_TRY(e.tap_copy(HIG_ETAP_DELTA, l, e.delta));
-  HIG_TRY(e.wgrad_act(dqkv, 3 * n, xin, n, g(HIG_TL_IN_W), M, g(HIG_TL_IN_B)));
-  return e.dgrad(dqkv, p(HIG_TL_IN_W), 3 * n, n, M, d, HIG_EPI_RES, dr1, nullptr);   // d = d(xin)
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 """The two fp32 encoder training chains -- the text head (hig_text_head_fwd with training = 1, hig_text_head_bwd; csrc/texthead.hip)
-and the evaluation classifiers (hig_eval_encoder_fwd_train, hig_eval_encoder_bwd; csrc/evalnet.hip) over the layer backward both
-share (hig_enc_layer_bwd, csrc/hig_host.h) -- restated launch by launch, with the element-wise bound of every launch and the
+and the evaluation classifiers (hig_eval_encoder_fwd_train, hig_eval_encoder_bwd; csrc/evalnet.hip) over the layer both share
+(hig_enc_layer_fwd, hig_enc_layer_bwd; csrc/enc_layers.h) -- restated launch by launch, with the element-wise bound of every launch and the
 composition mutants, in the form of tests/bf16_step_bounds.py (whose `Walk` supplies the buffers, `put` and the GEMM stages).
 Plain torch on the host: tests/test_cpu_enc_step_bounds.py proves without a GPU that the stages compose to oracle.text_head_ref /
 oracle.eval_models_ref under autograd, that an fp32 stand-in stays within the bounds and that every mutant breaks one;

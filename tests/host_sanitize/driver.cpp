@@ -445,6 +445,128 @@ int main() {
     EXPECT(hig_last_error(msg, sizeof(msg)) >= 0 && strstr(msg, "tap buffer") != nullptr);
     EXPECT(hig_denoiser_bwd_debug_tap(nullptr, 0) == HIG_OK);
   }
+  // ---- the encoder chains (text head, evaluation classifiers, CLIP text tower): the layouts by named slot and the eleven size
+  // queries over small dims.  None makes a HIP call. ----
+  {
+    auto tdims = [](int B, int N, int W, int Lt, int H, int ff, int L, int E) {
+      hig_text_dims t;
+      memset(&t, 0, sizeof(t));
+      t.B = B; t.N = N; t.W = W; t.Lt = Lt; t.H = H; t.ff = ff; t.L = L; t.E = E; t.prec = HIG_PREC_F32;
+      return t;
+    };
+    auto edims = [](int B, int T, int F, int d, int H, int ff, int L, int cls) {
+      hig_eval_dims e;
+      memset(&e, 0, sizeof(e));
+      e.B = B; e.T = T; e.F = F; e.d = d; e.H = H; e.ff = ff; e.L = L; e.C = cls ? 2 : 26; e.cls = cls; e.prec = HIG_PREC_F32;
+      return e;
+    };
+    int64_t v[64];
+    static_assert(HIG_TFW_NSLOTS < 64 && HIG_TBW_NSLOTS < 64 && HIG_EFW_NSLOTS < 64 && HIG_EBW_NSLOTS < 64 && HIG_ETAP_NSLOTS < 64, "v holds every table");
+    // a table of n slots whose slot `total` times 4 is `bytes`: every offset a multiple of 64 floats inside the total (`extent`: a
+    // slot that is a length, not an offset), -1 exactly on the slots of `absent`, n_out respected, a NULL out allowed
+    auto held = [&](auto layout, const auto& D, int which, int n, int total, int extent, int64_t bytes, std::initializer_list<int> absent) {
+      for (int64_t& x : v) x = -7;
+      EXPECT(layout(&D, which, v, 64) == n);
+      EXPECT(bytes > 0 && v[total] * 4 == bytes);
+      for (int s = 0; s < 64; ++s) {
+        bool gone = false;
+        for (int a : absent) gone = gone || a == s;
+        if (s >= n) EXPECT(v[s] == -7);
+        else if (gone) EXPECT(v[s] == -1);
+        else if (s == extent) EXPECT(v[s] > 0);
+        else EXPECT(v[s] >= 0 && v[s] % 64 == 0 && v[s] <= v[total]);
+      }
+      const int64_t v2 = v[2];
+      for (int64_t& x : v) x = -7;
+      EXPECT(layout(&D, which, v, 3) == n && v[2] == v2 && v[3] == -7);
+      for (int64_t& x : v) x = -7;
+      EXPECT(layout(&D, which, v, 0) == n && layout(&D, which, v, -1) == n && v[0] == -7);
+      EXPECT(layout(&D, which, nullptr, 64) == n);
+      EXPECT(layout(&D, 3, v, 64) == HIG_EINVAL && layout(&D, -1, v, 64) == HIG_EINVAL && v[0] == -7);
+    };
+    const hig_text_dims texts[] = {tdims(4, 24, 64, 64, 8, 128, 2, 128), tdims(3, 77, 64, 32, 4, 64, 2, 128), tdims(3, 77, 128, 128, 2, 128, 1, 256)};
+    for (const hig_text_dims& t : texts) {
+      held(hig_text_head_layout, t, HIG_ENC_LAYOUT_FWD, HIG_TFW_NSLOTS, HIG_TFW_TOTAL, -1, hig_text_head_workspace_bytes(&t, 1), {});
+      held(hig_text_head_layout, t, HIG_ENC_LAYOUT_BWD, HIG_TBW_NSLOTS, HIG_TBW_TOTAL, HIG_TBW_SLAB_FLOATS, hig_text_head_bwd_workspace_bytes(&t), {});
+      held(hig_text_head_layout, t, HIG_ENC_LAYOUT_TAP, HIG_ETAP_NSLOTS, HIG_ETAP_TOTAL, -1, hig_text_head_bwd_tap_bytes(&t), {HIG_ETAP_DH_L, HIG_ETAP_DH_0});
+      // inference: the prefix and two layer blocks, whatever L is
+      EXPECT(hig_text_head_layout(&t, HIG_ENC_LAYOUT_FWD, v, 64) == HIG_TFW_NSLOTS);
+      EXPECT(hig_text_head_workspace_bytes(&t, 0) == (v[HIG_TFW_LAYER0] + 2 * v[HIG_TFW_LSTRIDE]) * 4);
+      EXPECT(v[HIG_TFW_TOTAL] == v[HIG_TFW_LAYER0] + t.L * v[HIG_TFW_LSTRIDE]);
+    }
+    for (int cls = 0; cls <= 1; ++cls) {
+      const hig_eval_dims evals[] = {edims(4, 12, 15, 64, 8, 128, 2, cls), edims(4, 33, 15, 128, 2, 128, 2, cls), edims(4, 5, 15, 1024, 8, 64, 1, cls)};
+      for (const hig_eval_dims& e : evals) {
+        if (cls) {
+          held(hig_eval_encoder_layout, e, HIG_ENC_LAYOUT_FWD, HIG_EFW_NSLOTS, HIG_EFW_TOTAL, -1, hig_eval_encoder_train_workspace_bytes(&e), {HIG_EFW_O, HIG_EFW_FEAT});
+          held(hig_eval_encoder_layout, e, HIG_ENC_LAYOUT_BWD, HIG_EBW_NSLOTS, HIG_EBW_TOTAL, HIG_EBW_SLAB_FLOATS, hig_eval_encoder_bwd_workspace_bytes(&e),
+               {HIG_EBW_DFT, HIG_EBW_G, HIG_EBW_GN, HIG_EBW_G2, HIG_EBW_POOL1, HIG_EBW_POOL2, HIG_EBW_U1, HIG_EBW_U2});
+        } else {
+          held(hig_eval_encoder_layout, e, HIG_ENC_LAYOUT_FWD, HIG_EFW_NSLOTS, HIG_EFW_TOTAL, -1, hig_eval_encoder_train_workspace_bytes(&e), {});
+          held(hig_eval_encoder_layout, e, HIG_ENC_LAYOUT_BWD, HIG_EBW_NSLOTS, HIG_EBW_TOTAL, HIG_EBW_SLAB_FLOATS, hig_eval_encoder_bwd_workspace_bytes(&e), {});
+        }
+        held(hig_eval_encoder_layout, e, HIG_ENC_LAYOUT_TAP, HIG_ETAP_NSLOTS, HIG_ETAP_TOTAL, -1, hig_eval_encoder_bwd_tap_bytes(&e), {HIG_ETAP_DXF_TOTAL, HIG_ETAP_DGATH});
+        const int64_t inf = hig_eval_encoder_workspace_bytes(&e);
+        EXPECT(inf > 0 && inf % 256 == 0);
+      }
+    }
+    // illegal and NULL dims: every entry refuses, with the message of the dims check
+    {
+      hig_text_dims t = texts[0];
+      hig_eval_dims e = edims(4, 12, 15, 64, 8, 128, 2, 0);
+      auto text_refused = [&](const hig_text_dims* p) {
+        return hig_text_head_layout(p, HIG_ENC_LAYOUT_FWD, v, 64) == HIG_EINVAL && hig_text_head_workspace_bytes(p, 0) == -1 && hig_text_head_workspace_bytes(p, 1) == -1 &&
+               hig_text_head_bwd_workspace_bytes(p) == -1 && hig_text_head_bwd_tap_bytes(p) == HIG_EINVAL;
+      };
+      auto eval_refused = [&](const hig_eval_dims* p) {
+        return hig_eval_encoder_layout(p, HIG_ENC_LAYOUT_BWD, v, 64) == HIG_EINVAL && hig_eval_encoder_workspace_bytes(p) == -1 &&
+               hig_eval_encoder_train_workspace_bytes(p) == -1 && hig_eval_encoder_bwd_workspace_bytes(p) == -1 && hig_eval_encoder_bwd_tap_bytes(p) == HIG_EINVAL;
+      };
+      EXPECT(text_refused(nullptr) && eval_refused(nullptr));
+      hig_text_dims tb = t; tb.B = 0;      EXPECT(text_refused(&tb));
+      tb = t; tb.H = 5;                    EXPECT(text_refused(&tb));                          // Lt % H
+      tb = t; tb.Lt = 28; tb.H = 4;        EXPECT(text_refused(&tb));                          // head dim 7
+      EXPECT(hig_last_error(msg, sizeof(msg)) >= 0 && strcmp(msg, "hig text head: head dim 7 not in {8,16,32,64,128}") == 0);
+      tb = t; tb.ff = 130;                 EXPECT(text_refused(&tb));
+      tb = t; tb.Lt = 2048; tb.H = 16;     EXPECT(text_refused(&tb));                          // Lt > 1024
+      tb = t; tb.prec = 7;                 EXPECT(text_refused(&tb));
+      EXPECT(hig_last_error(msg, sizeof(msg)) >= 0 && strcmp(msg, "hig: unknown prec=7") == 0);
+      tb = t; tb.L = INT32_MIN;            EXPECT(text_refused(&tb));
+      hig_eval_dims eb = e; eb.T = 1;      EXPECT(eval_refused(&eb));
+      eb = e; eb.F = 3;                    EXPECT(eval_refused(&eb));
+      eb = e; eb.d = 48; eb.H = 4;         EXPECT(eval_refused(&eb));                          // head dim 12
+      EXPECT(hig_last_error(msg, sizeof(msg)) >= 0 && strcmp(msg, "hig eval encoder: head dim 12 not in {8,16,32,64,128}") == 0);
+      eb = e; eb.d = 2048; eb.H = 16;      EXPECT(eval_refused(&eb));                          // d > 1024
+      eb = e; eb.prec = -1;                EXPECT(eval_refused(&eb));
+      eb = e; eb.C = 0;                    EXPECT(eval_refused(&eb));
+    }
+    // the tower: positive sizes in whole 256-byte granules; training sizes only with exact-fp32 products
+    {
+      auto cd = [](int32_t* d, int B, int N, int W, int H, int L, int vocab, int prec) {
+        for (int i = 0; i < HIG_CD_NSLOTS; ++i) d[i] = 0;
+        d[HIG_CD_B] = B; d[HIG_CD_N] = N; d[HIG_CD_W] = W; d[HIG_CD_H] = H; d[HIG_CD_L] = L; d[HIG_CD_VOCAB] = vocab; d[HIG_CD_PREC] = prec;
+      };
+      int32_t d[HIG_CD_NSLOTS];
+      const int towers[][6] = {{3, 77, 128, 2, 2, 64}, {2, 20, 512, 8, 2, 49408}, {27, 77, 128, 2, 1, 64}, {1, 128, 64, 1, 1, 2}};
+      for (const auto& c : towers) {
+        cd(d, c[0], c[1], c[2], c[3], c[4], c[5], HIG_PREC_F32);
+        const int64_t inf = hig_clip_text_workspace_bytes(d), tr = hig_clip_text_train_bytes(d), bw = hig_clip_text_bwd_workspace_bytes(d);
+        EXPECT(inf > 0 && tr > 0 && bw > 0 && inf % 256 == 0 && tr % 256 == 0 && bw % 256 == 0);
+        EXPECT(bw >= (int64_t)1536 * 128 * 128 * 4);                                           // (the split-R slabs alone)
+        cd(d, c[0], c[1], c[2], c[3], c[4], c[5], HIG_PREC_BF16);
+        EXPECT(hig_clip_text_workspace_bytes(d) == inf && hig_clip_text_train_bytes(d) == -1 && hig_clip_text_bwd_workspace_bytes(d) == -1);
+        EXPECT(hig_last_error(msg, sizeof(msg)) >= 0 && strstr(msg, "hig_clip_text_bwd_workspace_bytes: prec=") != nullptr);
+      }
+      auto refused = [&]() { return hig_clip_text_workspace_bytes(d) == -1 && hig_clip_text_train_bytes(d) == -1 && hig_clip_text_bwd_workspace_bytes(d) == -1; };
+      cd(d, 3, 77, 128, 4, 2, 64, 0);    EXPECT(refused());                                    // head dim 32
+      cd(d, 3, 129, 128, 2, 2, 64, 0);   EXPECT(refused());                                    // N > 128
+      cd(d, 3, 77, 2048, 32, 2, 64, 0);  EXPECT(refused());                                    // W > 1024
+      cd(d, 0, 77, 128, 2, 2, 64, 0);    EXPECT(refused());
+      cd(d, 3, 77, 128, 2, 2, 64, 9);    EXPECT(refused());
+      EXPECT(hig_last_error(msg, sizeof(msg)) >= 0 && strcmp(msg, "hig: unknown prec=9") == 0);
+      EXPECT(hig_clip_text_workspace_bytes(nullptr) == -1 && hig_clip_text_train_bytes(nullptr) == -1 && hig_clip_text_bwd_workspace_bytes(nullptr) == -1);
+    }
+  }
   if (failures) {
     fprintf(stderr, "%d expectation(s) failed\n", failures);
     return 1;

@@ -230,6 +230,34 @@ def test_the_layout_hooks_answer_by_named_slot_without_a_hip_call():
     assert L.hig_eval_encoder_bwd_tap_bytes(None) == _lib.EINVAL and L.hig_text_head_bwd_tap_bytes(None) == _lib.EINVAL
 
 
+def test_both_chains_lay_the_layer_block_and_the_layer_scratch_out_alike():
+    """The same (B, S, n, ff, H): the text head at N = 24 tokens and the MotionEncoder `hd8` at S = 2 T = 24 share the per-layer
+    block of the forward tables slot for slot, and the extents of the layer backward's own scratch members."""
+    L = _lib.lib()
+    c = eb.EVAL_CASES["hd8"]
+    assert (c["B"], 2 * c["T"], c["d"], c["H"], c["ff"]) == (4, 24, 64, 8, 128)
+    e = _lib.EvalDims(B=c["B"], T=c["T"], F=c["F"], d=c["d"], H=c["H"], ff=c["ff"], L=c["L"], C=26, cls=0, prec=_lib.PREC_F32)
+    t = _lib.TextDims(B=4, N=24, W=64, Lt=64, H=8, ff=128, L=2, E=128, prec=_lib.PREC_F32)
+    tf, tb = (table(L.hig_text_head_layout, t, w, n)[1] for w, n in ((_lib.ENC_LAYOUT_FWD, _lib.TFW_NSLOTS), (_lib.ENC_LAYOUT_BWD, _lib.TBW_NSLOTS)))
+    ef, ebw = (table(L.hig_eval_encoder_layout, e, w, n)[1] for w, n in ((_lib.ENC_LAYOUT_FWD, _lib.EFW_NSLOTS), (_lib.ENC_LAYOUT_BWD, _lib.EBW_NSLOTS)))
+    block = ("QKV", "LSE", "ATT", "R1", "ST1", "X1", "Z", "F", "R2", "ST2", "X2")
+    assert len(block) == 11 and _lib.TFW_X2 - _lib.TFW_QKV == _lib.EFW_X2 - _lib.EFW_QKV == 10
+    for k in block + ("LSTRIDE",):
+        assert tf[getattr(_lib, "TFW_" + k)] == ef[getattr(_lib, "EFW_" + k)] >= 0, k
+    assert tf[_lib.TFW_QKV] == 0 and tf[_lib.TFW_LSTRIDE] > tf[_lib.TFW_X2]
+
+    def extent(v, names, prefix, k):           # from member k to the next member of its table
+        at = v[getattr(_lib, prefix + k)]
+        later = [v[getattr(_lib, prefix + m)] for m in names if m != "SLAB_FLOATS" and v[getattr(_lib, prefix + m)] > at]
+        return min(later) - at
+    tnames = [n[4:] for n in dir(_lib) if n.startswith("TBW_") and n != "TBW_NSLOTS"]
+    enames = [n[4:] for n in dir(_lib) if n.startswith("EBW_") and n != "EBW_NSLOTS"]
+    assert len(tnames) == _lib.TBW_NSLOTS and len(enames) == _lib.EBW_NSLOTS
+    M = 4 * 24
+    for k, floats in (("DFF", M * 128), ("DQKV", M * 3 * 64), ("DELTA", 4 * 8 * 24)):
+        assert extent(tb, tnames, "TBW_", k) == extent(ebw, enames, "EBW_", k) == (floats + 63) // 64 * 64, k
+
+
 def test_a_short_tap_is_refused_before_any_hip_call():
     """No device here: a call that got as far as a HIP call would fail with another code (or fault on the made-up addresses)."""
     L = _lib.lib()
